@@ -10,8 +10,11 @@ only inter-GPU traffic is one RCCL gather of the final detection records per ste
     python bench.py --gpus 1 --steps 10 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full                # + everything listed below
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR    # + the last timed step's outputs as DIR/<name>.npy
 
-The ONE JSON line carries, beside the headline (bf16, BASELINE config 3):
+A plain run sets up, warms up, times the steps and prints the headline (`value`, `ms_per_step`, `config`).  With --full the
+ONE JSON line also carries, beside the headline (bf16, BASELINE config 3):
   roofline       the dominant kernel's achieved TFLOP/s from HIP events inside the timed region
   cpu_baseline   the CPU port timed on this host (rank 0, N=1 only)
   parity_mode    the fastest precision mode that meets north_star's 1e-3 END TO END in this run -- f16mx4 / f16mx (round 5: head towers
@@ -450,6 +453,56 @@ class Telemetry(object):
         return out
 
 
+DUMP_BUDGET_BYTES = 63 * 10 ** 6   # --dump-outputs: all files together (64 MB with room for the .npy headers)
+
+
+def detections_to_arrays(host):
+    """Engine.collect's padded per-frame detections -> {name: float32 array, frame first}, rows past a frame's count zeroed."""
+    num = host["num"]
+    valid = (np.arange(host["scores"].shape[1])[None, :] < num[:, None]).astype(np.float32)
+    arrays = {"num_detections": num.astype(np.float32)}
+    for name in ("scores", "means", "covs", "counts"):
+        a = host[name]
+        arrays[name] = a * valid.reshape(valid.shape + (1,) * (a.ndim - 2))
+    return arrays
+
+
+def records_to_arrays(rec, num_classes):
+    """Packed detection records [frames, K, 1+4+16+2C] (distributed.pack_records: padding rows already zero) -> the arrays of
+    detections_to_arrays."""
+    c = num_classes
+    return {"num_detections": rec[:, :, 0].sum(axis=1), "scores": rec[:, :, 21:21 + c], "means": rec[:, :, 1:5],
+            "covs": rec[:, :, 5:21].reshape(rec.shape[0], rec.shape[1], 4, 4), "counts": rec[:, :, 21 + c:21 + 2 * c]}
+
+
+def dump_outputs(dirname, arrays):
+    """{name: array or device tensor, frame first} -> DIR/<name>.npy in float32.  Every frame when they fit in DUMP_BUDGET_BYTES,
+    else a fixed sample of frames (seed 0, ascending), and when one frame alone is over it, that frame's first MC samples (raw head
+    outputs [B,N,A,.]).  DIR/frame_index.npy holds the frames written.  Returns what was written, for the JSON line."""
+    import torch
+    b = int(arrays[next(iter(arrays))].shape[0])
+    budget = DUMP_BUDGET_BYTES - 8 * b                            # (frame_index.npy)
+    per_frame = sum(4 * int(np.prod(a.shape[1:])) for a in arrays.values())
+    keep = min(b, budget // per_frame)
+    idx = np.arange(b) if keep == b else np.sort(np.random.default_rng(0).choice(b, max(1, keep), replace=False))
+    samples = None
+    if keep < 1:
+        samples = max(1, budget // (per_frame // int(arrays[next(iter(arrays))].shape[1])))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "frame_index.npy"), idx.astype(np.float64))
+    written = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a[torch.as_tensor(idx, device=a.device)]
+            a = (a[:, :samples] if samples else a).cpu().numpy()
+        else:
+            a = a[idx][:, :samples] if samples else a[idx]
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return {"dir": dirname, "frames": int(len(idx)), "of": b, "mc_samples": samples, "arrays": written}
+
+
 def make_engine(hw, B, n, device, precision="bf16", weights=None, anchors=None, **kw):
     from bayes_od_rc_amd.engine import Engine, make_config
     eng = Engine(make_config(hw, batch=B, mc_samples=n, device=device, bayes_od_config=BAYES_CFG,
@@ -631,8 +684,14 @@ def main():
     ap.add_argument("--mc", type=int, default=10)
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip parity_mode / secondary / value_with_h2d (headline only)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: telemetry, roofline and stage figures, and (bf16, one rank) value_with_h2d, the "
+                         "aggregation A/B, parity_mode, secondary and cpu_baseline; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (detections, or raw head outputs with --forward-only) as "
+                         "DIR/<name>.npy, float32, at most 64 MB (a fixed sample of the frames beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip parity_mode / secondary / value_with_h2d")
     ap.add_argument("--calibrate", action="store_true", help="print the cls foreground bias for M~1000")
     ap.add_argument("--fg-bias", type=float, default=CALIBRATED_FG_BIAS)
     ap.add_argument("--forward-only", action="store_true",
@@ -748,6 +807,7 @@ def run(args, out, rank, world, local_rank, backend, hw, n, B, fwd_only):
     views = [bdist.torch_views(eng, s) for s in (0, 1)] if (world > 1 or force_gather) else None
     host_out = [None, None]
     gathered = None
+    last = {"slot": None}                 # slot of the batch collected last: after the timed steps, the last step's
 
     def collect(slot):
         """Detections of the batch in `slot` -> host (rank 0 receives every rank's records)."""
@@ -764,6 +824,7 @@ def run(args, out, rank, world, local_rank, backend, hw, n, B, fwd_only):
             torch.cuda.current_stream().synchronize()
         else:
             host_out[slot] = eng.collect(slot, host_out[slot])
+        last["slot"] = slot
 
     pending = []
 
@@ -797,10 +858,11 @@ def run(args, out, rank, world, local_rank, backend, hw, n, B, fwd_only):
     if os.environ.get("BOD_BENCH_FAULT_RANK") == str(rank):
         os._exit(17)
     fence()
-    # HIP events around every head-tower launch (and every posterior) of the timed steps, recorded on the streams the
-    # kernels run on; read back after the closing fence
-    eng.profile_begin(which=1)         # 1: the launches of the dominant kernel (row-reuse tower kernel, tower layers 1..3)
-    telemetry = Telemetry(local_rank) if rank == 0 else None
+    if args.full:
+        # HIP events around every head-tower launch (and every posterior) of the timed steps, recorded on the streams the
+        # kernels run on; read back after the closing fence
+        eng.profile_begin(which=1)     # 1: the launches of the dominant kernel (row-reuse tower kernel, tower layers 1..3)
+    telemetry = Telemetry(local_rank) if rank == 0 and args.full else None
     if telemetry:
         telemetry.start()
     t0 = time.perf_counter()
@@ -810,7 +872,8 @@ def run(args, out, rank, world, local_rank, backend, hw, n, B, fwd_only):
     t_local = time.perf_counter() - t0          # this rank's own clock, before the closing barrier
     fence()
     elapsed = time.perf_counter() - t0
-    out["telemetry"] = telemetry.stop() if telemetry else None
+    if args.full:
+        out["telemetry"] = telemetry.stop() if telemetry else None
     per_rank = [B * args.steps / t_local]
     if USE_DIST:
         dev = "cuda" if backend == "nccl" else "cpu"
@@ -826,6 +889,32 @@ def run(args, out, rank, world, local_rank, backend, hw, n, B, fwd_only):
     out["value"] = round(value, 3)
     out["ms_per_step"] = round(elapsed / args.steps * 1e3, 3)
     kept = [] if fwd_only else eng.num_kept()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path received from its last step: the cluster-fused detections of the batch (rank 0: every
+        # rank's, in rank order), or the raw head outputs with --forward-only
+        if fwd_only:
+            arrays = bdist.raw_views(eng)
+        elif gathered is not None:
+            arrays = records_to_arrays(gathered.reshape(-1, *gathered.shape[2:]).numpy(), eng.Ccls)
+        else:
+            arrays = detections_to_arrays(host_out[last["slot"]])
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, arrays)
+
+    out["config"] = {"workload": "ResNet-50 RetinaNet + covar head, N=%d MC-dropout, %dx%d, %s"
+                                 % (n, hw[0], hw[1], "forward only (raw head outputs, BASELINE config 2)" if fwd_only else
+                                    "full BayesOD pipeline (forward+posterior+soft-NMS+cluster-fuse)"),
+                     "frames_per_gpu_per_step": B, "global_batch": world * B, "mc_samples": n,
+                     "anchors": eng.A, "kept_anchors_M": [int(k) for k in kept[:4]],
+                     "parallelism": ("image-sharded x%d, one RCCL gather/step" % world) if world > 1 else "one GPU (no exchange; N > 1: image-sharded, one RCCL gather/step)",
+                     "per_rank_images_per_sec": [round(v, 1) for v in per_rank],
+                     # valid detections in the records rank 0 received from each rank in the last gathered step (N > 1 path)
+                     "gathered_detections_per_rank": ([int(g[:, :, 0].sum().item()) for g in gathered] if gathered is not None else None),
+                     "visible_gpus": torch.cuda.device_count(), "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
+    if not args.full:
+        eng.close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        return
 
     # ---- roofline of the dominant kernel (head 3x3 implicit-GEMM): the launches of the timed region itself
     # The dominant kernel is ONE kernel symbol -- conv_igemm_kernel<256,256,2,4,0,true>, the row-reuse loop that runs tower
@@ -949,23 +1038,14 @@ def run(args, out, rank, world, local_rank, backend, hw, n, B, fwd_only):
     known = sum(v for v in stages.values() if v)
     stages["stem_backbone_fpn_and_gaps"] = round(step_ms - known, 3) if tower_only else None
 
-    out["config"] = {"workload": "ResNet-50 RetinaNet + covar head, N=%d MC-dropout, %dx%d, %s"
-                                 % (n, hw[0], hw[1], "forward only (raw head outputs, BASELINE config 2)" if fwd_only else
-                                    "full BayesOD pipeline (forward+posterior+soft-NMS+cluster-fuse)"),
-                     "frames_per_gpu_per_step": B, "global_batch": world * B, "mc_samples": n,
-                     "anchors": eng.A, "kept_anchors_M": [int(k) for k in kept[:4]],
-                     "parallelism": ("image-sharded x%d, one RCCL gather/step" % world) if world > 1 else "one GPU (no exchange; N > 1: image-sharded, one RCCL gather/step)",
-                     "per_rank_images_per_sec": [round(v, 1) for v in per_rank],
-                     # valid detections in the records rank 0 received from each rank in the last gathered step (N > 1 path)
-                     "gathered_detections_per_rank": ([int(g[:, :, 0].sum().item()) for g in gathered] if gathered is not None else None),
-                     "visible_gpus": torch.cuda.device_count(), "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
-                     # posterior launches only; the default run (extras) replaces both fields with the stage's full cost: posterior +
-                     # the A/B-measured share of the tower launches that is the fused MC aggregation (see below)
-                     "per_anchor_covariance_latency_ns": round(post_us_per_anchor * 1e3, 4),
-                     "per_anchor_covariance_latency": {"posterior_only_ns": round(post_us_per_anchor * 1e3, 4),
-                                                       "note": "posterior launches only: the MC aggregation runs inside the tower "
-                                                               "epilogues and is not in this figure (A/B skipped in this invocation)"},
-                     "stages_ms_per_step": stages}
+    out["config"].update({
+        # posterior launches only; the --full run's extras replace both fields with the stage's full cost: posterior +
+        # the A/B-measured share of the tower launches that is the fused MC aggregation (see below)
+        "per_anchor_covariance_latency_ns": round(post_us_per_anchor * 1e3, 4),
+        "per_anchor_covariance_latency": {"posterior_only_ns": round(post_us_per_anchor * 1e3, 4),
+                                          "note": "posterior launches only: the MC aggregation runs inside the tower "
+                                                  "epilogues and is not in this figure (A/B skipped in this invocation)"},
+        "stages_ms_per_step": stages})
     out["roofline"] = roofline
 
     extras = rank == 0 and world == 1 and not args.no_secondary and not fwd_only and args.precision == "bf16"

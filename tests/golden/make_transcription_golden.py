@@ -12,6 +12,7 @@ uniforms) and the soft-NMS (oracle/nms.py is called) -- see the stand-in's heade
 The model call is replaced by a stub returning seeded prediction tensors (the function's first statement is
 ``prediction_dict = model(image, train_val_test='testing')``).
 """
+import json
 import os
 import sys
 
@@ -260,6 +261,32 @@ def main():
         out["train_fwd.out.%s" % k] = np.asarray(pred[k], np.float32)
     print("train_fwd", {k: np.asarray(v).shape for k, v in pred.items()})
     np.savez_compressed(sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "reference_transcription.npz"), **out)
+    if len(sys.argv) <= 1:
+        with open(os.path.join(HERE, "reference_findings.json"), "w") as fp:
+            json.dump({"gaussian_prior_none": gaussian_prior_none_finding(ref, constants, tf_numpy_shim)}, fp, indent=1)
+            fp.write("\n")
+
+
+GAUSSIAN_NONE_INPUTS = [1, 4, 16, 8, True]          # make_inputs(seed, n, a, c, covar)
+GAUSSIAN_NONE_CFG = {"ranking_method": "score", "dirichlet_prior": {"type": "None"}, "gaussian_prior": {"type": "None"}}
+
+
+def gaussian_prior_none_finding(ref, constants, tf_numpy_shim):
+    """What the reference's bayes_od_inference does with gaussian_prior 'None' (the case CASES cannot capture): it raises, at the
+    squeeze of its posterior means on axis 2 (:204-205), because the means it holds there are the likelihood's, rank 2."""
+    pred, anchors, u = make_inputs(*GAUSSIAN_NONE_INPUTS)
+    tf_numpy_shim.set_uniforms(u)
+    sample = {constants.IMAGE_NORMALIZED_KEY: np.zeros((1, 64, 64, 3)), constants.ANCHORS_KEY: anchors[None]}
+    rec = {"make_inputs": GAUSSIAN_NONE_INPUTS, "config": GAUSSIAN_NONE_CFG, "use_full_covar": True, "dataset": "bdd"}
+    try:
+        ref.bayes_od_inference(lambda x, train_val_test=None: dict(pred), sample, GAUSSIAN_NONE_CFG,
+                               {"max_output_size": 10, "iou_threshold": 0.5, "soft_nms_sigma": 0.5}, True, "bdd")
+        rec.update({"raised": None})
+    except Exception as e:
+        rec.update({"raised": type(e).__name__, "message": str(e), "means_rank": 2 if "dimension 2" in str(e) else None})
+    finally:
+        tf_numpy_shim.set_uniforms(None)
+    return rec
 
 
 if __name__ == "__main__":

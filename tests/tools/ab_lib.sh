@@ -4,7 +4,7 @@
 # fraction / fan-out launch ms per run.  Run on the GPU box through gpurun; keep the builds under .ab/ (git-ignored, travels).
 LIBS=$1; shift
 for l in $LIBS; do
-  BOD_LIB_OVERRIDE=$l python bench.py --steps 8 --no-secondary --no-cpu-baseline "$@" 2>/dev/null | VAL="$l" python -c "
+  BOD_LIB_OVERRIDE=$l python bench.py --steps 8 --full --no-secondary --no-cpu-baseline "$@" 2>/dev/null | VAL="$l" python -c "
 import json, os, sys
 d = json.loads([l for l in sys.stdin if l.startswith('{')][0])
 print(os.environ['VAL'], d['value'], d['ms_per_step'], d['config']['stages_ms_per_step'], d['roofline']['frac'], d['roofline'].get('other_head_launch', {}).get('avg_launch_ms'))"

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 V="${@:-0}"
 rm -rf gpurun_out/pmc_sq1 gpurun_out/pmc_sq2 gpurun_out/pmc_tcc
 if [ "$PMC_PRODUCTION" = "1" ]; then
-  CMD="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
+  CMD="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --full"
   rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_WAIT_INST_LDS --output-format csv -d gpurun_out/pmc_sq1 -o p -- $CMD > gpurun_out/pmc_sq1.log 2>&1
   rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_LDS_DATA_FIFO_FULL --output-format csv -d gpurun_out/pmc_sq2 -o p -- $CMD > gpurun_out/pmc_sq2.log 2>&1
   rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE GRBM_TA_BUSY TCC_HIT_sum TCC_MISS_sum --output-format csv -d gpurun_out/pmc_tcc -o p -- $CMD > gpurun_out/pmc_tcc.log 2>&1

@@ -3,7 +3,7 @@
 #   usage: pmc_kernel.sh <kernel name substring> [bench.py flags]      e.g.  pmc_kernel.sh stem_pool_fused --mc 1 --forward-only
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 K="$1"; shift
-CMD="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary $*"
+CMD="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --full $*"
 rm -rf gpurun_out/pmc_k1 gpurun_out/pmc_k2
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_WAIT_INST_LDS --output-format csv -d gpurun_out/pmc_k1 -o p -- $CMD > gpurun_out/pmc_k1.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_LDS_DATA_FIFO_FULL --output-format csv -d gpurun_out/pmc_k2 -o p -- $CMD > gpurun_out/pmc_k2.log 2>&1

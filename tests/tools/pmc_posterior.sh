@@ -6,7 +6,7 @@
 #   usage: pmc_posterior.sh [batch]   -> gpurun_out/posterior_pmc.json (copy to profiles/roundN_posterior_pmc.json)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 B=${1:-512}
-CMD="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --batch $B"
+CMD="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --full --batch $B"
 rm -rf gpurun_out/pmc_pf gpurun_out/pmc_pw
 BOD_FUSE_AGGREGATION=0 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_pf -o p -- $CMD > gpurun_out/pmc_pf.log 2>&1
 BOD_FUSE_AGGREGATION=0 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_pw -o p -- $CMD > gpurun_out/pmc_pw.log 2>&1
