@@ -2637,6 +2637,16 @@ template <int BC, int BP, int WC, int WP, int ABL, bool XR, bool SPLIT = false>
 __global__ __launch_bounds__(64 * WC * WP, (ABL == 10 ? (BC == 64 ? 3 : 2) : 1)) void conv_igemm_kernel(const ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int bx = blockIdx.x, by = blockIdx.y, gz = blockIdx.z;
+    if constexpr (XR) {
+        // device-side tile count (the sparse tail, kernels.h SparseTailArgs): grid (capacity, 1, groups), tile = blockIdx.x in launch
+        // order -- the valid tiles are dispatched first and spread over all XCDs; the rest of the worst-case grid retires at once.
+        // (The persistent form, which would not dispatch them, spills 54 VGPRs: the tile loop keeps the loop's descriptors live.)
+        if (a.tile_count) {
+            if (bx >= *a.tile_count) return;
+            conv_tile<BC, BP, WC, WP, ABL, XR, SPLIT>(a, gz, bx, by, smem);
+            return;
+        }
+    }
     const int ny_tiles = a.cout_pad / BC;
     if (!XR && gridDim.y == 1 && ny_tiles > 1) {
         // Several cout tiles per pixel tile, launched as ONE grid row with the cout tile as the fast index INSIDE an XCD (round 4): the
@@ -3025,6 +3035,7 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     }
     const ConvArgs& a = a_local;
     if (a.M <= 0) return hipSuccess;
+    if (a.tile_count && (a.mx || a.split || !a.xreuse || a.ksplit > 1)) return hipErrorInvalidValue;       // (the bf16 row-reuse loop only)
     if (a.cin % 64 != 0 || a.cout_pad % 64 != 0) return hipErrorInvalidValue;
     if (a.mx) {                                      // f16mx precision: head-tower launches on the row-reuse loop, whatever the tile heuristics say
         if ((a.mx < 1 || a.mx > 3) || !a.split || a.xreuse != 2 || a.cout_pad != 256 || a.cin != 512 || a.taps != 9 || a.KW != 3 || !a.ext || a.M % 256 != 0 ||
@@ -3099,6 +3110,8 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
         if (!(big && a.cout_pad == 256 && a.taps == 9 && a.KW == 3 && a.ext && a.M % 256 == 0)) return hipErrorInvalidValue;
         for (int g = 0; g < a.groups; ++g) if (a.g[g].res || a.g[g].out_relu) return hipErrorInvalidValue;   // compiled out of the row-reuse kernel
         if (a.flags & CONV_OUT_F32) return hipErrorInvalidValue;                                              // likewise
+        // device-side tile count (the sparse tail): the production loop (conv_igemm_kernel, above)
+        if (a.tile_count) return (a.xreuse == 2 && a.variant == 0 && a.fan_count <= 1) ? launch_cfg<256, 256, 2, 4, 0, true>(a, s) : hipErrorInvalidValue;
         // xreuse == 2: compact-state, software-pipelined loop (32-bit byte offsets against the tile's first extended row);
         // otherwise (or variant 81, for A/B timing) the first-generation loop with 64-bit pointers
         if (a.xreuse != 2 || a.variant == 81) return launch_cfg<256, 256, 2, 4, 81, true>(a, s);

@@ -41,7 +41,7 @@ struct Plane {               // NHWC view (bf16, or fp32 in fp32 precision mode)
 struct PackedConv { char* w = nullptr; float* bias = nullptr; int cout = 0, cout_pad = 0, taps = 0, kw = 0, cin = 0; };
 
 struct Op {
-    enum Kind { STEM, POOL, CONV } kind;
+    enum Kind { STEM, POOL, CONV, KEEP } kind;      // KEEP: the posterior's keep flags + the sparse tail's row table (build_plan)
     ConvArgs conv;
     bool is_head3x3 = false;
     double flops = 0;
@@ -282,6 +282,13 @@ struct bod_context {
     bool agg_plan = false;                               // the plan holds FLAVOUR_AGG ops
     bool plan_fused_out = false, plan_xreuse = false, plan_xreuse0 = false;     // bod_plan_info
     bool raw_valid = false, agg_valid = false;           // which of the two the last forward produced
+    // Sparse tail (build_plan): the box and covariance heads' aggregating launches run after the keep flags, over the pixels with a
+    // kept anchor only; their statistics [agg[1], agg[2]] then exist for the anchors kept at (keep_seed, keep_first) alone.
+    bool plan_sparse = false;
+    SparseTailArgs sparse{};
+    bool agg_sparse = false;                             // the last forward's agg[1] / agg[2] are sparse
+    bool keep_ready = false;                             // pb.keep / d_counts / block_counts / num_kept hold the keep stage's output
+    uint64_t keep_seed = 0; uint32_t keep_first = 0;
     uint64_t last_seed = 0; uint32_t last_first_image = 0;
     std::map<std::string, RowEnt*> tables;
     struct XrTable { RowEnt* rows = nullptr; int2* ext = nullptr; int m = 0; };
@@ -1011,6 +1018,34 @@ bod_status build_plan(bod_context* h) {
     } else {
         BODCHK(ensure_raw(h));                 // the ops below reference the raw tensors directly
     }
+    static const bool split_on = [] { const char* e = getenv("BOD_SPLIT_AGG_LAUNCH"); return !e || atoi(e) != 0; }();     // (=0: one launch per layer on the aggregated tiling, A/B aid)
+    // ---- Sparse tail: only the classification head's statistics decide which anchors are kept (post_sample_kernel), and everything
+    // behind the filter reads the box and covariance statistics of kept anchors only (post_fuse_kernel, through anchor_index) -- about
+    // 2 % of them at the reference's operating point.  So the launch of the heads that end at layer 2 (box regression) and at layer 3
+    // (covariance) moves behind the classification head's last layer and the keep flags, and runs over the pixels with a kept anchor
+    // (SparseTailArgs): the same rows, products and epilogue as the dense launch, for those pixels.  BOD_SPARSE_TAIL=0: the dense plan.
+    // (Not on pipeline_overlap handles, the experimental CU-partitioned mode: they keep the dense plan.)
+    bool sparse = agg && split_on && h->es == 2 && !h->split && !mx_plan && !c.pipeline_overlap && h->A == h->P * c.anchors_per_location &&
+                  h->P <= 65536;
+    if (const char* e = getenv("BOD_SPARSE_TAIL")) sparse = sparse && atoi(e) != 0;
+    if (sparse) {
+        SparseTailArgs& sa = h->sparse;
+        sa.B = B; sa.N = N; sa.P = h->P; sa.apl = c.anchors_per_location; sa.Ppad = h->Ppad;
+        sa.cap_tiles = B * (h->P / sparse_tail_min_pixels(N) + 1);
+        RowEnt* pix = nullptr;
+        BODCHK(h->dalloc(&pix, (size_t)h->P, false));
+        HIPCHK(h, hipMemcpyAsync(pix, t2.data(), (size_t)h->P * sizeof(RowEnt), hipMemcpyHostToDevice, h->stream));     // image 0, sample 0
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        sa.pix = pix;
+        BODCHK(h->dalloc(&sa.rows, (size_t)sa.cap_tiles * 256, false));
+        BODCHK(h->dalloc(&sa.ext, (size_t)sa.cap_tiles * XR_EXT_ROWS, false));
+        BODCHK(h->dalloc(&sa.tile_count, 1));
+        BODCHK(h->dalloc(&sa.chunks, (size_t)B * h->P, false));
+        BODCHK(h->dalloc(&sa.tiles, (size_t)B * h->P, false));
+    }
+    h->plan_sparse = sparse;
+    Op sparse_op; sparse_op.kind = Op::CONV; sparse_op.is_head3x3 = true; sparse_op.flavour = FLAVOUR_AGG;
+    int sparse_groups = 0; PackedConv sparse_pc{};
     h->agg_plan = agg; h->plan_fused_out = fuse_out; h->plan_xreuse = xreuse; h->plan_xreuse0 = xreuse0; h->plan_mx = mx_plan ? mxf : 0;
     // A layer's launch takes the sample-complete ("aggregated") tiling only for the heads that END there (fused 1x1 + MC aggregation): such
     // a tile holds 25 pixels x 10 samples = 250 of its 256 rows (240 at N = 30), so every other head's conv of that layer -- the
@@ -1035,7 +1070,6 @@ bod_status build_plan(bod_context* h) {
     for (int fpass = 0; fpass < 2; ++fpass)
     for (int part = 0; part < 2; ++part)
     for (int flav = (agg && layer >= 2) ? FLAVOUR_RAW : FLAVOUR_BOTH; flav <= ((agg && layer >= 2) ? FLAVOUR_AGG : FLAVOUR_BOTH); ++flav) {
-        static const bool split_on = [] { const char* e = getenv("BOD_SPLIT_AGG_LAUNCH"); return !e || atoi(e) != 0; }();     // (=0: one launch per layer on the aggregated tiling, A/B aid)
         const bool split_launch = agg && layer >= 2 && split_on;       // part 0: heads that continue, part 1: heads that end at this layer
         if (fpass == 1 && (!mixed || layer == 0)) continue;
         const int lfmt = !mx_plan ? 0 : layer == 0 ? pyr_fmt : mixed ? (fpass == 0 ? 2 : 1) : mxf;       // row format this launch READS
@@ -1074,6 +1108,17 @@ bod_status build_plan(bod_context* h) {
                 }
                 fused_flops += 2.0 * ((double)B * N * h->P) * 256.0 * out_ch[hd];      // the 1x1 output conv runs inside this launch
             }
+            if (sparse && flav == FLAVOUR_AGG && hd != 0) {          // -> the sparse tail's launch, planned behind the keep stage
+                sparse_op.conv.g[sparse_groups] = cg;
+                sparse_op.wname[sparse_groups] = op.wname[g];
+                sparse_op.head[sparse_groups] = hd;
+                if (sparse_groups++ == 0) sparse_pc = pc;
+                // the dense launch's algorithmic count: the profiler's head-conv FLOPs stay those of the dense plan
+                sparse_op.flops += 2.0 * ((double)B * N * h->P) * 256.0 * 2304.0 + 2.0 * ((double)B * N * h->P) * 256.0 * out_ch[hd];
+                fused_flops -= 2.0 * ((double)B * N * h->P) * 256.0 * out_ch[hd];
+                op.head[g] = -1; op.wname[g].clear();
+                continue;
+            }
             op.conv.g[g] = cg;
             if (g == 0) pc0 = pc;
             ++g;
@@ -1107,6 +1152,22 @@ bod_status build_plan(bod_context* h) {
         op.name = "head_tower_layer_" + std::to_string(layer) + (both ? "" : flav == FLAVOUR_AGG ? "(aggregating)" : flav == FLAVOUR_RAW ? "(raw)" : "");
         op.same_geom = N == 1;            // pyramid [B][Ppad] and head planes [B*N][Ppad] coincide at N = 1
         h->ops.push_back(op);
+    }
+    if (sparse_groups > 0) {
+        Op keep; keep.kind = Op::KEEP; keep.flavour = FLAVOUR_AGG; keep.name = "head_tower_layer_3(keep)";
+        h->ops.push_back(keep);
+        const SparseTailArgs& sa = h->sparse;
+        ConvArgs a = base_args(sparse_pc, sa.rows, sa.cap_tiles * 256, 256, 256);
+        for (int q = 0; q < sparse_groups; ++q) a.g[q] = sparse_op.conv.g[q];
+        a.groups = sparse_groups;
+        a.flags = CONV_RELU | (mc ? CONV_DROPOUT : 0);
+        a.fan_count = 1; a.fan_stride = (int32_t)h->Ppad;
+        a.drop_threshold = thr; a.drop_scale = dscale;
+        a.ext = sa.ext; a.xreuse = 2; a.tile_count = sa.tile_count;
+        a.mx_loader = getenv("BOD_TOWER_LOADER") ? atoi(getenv("BOD_TOWER_LOADER")) : 0;      // (as the dense launches of the towers)
+        sparse_op.conv = a;
+        sparse_op.name = "head_tower_layer_3(sparse)";
+        h->ops.push_back(sparse_op);
     }
     for (int hd = 0; hd < nheads && !fuse_out; ++hd) {
         PackedConv pc;
@@ -1280,7 +1341,7 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
         par = h->fwd_parity; h->fwd_parity ^= 1;
         if (h->l0_pending[par]) { HIPCHK(h, hipStreamWaitEvent(fs, h->ev_l0_done[par], 0)); h->l0_pending[par] = false; }
     }
-    if (!only_flavoured) h->pyr_last = par;
+    if (!only_flavoured) { h->pyr_last = par; h->keep_ready = false; }
     // Kernel CHOICES (sliding-window / pointwise / fused-stem eligibility: launch_conv_igemm, workgroups against compute units) are made
     // against the WHOLE chip on every stream: a CU-masked front stream that chose by its own 32 CUs ran other kernels than bod_infer
     // and a serial handle at mid-size batches (64 frames at 512x512: 64 column strips >= 32 take slide3x3_c128, which re-associates one
@@ -1345,6 +1406,22 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
                 if (!h->train) BODCHK(mark_images_consumed(h, st));
                 break;
             }
+            case Op::KEEP: {
+                // the posterior's keep flags, then the sparse tail's row table from them -- on the device, no host round trip.  The
+                // flags and counts are the posterior's buffers: ordered behind the readers of an earlier call as run_posterior is.
+                for (int sidx = 0; sidx < 2; ++sidx)
+                    if (h->side_pending[sidx]) HIPCHK(h, hipStreamWaitEvent(st, h->ev_done[sidx], 0));
+                PostCfg pc = post_cfg(h, seed, first_image);
+                pc.aggregated = 1;
+                PostBuffers pb = h->pb;
+                pb.agg_cls = h->agg[0];
+                HIPCHK(h, launch_posterior_keep(pc, pb, st));
+                SparseTailArgs sa = h->sparse;
+                sa.keep = h->pb.keep;
+                HIPCHK(h, launch_sparse_tail_rows(sa, st));
+                h->keep_ready = true; h->keep_seed = seed; h->keep_first = first_image;
+                break;
+            }
             case Op::POOL:
                 if (stem_pool_fused) break;
                 HIPCHK(h, launch_stem_pool(h->stem_out, op.conv.g[0].out, h->split ? 2 : (h->es == 4 ? 1 : 0), c.batch,
@@ -1405,7 +1482,7 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
     }
     h->forward_done = true; h->posterior_done = h->nms_done = h->cluster_done = false; h->affinity_img = -1;
     h->last_seed = seed; h->last_first_image = first_image;
-    if (flavour == FLAVOUR_AGG) { h->agg_valid = true; h->raw_valid = false; }
+    if (flavour == FLAVOUR_AGG) { h->agg_valid = true; h->raw_valid = false; h->agg_sparse = h->plan_sparse; }
     else { h->raw_valid = true; if (!only_flavoured) h->agg_valid = false; }
     return BOD_OK;
 }
@@ -1436,12 +1513,21 @@ bod_status run_posterior(bod_context* h, uint64_t seed, uint32_t first_image) {
     pb.cls = h->raw[0]; pb.box = h->raw[1]; pb.cov = h->raw[2]; pb.anchors = h->d_anchors;
     pc.aggregated = (h->agg_valid && !h->raw_valid) ? 1 : 0;        // statistics from the conv epilogue, no [B,N,A,.] tensors
     pb.agg_cls = h->agg[0]; pb.agg_box = h->agg[1]; pb.agg_cov = h->agg[2];
+    // bod_infer: the forward's keep stage already sampled with this seed.  A posterior under another seed may keep other anchors,
+    // whose box / covariance statistics the sparse tail did not compute: it takes the raw tensors (re-run on the activations in HBM).
+    const bool keep_done = pc.aggregated && h->keep_ready && seed == h->keep_seed && first_image == h->keep_first;
+    h->keep_ready = false;
+    if (pc.aggregated && h->agg_sparse && (seed != h->keep_seed || first_image != h->keep_first)) {
+        BODCHK(materialise_raw(h));
+        pc.aggregated = 0;
+        pb.cls = h->raw[0]; pb.box = h->raw[1]; pb.cov = h->raw[2];
+    }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (h->profiling) {
         HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
         HIPCHK(h, hipEventRecord(e0, h->stream));
     }
-    HIPCHK(h, launch_posterior(pc, pb, h->stream));
+    HIPCHK(h, keep_done ? launch_posterior_fuse(pc, pb, h->stream) : launch_posterior(pc, pb, h->stream));
     if (h->cfg.ranking_method == BOD_RANK_JOINT_ENTROPY && h->cfg.gaussian_isotropic && h->cfg.dirichlet_non_informative)
         HIPCHK(h, launch_joint_entropy_rank(pc, pb, h->stream));
     if (h->profiling) { HIPCHK(h, hipEventRecord(e1, h->stream)); h->ev_post.emplace_back(e0, e1); }
@@ -2798,6 +2884,7 @@ bod_status bod_plan_info(bod_handle h, int32_t* info8) {
     info8[4] = (int32_t)h->ops.size();
     for (const Op& o : h->ops) if (o.kind == Op::CONV && !o.is_head3x3 && o.conv.xreuse) ++info8[5];
     info8[6] = h->plan_mx;
+    info8[7] = h->plan_sparse;
     return BOD_OK;
 }
 

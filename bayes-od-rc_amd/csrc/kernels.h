@@ -127,6 +127,9 @@ struct ConvArgs {
     // the 256 rows).  0 = off.
     int32_t mx;
     int32_t mx_loader;     // f16mx loop: which waves issue the weight pieces (conv_igemm.hip; 0 all, 1 lower four, 2 upper four)
+    // Row-reuse launch whose tile count is only known on the device (the sparse tail, launch_sparse_tail_rows): `rows` / `ext` hold
+    // capacity for M / 256 tiles, the first *tile_count of them are valid (conv_igemm_kernel).  nullptr = M / 256 tiles.
+    const int32_t* tile_count;
 };
 
 // hipFuncSetAttribute is per device: remember which devices of this process already have the attribute
@@ -201,6 +204,28 @@ struct PostBuffers {
 };
 
 hipError_t launch_posterior(const PostCfg& c, const PostBuffers& b, hipStream_t s);
+// launch_posterior in two halves: the keep flags (sampling + per-image scan) and the rest (compaction + per-anchor fusion)
+hipError_t launch_posterior_keep(const PostCfg& c, const PostBuffers& b, hipStream_t s);
+hipError_t launch_posterior_fuse(const PostCfg& c, const PostBuffers& b, hipStream_t s);
+
+// Sparse tail (engine.hip): the aggregating launches of the box and covariance heads run only over the pixels with at least one kept
+// anchor.  One workgroup per image lists those pixels (a pixel between two kept, x-adjacent ones is taken along: a run of three costs
+// fewer extended rows than two runs of one) and packs them into sample-complete row-reuse tiles under the rules of
+// xr_tile_rows_aggregated (plan_tables.h).  Every RowEnt is the one of the dense per-sample table (same dropout counters, same
+// aggregation slot); `pix` is that table's image 0 / sample 0 part (P entries), the others differ by closed forms.
+struct SparseTailArgs {
+    const uint8_t* keep;        // [B, A] (post_sample_kernel)
+    const RowEnt* pix;          // [P]
+    RowEnt* rows;               // [cap_tiles * 256]
+    int2* ext;                  // [cap_tiles * XR_EXT_ROWS]
+    int32_t* tile_count;        // one int, zeroed by the launcher
+    int4* chunks;               // scratch [B * P]: {pixel, tile, slot, extended row} of every run piece
+    int4* tiles;                // scratch [B * P]: {first pixel, slots used, extended rows used, -}
+    int32_t B, N, P, apl, cap_tiles;
+    int64_t Ppad;
+};
+int sparse_tail_min_pixels(int N);                  // fewest pixels a tile closed before the image's end holds
+hipError_t launch_sparse_tail_rows(const SparseTailArgs& a, hipStream_t s);
 hipError_t launch_joint_entropy_rank(const PostCfg& c, const PostBuffers& b, hipStream_t s);
 hipError_t launch_validation_post(const PostCfg& c, const PostBuffers& b, hipStream_t s);   // validation_utils.py:10-77
 

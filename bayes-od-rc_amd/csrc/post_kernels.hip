@@ -532,22 +532,133 @@ extern "C" int bod_debug_selfcheck_read(unsigned int* count, unsigned long long*
 }
 #endif
 
-hipError_t launch_posterior(const PostCfg& c, const PostBuffers& b, hipStream_t s) {
+hipError_t launch_posterior_keep(const PostCfg& c, const PostBuffers& b, hipStream_t s) {
     const int nblocks = (c.A + POST_BLOCK - 1) / POST_BLOCK;
     dim3 grid(nblocks, c.B);
-    if (c.C == 8) {
-        hipLaunchKernelGGL(post_sample_kernel<8>, grid, dim3(POST_BLOCK), 0, s, c, b, nblocks);
-        hipLaunchKernelGGL(post_scan_kernel, dim3(c.B), dim3(POST_BLOCK), 0, s, b, nblocks);
-        hipLaunchKernelGGL(post_compact_kernel, grid, dim3(POST_BLOCK), 0, s, c, b, nblocks);
-        hipLaunchKernelGGL(post_fuse_kernel<8>, dim3(std::min(nblocks, POST_FUSE_BLOCKS), c.B), dim3(POST_BLOCK), 0, s, c, b, nblocks);
-    } else if (c.C == 4) {
-        hipLaunchKernelGGL(post_sample_kernel<4>, grid, dim3(POST_BLOCK), 0, s, c, b, nblocks);
-        hipLaunchKernelGGL(post_scan_kernel, dim3(c.B), dim3(POST_BLOCK), 0, s, b, nblocks);
-        hipLaunchKernelGGL(post_compact_kernel, grid, dim3(POST_BLOCK), 0, s, c, b, nblocks);
-        hipLaunchKernelGGL(post_fuse_kernel<4>, dim3(std::min(nblocks, POST_FUSE_BLOCKS), c.B), dim3(POST_BLOCK), 0, s, c, b, nblocks);
-    } else {
-        return hipErrorInvalidValue;
+    if (c.C == 8) hipLaunchKernelGGL(post_sample_kernel<8>, grid, dim3(POST_BLOCK), 0, s, c, b, nblocks);
+    else if (c.C == 4) hipLaunchKernelGGL(post_sample_kernel<4>, grid, dim3(POST_BLOCK), 0, s, c, b, nblocks);
+    else return hipErrorInvalidValue;
+    hipLaunchKernelGGL(post_scan_kernel, dim3(c.B), dim3(POST_BLOCK), 0, s, b, nblocks);
+    return hipGetLastError();
+}
+
+hipError_t launch_posterior_fuse(const PostCfg& c, const PostBuffers& b, hipStream_t s) {
+    const int nblocks = (c.A + POST_BLOCK - 1) / POST_BLOCK;
+    dim3 grid(nblocks, c.B);
+    if (c.C != 8 && c.C != 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(post_compact_kernel, grid, dim3(POST_BLOCK), 0, s, c, b, nblocks);
+    if (c.C == 8) hipLaunchKernelGGL(post_fuse_kernel<8>, dim3(std::min(nblocks, POST_FUSE_BLOCKS), c.B), dim3(POST_BLOCK), 0, s, c, b, nblocks);
+    else hipLaunchKernelGGL(post_fuse_kernel<4>, dim3(std::min(nblocks, POST_FUSE_BLOCKS), c.B), dim3(POST_BLOCK), 0, s, c, b, nblocks);
+    return hipGetLastError();
+}
+
+hipError_t launch_posterior(const PostCfg& c, const PostBuffers& b, hipStream_t s) {
+    const hipError_t e = launch_posterior_keep(c, b, s);
+    return e != hipSuccess ? e : launch_posterior_fuse(c, b, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Sparse tail row table (kernels.h SparseTailArgs).  One workgroup per image: the pixel flags go to LDS, thread 0 walks them and cuts
+// the runs into tile pieces ("chunks"), then the workgroup writes the pieces' rows and extended rows and pads every tile as
+// xr_tile_rows_aggregated does.  Tiles of different images land in the order the images reserve them (atomicAdd): each tile holds
+// one image's pixels with all N samples, so the order changes no result.
+// ------------------------------------------------------------------------------------------------
+int sparse_tail_min_pixels(int N) {
+    // a tile closes before the image's end when its slots are full or when a piece of one pixel (3N extended rows) no longer fits;
+    // a piece of k pixels costs N * (k + 2) <= 3N * k extended rows
+    const int Qmax = 256 / N;
+    return std::max(1, std::min(Qmax, (XR_EXT_ROWS - 3 * N) / (3 * N) + 1));
+}
+
+__device__ __forceinline__ RowEnt sparse_tail_ent(const SparseTailArgs& a, int b, int n, int p) {
+    RowEnt e = a.pix[p];
+    const int32_t plane = (int32_t)(((int64_t)b * a.N + n) * a.Ppad);
+    e.in_off += plane;
+    e.out_off += plane;
+    e.rng_zs = n | (b << 16);
+    e.pad0 = (int32_t)(((int64_t)b * a.N + n) * a.P + p);
+    return e;
+}
+
+__global__ __launch_bounds__(256) void sparse_tail_rows_kernel(SparseTailArgs a) {
+    extern __shared__ uint8_t s_flag[];            // [P]: 1 kept pixel, 0 not
+    __shared__ int s_nchunk, s_ntile, s_base;
+    const int b = blockIdx.x, tid = threadIdx.x, N = a.N, P = a.P;
+    const uint8_t* keep = a.keep + (size_t)b * P * a.apl;
+    for (int p = tid; p < P; p += blockDim.x) {
+        uint8_t f = 0;
+        for (int k = 0; k < a.apl; ++k) f |= keep[(size_t)p * a.apl + k];
+        s_flag[p] = f ? 1 : 0;
     }
+    __syncthreads();
+    int4* chunks = a.chunks + (size_t)b * P;
+    int4* tiles = a.tiles + (size_t)b * P;
+    if (tid == 0) {
+        const int Qmax = 256 / N;
+        auto adjacent = [&](int p) { return a.pix[p].in_off == a.pix[p - 1].in_off + 1 && a.pix[p].in_pitch == a.pix[p - 1].in_pitch; };
+        int nchunk = 0, ntile = 0, Q = 0, X = 0, first = 0;
+        bool open = false;
+        auto close_tile = [&]() { tiles[ntile++] = make_int4(first, Q, X, 0); open = false; };
+        int p = 0;
+        while (p < P) {
+            if (!s_flag[p]) { ++p; continue; }
+            int L = 1;                 // run of x-adjacent pixels from p, through single unkept pixels between two kept ones
+            while (p + L < P && adjacent(p + L) &&
+                   (s_flag[p + L] || (p + L + 1 < P && s_flag[p + L + 1] && adjacent(p + L + 1)))) ++L;
+            while (L > 0) {
+                if (!open) { first = p; Q = 0; X = 0; open = true; }
+                const int take = min(min(L, Qmax - Q), (XR_EXT_ROWS - X) / N - 2);
+                if (take < 1) { close_tile(); continue; }
+                chunks[nchunk++] = make_int4(p, ntile, Q, X | (take << 16));
+                X += N * (take + 2); Q += take; p += take; L -= take;
+                if (Q == Qmax) close_tile();
+            }
+        }
+        if (open) close_tile();
+        s_nchunk = nchunk; s_ntile = ntile;
+        s_base = atomicAdd(a.tile_count, ntile);
+    }
+    __syncthreads();
+    const int nchunk = s_nchunk, ntile = s_ntile, base = s_base;
+    if (base + ntile > a.cap_tiles) return;         // (cannot happen: cap_tiles is sized by sparse_tail_min_pixels)
+    // the pieces: N * take rows and N * (take + 2) extended rows each
+    for (int i = tid; i < nchunk * N; i += blockDim.x) {
+        const int ci = i / N, n = i - ci * N;
+        const int4 c = chunks[ci];
+        const int p0 = c.x, t = base + c.y, Q0 = c.z, X0 = c.w & 0xFFFF, take = c.w >> 16;
+        const int x0 = X0 + n * (take + 2);
+        const RowEnt first = sparse_tail_ent(a, b, n, p0);
+        int2* ext = a.ext + (size_t)t * XR_EXT_ROWS + x0;
+        for (int k = 0; k < take + 2; ++k) ext[k] = make_int2(first.in_off + k, first.in_pitch);
+        RowEnt* rows = a.rows + (size_t)t * 256;
+        for (int k = 0; k < take; ++k) {
+            RowEnt q = sparse_tail_ent(a, b, n, p0 + k);
+            q.pad1 = x0 + k;
+            rows[(Q0 + k) * N + n] = q;
+        }
+    }
+    // the padding: invalid rows behind the last slot, the tile's first extended row behind the last extended row
+    RowEnt invalid = a.pix[0];
+    invalid.out_off = -1; invalid.pad0 = 0; invalid.pad1 = 0;
+    for (int i = tid; i < ntile * 256; i += blockDim.x) {
+        const int t = i >> 8, r = i & 255;
+        if (r >= tiles[t].y * N) a.rows[(size_t)(base + t) * 256 + r] = invalid;
+    }
+    for (int i = tid; i < ntile * XR_EXT_ROWS; i += blockDim.x) {
+        const int t = i / XR_EXT_ROWS, r = i - t * XR_EXT_ROWS;
+        const int4 ti = tiles[t];
+        if (r >= ti.z) {
+            const RowEnt first = sparse_tail_ent(a, b, 0, ti.x);
+            a.ext[(size_t)(base + t) * XR_EXT_ROWS + r] = make_int2(first.in_off, first.in_pitch);
+        }
+    }
+}
+
+hipError_t launch_sparse_tail_rows(const SparseTailArgs& a, hipStream_t s) {
+    if (a.B <= 0 || a.P <= 0 || a.N < 1 || 256 / a.N < 1 || XR_EXT_ROWS / a.N - 2 < 1 || a.P > 65536) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(a.tile_count, 0, sizeof(int32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sparse_tail_rows_kernel, dim3(a.B), dim3(256), (size_t)a.P, s, a);
     return hipGetLastError();
 }
 

@@ -393,7 +393,8 @@ bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, in
  * head output convs are fused into the last tower layers' epilogues, [2] = 1 when the per-sample tower layers run on the
  * activation-row-reuse kernel, [3] = 1 when the fan-out layer does, [4] = number of ops of the forward plan, [5] = number of
  * backbone / FPN 3x3 layers planned on the row-reuse kernel, [6] = 1 / 2 when the head towers run the f16mx / f16mx4 arithmetic
- * (BOD_PRECISION_F16MX / BOD_PRECISION_F16MX4), [7] = 0. */
+ * (BOD_PRECISION_F16MX / BOD_PRECISION_F16MX4), [7] = 1 when the box / covariance heads' last layers run over the pixels with a kept
+ * anchor only (the sparse tail; BOD_SPARSE_TAIL=0: dense). */
 bod_status bod_plan_info(bod_handle h, int32_t* info8);
 
 #ifdef __cplusplus
