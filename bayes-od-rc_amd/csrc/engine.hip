@@ -54,6 +54,10 @@ struct Op {
     int flavour = 0;
     int head[3] = {-1, -1, -1};          // per group: BOD_HEAD_* whose raw buffer the fused 1x1 writes (raw buffers are allocated lazily)
     bool hx_pyramid = false;             // f16mx: this launch (the first tower layer) reads the pyramid as hx rows -- converted right in front of it
+    // Sparse halo (build_plan): a raw forward runs layers 1 and 2 as before (RAW_FORWARD: skipped by materialise_raw, whose
+    // activations of the other heads are no longer the layers' inputs); materialise_raw re-runs only the two halo convs (RAW_RERUN)
+    enum { ANY_RAW = 0, RAW_FORWARD = 1, RAW_RERUN = 2 };
+    int raw_use = ANY_RAW;
 };
 enum { FLAVOUR_BOTH = 0, FLAVOUR_RAW = 1, FLAVOUR_AGG = 2 };
 
@@ -285,6 +289,8 @@ struct bod_context {
     // Sparse tail (build_plan): the box and covariance heads' aggregating launches run after the keep flags, over the pixels with a
     // kept anchor only; their statistics [agg[1], agg[2]] then exist for the anchors kept at (keep_seed, keep_first) alone.
     bool plan_sparse = false;
+    bool plan_halo = false;                              // ... and box layer 1 / covariance layer 2 over the tail's 3x3 halo
+    int dense_plain_tiles = 0;                           // (BOD_SPARSE_STATS)
     SparseTailArgs sparse{};
     bool agg_sparse = false;                             // the last forward's agg[1] / agg[2] are sparse
     bool keep_ready = false;                             // pb.keep / d_counts / block_counts / num_kept hold the keep stage's output
@@ -955,6 +961,7 @@ bod_status build_plan(bod_context* h) {
         return BOD_OK;
     };
     if (xreuse) BODCHK(make_xr_tiles(t2, &d2x, &dext, &m2x));
+    h->dense_plain_tiles = m2x / 256;
     // the first tower layer (one convolution per image, N-way dropout fan-out epilogue) takes the row-reuse loop too once
     // its launch is on the 256x256 tile (conv_igemm.hip: from 1 024 tiles on): activation reads x4.5 -> x1.2 of the
     // algorithmic bytes (profiles/round1_head_conv_pmc.json, launch 0).  BOD_FAN_XREUSE=0: A/B aid.
@@ -1028,10 +1035,25 @@ bod_status build_plan(bod_context* h) {
     bool sparse = agg && split_on && h->es == 2 && !h->split && !mx_plan && !c.pipeline_overlap && h->A == h->P * c.anchors_per_location &&
                   h->P <= 65536;
     if (const char* e = getenv("BOD_SPARSE_TAIL")) sparse = sparse && atoi(e) != 0;
+    // ---- Sparse halo: the tail's 3x3 windows read box layer 1's and covariance layer 2's outputs only around the tail's pixels, and
+    // nothing else reads them in an aggregating forward.  So in aggregating forwards those two convs leave the dense launches of
+    // layers 1 and 2 and run as one launch behind the keep stage, over the 3x3 dilation of the tail's pixels (sparse_tables.h
+    // ST_HALO).  Raw forwards keep today's launches of layers 1 and 2; materialise_raw re-runs the two convs densely (Op::raw_use).
+    // BOD_SPARSE_HALO=0: the tail alone.
+    bool halo = sparse && !train_mode;
+    if (const char* e = getenv("BOD_SPARSE_HALO")) halo = halo && atoi(e) != 0;
     if (sparse) {
         SparseTailArgs& sa = h->sparse;
+        const int tables = halo ? 2 : 1;
         sa.B = B; sa.N = N; sa.P = h->P; sa.apl = c.anchors_per_location; sa.Ppad = h->Ppad;
-        sa.cap_tiles = B * (h->P / sparse_tail_min_pixels(N) + 1);
+        // both tables: B * (P / st_min_pixels + 1) tiles of 256 rows (8 KiB) + XR_EXT_ROWS extended rows (2.5 KiB) each; 512 frames
+        // of 512x512 at N = 10: 279 552 tiles, 3.0 GB per table
+        sa.cap_tiles = B * (h->P / st_min_pixels(N) + 1);
+        sa.lv.n = 5;
+        {
+            const PyramidGeometry pg = pyramid_geometry(h->lh, h->lw);
+            for (int l = 0; l < 5; ++l) { sa.lv.lw[l] = pg.lw[l]; sa.lv.lh[l] = pg.lh[l]; sa.lv.p0[l] = (int32_t)pg.lvl_p0[l]; }
+        }
         RowEnt* pix = nullptr;
         BODCHK(h->dalloc(&pix, (size_t)h->P, false));
         HIPCHK(h, hipMemcpyAsync(pix, t2.data(), (size_t)h->P * sizeof(RowEnt), hipMemcpyHostToDevice, h->stream));     // image 0, sample 0
@@ -1039,13 +1061,21 @@ bod_status build_plan(bod_context* h) {
         sa.pix = pix;
         BODCHK(h->dalloc(&sa.rows, (size_t)sa.cap_tiles * 256, false));
         BODCHK(h->dalloc(&sa.ext, (size_t)sa.cap_tiles * XR_EXT_ROWS, false));
-        BODCHK(h->dalloc(&sa.tile_count, 1));
-        BODCHK(h->dalloc(&sa.chunks, (size_t)B * h->P, false));
-        BODCHK(h->dalloc(&sa.tiles, (size_t)B * h->P, false));
+        if (halo) {
+            BODCHK(h->dalloc(&sa.halo_rows, (size_t)sa.cap_tiles * 256, false));
+            BODCHK(h->dalloc(&sa.halo_ext, (size_t)sa.cap_tiles * XR_EXT_ROWS, false));
+        }
+        BODCHK(h->dalloc(&sa.tile_count, 2));
+        BODCHK(h->dalloc(&sa.runs, (size_t)tables * B * h->P, false));
+        BODCHK(h->dalloc(&sa.chunks, (size_t)tables * B * h->P, false));
+        BODCHK(h->dalloc(&sa.tiles, (size_t)tables * B * h->P, false));
     }
     h->plan_sparse = sparse;
+    h->plan_halo = halo;
     Op sparse_op; sparse_op.kind = Op::CONV; sparse_op.is_head3x3 = true; sparse_op.flavour = FLAVOUR_AGG;
     int sparse_groups = 0; PackedConv sparse_pc{};
+    Op halo_op = sparse_op;
+    int halo_groups = 0; PackedConv halo_pc{};
     h->agg_plan = agg; h->plan_fused_out = fuse_out; h->plan_xreuse = xreuse; h->plan_xreuse0 = xreuse0; h->plan_mx = mx_plan ? mxf : 0;
     // A layer's launch takes the sample-complete ("aggregated") tiling only for the heads that END there (fused 1x1 + MC aggregation): such
     // a tile holds 25 pixels x 10 samples = 250 of its 256 rows (240 at N = 30), so every other head's conv of that layer -- the
@@ -1079,6 +1109,10 @@ bod_status build_plan(bod_context* h) {
         Op op; op.kind = Op::CONV; op.is_head3x3 = true; op.flavour = both ? FLAVOUR_BOTH : flav;
         int g = 0; PackedConv pc0{};
         double fused_flops = 0;
+        const bool both_flav = op.flavour == FLAVOUR_BOTH;
+        // the halo's dense twins: the layer's full launch for raw forwards, the halo conv alone for materialise_raw
+        ConvGroup raw_cg{}; PackedConv raw_pc{}; std::string raw_wname; bool has_raw = false;
+        ConvGroup full_cg[3]{}; std::string full_wname[3]; PackedConv full_pc{}; int nfull = 0;
         for (int hd = 0; hd < nheads; ++hd) {
             if (layer >= kHeadConvs[hd]) continue;
             if (split_launch && (part == 1) != (layer == kHeadConvs[hd] - 1)) continue;
@@ -1108,6 +1142,18 @@ bod_status build_plan(bod_context* h) {
                 }
                 fused_flops += 2.0 * ((double)B * N * h->P) * 256.0 * out_ch[hd];      // the 1x1 output conv runs inside this launch
             }
+            if (halo && both_flav && ((layer == 1 && hd == 1) || (layer == 2 && hd == 2))) {
+                // -> the halo launch, planned behind the keep stage; the dense launch stays, for the raw flavour alone
+                halo_op.conv.g[halo_groups] = cg;
+                halo_op.wname[halo_groups] = op.wname[g];
+                if (halo_groups++ == 0) halo_pc = pc;
+                halo_op.flops += 2.0 * ((double)B * N * h->P) * 256.0 * 2304.0;      // (the dense launch's algorithmic count, as the tail's)
+                raw_cg = cg; raw_pc = pc; raw_wname = op.wname[g]; has_raw = true;
+                if (nfull == 0) full_pc = pc;
+                full_cg[nfull] = cg; full_wname[nfull++] = op.wname[g];
+                op.wname[g].clear();
+                continue;
+            }
             if (sparse && flav == FLAVOUR_AGG && hd != 0) {          // -> the sparse tail's launch, planned behind the keep stage
                 sparse_op.conv.g[sparse_groups] = cg;
                 sparse_op.wname[sparse_groups] = op.wname[g];
@@ -1121,42 +1167,72 @@ bod_status build_plan(bod_context* h) {
             }
             op.conv.g[g] = cg;
             if (g == 0) pc0 = pc;
+            if (nfull == 0) full_pc = pc;
+            full_cg[nfull] = cg; full_wname[nfull++] = op.wname[g];
             ++g;
         }
-        if (g == 0) continue;                                // (no head of this part at this layer)
+        if (g == 0 && !has_raw) continue;                    // (no head of this part at this layer)
         const int M = layer == 0 ? B * h->P : B * N * h->P;
-        ConvArgs a = base_args(pc0, layer == 0 ? d1 : d2, M, 256, 256);
-        for (int q = 0; q < g; ++q) a.g[q] = op.conv.g[q];
-        a.groups = g;
-        a.flags = CONV_RELU | (mc ? CONV_DROPOUT : 0);
-        a.fan_count = layer == 0 ? N : 1;
-        a.fan_stride = (int32_t)h->Ppad;
-        a.drop_threshold = thr; a.drop_scale = dscale;
-        a.mx = mx_plan ? ((layer == 0 && !mx_l0) ? 2 : (lfmt == 2 ? 3 : 1)) : 0;
-        op.hx_pyramid = mx_l0 && layer == 0;
-        {   // BOD_MX_LOADER=0|1|2: which waves of the f16mx loop issue the weight pieces (conv_igemm.hip: all / lower four / upper four)
-            // (same-box A/B at 256 frames, two rounds each: towers 198.0 / 196.2 / 199.7 ms with 0 / 1 / 2)
-            static const int mx_loader = getenv("BOD_MX_LOADER") ? atoi(getenv("BOD_MX_LOADER")) : 1;
-            // BOD_TOWER_LOADER=1: the same pairing in the bf16 tower loop (A/B switch; measured 0.8 % SLOWER there: 211.6 against 209.9 ms per 512 frames)
-            static const int tower_loader = getenv("BOD_TOWER_LOADER") ? atoi(getenv("BOD_TOWER_LOADER")) : 0;
-            a.mx_loader = mx_plan ? mx_loader : ((h->es == 2 && layer > 0) ? tower_loader : 0);
+        if (has_raw) op.flavour = FLAVOUR_AGG;               // the layer without the halo conv: aggregating forwards only
+        for (int twin = 0; twin < 3; ++twin) {
+            if (twin == 0 ? g == 0 : !has_raw) continue;
+            if (twin > 0) {
+                op = Op{}; op.kind = Op::CONV; op.is_head3x3 = true; op.flavour = FLAVOUR_RAW; fused_flops = 0;
+                if (twin == 1) {                             // today's launch of the layer, for raw forwards
+                    for (int q = 0; q < nfull; ++q) { op.conv.g[q] = full_cg[q]; op.wname[q] = full_wname[q]; }
+                    pc0 = full_pc; g = nfull; op.raw_use = Op::RAW_FORWARD;
+                } else {                                     // the halo conv densely, for materialise_raw
+                    op.conv.g[0] = raw_cg; op.wname[0] = raw_wname;
+                    pc0 = raw_pc; g = 1; op.raw_use = Op::RAW_RERUN;
+                }
+            }
+            ConvArgs a = base_args(pc0, layer == 0 ? d1 : d2, M, 256, 256);
+            for (int q = 0; q < g; ++q) a.g[q] = op.conv.g[q];
+            a.groups = g;
+            a.flags = CONV_RELU | (mc ? CONV_DROPOUT : 0);
+            a.fan_count = layer == 0 ? N : 1;
+            a.fan_stride = (int32_t)h->Ppad;
+            a.drop_threshold = thr; a.drop_scale = dscale;
+            a.mx = mx_plan ? ((layer == 0 && !mx_l0) ? 2 : (lfmt == 2 ? 3 : 1)) : 0;
+            op.hx_pyramid = mx_l0 && layer == 0;
+            {   // BOD_MX_LOADER=0|1|2: which waves of the f16mx loop issue the weight pieces (conv_igemm.hip: all / lower four / upper four)
+                // (same-box A/B at 256 frames, two rounds each: towers 198.0 / 196.2 / 199.7 ms with 0 / 1 / 2)
+                static const int mx_loader = getenv("BOD_MX_LOADER") ? atoi(getenv("BOD_MX_LOADER")) : 1;
+                // BOD_TOWER_LOADER=1: the same pairing in the bf16 tower loop (A/B switch; measured 0.8 % SLOWER there: 211.6 against 209.9 ms per 512 frames)
+                static const int tower_loader = getenv("BOD_TOWER_LOADER") ? atoi(getenv("BOD_TOWER_LOADER")) : 0;
+                a.mx_loader = mx_plan ? mx_loader : ((h->es == 2 && layer > 0) ? tower_loader : 0);
+            }
+            if (xreuse0 && layer == 0) { a.rows = d1x; a.M = m1x; a.ext = dext1; a.xreuse = 2; }
+            if (xreuse && layer > 0) {
+                a.rows = d2x; a.M = m2x; a.ext = dext;
+                if (agg && layer >= 2 && !(split_launch && part == 0)) { a.rows = d2a; a.M = m2a; a.ext = dexta; }       // sample-complete tiles (both flavours)
+                a.xreuse = 2;       // 32-bit activation offsets against the tile's first extended row: any buffer size
+            }
+            op.conv = a;
+            op.flops = 2.0 * M * 256.0 * 2304.0 * g + fused_flops;
+            op.name = "head_tower_layer_" + std::to_string(layer) + (twin == 1 ? "(raw)" : twin == 2 ? "(rerun)" : has_raw ? "(aggregating)" :
+                      both ? "" : flav == FLAVOUR_AGG ? "(aggregating)" : flav == FLAVOUR_RAW ? "(raw)" : "");
+            op.same_geom = N == 1;            // pyramid [B][Ppad] and head planes [B*N][Ppad] coincide at N = 1
+            h->ops.push_back(op);
         }
-        if (xreuse0 && layer == 0) { a.rows = d1x; a.M = m1x; a.ext = dext1; a.xreuse = 2; }
-        if (xreuse && layer > 0) {
-            a.rows = d2x; a.M = m2x; a.ext = dext;
-            if (agg && layer >= 2 && !(split_launch && part == 0)) { a.rows = d2a; a.M = m2a; a.ext = dexta; }       // sample-complete tiles (both flavours)
-            a.xreuse = 2;       // 32-bit activation offsets against the tile's first extended row: any buffer size
-        }
-        op.conv = a;
-        op.flops = 2.0 * M * 256.0 * 2304.0 * g + fused_flops;
-        op.name = "head_tower_layer_" + std::to_string(layer) + (both ? "" : flav == FLAVOUR_AGG ? "(aggregating)" : flav == FLAVOUR_RAW ? "(raw)" : "");
-        op.same_geom = N == 1;            // pyramid [B][Ppad] and head planes [B*N][Ppad] coincide at N = 1
-        h->ops.push_back(op);
     }
     if (sparse_groups > 0) {
         Op keep; keep.kind = Op::KEEP; keep.flavour = FLAVOUR_AGG; keep.name = "head_tower_layer_3(keep)";
         h->ops.push_back(keep);
         const SparseTailArgs& sa = h->sparse;
+        if (halo_groups > 0) {           // box layer 1 + covariance layer 2 over the halo table: plain epilogue, the tile count on the device
+            ConvArgs a = base_args(halo_pc, sa.halo_rows, sa.cap_tiles * 256, 256, 256);
+            for (int q = 0; q < halo_groups; ++q) a.g[q] = halo_op.conv.g[q];
+            a.groups = halo_groups;
+            a.flags = CONV_RELU | (mc ? CONV_DROPOUT : 0);
+            a.fan_count = 1; a.fan_stride = (int32_t)h->Ppad;
+            a.drop_threshold = thr; a.drop_scale = dscale;
+            a.ext = sa.halo_ext; a.xreuse = 2; a.tile_count = sa.tile_count + 1;
+            a.mx_loader = getenv("BOD_TOWER_LOADER") ? atoi(getenv("BOD_TOWER_LOADER")) : 0;
+            halo_op.conv = a;
+            halo_op.name = "head_tower_layer_2(halo)";
+            h->ops.push_back(halo_op);
+        }
         ConvArgs a = base_args(sparse_pc, sa.rows, sa.cap_tiles * 256, 256, 256);
         for (int q = 0; q < sparse_groups; ++q) a.g[q] = sparse_op.conv.g[q];
         a.groups = sparse_groups;
@@ -1268,6 +1344,50 @@ PostCfg post_cfg(bod_context* h, uint64_t seed, uint32_t first_image) {
     return p;
 }
 
+// BOD_SPARSE_STATS=1 (development aid): after each keep stage, the tile counts of the tail and halo tables against the dense plain
+// table's, and the share of each pyramid level's pixels in each table (the flags replayed on the host with the kernel's rules), on
+// stderr.  Synchronises the stream.
+bod_status sparse_stats(bod_context* h, hipStream_t st) {
+    const SparseTailArgs& sa = h->sparse;
+    int32_t cnt[2] = {0, 0};
+    std::vector<uint8_t> keep((size_t)sa.B * sa.P * sa.apl);
+    HIPCHK(h, hipMemcpyAsync(cnt, sa.tile_count, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(keep.data(), h->pb.keep, keep.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    const SparseLevels& lv = sa.lv;
+    std::vector<uint8_t> f((size_t)sa.P);
+    std::vector<double> share[3];
+    for (auto& v : share) v.assign(lv.n + 1, 0.0);
+    for (int b = 0; b < sa.B; ++b) {
+        for (int p = 0; p < sa.P; ++p) {
+            uint8_t k = 0;
+            for (int a = 0; a < sa.apl; ++a) k |= keep[((size_t)b * sa.P + p) * sa.apl + a];
+            f[p] = k ? ST_KEPT : 0;
+        }
+        for (int p = 0; p < sa.P; ++p) if (st_member(f.data(), lv, p, ST_KEPT)) f[p] |= ST_TAIL;
+        for (int p = 0; p < sa.P; ++p) if (st_dilated(f.data(), lv, p)) f[p] |= ST_DIL;
+        for (int p = 0; p < sa.P; ++p) if (st_member(f.data(), lv, p, ST_DIL)) f[p] |= ST_HALO;
+        for (int p = 0; p < sa.P; ++p) {
+            int l, y, x;
+            st_level_x(lv, p, l, y, x);
+            const uint8_t bits[3] = {ST_KEPT, ST_TAIL, ST_HALO};
+            for (int t = 0; t < 3; ++t) if (f[p] & bits[t]) { share[t][l] += 1; share[t][lv.n] += 1; }
+        }
+    }
+    fprintf(stderr, "# sparse tables: B %d N %d P %d  tail tiles %d  halo tiles %d  dense plain tiles %d  f = %.4f  tail / dense %.4f\n",
+            sa.B, sa.N, sa.P, cnt[0], cnt[1], h->dense_plain_tiles, (double)cnt[1] / h->dense_plain_tiles, (double)cnt[0] / h->dense_plain_tiles);
+    const char* what[3] = {"kept", "tail", "halo"};
+    for (int t = 0; t < 3; ++t) {
+        fprintf(stderr, "# sparse tables: %s pixel share per level", what[t]);
+        for (int l = 0; l <= lv.n; ++l) {
+            const double pix = l < lv.n ? (double)sa.B * lv.lw[l] * lv.lh[l] : (double)sa.B * sa.P;
+            fprintf(stderr, " %s%.4f", l < lv.n ? "" : "all ", share[t][l] / pix);
+        }
+        fprintf(stderr, "\n");
+    }
+    return BOD_OK;
+}
+
 // flavour: FLAVOUR_RAW = per-sample head outputs into raw[] (RetinaNetModel.call's tensors), FLAVOUR_AGG = MC statistics
 // reduced inside the last tower layers' tiles (plans with agg_plan only).  only_flavoured: run just the ops that differ
 // between the two (materialise_raw re-runs the raw flavour of the last layers on the activations still in HBM).
@@ -1371,6 +1491,7 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
         hipStream_t st = is_front ? fs : h->stream;
         ++op_i;
         if ((op.flavour != FLAVOUR_BOTH && op.flavour != flavour) || (only_flavoured && op.flavour == FLAVOUR_BOTH)) continue;
+        if (op.raw_use == (only_flavoured ? Op::RAW_FORWARD : Op::RAW_RERUN)) continue;
         if ((int)op_i - 1 < h->dev_op_lo || (int)op_i - 1 >= h->dev_op_hi) continue;          // (BOD_FORWARD_OPS: development)
         if (ov && first_back) {                          // the pyramid is complete: hand it to the back
             HIPCHK(h, hipEventRecord(h->ev_front_done[par], fs));
@@ -1420,6 +1541,8 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
                 sa.keep = h->pb.keep;
                 HIPCHK(h, launch_sparse_tail_rows(sa, st));
                 h->keep_ready = true; h->keep_seed = seed; h->keep_first = first_image;
+                static const bool stats = [] { const char* e = getenv("BOD_SPARSE_STATS"); return e && atoi(e) != 0; }();
+                if (stats) BODCHK(sparse_stats(h, st));          // (development aid: synchronises; never inside a timed region)
                 break;
             }
             case Op::POOL:
@@ -2885,6 +3008,15 @@ bod_status bod_plan_info(bod_handle h, int32_t* info8) {
     for (const Op& o : h->ops) if (o.kind == Op::CONV && !o.is_head3x3 && o.conv.xreuse) ++info8[5];
     info8[6] = h->plan_mx;
     info8[7] = h->plan_sparse;
+    return BOD_OK;
+}
+
+bod_status bod_plan_info_n(bod_handle h, int32_t* info, int32_t n) {
+    if (!h || !info || n < 0) return BOD_ERR_INVALID_ARG;
+    int32_t all[9];
+    BODCHK(bod_plan_info(h, all));
+    all[8] = h->plan_halo;
+    for (int i = 0; i < n && i < 9; ++i) info[i] = all[i];
     return BOD_OK;
 }
 

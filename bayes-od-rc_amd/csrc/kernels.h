@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "plan_tables.h"
+#include "sparse_tables.h"
 
 // ------------------------------------------------------------------------------------------------
 // Implicit-GEMM convolution (conv_igemm.hip)
@@ -209,22 +210,26 @@ hipError_t launch_posterior_keep(const PostCfg& c, const PostBuffers& b, hipStre
 hipError_t launch_posterior_fuse(const PostCfg& c, const PostBuffers& b, hipStream_t s);
 
 // Sparse tail (engine.hip): the aggregating launches of the box and covariance heads run only over the pixels with at least one kept
-// anchor.  One workgroup per image lists those pixels (a pixel between two kept, x-adjacent ones is taken along: a run of three costs
-// fewer extended rows than two runs of one) and packs them into sample-complete row-reuse tiles under the rules of
-// xr_tile_rows_aggregated (plan_tables.h).  Every RowEnt is the one of the dense per-sample table (same dropout counters, same
-// aggregation slot); `pix` is that table's image 0 / sample 0 part (P entries), the others differ by closed forms.
+// anchor, and (with `halo_rows`) the two layers that feed them -- box layer 1, covariance layer 2 -- only over the 3x3 dilation of
+// those pixels.  One workgroup per image flags the pixels of both tables, lists their runs with prefix scans, packs the runs into
+// sample-complete row-reuse tiles (one wave per table) and writes the rows (sparse_tables.h).  Every RowEnt is the one of the dense
+// per-sample table (same dropout counters, same aggregation slot); `pix` is that table's image 0 / sample 0 part (P entries), the
+// others differ by closed forms.
 struct SparseTailArgs {
     const uint8_t* keep;        // [B, A] (post_sample_kernel)
     const RowEnt* pix;          // [P]
-    RowEnt* rows;               // [cap_tiles * 256]
-    int2* ext;                  // [cap_tiles * XR_EXT_ROWS]
-    int32_t* tile_count;        // one int, zeroed by the launcher
-    int4* chunks;               // scratch [B * P]: {pixel, tile, slot, extended row} of every run piece
-    int4* tiles;                // scratch [B * P]: {first pixel, slots used, extended rows used, -}
+    RowEnt* rows;               // tail: [cap_tiles * 256]
+    int2* ext;                  // tail: [cap_tiles * XR_EXT_ROWS]
+    RowEnt* halo_rows;          // halo: [cap_tiles * 256], or nullptr (tail only)
+    int2* halo_ext;             // halo: [cap_tiles * XR_EXT_ROWS]
+    int32_t* tile_count;        // [2]: tail, halo tiles; zeroed by the launcher
+    int2* runs;                 // scratch [tables * B * P]: {first, last pixel} of every run
+    StQuad* chunks;             // scratch [tables * B * P]: pieces (sparse_tables.h StPack)
+    StQuad* tiles;              // scratch [tables * B * P]: tiles
     int32_t B, N, P, apl, cap_tiles;
     int64_t Ppad;
+    SparseLevels lv;
 };
-int sparse_tail_min_pixels(int N);                  // fewest pixels a tile closed before the image's end holds
 hipError_t launch_sparse_tail_rows(const SparseTailArgs& a, hipStream_t s);
 hipError_t launch_joint_entropy_rank(const PostCfg& c, const PostBuffers& b, hipStream_t s);
 hipError_t launch_validation_post(const PostCfg& c, const PostBuffers& b, hipStream_t s);   // validation_utils.py:10-77

@@ -558,105 +558,120 @@ hipError_t launch_posterior(const PostCfg& c, const PostBuffers& b, hipStream_t 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Sparse tail row table (kernels.h SparseTailArgs).  One workgroup per image: the pixel flags go to LDS, thread 0 walks them and cuts
-// the runs into tile pieces ("chunks"), then the workgroup writes the pieces' rows and extended rows and pads every tile as
-// xr_tile_rows_aggregated does.  Tiles of different images land in the order the images reserve them (atomicAdd): each tile holds
-// one image's pixels with all N samples, so the order changes no result.
+// Sparse tail and halo row tables (kernels.h SparseTailArgs, sparse_tables.h).  One workgroup per image:
+//   1. the pixel flags go to LDS, one phase per flag (kept, tail, 3x3 dilation, halo), all threads;
+//   2. every thread counts the run starts of both tables in its contiguous share of the pixels, a block scan places them, and the
+//      threads list the runs {first, last} in pixel order;
+//   3. one wave per table packs the runs into tiles: the packing is a serial recurrence (pieces cut by free slots and extended
+//      rows), so all 64 lanes run it in lockstep on 64 runs loaded at a time (one global load per 64 runs, not one per pixel);
+//   4. all threads write the pieces' rows and extended rows and pad the tiles.
+// Tiles of different images land in the order the images reserve them (atomicAdd): each tile holds one image's pixels with all N
+// samples, so the order changes no result.
 // ------------------------------------------------------------------------------------------------
-int sparse_tail_min_pixels(int N) {
-    // a tile closes before the image's end when its slots are full or when a piece of one pixel (3N extended rows) no longer fits;
-    // a piece of k pixels costs N * (k + 2) <= 3N * k extended rows
-    const int Qmax = 256 / N;
-    return std::max(1, std::min(Qmax, (XR_EXT_ROWS - 3 * N) / (3 * N) + 1));
-}
-
-__device__ __forceinline__ RowEnt sparse_tail_ent(const SparseTailArgs& a, int b, int n, int p) {
-    RowEnt e = a.pix[p];
-    const int32_t plane = (int32_t)(((int64_t)b * a.N + n) * a.Ppad);
-    e.in_off += plane;
-    e.out_off += plane;
-    e.rng_zs = n | (b << 16);
-    e.pad0 = (int32_t)(((int64_t)b * a.N + n) * a.P + p);
-    return e;
-}
-
 __global__ __launch_bounds__(256) void sparse_tail_rows_kernel(SparseTailArgs a) {
-    extern __shared__ uint8_t s_flag[];            // [P]: 1 kept pixel, 0 not
-    __shared__ int s_nchunk, s_ntile, s_base;
-    const int b = blockIdx.x, tid = threadIdx.x, N = a.N, P = a.P;
+    extern __shared__ uint8_t s_flag[];            // [P]: ST_* bits
+    __shared__ int s_cnt[2][256];
+    __shared__ int s_nrun[2], s_nchunk[2], s_ntile[2], s_base[2];
+    const int b = blockIdx.x, tid = threadIdx.x, N = a.N, P = a.P, B = a.B;
+    const int T = a.halo_rows ? 2 : 1;
+    const SparseLevels& lv = a.lv;
     const uint8_t* keep = a.keep + (size_t)b * P * a.apl;
     for (int p = tid; p < P; p += blockDim.x) {
         uint8_t f = 0;
         for (int k = 0; k < a.apl; ++k) f |= keep[(size_t)p * a.apl + k];
-        s_flag[p] = f ? 1 : 0;
+        s_flag[p] = f ? ST_KEPT : 0;
     }
     __syncthreads();
-    int4* chunks = a.chunks + (size_t)b * P;
-    int4* tiles = a.tiles + (size_t)b * P;
-    if (tid == 0) {
-        const int Qmax = 256 / N;
-        auto adjacent = [&](int p) { return a.pix[p].in_off == a.pix[p - 1].in_off + 1 && a.pix[p].in_pitch == a.pix[p - 1].in_pitch; };
-        int nchunk = 0, ntile = 0, Q = 0, X = 0, first = 0;
-        bool open = false;
-        auto close_tile = [&]() { tiles[ntile++] = make_int4(first, Q, X, 0); open = false; };
-        int p = 0;
-        while (p < P) {
-            if (!s_flag[p]) { ++p; continue; }
-            int L = 1;                 // run of x-adjacent pixels from p, through single unkept pixels between two kept ones
-            while (p + L < P && adjacent(p + L) &&
-                   (s_flag[p + L] || (p + L + 1 < P && s_flag[p + L + 1] && adjacent(p + L + 1)))) ++L;
-            while (L > 0) {
-                if (!open) { first = p; Q = 0; X = 0; open = true; }
-                const int take = min(min(L, Qmax - Q), (XR_EXT_ROWS - X) / N - 2);
-                if (take < 1) { close_tile(); continue; }
-                chunks[nchunk++] = make_int4(p, ntile, Q, X | (take << 16));
-                X += N * (take + 2); Q += take; p += take; L -= take;
-                if (Q == Qmax) close_tile();
+    for (int p = tid; p < P; p += blockDim.x) if (st_member(s_flag, lv, p, ST_KEPT)) s_flag[p] |= ST_TAIL;
+    if (T == 2) {
+        __syncthreads();
+        for (int p = tid; p < P; p += blockDim.x) if (st_dilated(s_flag, lv, p)) s_flag[p] |= ST_DIL;
+        __syncthreads();
+        for (int p = tid; p < P; p += blockDim.x) if (st_member(s_flag, lv, p, ST_DIL)) s_flag[p] |= ST_HALO;
+    }
+    __syncthreads();
+    // 2. runs: contiguous shares, block scan of the start counts
+    const int share = (P + 255) / 256, q0 = min(P, tid * share), q1 = min(P, q0 + share);
+    int cnt[2] = {0, 0};
+    for (int t = 0; t < T; ++t) {
+        const uint8_t bit = t == 0 ? ST_TAIL : ST_HALO;
+        for (int p = q0; p < q1; ++p) cnt[t] += st_run_edge(s_flag, lv, p, bit) & 1;
+        s_cnt[t][tid] = cnt[t];
+    }
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {             // inclusive Hillis-Steele scan
+        int v[2] = {0, 0};
+        for (int t = 0; t < T; ++t) v[t] = tid >= d ? s_cnt[t][tid - d] : 0;
+        __syncthreads();
+        for (int t = 0; t < T; ++t) s_cnt[t][tid] += v[t];
+        __syncthreads();
+    }
+    for (int t = 0; t < T; ++t) {
+        const uint8_t bit = t == 0 ? ST_TAIL : ST_HALO;
+        int2* runs = a.runs + ((size_t)t * B + b) * P;
+        int r = s_cnt[t][tid] - cnt[t];              // runs started in front of this share
+        for (int p = q0; p < q1; ++p) {
+            const int edge = st_run_edge(s_flag, lv, p, bit);
+            if (edge & 1) runs[r++].x = p;
+            if (edge & 2) runs[r - 1].y = p;         // (a run that ends here started here or in front)
+        }
+        if (tid == 255) s_nrun[t] = s_cnt[t][255];
+    }
+    __syncthreads();
+    // 3. packing: wave t packs table t
+    const int wave = tid >> 6, lane = tid & 63;
+    if (wave < T) {
+        const int t = wave;
+        const int2* runs = a.runs + ((size_t)t * B + b) * P;
+        StQuad* chunks = a.chunks + ((size_t)t * B + b) * P;
+        StQuad* tiles = a.tiles + ((size_t)t * B + b) * P;
+        const int nrun = s_nrun[t];
+        StPack st{0, 0, 0, 0, 0, 0};
+        for (int r0 = 0; r0 < nrun; r0 += 64) {
+            const int2 mine = r0 + lane < nrun ? runs[r0 + lane] : make_int2(0, 0);
+            const int n = min(64, nrun - r0);
+            for (int j = 0; j < n; ++j) {
+                const int p = __shfl(mine.x, j), q = __shfl(mine.y, j);
+                st_pack_run(st, p, q - p + 1, N, chunks, tiles, lane == 0);
             }
         }
-        if (open) close_tile();
-        s_nchunk = nchunk; s_ntile = ntile;
-        s_base = atomicAdd(a.tile_count, ntile);
-    }
-    __syncthreads();
-    const int nchunk = s_nchunk, ntile = s_ntile, base = s_base;
-    if (base + ntile > a.cap_tiles) return;         // (cannot happen: cap_tiles is sized by sparse_tail_min_pixels)
-    // the pieces: N * take rows and N * (take + 2) extended rows each
-    for (int i = tid; i < nchunk * N; i += blockDim.x) {
-        const int ci = i / N, n = i - ci * N;
-        const int4 c = chunks[ci];
-        const int p0 = c.x, t = base + c.y, Q0 = c.z, X0 = c.w & 0xFFFF, take = c.w >> 16;
-        const int x0 = X0 + n * (take + 2);
-        const RowEnt first = sparse_tail_ent(a, b, n, p0);
-        int2* ext = a.ext + (size_t)t * XR_EXT_ROWS + x0;
-        for (int k = 0; k < take + 2; ++k) ext[k] = make_int2(first.in_off + k, first.in_pitch);
-        RowEnt* rows = a.rows + (size_t)t * 256;
-        for (int k = 0; k < take; ++k) {
-            RowEnt q = sparse_tail_ent(a, b, n, p0 + k);
-            q.pad1 = x0 + k;
-            rows[(Q0 + k) * N + n] = q;
+        st_pack_close(st, tiles, lane == 0);
+        if (lane == 0) {
+            s_nchunk[t] = st.nchunk; s_ntile[t] = st.ntile;
+            s_base[t] = atomicAdd(a.tile_count + t, st.ntile);
         }
     }
-    // the padding: invalid rows behind the last slot, the tile's first extended row behind the last extended row
-    RowEnt invalid = a.pix[0];
-    invalid.out_off = -1; invalid.pad0 = 0; invalid.pad1 = 0;
-    for (int i = tid; i < ntile * 256; i += blockDim.x) {
-        const int t = i >> 8, r = i & 255;
-        if (r >= tiles[t].y * N) a.rows[(size_t)(base + t) * 256 + r] = invalid;
-    }
-    for (int i = tid; i < ntile * XR_EXT_ROWS; i += blockDim.x) {
-        const int t = i / XR_EXT_ROWS, r = i - t * XR_EXT_ROWS;
-        const int4 ti = tiles[t];
-        if (r >= ti.z) {
-            const RowEnt first = sparse_tail_ent(a, b, 0, ti.x);
-            a.ext[(size_t)(base + t) * XR_EXT_ROWS + r] = make_int2(first.in_off, first.in_pitch);
+    __syncthreads();
+    // 4. rows, extended rows, padding
+    const RowEnt invalid = st_invalid_row(a.pix[0]);
+    for (int t = 0; t < T; ++t) {
+        const int nchunk = s_nchunk[t], ntile = s_ntile[t], base = s_base[t];
+        if (base + ntile > a.cap_tiles) continue;       // (cannot happen: cap_tiles is sized by st_min_pixels)
+        RowEnt* rows = t == 0 ? a.rows : a.halo_rows;
+        ExtRow* ext = reinterpret_cast<ExtRow*>(t == 0 ? a.ext : a.halo_ext);
+        const StQuad* chunks = a.chunks + ((size_t)t * B + b) * P;
+        const StQuad* tiles = a.tiles + ((size_t)t * B + b) * P;
+        for (int i = tid; i < nchunk * N; i += blockDim.x) {
+            const int ci = i / N, n = i - ci * N;
+            const StQuad c = chunks[ci];
+            st_write_piece(c, n, b, base + c.y, a.pix, N, P, a.Ppad, rows, ext);
+        }
+        for (int i = tid; i < ntile * 256; i += blockDim.x) {
+            const int tt = i >> 8, r = i & 255;
+            if (st_pad_row(tiles[tt], r, N)) rows[(size_t)(base + tt) * 256 + r] = invalid;
+        }
+        for (int i = tid; i < ntile * XR_EXT_ROWS; i += blockDim.x) {
+            const int tt = i / XR_EXT_ROWS, r = i - tt * XR_EXT_ROWS;
+            const StQuad ti = tiles[tt];
+            if (r >= ti.z) ext[(size_t)(base + tt) * XR_EXT_ROWS + r] = st_pad_ext(ti, b, a.pix, N, P, a.Ppad);
         }
     }
 }
 
 hipError_t launch_sparse_tail_rows(const SparseTailArgs& a, hipStream_t s) {
-    if (a.B <= 0 || a.P <= 0 || a.N < 1 || 256 / a.N < 1 || XR_EXT_ROWS / a.N - 2 < 1 || a.P > 65536) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(a.tile_count, 0, sizeof(int32_t), s);
+    if (a.B <= 0 || a.P <= 0 || a.N < 1 || 256 / a.N < 1 || XR_EXT_ROWS / a.N - 2 < 1 || a.P > 65536 || a.lv.n < 1 || a.lv.n > 5)
+        return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(a.tile_count, 0, 2 * sizeof(int32_t), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(sparse_tail_rows_kernel, dim3(a.B), dim3(256), (size_t)a.P, s, a);
     return hipGetLastError();

@@ -136,3 +136,4 @@ int32_t bod_record_width(bod_handle h);
 bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, int32_t world, int32_t rank, int32_t root,
                                  float* gathered_host, float** gathered_device);
 bod_status bod_plan_info(bod_handle h, int32_t* info8);
+bod_status bod_plan_info_n(bod_handle h, int32_t* info, int32_t n);
