@@ -49,6 +49,7 @@ class BodSizes(C.Structure):
 
 _F = C.POINTER(C.c_float)
 _I = C.POINTER(C.c_int32)
+_D = C.POINTER(C.c_double)
 _H = C.c_void_p
 
 # name -> (restype, argtypes); must list every symbol include/bayesod.h declares
@@ -108,6 +109,8 @@ SIGNATURES = {
     "bod_loss_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F, _F, _F, _F, _F,
                                     C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_float,
                                     C.c_float, C.c_float, C.POINTER(C.c_double), _F, _F, _F]),
+    "bod_pdq_corner_heatmaps": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, _I, _F]),
+    "bod_pdq_frames": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, _I, _I, _I, _D, _D, _D, _D, _F]),
     "bod_bench_head_conv": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bod_profile_begin": (C.c_int, [_H]),
     "bod_profile_select": (C.c_int, [_H, C.c_int32]),
@@ -142,6 +145,10 @@ def load():
 
 def fptr(a):
     return None if a is None else a.ctypes.data_as(_F)
+
+
+def dptr(a):
+    return None if a is None else a.ctypes.data_as(_D)
 
 
 def iptr(a):

@@ -17,6 +17,7 @@ SOURCES = [
     # the Bayesian stages are compared against a NumPy oracle: no FMA contraction
     ("post_kernels.hip", ["-ffp-contract=off"]),
     ("loss_kernels.hip", ["-ffp-contract=off"]),
+    ("pdq_kernels.hip", ["-ffp-contract=off"]),
     ("train_kernels.hip", []),
     ("engine.hip", []),
 ]

@@ -2830,6 +2830,45 @@ bod_status bod_loss_backward(int32_t device, int32_t B, int32_t A, int32_t C, co
                      w_cls, w_reg, dcls, dbox, dcov);
 }
 
+// PDQ evaluation (pdq_kernels.hip): stateless, one stream for the call
+static bod_status pdq_call(int32_t device, const std::function<int(hipStream_t, char*, size_t)>& run) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "no HIP device %d: libbayesod_hip has no CPU fallback", device);
+        g_create_error = buf;
+        return BOD_ERR_NO_DEVICE;
+    }
+    hipStream_t s = nullptr;
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
+        g_create_error = "cannot set up the device for the PDQ evaluation";
+        return BOD_ERR_HIP;
+    }
+    char err[1024] = {0};
+    const int st = run(s, err, sizeof err);
+    hipStreamSynchronize(s);
+    hipStreamDestroy(s);
+    if (st != BOD_OK) g_create_error = err;
+    return (bod_status)st;
+}
+
+bod_status bod_pdq_corner_heatmaps(int32_t device, int32_t img_h, int32_t img_w, int32_t n, const double* means_yx,
+                                   const double* covs_yx, int32_t* rois, float* heatmaps) {
+    return pdq_call(device, [&](hipStream_t s, char* err, size_t cap) {
+        return pdq_corner_heatmaps_run(img_h, img_w, n, means_yx, covs_yx, rois, heatmaps, s, err, cap);
+    });
+}
+
+bod_status bod_pdq_frames(int32_t device, int32_t img_h, int32_t img_w, int32_t num_frames, const int32_t* num_gt,
+                          const int32_t* gt_boxes, const int32_t* num_det, const int32_t* det_boxes,
+                          const double* det_corner_covs, double* fg_loss, double* bg_loss, double* det_bg_loss,
+                          float* heatmaps) {
+    return pdq_call(device, [&](hipStream_t s, char* err, size_t cap) {
+        return pdq_frames_run(img_h, img_w, num_frames, num_gt, gt_boxes, num_det, det_boxes, det_corner_covs, fg_loss, bg_loss,
+                              det_bg_loss, heatmaps, s, err, cap);
+    });
+}
+
 bod_status bod_bench_head_conv(bod_handle h, int32_t layer, int32_t variant, int32_t iters, double* mean_ms, double* flops) {
     if (!h || !mean_ms || iters < 1 || layer < 0 || layer > 7) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));

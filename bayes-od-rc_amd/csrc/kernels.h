@@ -371,3 +371,13 @@ hipError_t launch_adam(float* w, const float* g, float* m, float* v, long n, con
                        float eps, hipStream_t s);
 hipError_t launch_f32_to_bf16(const float* in, void* out, long n, hipStream_t s);
 hipError_t launch_make_dgrad_rows(const RowEnt* fwd, RowEnt* out, int M, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
+// PDQ evaluation (pdq_kernels.hip): host drivers of bod_pdq_corner_heatmaps / bod_pdq_frames on the caller's stream and
+// current device.  Return a bod_status value; on failure errbuf holds the message.
+// ------------------------------------------------------------------------------------------------
+int pdq_corner_heatmaps_run(int H, int W, int n, const double* means_yx, const double* covs_yx, int32_t* rois, float* heatmaps,
+                            hipStream_t s, char* errbuf, size_t errcap);
+int pdq_frames_run(int H, int W, int F, const int32_t* num_gt, const int32_t* gt_boxes, const int32_t* num_det, const int32_t* det_boxes,
+                   const double* det_corner_covs, double* fg_loss, double* bg_loss, double* det_bg_loss, float* heatmaps, hipStream_t s,
+                   char* errbuf, size_t errcap);

@@ -498,3 +498,53 @@ def stage_conv_dgrad(dy, w, padding="same", device=0):
         raise ValueError("stage_conv_dgrad covers stride-1 SAME convolutions with odd kernels")
     wt = np.ascontiguousarray(np.transpose(w[::-1, ::-1], (0, 1, 3, 2)))
     return stage_conv(dy, wt, None, stride=1, padding="same", device=device)
+
+
+def pdq_corner_heatmaps(img_hw, means_yx, covs_yx, device=0, heatmaps=True):
+    """Gaussian corners on the device (``bod_pdq_corner_heatmaps``), for parity tests of prob_detection_quality.corner_roi /
+    corner_heatmap: means_yx [n,2], covs_yx [n,2,2] in (y, x) order; returns (rois [n,4] x0 y0 x1 y1, heatmaps [n,H,W] float32
+    or None)."""
+    lib = _lib.load()
+    h, w = int(img_hw[0]), int(img_hw[1])
+    means = np.ascontiguousarray(means_yx, dtype=np.float64).reshape(-1, 2)
+    covs = np.ascontiguousarray(covs_yx, dtype=np.float64).reshape(-1, 2, 2)
+    n = means.shape[0]
+    rois = np.zeros((n, 4), np.int32)
+    heat = np.empty((n, h, w), np.float32) if heatmaps else None
+    st = lib.bod_pdq_corner_heatmaps(device, h, w, n, _lib.dptr(means), _lib.dptr(covs), iptr(rois), fptr(heat))
+    _lib.check(lib, None, st)
+    return rois, heat
+
+
+def pdq_frames(img_hw, num_gt, gt_boxes, num_det, det_boxes, det_corner_covs, device=0, heatmaps=False):
+    """Per-frame PDQ losses on the device (``bod_pdq_frames``) for frames of one image size: gt_boxes [sum G,4] and
+    det_boxes [sum D,4] as int32 x1 y1 x2 y2, det_corner_covs [sum D,2,2,2] (PBoxDetInst.covs).  Returns per frame lists
+    (fg_loss [G,D], bg_loss [G,D], det_bg_loss [D]) as float64 arrays, and the heatmaps [sum D,H,W] (or None)."""
+    lib = _lib.load()
+    h, w = int(img_hw[0]), int(img_hw[1])
+    ng = np.ascontiguousarray(num_gt, dtype=np.int32).reshape(-1)
+    nd = np.ascontiguousarray(num_det, dtype=np.int32).reshape(-1)
+    if ng.shape != nd.shape:
+        raise ValueError("num_gt and num_det must have one entry per frame")
+    gtb = np.ascontiguousarray(gt_boxes, dtype=np.int32).reshape(-1, 4)
+    detb = np.ascontiguousarray(det_boxes, dtype=np.int32).reshape(-1, 4)
+    covs = np.ascontiguousarray(det_corner_covs, dtype=np.float64).reshape(-1, 2, 2, 2)
+    if gtb.shape[0] != int(ng.sum()) or detb.shape[0] != int(nd.sum()) or covs.shape[0] != detb.shape[0]:
+        raise ValueError("box / covariance rows do not match the per-frame counts")
+    pairs = int(np.sum(ng.astype(np.int64) * nd))
+    fg = np.zeros(pairs, np.float64)
+    bg = np.zeros(pairs, np.float64)
+    dbg = np.zeros(detb.shape[0], np.float64)
+    heat = np.empty((detb.shape[0], h, w), np.float32) if heatmaps else None
+    st = lib.bod_pdq_frames(device, h, w, ng.size, iptr(ng), iptr(gtb), iptr(nd), iptr(detb), _lib.dptr(covs), _lib.dptr(fg),
+                            _lib.dptr(bg), _lib.dptr(dbg), fptr(heat))
+    _lib.check(lib, None, st)
+    fgs, bgs, dbgs = [], [], []
+    p = d = 0
+    for g_n, d_n in zip(ng.tolist(), nd.tolist()):
+        fgs.append(fg[p:p + g_n * d_n].reshape(g_n, d_n))
+        bgs.append(bg[p:p + g_n * d_n].reshape(g_n, d_n))
+        dbgs.append(dbg[d:d + d_n])
+        p += g_n * d_n
+        d += d_n
+    return fgs, bgs, dbgs, heat

@@ -11,6 +11,8 @@ The reference scripts hard-code their paths and print a table; here the same com
 
     python -m bayes_od_rc_amd.offline_eval ap|pdq --dataset kitti --labels <label_2 dir> --predictions <..>/bayes_od_none
 
+``pdq --gpu-device N`` computes the per-pair losses on GPU N (bod_pdq_frames, pdq_kernels.hip); the rest is the same code.
+
 ``--predictions`` is the directory holding ``data/ mean/ cov/ cat_param/`` (run_inference.py:90-115); labels are
 BDD-format records ``{name, category, bbox: [x1, y1, x2, y2]}`` or, for KITTI, the label_2 text files (converted to the
 same records by ``kitti_records``).  Host NumPy like the reference.
@@ -88,7 +90,11 @@ def read_bdd_frame(frame, gt_records, categories=BDD_CATEGORIES):
     """One frame's (one-hot classes [G, C+1], boxes [G, 4] as x1 y1 x2 y2); a frame without labelled objects yields one
     background-class unit box, as the reference's reader does (demos/demo_utils/bdd_demo_utils.py:4-61, pdq_eval=True):
     it is too small to count but takes part in the assignment."""
-    rows = [g for g in gt_records if g['name'] == frame and g['category'] in categories]
+    return _bdd_frame_arrays([g for g in gt_records if g['name'] == frame], categories)
+
+
+def _bdd_frame_arrays(frame_records, categories=BDD_CATEGORIES):
+    rows = [g for g in frame_records if g['category'] in categories]
     if not rows:
         onehot = np.zeros((1, len(categories) + 1), np.float32)
         onehot[0, len(categories)] = 1
@@ -97,6 +103,14 @@ def read_bdd_frame(frame, gt_records, categories=BDD_CATEGORIES):
     for k, g in enumerate(rows):
         onehot[k, categories.index(g['category'].lower())] = 1
     return onehot, np.array([g['bbox'] for g in rows], np.float32)
+
+
+def _records_by_frame(gt_records):
+    """{name: that frame's records in file order}: one pass instead of read_bdd_frame's scan per frame."""
+    out = {}
+    for g in gt_records:
+        out.setdefault(g['name'], []).append(g)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -162,33 +176,44 @@ def kitti_records(label_dir, tree, difficulty='all', categories=('car', 'pedestr
     return gt, pred
 
 
-def kitti_pdq_report(label_dir, tree, difficulty='all', categories=('car', 'pedestrian'), img_shape=(375, 1300)):
-    """kitti/compute_pdq.py:59-135: every frame of the tree in ONE evaluation."""
+def kitti_pdq_report(label_dir, tree, difficulty='all', categories=('car', 'pedestrian'), img_shape=(375, 1300), device=None):
+    """kitti/compute_pdq.py:59-135: every frame of the tree in ONE evaluation.  ``device`` = a GPU index: the losses come
+    from bod_pdq_frames (pdq_kernels.hip), the rest of the evaluation is the same host code."""
     matches = []
+    convert = pdq.frame_instances if device is None else pdq.frame_boxes
     for frame in sorted(os.listdir(os.path.join(tree, 'mean'))):
         fid = int(frame[0:6])
         g_cls, g_box = read_kitti_labels(os.path.join(label_dir, '%06d.txt' % fid), difficulty, categories)
         name = '%06d' % fid
-        matches.append(pdq.frame_instances(g_cls, g_box, _load(tree, 'mean', name), _load(tree, 'cov', name), _load(tree, 'cat_param', name),
-                                           tuple(img_shape), score_threshold=0.5, class_columns=(0, 3), gt_boxes_vuvu=True, clip_max=1300))
-    return pdq.evaluate(matches)
+        matches.append(convert(g_cls, g_box, _load(tree, 'mean', name), _load(tree, 'cov', name), _load(tree, 'cat_param', name),
+                               tuple(img_shape), score_threshold=0.5, class_columns=(0, 3), gt_boxes_vuvu=True, clip_max=1300))
+    if device is None:
+        return pdq.evaluate(matches)
+    return pdq.evaluate_boxes(matches, tuple(img_shape), device)
 
 
-def pdq_report(gt_records, tree, frames, img_shape, categories=BDD_CATEGORIES, chunk=1000, score_threshold=0.5445):
+def pdq_report(gt_records, tree, frames, img_shape, categories=BDD_CATEGORIES, chunk=1000, score_threshold=0.5445, device=None):
     """compute_pdq.py:64-160: PDQ per chunk of 1000 frames, chunk scores averaged, counts summed.  Frames whose
-    prediction files are empty are skipped (as the reference does)."""
+    prediction files are empty are skipped (as the reference does).  ``device`` = a GPU index: each chunk's losses come
+    from bod_pdq_frames (pdq_kernels.hip), without a mask per object; the label records are grouped by frame once."""
     rows = []
+    by_frame = _records_by_frame(gt_records) if device is not None else None
     for lo in range(0, len(frames), chunk):
         matches = []
         for frame in frames[lo:lo + chunk]:
             covs = _load(tree, 'cov', frame)
             if not covs.size:
                 continue
-            onehot, boxes = read_bdd_frame(frame, gt_records, categories)
-            matches.append(pdq.frame_instances(onehot, boxes, _load(tree, 'mean', frame), covs, _load(tree, 'cat_param', frame),
+            if device is None:
+                onehot, boxes = read_bdd_frame(frame, gt_records, categories)
+                matches.append(pdq.frame_instances(onehot, boxes, _load(tree, 'mean', frame), covs, _load(tree, 'cat_param', frame),
+                                                   tuple(img_shape), score_threshold=score_threshold))
+            else:
+                onehot, boxes = _bdd_frame_arrays(by_frame.get(frame, []), categories)
+                matches.append(pdq.frame_boxes(onehot, boxes, _load(tree, 'mean', frame), covs, _load(tree, 'cat_param', frame),
                                                tuple(img_shape), score_threshold=score_threshold))
         if matches:
-            rows.append(pdq.evaluate(matches))
+            rows.append(pdq.evaluate(matches) if device is None else pdq.evaluate_boxes(matches, tuple(img_shape), device))
     if not rows:
         return {'score': 0.0, 'TP': 0, 'FP': 0, 'FN': 0, 'avg_spatial_quality': 0.0, 'avg_label_quality': 0.0, 'avg_overall_quality': 0.0}
     out = {k: float(np.mean([r[k] for r in rows])) for k in ('score', 'avg_spatial_quality', 'avg_label_quality', 'avg_overall_quality')}
@@ -206,12 +231,13 @@ def main(argv=None):
     ap.add_argument('--entropy', default='gaussian', choices=('gaussian', 'categorical'))
     ap.add_argument('--compute-method', default='Categorical', choices=('Categorical', 'All'))
     ap.add_argument('--image-size', type=int, nargs=2, default=(720, 1280), metavar=('H', 'W'))
+    ap.add_argument('--gpu-device', type=int, default=None, metavar='N', help='pdq: compute the losses on GPU N (pdq_kernels.hip)')
     args = ap.parse_args(argv)
     if args.dataset == 'kitti':
         if args.metric == 'ap':
             out = ap_report(*kitti_records(args.labels, args.predictions, args.difficulty))
         elif args.metric == 'pdq':
-            out = kitti_pdq_report(args.labels, args.predictions, args.difficulty)
+            out = kitti_pdq_report(args.labels, args.predictions, args.difficulty, device=args.gpu_device)
         else:
             raise SystemExit('mue --dataset kitti: convert the labels to records with kitti_records() and call uncertainty_error_report()')
         print(json.dumps(out, indent=1))
@@ -226,7 +252,7 @@ def main(argv=None):
         if args.metric == 'mue':
             out = uncertainty_error_report(gt, args.predictions, frames, entropy_method=args.entropy, compute_method=args.compute_method)
         else:
-            out = pdq_report(gt, args.predictions, frames, args.image_size)
+            out = pdq_report(gt, args.predictions, frames, args.image_size, device=args.gpu_device)
     print(json.dumps(out, indent=1))
     return out
 

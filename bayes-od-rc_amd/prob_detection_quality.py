@@ -187,40 +187,62 @@ def gt_counts_for_pdq(gt):
     return (b[2] - b[0] > 10) and (b[3] - b[1] > 10) and np.count_nonzero(gt.segmentation_mask) > 100
 
 
-def pair_qualities(gt_instances, det_instances):
-    """(overall, spatial, label) quality matrices [G, D] of one image plus the stacked heatmaps [H, W, D] and class
-    probabilities [D, C] (pdq.py:157-308)."""
+def pair_losses(gt_instances, det_instances):
+    """The log-losses of one image on the CPU (pdq.py:157-308): fg_loss / bg_loss [G, D] (float32 tensordots of the masks with
+    the per-pixel log terms), det_bg_loss [D] (float32 sum of the background term over each detection's whole map, the
+    false-positive credit's numerator) and the stacked heatmaps [H, W, D]."""
     shape = gt_instances[0].segmentation_mask.shape
     fg = np.stack([g.segmentation_mask for g in gt_instances], axis=2)                   # [H, W, G]
     bg = np.ones(shape + (len(gt_instances),), dtype=bool)
     for k, g in enumerate(gt_instances):
         b = g.bounding_box
         bg[b[1]:b[3] + 1, b[0]:b[2] + 1, k] = False
-    n_fg = np.array([[g.num_pixels] for g in gt_instances], dtype=np.int64)              # [G, 1]
-    labels = np.array([g.class_label for g in gt_instances], dtype=np.int64)
-    probs = np.stack([d.class_list for d in det_instances], axis=0)                      # [D, C]
     heat = np.stack([d.calc_heatmap(shape) for d in det_instances], axis=2)              # [H, W, D]
     fg_loss = np.tensordot(fg, _log(heat), axes=([0, 1], [0, 1]))                        # [G, D]
     bg_loss = np.tensordot(bg, _log(1 - heat) * (heat > 0), axes=([0, 1], [0, 1]))
+    maps = np.array([heat[:, :, c] for c in range(heat.shape[2])])
+    det_bg_loss = np.sum(_log(1 - maps) * (maps > 0), axis=(1, 2))
+    return fg_loss, bg_loss, det_bg_loss, heat
+
+
+def qualities_from_losses(labels, n_fg, probs, fg_loss, bg_loss):
+    """(overall, spatial, label) quality matrices [G, D] from the losses: labels [G] (int64), n_fg [G, 1] object pixel
+    counts (int64), probs [D, C] class probabilities."""
     spatial = np.exp((fg_loss + bg_loss) / n_fg)
     spatial[np.isclose(spatial, 0)] = 0
     spatial[np.isclose(spatial, 1)] = 1
     label = probs[:, labels].T.astype(np.float32)
     with np.errstate(divide='ignore'):
         overall = np.exp(0.5 * (np.log(label) + np.log(spatial)))                        # geometric mean (0 if either is 0)
+    return overall, spatial, label
+
+
+def _gt_arrays(gt_instances):
+    labels = np.array([g.class_label for g in gt_instances], dtype=np.int64)
+    n_fg = np.array([[g.num_pixels] for g in gt_instances], dtype=np.int64)              # [G, 1]
+    return labels, n_fg
+
+
+def pair_qualities(gt_instances, det_instances):
+    """(overall, spatial, label) quality matrices [G, D] of one image plus the stacked heatmaps [H, W, D] and class
+    probabilities [D, C] (pdq.py:157-308)."""
+    fg_loss, bg_loss, _, heat = pair_losses(gt_instances, det_instances)
+    labels, n_fg = _gt_arrays(gt_instances)
+    probs = np.stack([d.class_list for d in det_instances], axis=0)                      # [D, C]
+    overall, spatial, label = qualities_from_losses(labels, n_fg, probs, fg_loss, bg_loss)
     return overall, spatial, label, heat, probs
 
 
-def image_quality(gt_instances, det_instances):
-    """Sums for one image: {'overall', 'spatial', 'label', 'TP', 'FP', 'FN'} (pdq.py:311-452).  Optimal one-to-one
-    assignment on 1 - overall quality; assigned pairs of positive quality are true positives (unless the object is
-    too small: then the pair is dropped), the rest are false negatives / false positives.  This code base's variant
-    also credits every false positive with gmean(exp(mean log(1 - p) over its own box), 1 - max class probability)."""
-    n_gt, n_det = len(gt_instances), len(det_instances)
-    if n_gt == 0 or n_det == 0:
-        return {'overall': 0.0, 'spatial': 0.0, 'label': 0.0, 'TP': 0, 'FP': n_det,
-                'FN': int(sum(1 for g in gt_instances if gt_counts_for_pdq(g)))}
-    overall, spatial, label, heat, probs = pair_qualities(gt_instances, det_instances)
+def _empty_image(counted, n_det):
+    return {'overall': 0.0, 'spatial': 0.0, 'label': 0.0, 'TP': 0, 'FP': n_det, 'FN': int(sum(1 for c in counted if c))}
+
+
+def image_quality_from_losses(labels, n_fg, counted, det_instances, fg_loss, bg_loss, det_bg_loss):
+    """``image_quality``'s sums from the losses of one image (both paths): labels [G] / n_fg [G, 1] as ``_gt_arrays``,
+    counted [G] = ``gt_counts_for_pdq`` of each object, fg_loss / bg_loss [G, D], det_bg_loss [D]."""
+    n_gt, n_det = len(counted), len(det_instances)
+    probs = np.stack([d.class_list for d in det_instances], axis=0)                      # [D, C]
+    overall, spatial, label = qualities_from_losses(labels, n_fg, probs, fg_loss, bg_loss)
     n = max(n_gt, n_det)
     q = {k: np.zeros((n, n), dtype=np.float32) for k in ('overall', 'spatial', 'label')}
     q['overall'][:n_gt, :n_det] = overall
@@ -233,14 +255,14 @@ def image_quality(gt_instances, det_instances):
     tp = fp = fn = 0
     fp_cols = []
     for r, c in zip(rows, cols):
-        counted = r < n_gt and gt_counts_for_pdq(gt_instances[r])
+        is_counted = r < n_gt and counted[r]
         if q['overall'][r, c] > 0:
-            if counted:
+            if is_counted:
                 tp += 1
             else:
                 q['overall'][r, c] = 0.0
         else:
-            if counted:
+            if is_counted:
                 fn += 1
             if c < n_det:
                 fp += 1
@@ -253,10 +275,9 @@ def image_quality(gt_instances, det_instances):
     fp_label = np.array([1.0 - np.max(probs[c]) for c in fp_cols])
     fp_spatial_sum = fp_overall_sum = 0.0
     if fp_label.size:
-        maps = np.array([heat[:, :, c] for c in fp_cols])
         area = np.array([(det_instances[c].box[3] - det_instances[c].box[1]) * (det_instances[c].box[2] - det_instances[c].box[0])
                          for c in fp_cols])
-        fp_spatial = np.exp(np.sum(_log(1 - maps) * (maps > 0), axis=(1, 2)) / area)
+        fp_spatial = np.exp(det_bg_loss[fp_cols] / area)
         fp_spatial_sum = np.sum(fp_spatial)
         with np.errstate(divide='ignore'):
             fp_overall_sum = np.sum(np.exp(0.5 * (np.log(fp_spatial) + np.log(fp_label))))
@@ -264,19 +285,91 @@ def image_quality(gt_instances, det_instances):
             'label': tp_label + np.sum(fp_label), 'TP': tp, 'FP': fp, 'FN': fn}
 
 
+def image_quality(gt_instances, det_instances):
+    """Sums for one image: {'overall', 'spatial', 'label', 'TP', 'FP', 'FN'} (pdq.py:311-452).  Optimal one-to-one
+    assignment on 1 - overall quality; assigned pairs of positive quality are true positives (unless the object is
+    too small: then the pair is dropped), the rest are false negatives / false positives.  This code base's variant
+    also credits every false positive with gmean(exp(mean log(1 - p) over its own box), 1 - max class probability)."""
+    counted = [gt_counts_for_pdq(g) for g in gt_instances]
+    if len(gt_instances) == 0 or len(det_instances) == 0:
+        return _empty_image(counted, len(det_instances))
+    fg_loss, bg_loss, det_bg_loss, _ = pair_losses(gt_instances, det_instances)
+    labels, n_fg = _gt_arrays(gt_instances)
+    return image_quality_from_losses(labels, n_fg, counted, det_instances, fg_loss, bg_loss, det_bg_loss)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Device path: the same sums, with every frame's losses from bod_pdq_frames (pdq_kernels.hip) in batched calls.
+# Ground truths are box masks and detections PBoxDetInst; everything after the losses is the code above.
+# ---------------------------------------------------------------------------------------------------------------
+def _box_pixels(box, img_shape):
+    """Pixels of mask[y1:y2, x1:x2] (NumPy slice semantics)."""
+    h, w = img_shape
+    return len(range(h)[box[1]:box[3]]) * len(range(w)[box[0]:box[2]])
+
+
+def box_frame_from_instances(gt_instances, det_instances, img_shape):
+    """(gt_boxes, gt_labels, gt_pixels, gt_counted, det_instances) of instances the device path can evaluate; ValueError
+    for a ground-truth mask that is not mask[y1:y2, x1:x2] of its bounding_box or a detection that is not PBoxDetInst."""
+    boxes = []
+    for g in gt_instances:
+        b = [int(v) for v in g.bounding_box]
+        m = np.asarray(g.segmentation_mask)
+        if m.shape != tuple(img_shape) or np.count_nonzero(m) != _box_pixels(b, img_shape) or not m[b[1]:b[3], b[0]:b[2]].all():
+            raise ValueError("PDQ on the device needs box-shaped ground-truth masks (mask[y1:y2, x1:x2] of bounding_box)")
+        boxes.append(b)
+    for d in det_instances:
+        if not isinstance(d, PBoxDetInst):
+            raise ValueError("PDQ on the device evaluates PBoxDetInst detections only (got %s)" % type(d).__name__)
+    return (np.array(boxes, dtype=np.int32).reshape(-1, 4), [g.class_label for g in gt_instances],
+            [g.num_pixels for g in gt_instances], [gt_counts_for_pdq(g) for g in gt_instances], list(det_instances))
+
+
+def _det_arrays(det_instances):
+    boxes = np.array([np.asarray(d.box) for d in det_instances]).reshape(-1, 4)
+    if boxes.size and not np.array_equal(boxes, boxes.astype(np.int32)):
+        raise ValueError("PDQ on the device needs integer detection boxes (PBoxDetInst.box)")
+    covs = np.array([np.asarray(d.covs, dtype=np.float64) for d in det_instances], dtype=np.float64).reshape(-1, 2, 2, 2)
+    return boxes.astype(np.int32), covs
+
+
+def box_frame_qualities(frames, img_shape, device):
+    """``image_quality`` of every frame of ``frames`` (records of ``frame_boxes`` / ``box_frame_from_instances``), the
+    losses computed by ONE bod_pdq_frames call (which batches internally)."""
+    from .engine import pdq_frames
+    work = [k for k, f in enumerate(frames) if len(f[1]) and len(f[4])]
+    losses = {}
+    if work:
+        dets = [_det_arrays(frames[k][4]) for k in work]
+        fg, bg, dbg, _ = pdq_frames(img_shape, [len(frames[k][1]) for k in work], np.concatenate([frames[k][0] for k in work]),
+                                    [len(frames[k][4]) for k in work], np.concatenate([d[0] for d in dets]),
+                                    np.concatenate([d[1] for d in dets]), device=device)
+        losses = dict(zip(work, zip(fg, bg, dbg)))
+    out = []
+    for k, (boxes, labels, pixels, counted, det_instances) in enumerate(frames):
+        if k not in losses:
+            out.append(_empty_image(counted, len(det_instances)))
+            continue
+        fg_loss, bg_loss, det_bg_loss = losses[k]
+        out.append(image_quality_from_losses(np.array(labels, dtype=np.int64), np.array([[p] for p in pixels], dtype=np.int64),
+                                             counted, det_instances, fg_loss, bg_loss, det_bg_loss))
+    return out
+
+
 class PDQ(object):
     """Accumulator with the reference's method names (pdq.py:11-142).  ``score`` evaluates the images one after the
-    other (the reference fans them out over a multiprocessing pool; the sums are the same)."""
+    other (the reference fans them out over a multiprocessing pool; the sums are the same).  ``device`` = a GPU index:
+    every image's losses come from bod_pdq_frames (box-mask ground truths and PBoxDetInst detections only)."""
 
-    def __init__(self):
+    def __init__(self, device=None):
+        self.device = device
         self.reset()
 
     def reset(self):
         self._tot_overall_quality = self._tot_spatial_quality = self._tot_label_quality = 0.0
         self._tot_TP = self._tot_FP = self._tot_FN = 0
 
-    def add_img_eval(self, gt_instances, det_instances):
-        r = image_quality(gt_instances, det_instances)
+    def _add(self, r):
         self._tot_overall_quality += r['overall']
         self._tot_spatial_quality += r['spatial']
         self._tot_label_quality += r['label']
@@ -284,10 +377,42 @@ class PDQ(object):
         self._tot_FP += r['FP']
         self._tot_FN += r['FN']
 
+    def add_img_eval(self, gt_instances, det_instances):
+        if self.device is None:
+            self._add(image_quality(gt_instances, det_instances))
+        else:
+            self.score_frames([(gt_instances, det_instances)], reset=False)
+
+    def score_frames(self, matches, reset=True):
+        """Device path: all images of ``matches`` in one batched evaluation."""
+        if reset:
+            self.reset()
+        matches = list(matches)
+        if not matches:
+            return
+        shape = None
+        for gts, _ in matches:
+            if gts:
+                shape = np.asarray(gts[0].segmentation_mask).shape
+                break
+        frames = [box_frame_from_instances(gts, dets, shape) for gts, dets in matches]
+        self.score_boxes(frames, shape, reset=False)
+
+    def score_boxes(self, frames, img_shape, reset=True):
+        """Device path on ``frame_boxes`` records (no masks); returns the PDQ score."""
+        if reset:
+            self.reset()
+        for r in box_frame_qualities(frames, img_shape, self.device):
+            self._add(r)
+        return self.get_pdq_score()
+
     def score(self, matches):
         self.reset()
-        for gt_instances, det_instances in matches:
-            self.add_img_eval(gt_instances, det_instances)
+        if self.device is not None:
+            self.score_frames(matches)
+        else:
+            for gt_instances, det_instances in matches:
+                self.add_img_eval(gt_instances, det_instances)
         return self.get_pdq_score()
 
     def get_pdq_score(self):
@@ -314,26 +439,19 @@ class PDQ(object):
 _VUHW_TO_CORNERS = np.array([[0, 1, 0, -0.5], [1, 0, -0.5, 0], [0, 1, 0, 0.5], [1, 0, 0.5, 0]], dtype=np.float64)
 
 
-def frame_instances(gt_classes_onehot, gt_boxes_xyxy, pred_means_vuhw, pred_covs, pred_cat_params, img_shape,
-                    score_threshold=0.5445, cov_scale=70.0, class_columns=None, gt_boxes_vuvu=False, clip_max=None):
-    """One frame of the compute_pdq drivers: ground-truth boxes become box-shaped masks, predictions above
-    ``score_threshold`` become PBoxDetInst with the corner covariances T cov T^T * 70 (the x70 of the drivers comes on
-    top of the one bayes_od_clustering applied).  Defaults = the BDD driver (offline_eval/bdd/compute_pdq.py:83-140);
-    the KITTI driver (kitti/compute_pdq.py:66-118) is ``img_shape=(375, 1300), score_threshold=0.5,
-    class_columns=(0, 3)`` (car and person out of the BDD-trained class vector), ``gt_boxes_vuvu=True`` (its label
-    reader returns v1 u1 v2 u2) and ``clip_max=1300``.  Returns (gt_instances, det_instances)."""
+def _frame_gt(onehot, box, gt_boxes_vuvu, clip_max):
+    """(int32 box index, class label) of one ground-truth row of the drivers."""
+    idx = np.asarray(box).astype(np.int32)
+    if gt_boxes_vuvu:
+        idx = np.array([idx[1], idx[0], idx[3], idx[2]])
+    if clip_max is not None:
+        idx = np.clip(idx, 0.0, clip_max).astype(np.int32)
+    label = int(np.argmax(onehot)) if gt_boxes_vuvu else int(np.where(np.asarray(onehot) == 1)[0].item(0))
+    return idx, label
+
+
+def _frame_detections(pred_means_vuhw, pred_covs, pred_cat_params, score_threshold, cov_scale, class_columns):
     from .box_utils import vuhw_to_vuvu_np
-    gts = []
-    for onehot, box in zip(gt_classes_onehot, gt_boxes_xyxy):
-        idx = np.asarray(box).astype(np.int32)
-        if gt_boxes_vuvu:
-            idx = np.array([idx[1], idx[0], idx[3], idx[2]])
-        if clip_max is not None:
-            idx = np.clip(idx, 0.0, clip_max).astype(np.int32)
-        mask = np.zeros(img_shape, dtype=bool)
-        mask[idx[1]:idx[3], idx[0]:idx[2]] = True
-        label = int(np.argmax(onehot)) if gt_boxes_vuvu else int(np.where(np.asarray(onehot) == 1)[0].item(0))
-        gts.append(GroundTruthInstance(mask, label, 0, 0, bounding_box=idx))
     dets = []
     if np.asarray(pred_covs).size:
         covs = np.matmul(np.matmul(_VUHW_TO_CORNERS, np.asarray(pred_covs, np.float64) * cov_scale), _VUHW_TO_CORNERS.T)
@@ -343,13 +461,57 @@ def frame_instances(gt_classes_onehot, gt_boxes_xyxy, pred_means_vuhw, pred_covs
         for cat, b, cv in zip(pred_cat_params, boxes, covs):
             if np.max(cat) >= score_threshold:
                 dets.append(PBoxDetInst(cat, np.array([b[1], b[0], b[3], b[2]]).astype(np.int32), [cv[0:2, 0:2], cv[2:4, 2:4]]))
-    return gts, dets
+    return dets
 
 
-def evaluate(matches):
-    """PDQ of a list of (gt_instances, det_instances): the row the drivers print (score in percent)."""
-    ev = PDQ()
+def frame_instances(gt_classes_onehot, gt_boxes_xyxy, pred_means_vuhw, pred_covs, pred_cat_params, img_shape,
+                    score_threshold=0.5445, cov_scale=70.0, class_columns=None, gt_boxes_vuvu=False, clip_max=None):
+    """One frame of the compute_pdq drivers: ground-truth boxes become box-shaped masks, predictions above
+    ``score_threshold`` become PBoxDetInst with the corner covariances T cov T^T * 70 (the x70 of the drivers comes on
+    top of the one bayes_od_clustering applied).  Defaults = the BDD driver (offline_eval/bdd/compute_pdq.py:83-140);
+    the KITTI driver (kitti/compute_pdq.py:66-118) is ``img_shape=(375, 1300), score_threshold=0.5,
+    class_columns=(0, 3)`` (car and person out of the BDD-trained class vector), ``gt_boxes_vuvu=True`` (its label
+    reader returns v1 u1 v2 u2) and ``clip_max=1300``.  Returns (gt_instances, det_instances)."""
+    gts = []
+    for onehot, box in zip(gt_classes_onehot, gt_boxes_xyxy):
+        idx, label = _frame_gt(onehot, box, gt_boxes_vuvu, clip_max)
+        mask = np.zeros(img_shape, dtype=bool)
+        mask[idx[1]:idx[3], idx[0]:idx[2]] = True
+        gts.append(GroundTruthInstance(mask, label, 0, 0, bounding_box=idx))
+    return gts, _frame_detections(pred_means_vuhw, pred_covs, pred_cat_params, score_threshold, cov_scale, class_columns)
+
+
+def frame_boxes(gt_classes_onehot, gt_boxes_xyxy, pred_means_vuhw, pred_covs, pred_cat_params, img_shape,
+                score_threshold=0.5445, cov_scale=70.0, class_columns=None, gt_boxes_vuvu=False, clip_max=None):
+    """``frame_instances`` without a mask per object (same arguments and conversions), for the device path: returns the
+    record (gt_boxes int32 [G, 4] = the instances' bounding_box, gt_labels [G], gt_pixels [G] = their num_pixels,
+    gt_counted [G] = gt_counts_for_pdq, det_instances)."""
+    boxes, labels, pixels, counted = [], [], [], []
+    for onehot, box in zip(gt_classes_onehot, gt_boxes_xyxy):
+        idx, label = _frame_gt(onehot, box, gt_boxes_vuvu, clip_max)
+        n = _box_pixels(idx, img_shape)
+        boxes.append(idx)
+        labels.append(label)
+        pixels.append(n)
+        counted.append((idx[2] - idx[0] > 10) and (idx[3] - idx[1] > 10) and n > 100)
+    dets = _frame_detections(pred_means_vuhw, pred_covs, pred_cat_params, score_threshold, cov_scale, class_columns)
+    return np.array(boxes, dtype=np.int32).reshape(-1, 4), labels, pixels, counted, dets
+
+
+def evaluate(matches, device=None):
+    """PDQ of a list of (gt_instances, det_instances): the row the drivers print (score in percent).  ``device`` = a GPU
+    index: the losses of every image come from bod_pdq_frames in batched calls."""
+    ev = PDQ(device=device)
     score = ev.score(matches) * 100
+    tp, fp, fn = ev.get_assignment_counts()
+    return {'score': float(score), 'TP': int(tp), 'FP': int(fp), 'FN': int(fn), 'avg_spatial_quality': float(ev.get_avg_spatial_score()),
+            'avg_label_quality': float(ev.get_avg_label_score()), 'avg_overall_quality': float(ev.get_avg_overall_quality_score())}
+
+
+def evaluate_boxes(frames, img_shape, device):
+    """``evaluate`` on the device from ``frame_boxes`` records."""
+    ev = PDQ(device=device)
+    score = ev.score_boxes(frames, img_shape) * 100
     tp, fp, fn = ev.get_assignment_counts()
     return {'score': float(score), 'TP': int(tp), 'FP': int(fp), 'FN': int(fn), 'avg_spatial_quality': float(ev.get_avg_spatial_score()),
             'avg_label_quality': float(ev.get_avg_label_score()), 'avg_overall_quality': float(ev.get_avg_overall_quality_score())}

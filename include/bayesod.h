@@ -343,6 +343,25 @@ bod_status bod_loss_backward(int32_t device, int32_t B, int32_t A, int32_t C, co
                              const uint8_t* negative_mask, int32_t do_cls, int32_t reg_kind, float label_smoothing,
                              float w_cls, float w_reg, double* out4, float* dcls, float* dbox, float* dcov);
 
+/* PDQ (Probability-based Detection Quality, prob_detection_quality.py) on the device; stateless, like bod_loss_forward.
+ * Results match the CPU path's rules: corner regions, fp64 bivariate-normal CDFs stored as float32 heatmaps, NumPy slice
+ * semantics for the boxes, per-pixel loss arguments formed in float32 and summed in fp64 (bitwise repeatable, independent
+ * of how frames are split over calls).  Non-finite inputs, a non-positive variance, |correlation| > 1 or a corner whose
+ * mean lies outside its region (where the CPU path raises) fail with BOD_ERR_INVALID_ARG.  Errors via bod_last_error(NULL).
+ *
+ * One Gaussian corner per row (stage entry for parity tests): means_yx [n,2], covs_yx [n,2,2];
+ * rois [n,4] = x0 y0 x1 y1 (may be NULL), heatmaps [n,H,W] float32 (may be NULL). */
+bod_status bod_pdq_corner_heatmaps(int32_t device, int32_t img_h, int32_t img_w, int32_t n, const double* means_yx,
+                                   const double* covs_yx, int32_t* rois, float* heatmaps);
+/* Frames of one image size: num_gt[F], gt_boxes [sum G,4] x1 y1 x2 y2; num_det[F], det_boxes [sum D,4] (PBoxDetInst.box),
+ * det_corner_covs [sum D,2,2,2] (PBoxDetInst.covs: top-left then bottom-right, (x, y) order);
+ * out: fg_loss / bg_loss [sum G_f*D_f] (per frame a row-major [G_f][D_f] block), det_bg_loss [sum D],
+ * heatmaps [sum D,H,W] (may be NULL).  Image width at most 4000. */
+bod_status bod_pdq_frames(int32_t device, int32_t img_h, int32_t img_w, int32_t num_frames, const int32_t* num_gt,
+                          const int32_t* gt_boxes, const int32_t* num_det, const int32_t* det_boxes,
+                          const double* det_corner_covs, double* fg_loss, double* bg_loss, double* det_bg_loss,
+                          float* heatmaps);
+
 /* Kernel micro-benchmark (tests/tools): re-launches the `layer`-th head-tower launch of a bod_infer step
  * (0 = de-duplicated fan-out layer, 1 = tower layer 1; on plans with the fused MC aggregation 2 = layer 2 of the
  * heads that continue, 3 = layer 2 of the head that ends there (aggregating), 4 = layer 3; otherwise 2, 3 = layers

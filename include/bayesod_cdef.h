@@ -126,6 +126,12 @@ bod_status bod_loss_backward(int32_t device, int32_t B, int32_t A, int32_t C, co
                              const float* covar_params, const float* anchors, const uint8_t* positive_mask,
                              const uint8_t* negative_mask, int32_t do_cls, int32_t reg_kind, float label_smoothing,
                              float w_cls, float w_reg, double* out4, float* dcls, float* dbox, float* dcov);
+bod_status bod_pdq_corner_heatmaps(int32_t device, int32_t img_h, int32_t img_w, int32_t n, const double* means_yx,
+                                   const double* covs_yx, int32_t* rois, float* heatmaps);
+bod_status bod_pdq_frames(int32_t device, int32_t img_h, int32_t img_w, int32_t num_frames, const int32_t* num_gt,
+                          const int32_t* gt_boxes, const int32_t* num_det, const int32_t* det_boxes,
+                          const double* det_corner_covs, double* fg_loss, double* bg_loss, double* det_bg_loss,
+                          float* heatmaps);
 bod_status bod_bench_head_conv(bod_handle h, int32_t layer, int32_t variant, int32_t iters,
                                double* mean_ms, double* flops_per_launch);
 bod_status bod_profile_begin(bod_handle h);
