@@ -101,6 +101,9 @@ SIGNATURES = {
                                    C.POINTER(C.c_double)]),
     "bod_train_step": (C.c_int, [_H, C.c_void_p, C.c_int32, _F, _F, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_uint64, C.c_uint32,
                                  C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_double)]),
+    "bod_train_step_boxes": (C.c_int, [_H, C.c_void_p, C.c_int32, _I, _F, _F, C.c_float, C.c_float, C.c_uint64, C.c_uint32,
+                                       C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_double)]),
+    "bod_train_get_targets": (C.c_int, [_H, _F, _F, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "bod_train_gradients": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "bod_train_apply": (C.c_int, [_H, C.c_float, C.POINTER(C.c_double)]),
     "bod_train_get": (C.c_int, [_H, C.c_char_p, C.c_int32, C.c_int32, _F, C.c_int64]),
@@ -109,6 +112,8 @@ SIGNATURES = {
     "bod_loss_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F, _F, _F, _F, _F,
                                     C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_float,
                                     C.c_float, C.c_float, C.POINTER(C.c_double), _F, _F, _F]),
+    "bod_anchor_targets": (C.c_int, [C.c_int32, C.c_int32, _F, C.c_int32, _I, _F, _F, C.c_int32, C.c_float, C.c_float, _F, _F,
+                                     C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _I, _F]),
     "bod_pdq_corner_heatmaps": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, _I, _F]),
     "bod_pdq_frames": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, _I, _I, _I, _D, _D, _D, _D, _F]),
     "bod_bench_head_conv": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

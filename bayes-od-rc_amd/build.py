@@ -18,6 +18,7 @@ SOURCES = [
     ("post_kernels.hip", ["-ffp-contract=off"]),
     ("loss_kernels.hip", ["-ffp-contract=off"]),
     ("pdq_kernels.hip", ["-ffp-contract=off"]),
+    ("target_kernels.hip", ["-ffp-contract=off"]),
     ("train_kernels.hip", []),
     ("engine.hip", []),
 ]

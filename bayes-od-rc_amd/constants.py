@@ -22,6 +22,10 @@ ANCHORS_BOX_TARGETS_KEY = 'anchors_box_targets'
 ANCHORS_CLASS_TARGETS_KEY = 'anchors_class_targets'
 POSITIVE_ANCHORS_MASK_KEY = 'positive_anchors_mask'
 NEGATIVE_ANCHOR_MASK_KEY = 'negative_anchors_mask'
+# not reference keys: the frame's ground truth itself ([G,4] corners, [G,C] class rows), from which the training step assigns
+# the dense targets on the device
+BOXES_2D_GT_KEY = 'boxes_2d_gt'
+BOXES_CLASS_GT_KEY = 'boxes_class_gt'
 
 ANCHORS_BOX_PREDICTIONS_KEY = 'anchors_box_predictions'
 ANCHORS_COVAR_PREDICTIONS_KEY = 'anchors_box_covar_predictions'

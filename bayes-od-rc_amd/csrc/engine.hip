@@ -2830,6 +2830,78 @@ bod_status bod_loss_backward(int32_t device, int32_t B, int32_t A, int32_t C, co
                      w_cls, w_reg, dcls, dbox, dcov);
 }
 
+// Packs a minibatch's ground truth for launch_anchor_targets: [B+1] row offsets, then the [sum G,4] corners, then the [sum G,C]
+// class rows, each part starting on a 16-byte boundary (the kernel reads rows as float4)
+struct PackedGt { std::vector<char> bytes; size_t box_off = 0, cls_off = 0; long long sum_g = 0; };
+static void pack_gt(int32_t B, const int32_t* num_gt, const float* gt_boxes, const float* gt_classes, int32_t C, PackedGt* p) {
+    p->sum_g = 0;
+    for (int b = 0; b < B; ++b) p->sum_g += num_gt[b];
+    p->box_off = ((size_t)(B + 1) * 4 + 15) & ~(size_t)15;
+    p->cls_off = p->box_off + (size_t)p->sum_g * 16;
+    p->bytes.resize(p->cls_off + (size_t)p->sum_g * C * 4);
+    int32_t* off = reinterpret_cast<int32_t*>(p->bytes.data());
+    off[0] = 0;
+    for (int b = 0; b < B; ++b) off[b + 1] = off[b] + num_gt[b];
+    std::memcpy(p->bytes.data() + p->box_off, gt_boxes, (size_t)p->sum_g * 16);
+    std::memcpy(p->bytes.data() + p->cls_off, gt_classes, (size_t)p->sum_g * C * 4);
+}
+
+bod_status bod_anchor_targets(int32_t device, int32_t A, const float* anchors_vuhw, int32_t B, const int32_t* num_gt,
+                              const float* gt_boxes_vuvu, const float* gt_classes, int32_t C, float min_positive_iou,
+                              float max_negative_iou, float* cls_targets, float* box_targets, uint8_t* positive_mask,
+                              uint8_t* negative_mask, int32_t* best_gt, float* best_iou) {
+    bod_context ctx;
+    bod_context* h = &ctx;
+    auto done = [&](bod_status s) {
+        if (s != BOD_OK) g_create_error = h->err;
+        if (h->stream) hipStreamSynchronize(h->stream);
+        for (void* p : h->allocs) hipFree(p);
+        if (h->stream) hipStreamDestroy(h->stream);
+        h->allocs.clear(); h->stream = nullptr;
+        return s;
+    };
+    if (A < 1 || B < 1 || B > 65535 || C < 2)
+        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_anchor_targets: bad argument (A = %d, B = %d in 1..65535, C = %d >= 2)", A, B, C));
+    if (!anchors_vuhw || !num_gt || !gt_boxes_vuvu || !gt_classes || !cls_targets || !box_targets || !positive_mask || !negative_mask)
+        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_anchor_targets: a required array is NULL"));
+    for (int b = 0; b < B; ++b)
+        if (num_gt[b] < 1)
+            return done(h->fail(BOD_ERR_INVALID_ARG, "bod_anchor_targets: frame %d has %d ground-truth rows (at least the placeholder row is "
+                                "required)", b, num_gt[b]));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+        return done(h->fail(BOD_ERR_NO_DEVICE, "no HIP device %d: libbayesod_hip has no CPU fallback", device));
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
+        return done(h->fail(BOD_ERR_HIP, "cannot set up device %d", device));
+    auto run = [&]() -> bod_status {
+        const size_t n = (size_t)B * A;
+        PackedGt p;
+        pack_gt(B, num_gt, gt_boxes_vuvu, gt_classes, C, &p);
+        char* d_gt = nullptr; float* d_anchors = nullptr;
+        BODCHK(h->dalloc(&d_gt, p.bytes.size(), false)); BODCHK(h->dalloc(&d_anchors, (size_t)A * 4, false));
+        HIPCHK(h, hipMemcpyAsync(d_gt, p.bytes.data(), p.bytes.size(), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_anchors, anchors_vuhw, (size_t)A * 16, hipMemcpyHostToDevice, h->stream));
+        TargetArgs a{};
+        a.A = A; a.B = B; a.C = C; a.min_positive_iou = min_positive_iou; a.max_negative_iou = max_negative_iou;
+        a.anchors = d_anchors; a.gt_off = reinterpret_cast<const int32_t*>(d_gt);
+        a.gt_boxes = reinterpret_cast<const float*>(d_gt + p.box_off); a.gt_classes = reinterpret_cast<const float*>(d_gt + p.cls_off);
+        BODCHK(h->dalloc(&a.cls_t, n * C, false)); BODCHK(h->dalloc(&a.box_t, n * 4, false));
+        BODCHK(h->dalloc(&a.pos, n, false)); BODCHK(h->dalloc(&a.neg, n, false));
+        if (best_gt) BODCHK(h->dalloc(&a.best_gt, n, false));
+        if (best_iou) BODCHK(h->dalloc(&a.best_iou, n, false));
+        HIPCHK(h, launch_anchor_targets(a, h->stream));
+        HIPCHK(h, hipMemcpyAsync(cls_targets, a.cls_t, n * C * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(box_targets, a.box_t, n * 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(positive_mask, a.pos, n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(negative_mask, a.neg, n, hipMemcpyDeviceToHost, h->stream));
+        if (best_gt) HIPCHK(h, hipMemcpyAsync(best_gt, a.best_gt, n * 4, hipMemcpyDeviceToHost, h->stream));
+        if (best_iou) HIPCHK(h, hipMemcpyAsync(best_iou, a.best_iou, n * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return BOD_OK;
+    };
+    return done(run());
+}
+
 // PDQ evaluation (pdq_kernels.hip): stateless, one stream for the call
 static bod_status pdq_call(int32_t device, const std::function<int(hipStream_t, char*, size_t)>& run) {
     int ndev = 0;

@@ -304,6 +304,22 @@ hipError_t launch_loss_backward(const LossArgs& a, const float* sums4, float w_c
                                 hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
+// Anchor-target assignment (target_kernels.hip): IoU of every anchor with its frame's GT rows, positive / negative masks, the best
+// GT per anchor and the dense class / box targets the loss reads -- one launch for all frames and pyramid levels
+struct TargetArgs {
+    int32_t A, B, C;
+    float min_positive_iou, max_negative_iou;
+    const float* anchors;                       // [A,4] (v, u, h, w)
+    const int32_t* gt_off;                      // [B+1] first GT row of every frame (>= 1 row per frame)
+    const float* gt_boxes;                      // [sum G,4] corners (y1, x1, y2, x2), 16-byte aligned
+    const float* gt_classes;                    // [sum G,C], 16-byte aligned
+    float* cls_t; float* box_t;                 // [B,A,C], [B,A,4]
+    uint8_t* pos; uint8_t* neg;                 // [B,A]
+    int32_t* best_gt; float* best_iou;          // [B,A] row within the frame / its IoU (nullptr = not wanted)
+};
+hipError_t launch_anchor_targets(const TargetArgs& a, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // Streaming pointwise (1x1) convolution for reductions of <= 256 channels (conv_pointwise.hip); launch_conv_igemm routes eligible
 // launches there (BOD_POINTWISE=0: off)
 bool conv_pointwise_eligible(const ConvArgs& a);

@@ -102,6 +102,8 @@ struct TrainState {
     uint16_t* img_bf16 = nullptr; RowEnt* stem_rows = nullptr; uint16_t* stem_dz = nullptr;
     // loss
     float *cls_t = nullptr, *box_t = nullptr; uint8_t *pos = nullptr, *neg = nullptr;
+    // ground truth of bod_train_step_boxes: packed host copy, its device buffer (grown on demand) and the event of the last upload
+    PackedGt gt_host; char* gt_dev = nullptr; size_t gt_cap = 0; hipEvent_t gt_ev = nullptr; bool gt_pending = false;
     float *loss_partial = nullptr, *loss_sums = nullptr, *scalars = nullptr, *sumsq_partial = nullptr;   // scalars: [0] l2 loss, [1] sum of squared gradients
     int loss_blocks = 0;
     long step = 0;
@@ -342,6 +344,8 @@ void train_destroy(bod_context* h) {
     if (TrainState* t = h->train) {
         t->worker.shutdown();
         if (t->graph) hipGraphExecDestroy(t->graph);
+        if (t->gt_ev) hipEventDestroy(t->gt_ev);
+        if (t->gt_dev) hipFree(t->gt_dev);
         for (int k = 0; k < TrainState::WS; ++k) if (t->wstreams[k]) { hipStreamSynchronize(t->wstreams[k]); hipStreamDestroy(t->wstreams[k]); }
         for (int k = 0; k < TrainState::WS; ++k) { if (t->ev_ready[k]) hipEventDestroy(t->ev_ready[k]); if (t->ev_done[k]) hipEventDestroy(t->ev_done[k]); }
     }
@@ -666,22 +670,14 @@ bod_status bod_train_apply(bod_handle h, float learning_rate, double* grad_norm)
     return BOD_OK;
 }
 
-bod_status bod_train_step(bod_handle h, const float* images, int32_t on_device, const float* cls_targets, const float* box_targets,
-                          const uint8_t* positive_mask, const uint8_t* negative_mask, uint64_t seed, uint32_t first_image_id,
-                          int32_t reg_kind, float label_smoothing, float w_cls, float w_reg, float l2_rate, float learning_rate,
-                          int32_t apply_update, double* out6) {
-    if (!h || !cls_targets || !box_targets || !positive_mask || !negative_mask) return BOD_ERR_INVALID_ARG;
-    if (!h->train || !h->weights_ready) return h->fail(BOD_ERR_NOT_READY, "bod_train_step needs a handle created with training = 1 and finalized weights");
-    if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called");
-    if (reg_kind < 1 || reg_kind > 3 || (reg_kind >= 2 && !h->cfg.has_covar_head)) return h->fail(BOD_ERR_INVALID_ARG, "bod_train_step: reg_kind %d", reg_kind);
+namespace {
+// A step from "stage the frames" onward, with the targets already in t->cls_t / box_t / pos / neg (copied there by
+// bod_train_step, assigned there by bod_train_step_boxes): eager, two-thread or hipGraph form, then the out6 read-back.
+bod_status train_run_step(bod_context* h, const float* images, int32_t on_device, uint64_t seed, uint32_t first_image_id, int32_t reg_kind,
+                          float label_smoothing, float w_cls, float w_reg, float l2_rate, float learning_rate, int32_t apply_update,
+                          double* out6) {
     TrainState* t = h->train;
     const bod_config& c = h->cfg;
-    HIPCHK(h, hipSetDevice(c.device));
-    const size_t BA = (size_t)c.batch * h->A;
-    HIPCHK(h, hipMemcpyAsync(t->cls_t, cls_targets, BA * c.num_classes * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(t->box_t, box_targets, BA * 16, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(t->pos, positive_mask, BA, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(t->neg, negative_mask, BA, hipMemcpyHostToDevice, h->stream));
     const float* dev = nullptr;
     BODCHK(stage_images(h, images, on_device, &dev));
     {
@@ -744,6 +740,85 @@ bod_status bod_train_step(bod_handle h, const float* images, int32_t on_device, 
         out6[0] = out6[1] + w_reg * (out6[2] + out6[3]) + out6[4];        // total_loss (run_training.py:226-236)
         out6[5] = std::sqrt((double)sc[1]);                               // global gradient norm before clipping
     }
+    return BOD_OK;
+}
+
+bod_status train_step_check(bod_context* h, const char* who, int32_t reg_kind) {
+    if (!h->train || !h->weights_ready) return h->fail(BOD_ERR_NOT_READY, "%s needs a handle created with training = 1 and finalized weights", who);
+    if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called");
+    if (reg_kind < 1 || reg_kind > 3 || (reg_kind >= 2 && !h->cfg.has_covar_head)) return h->fail(BOD_ERR_INVALID_ARG, "%s: reg_kind %d", who, reg_kind);
+    return BOD_OK;
+}
+}  // namespace
+
+bod_status bod_train_step(bod_handle h, const float* images, int32_t on_device, const float* cls_targets, const float* box_targets,
+                          const uint8_t* positive_mask, const uint8_t* negative_mask, uint64_t seed, uint32_t first_image_id,
+                          int32_t reg_kind, float label_smoothing, float w_cls, float w_reg, float l2_rate, float learning_rate,
+                          int32_t apply_update, double* out6) {
+    if (!h || !cls_targets || !box_targets || !positive_mask || !negative_mask) return BOD_ERR_INVALID_ARG;
+    BODCHK(train_step_check(h, "bod_train_step", reg_kind));
+    TrainState* t = h->train;
+    const bod_config& c = h->cfg;
+    HIPCHK(h, hipSetDevice(c.device));
+    const size_t BA = (size_t)c.batch * h->A;
+    HIPCHK(h, hipMemcpyAsync(t->cls_t, cls_targets, BA * c.num_classes * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(t->box_t, box_targets, BA * 16, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(t->pos, positive_mask, BA, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(t->neg, negative_mask, BA, hipMemcpyHostToDevice, h->stream));
+    return train_run_step(h, images, on_device, seed, first_image_id, reg_kind, label_smoothing, w_cls, w_reg, l2_rate, learning_rate, apply_update,
+                          out6);
+}
+
+bod_status bod_train_step_boxes(bod_handle h, const float* images, int32_t on_device, const int32_t* num_gt, const float* gt_boxes_vuvu,
+                                const float* gt_classes, float min_positive_iou, float max_negative_iou, uint64_t seed,
+                                uint32_t first_image_id, int32_t reg_kind, float label_smoothing, float w_cls, float w_reg, float l2_rate,
+                                float learning_rate, int32_t apply_update, double* out6) {
+    if (!h || !num_gt || !gt_boxes_vuvu || !gt_classes) return BOD_ERR_INVALID_ARG;
+    BODCHK(train_step_check(h, "bod_train_step_boxes", reg_kind));
+    TrainState* t = h->train;
+    const bod_config& c = h->cfg;
+    for (int b = 0; b < c.batch; ++b)
+        if (num_gt[b] < 1)
+            return h->fail(BOD_ERR_INVALID_ARG, "bod_train_step_boxes: frame %d has %d ground-truth rows (at least the placeholder row is required)",
+                           b, num_gt[b]);
+    HIPCHK(h, hipSetDevice(c.device));
+    // ---- the few GT rows go up in one copy; the kernel then writes the buffers bod_train_step fills by four copies
+    if (!t->gt_ev) HIPCHK(h, hipEventCreateWithFlags(&t->gt_ev, hipEventDisableTiming));
+    if (t->gt_pending) { HIPCHK(h, hipEventSynchronize(t->gt_ev)); t->gt_pending = false; }      // the last upload has left gt_host
+    pack_gt(c.batch, num_gt, gt_boxes_vuvu, gt_classes, c.num_classes, &t->gt_host);
+    const size_t bytes = t->gt_host.bytes.size();
+    if (bytes > t->gt_cap) {
+        if (t->gt_dev) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(t->gt_dev); t->gt_dev = nullptr; t->gt_cap = 0; }
+        const size_t cap = std::max<size_t>(2 * bytes, 4096);
+        if (hipMalloc(reinterpret_cast<void**>(&t->gt_dev), cap) != hipSuccess)
+            return h->fail(BOD_ERR_OOM, "bod_train_step_boxes: %zu bytes for the ground truth", cap);
+        t->gt_cap = cap;
+    }
+    HIPCHK(h, hipMemcpyAsync(t->gt_dev, t->gt_host.bytes.data(), bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(t->gt_ev, h->stream));
+    t->gt_pending = true;
+    TargetArgs ta{};
+    ta.A = h->A; ta.B = c.batch; ta.C = c.num_classes; ta.min_positive_iou = min_positive_iou; ta.max_negative_iou = max_negative_iou;
+    ta.anchors = h->d_anchors; ta.gt_off = reinterpret_cast<const int32_t*>(t->gt_dev);
+    ta.gt_boxes = reinterpret_cast<const float*>(t->gt_dev + t->gt_host.box_off);
+    ta.gt_classes = reinterpret_cast<const float*>(t->gt_dev + t->gt_host.cls_off);
+    ta.cls_t = t->cls_t; ta.box_t = t->box_t; ta.pos = t->pos; ta.neg = t->neg;
+    HIPCHK(h, launch_anchor_targets(ta, h->stream));
+    return train_run_step(h, images, on_device, seed, first_image_id, reg_kind, label_smoothing, w_cls, w_reg, l2_rate, learning_rate, apply_update,
+                          out6);
+}
+
+bod_status bod_train_get_targets(bod_handle h, float* cls_targets, float* box_targets, uint8_t* positive_mask, uint8_t* negative_mask) {
+    if (!h || !cls_targets || !box_targets || !positive_mask || !negative_mask) return BOD_ERR_INVALID_ARG;
+    if (!h->train) return h->fail(BOD_ERR_NOT_READY, "not a training handle");
+    TrainState* t = h->train;
+    const size_t BA = (size_t)h->cfg.batch * h->A;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpyAsync(cls_targets, t->cls_t, BA * h->cfg.num_classes * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(box_targets, t->box_t, BA * 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(positive_mask, t->pos, BA, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(negative_mask, t->neg, BA, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return BOD_OK;
 }
 

@@ -52,6 +52,7 @@ class DatasetHandler(object):
     def __init__(self, dataset_config):
         self.data_split = dataset_config['data_split']
         self.im_normalization = dataset_config['im_normalization']
+        self.dense_targets = True        # False: samples carry the GT boxes only (targets are assigned on the device)
 
 
 class BddDatasetHandler(DatasetHandler):
@@ -109,7 +110,8 @@ class BddDatasetHandler(DatasetHandler):
         rgb = _decode(im_path)
         norm = normalize_frame(rgb, self.im_normalization)
         cls_gt, box_gt, _ = self._read_labels(sample_id)
-        sample = create_sample_dict(norm, self.anchor_gen_config, box_gt, cls_gt, is_testing=self.is_testing)
+        sample = create_sample_dict(norm, self.anchor_gen_config, box_gt, cls_gt, is_testing=self.is_testing,
+                                    dense_targets=self.dense_targets)
         sample[constants.ORIGINAL_IM_SIZE_KEY] = np.asarray(rgb.shape, dtype=np.int32)
         sample[IMAGE_UINT8_KEY] = rgb
         return sample
@@ -183,7 +185,8 @@ class KittiDatasetHandler(DatasetHandler):
         nh, nw = self.resize_shape
         box_gt = (box_gt / np.array([oh, ow, oh, ow], np.float32)) * np.array([nh, nw, nh, nw], np.float32)
         placeholder = np.zeros((nh, nw, 3), np.float32)       # shape carrier: the pixels are produced on the device
-        sample = create_sample_dict(placeholder, self.anchor_gen_config, box_gt, cls_gt, is_testing=self.is_testing)
+        sample = create_sample_dict(placeholder, self.anchor_gen_config, box_gt, cls_gt, is_testing=self.is_testing,
+                                    dense_targets=self.dense_targets)
         sample[constants.IMAGE_NORMALIZED_KEY] = None
         sample[constants.ORIGINAL_IM_SIZE_KEY] = np.asarray(rgb.shape, dtype=np.int32)
         sample[IMAGE_UINT8_KEY] = rgb

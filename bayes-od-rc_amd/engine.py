@@ -264,6 +264,35 @@ class Engine(object):
         keys = ("total_loss", "cls_loss", "reg_loss", "covariance_loss", "regularization_loss", "grad_norm")
         return dict(zip(keys, [out[i] for i in range(6)]))
 
+    def train_step_boxes(self, images, gt_boxes, gt_classes, min_positive_iou=0.5, max_negative_iou=0.4, seed=0, first_image_id=0,
+                         reg_kind=3, label_smoothing=0.001, w_cls=5.0, w_reg=1.0, l2_rate=1e-6, learning_rate=1e-3,
+                         apply_update=True):
+        """train_step from ground-truth boxes (``bod_train_step_boxes``): per-frame lists of [G_b,4] corners (y1,x1,y2,x2)
+        and [G_b,C] class rows; the dense targets are assigned on the device against the handle's anchors."""
+        ng, boxes, classes = _pack_gt(gt_boxes, gt_classes, self.B, self.Ccls)
+        out = (C.c_double * 6)()
+        if images is None:
+            ptr, on_dev = self.lib.bod_device_images(self.h), 1
+        else:
+            img = self._img(images)
+            ptr, on_dev = img.ctypes.data, 0
+        self._chk(self.lib.bod_train_step_boxes(self.h, ptr, on_dev, iptr(ng), fptr(boxes), fptr(classes), float(min_positive_iou),
+                                                float(max_negative_iou), seed, first_image_id, int(reg_kind), float(label_smoothing),
+                                                float(w_cls), float(w_reg), float(l2_rate), float(learning_rate),
+                                                int(bool(apply_update)), out))
+        keys = ("total_loss", "cls_loss", "reg_loss", "covariance_loss", "regularization_loss", "grad_norm")
+        return dict(zip(keys, [out[i] for i in range(6)]))
+
+    def train_targets(self):
+        """The dense targets the last training step used (``bod_train_get_targets``): cls [B,A,C], box [B,A,4], positive and
+        negative masks [B,A] (bool)."""
+        b, a = self.B, self.A
+        ct, bt = np.empty((b, a, self.Ccls), np.float32), np.empty((b, a, 4), np.float32)
+        pm, nm = np.empty((b, a), np.uint8), np.empty((b, a), np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        self._chk(self.lib.bod_train_get_targets(self.h, fptr(ct), fptr(bt), pm.ctypes.data_as(u8), nm.ctypes.data_as(u8)))
+        return ct, bt, pm.astype(bool), nm.astype(bool)
+
     def train_gradients_view(self):
         """torch tensor aliasing the contiguous fp32 gradient arena (for the data-parallel all-reduce)."""
         import torch
@@ -447,6 +476,43 @@ class Engine(object):
         self._chk(self.lib.bod_profile_end(self.h, C.byref(hm), C.byref(hl), C.byref(fl), C.byref(pm), C.byref(pl)))
         return {"head_conv_ms": hm.value, "head_conv_launches": hl.value, "head_conv_flops": fl.value,
                 "posterior_ms": pm.value, "posterior_launches": pl.value}
+
+
+def _pack_gt(gt_boxes, gt_classes, batch, num_classes=None):
+    """Per-frame lists -> (num_gt [B] int32, boxes [sum G,4], class rows [sum G,C]) as the C ABI takes them."""
+    if len(gt_boxes) != batch or len(gt_classes) != batch:
+        raise ValueError("expected ground truth for %d frames, got %d box and %d class arrays" % (batch, len(gt_boxes), len(gt_classes)))
+    boxes = [as_f32(b).reshape(-1, 4) for b in gt_boxes]
+    classes = [as_f32(c) for c in gt_classes]
+    classes = [c.reshape(b.shape[0], -1) if c.ndim != 2 else c for b, c in zip(boxes, classes)]
+    width = classes[0].shape[1] if num_classes is None else num_classes
+    for b, c in zip(boxes, classes):
+        if c.shape != (b.shape[0], width):
+            raise ValueError("class rows of shape %s do not match %d boxes x %d classes" % (c.shape, b.shape[0], width))
+    ng = np.asarray([b.shape[0] for b in boxes], np.int32)
+    return ng, as_f32(np.concatenate(boxes, axis=0)), as_f32(np.concatenate(classes, axis=0))
+
+
+def anchor_targets(anchors, gt_boxes, gt_classes, min_positive_iou=0.5, max_negative_iou=0.4, device=0, return_best=False):
+    """Dense anchor targets on the device (``bod_anchor_targets``): anchors [A,4] (v,u,h,w); gt_boxes / gt_classes are
+    per-frame lists of [G_b,4] corners (y1,x1,y2,x2) and [G_b,C] class rows.  Returns cls_targets [B,A,C], box_targets
+    [B,A,4], positive and negative masks [B,A] (bool), plus best_gt [B,A] int32 and best_iou [B,A] with return_best."""
+    lib = _lib.load()
+    anchors = as_f32(anchors).reshape(-1, 4)
+    b, a = len(gt_boxes), anchors.shape[0]
+    ng, boxes, classes = _pack_gt(gt_boxes, gt_classes, b)
+    c = classes.shape[1]
+    ct, bt = np.empty((b, a, c), np.float32), np.empty((b, a, 4), np.float32)
+    pm, nm = np.empty((b, a), np.uint8), np.empty((b, a), np.uint8)
+    bg = np.empty((b, a), np.int32) if return_best else None
+    bi = np.empty((b, a), np.float32) if return_best else None
+    u8 = C.POINTER(C.c_uint8)
+    st = lib.bod_anchor_targets(device, a, fptr(anchors), b, iptr(ng), fptr(boxes), fptr(classes), c, float(min_positive_iou),
+                                float(max_negative_iou), fptr(ct), fptr(bt), pm.ctypes.data_as(u8), nm.ctypes.data_as(u8),
+                                iptr(bg), fptr(bi))
+    _lib.check(lib, None, st)
+    out = (ct, bt, pm.astype(bool), nm.astype(bool))
+    return out + (bg, bi) if return_best else out
 
 
 def stage_conv(x, w, bias=None, stride=1, padding="same", relu=False, residual=None, dropout_rate=0.0,

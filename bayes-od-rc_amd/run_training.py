@@ -6,7 +6,9 @@
 The step itself -- forward in training mode, losses, backward, global-norm clipping, Adam -- runs on the GPU in
 ``bod_train_step``; this file keeps what the reference keeps on the host: the piecewise-constant learning-rate
 schedule (:48-61), the batching of the dataset handler's sample dictionaries, the summary print and the checkpoint
-cadence.  Checkpoints are ``.npz`` files in the schema ``RetinaNetModel.load_weights`` reads (the TF-checkpoint
+cadence.  With ``--dataset`` the split is streamed one minibatch at a time and the anchor targets are assigned on the GPU from
+the frames' ground-truth boxes (``bod_train_step_boxes``); KITTI frames are resized there too.  Checkpoints are ``.npz``
+files in the schema ``RetinaNetModel.load_weights`` reads (the TF-checkpoint
 format is the converter's business, convert_checkpoint.py)."""
 import argparse
 import os
@@ -69,23 +71,46 @@ class Trainer(object):
                                          backbone_depth=101 if '101' in str(model_config.get('feature_extractor', {}).get('name', '')) else 50))
         self.engine.load_weights(weights)
         self._init = weights
+        self.anchor_config = config['dataset_config']['anchor_generator']
+        self.im_normalization = config['dataset_config'].get('im_normalization', 'ImageNet')
+
+    def _train_step_from_boxes(self, sample_dicts, learning_rate):
+        """Samples that carry the ground truth only (``dense_targets=False``): the targets are assigned on the device.  KITTI
+        samples have no host image (IMAGE_NORMALIZED_KEY is None): their uint8 frames are resized and normalised on the device."""
+        if sample_dicts[0][constants.IMAGE_NORMALIZED_KEY] is None:
+            frames = np.stack([s['image_uint8'] for s in sample_dicts])
+            self.engine.upload_frames_u8(frames, constants.MEANS_DICT[self.im_normalization], aspect_resize=True)
+            imgs = None
+        else:
+            imgs = np.stack([s[constants.IMAGE_NORMALIZED_KEY] for s in sample_dicts]).astype(np.float32)
+        return self.engine.train_step_boxes(
+            imgs, [s[constants.BOXES_2D_GT_KEY] for s in sample_dicts], [s[constants.BOXES_CLASS_GT_KEY] for s in sample_dicts],
+            float(self.anchor_config['min_positive_iou']), float(self.anchor_config['max_negative_iou']),
+            seed=self.seed, first_image_id=self.step * self.batch, reg_kind=self.reg_kind, label_smoothing=self.label_smoothing,
+            w_cls=self.w_cls, w_reg=self.w_reg, l2_rate=self.l2_rate, learning_rate=learning_rate)
 
     def train_single_step(self, sample_dicts, learning_rate):
-        imgs = np.stack([s[constants.IMAGE_NORMALIZED_KEY] for s in sample_dicts]).astype(np.float32)
         if not self.engine._anchors_set:
             self.engine.set_anchors(np.asarray(sample_dicts[0][constants.ANCHORS_KEY], np.float32))
-        out = self.engine.train_step(
+        if constants.ANCHORS_CLASS_TARGETS_KEY in sample_dicts[0]:
+            out = self._train_step_dense(sample_dicts, learning_rate)
+        else:
+            out = self._train_step_from_boxes(sample_dicts, learning_rate)
+        self.step += 1
+        loss_dict = {'cls_loss': out['cls_loss'], 'reg_loss': out['reg_loss'], 'regularization_loss': out['regularization_loss']}
+        if self.reg_kind >= 2:
+            loss_dict['covariance_loss'] = out['covariance_loss']
+        return out['total_loss'], loss_dict
+
+    def _train_step_dense(self, sample_dicts, learning_rate):
+        imgs = np.stack([s[constants.IMAGE_NORMALIZED_KEY] for s in sample_dicts]).astype(np.float32)
+        return self.engine.train_step(
             imgs, np.stack([s[constants.ANCHORS_CLASS_TARGETS_KEY] for s in sample_dicts]),
             np.stack([s[constants.ANCHORS_BOX_TARGETS_KEY] for s in sample_dicts]),
             np.stack([s[constants.POSITIVE_ANCHORS_MASK_KEY] for s in sample_dicts]),
             np.stack([s[constants.NEGATIVE_ANCHOR_MASK_KEY] for s in sample_dicts]),
             seed=self.seed, first_image_id=self.step * self.batch, reg_kind=self.reg_kind, label_smoothing=self.label_smoothing,
             w_cls=self.w_cls, w_reg=self.w_reg, l2_rate=self.l2_rate, learning_rate=learning_rate)
-        self.step += 1
-        loss_dict = {'cls_loss': out['cls_loss'], 'reg_loss': out['reg_loss'], 'regularization_loss': out['regularization_loss']}
-        if self.reg_kind >= 2:
-            loss_dict['covariance_loss'] = out['covariance_loss']
-        return out['total_loss'], loss_dict
 
     def optimizer_state(self):
         """{'<layer>/<field>/adam_m' | '.../adam_v': array} + 'optimizer/step', 'trainer/step' -- what tf.train.Checkpoint(step,
@@ -146,21 +171,58 @@ def synthetic_samples(n, image_hw, anchor_gen_config, num_classes, seed=0):
     return out
 
 
+def bucket_minibatches(samples, minibatch_size, carry):
+    """Generator of full minibatches from an iterable of sample dicts, walked lazily.  All frames of a minibatch go up in one
+    ``bod_upload_frames_u8`` call, which takes one source size, so frames are bucketed by source size and a minibatch is
+    emitted when a bucket is full.  ``carry`` ({size: [samples]}) holds the partial buckets; the caller passes the same dict
+    for the next epoch, so no frame is dropped.  This reorders frames relative to the reference's shuffled order (which
+    resizes on the host and can batch any frames together): within a size the order is kept."""
+    for sample in samples:
+        key = tuple(int(v) for v in np.asarray(sample[constants.ORIGINAL_IM_SIZE_KEY]).ravel()[:2])
+        carry.setdefault(key, []).append(sample)
+        del sample                                    # (no reference stays behind in this frame once a minibatch has been handed out)
+        if len(carry[key]) == minibatch_size:
+            yield carry.pop(key)
+
+
+def stream_minibatches(handler, minibatch_size):
+    """Endless generator of minibatches over ``handler.create_dataset()``: one pass per epoch, restarted at its end, never more
+    than the current minibatch and the partial buckets in memory."""
+    carry = {}
+    while True:
+        seen = [0]
+
+        def counted(samples):
+            for sample in samples:
+                seen[0] += 1
+                yield sample
+                del sample
+        yield from bucket_minibatches(counted(handler.create_dataset()), minibatch_size, carry)
+        if not seen[0]:
+            raise ValueError('the data split is empty')
+
+
 def train(config, args):
     training_config = config['training_config']
     dataset_config = config['dataset_config']
     num_classes = int(config['model_config']['header']['num_classes'])
+    mb = int(training_config['minibatch_size'])
     if args.dataset:
         from . import datasets
+        # the split is streamed: samples carry the GT boxes only (the step assigns the dense targets on the device) and are read
+        # one minibatch at a time
         handler = datasets.build_dataset(dataset_config, 'train')
-        samples = list(handler.create_dataset())
-        if dataset_config['dataset'] == 'kitti':
-            raise ValueError("KITTI training needs the resized frames on the host; use --synthetic or BDD")
+        handler.dense_targets = False
+        stream = stream_minibatches(handler, mb)
+        pending = next(stream)                                        # the first minibatch also tells the frame size
+        first = pending[0][constants.IMAGE_NORMALIZED_KEY]
+        hw = tuple(handler.resize_shape) if first is None else first.shape[:2]
+        samples = None
+        epoch_size = max(handler.epoch_size // mb, 1)
     else:
         samples = synthetic_samples(args.synthetic, args.image_size, dataset_config['anchor_generator'], num_classes, seed=args.seed)
-    hw = samples[0][constants.IMAGE_NORMALIZED_KEY].shape[:2]
-    mb = int(training_config['minibatch_size'])
-    epoch_size = max(len(samples) // mb, 1)
+        hw = samples[0][constants.IMAGE_NORMALIZED_KEY].shape[:2]
+        epoch_size = max(len(samples) // mb, 1)
     lr = piecewise_learning_rate(training_config, epoch_size)
     weights = args.weights if args.weights else synthetic.make_weights(num_classes + 1, int(config['model_config']['header']['anchors_per_location']))
     if isinstance(weights, str):
@@ -216,8 +278,14 @@ def train(config, args):
     last = time.time()
     history = []
     for step in range(trainer.step, total_steps):
-        lo = (step * mb) % max(len(samples) - mb + 1, 1)
-        total_loss, loss_dict = trainer.train_single_step(samples[lo:lo + mb], lr(step))
+        if samples is None:
+            batch = pending if pending is not None else next(stream)
+            pending = None
+        else:
+            lo = (step * mb) % max(len(samples) - mb + 1, 1)
+            batch = samples[lo:lo + mb]
+        total_loss, loss_dict = trainer.train_single_step(batch, lr(step))
+        batch = None
         history.append(total_loss)
         if step % int(training_config['summary_interval']) == 0:
             print('Step {}, Total Loss {:0.3f}, Time Elapsed {:0.3f} s'.format(step, total_loss, time.time() - last))

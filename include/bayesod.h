@@ -304,6 +304,19 @@ bod_status bod_train_step(bod_handle h, const float* images, int32_t images_on_d
                           uint64_t seed, uint32_t first_image_id, int32_t reg_kind, float label_smoothing,
                           float w_cls, float w_reg, float l2_rate, float learning_rate, int32_t apply_update,
                           double* out6);
+/* The same step from what a dataset gives: per frame num_gt[b] >= 1 ground-truth rows (the handlers' placeholder row
+ * [0,0,1,1] with a background class for a frame without boxes), gt_boxes_vuvu [sum G,4] corners (y1, x1, y2, x2) and
+ * gt_classes [sum G,C] rows (C = the handle's num_classes).  The dense targets are assigned on the device against the
+ * handle's anchors (bod_set_anchors) by the kernel of bod_anchor_targets, into the buffers bod_train_step copies its
+ * targets to; everything after that is bod_train_step, arguments from `seed` on included. */
+bod_status bod_train_step_boxes(bod_handle h, const float* images, int32_t images_on_device, const int32_t* num_gt,
+                                const float* gt_boxes_vuvu, const float* gt_classes, float min_positive_iou,
+                                float max_negative_iou, uint64_t seed, uint32_t first_image_id, int32_t reg_kind,
+                                float label_smoothing, float w_cls, float w_reg, float l2_rate, float learning_rate,
+                                int32_t apply_update, double* out6);
+/* The targets the last step (either entry point) used, read back: cls_targets [B,A,C], box_targets [B,A,4], masks [B,A]. */
+bod_status bod_train_get_targets(bod_handle h, float* cls_targets, float* box_targets, uint8_t* positive_mask,
+                                 uint8_t* negative_mask);
 /* Data-parallel training (one process per GPU): after bod_train_step(..., apply_update = 0) the gradients of ALL
  * trainable tensors lie in one contiguous fp32 device array -- bod_train_gradients returns its address and length
  * (the handle's stream is synchronised first) -- so the ranks need ONE all-reduce (RCCL) over it, then
@@ -332,6 +345,19 @@ bod_status bod_loss_forward(int32_t device, int32_t B, int32_t A, int32_t C, con
                             const float* covar_params, const float* anchors, const uint8_t* positive_mask,
                             const uint8_t* negative_mask, int32_t do_classification, int32_t reg_kind,
                             float label_smoothing, double* out4);
+
+/* Anchor-target assignment (bbox_iou_vuvu + positive_negative_batching + generate_anchor_targets of the dataset handlers;
+ * stateless, host arrays in and out): anchors_vuhw [A,4], per frame num_gt[b] >= 1 rows of gt_boxes_vuvu [sum G,4] and
+ * gt_classes [sum G,C], C >= 2 with the background class last.  All fp32 in the host code's op order: IoU with the +1 pixel
+ * convention and the reference's area expression, positive = any IoU >= min_positive_iou, negative = all IoU <=
+ * max_negative_iou, best GT = first row of the largest IoU; box_targets [B,A,4] are written for every anchor, cls_targets
+ * [B,A,C] hold the best GT's class row where positive and the background row elsewhere, masks [B,A] are bytes.  best_gt
+ * [B,A] (row within the frame) and best_iou [B,A] may be NULL.  Degenerate boxes are not rejected (a non-finite target is
+ * the caller's data).  Errors via bod_last_error(NULL). */
+bod_status bod_anchor_targets(int32_t device, int32_t A, const float* anchors_vuhw, int32_t B, const int32_t* num_gt,
+                              const float* gt_boxes_vuvu, const float* gt_classes, int32_t C, float min_positive_iou,
+                              float max_negative_iou, float* cls_targets, float* box_targets, uint8_t* positive_mask,
+                              uint8_t* negative_mask, int32_t* best_gt, float* best_iou);
 
 /* Gradient of  total = w_cls * S_cls / max(n_pos,1) + w_reg * (S_cmp + S_reg) / max(n_pos,1)  (the reference's
  * total_loss before the L2 term, retinanet_model.py:183-323) with respect to the raw head outputs: dcls [B,A,C],

@@ -111,6 +111,13 @@ bod_status bod_train_step(bod_handle h, const float* images, int32_t images_on_d
                           uint64_t seed, uint32_t first_image_id, int32_t reg_kind, float label_smoothing,
                           float w_cls, float w_reg, float l2_rate, float learning_rate, int32_t apply_update,
                           double* out6);
+bod_status bod_train_step_boxes(bod_handle h, const float* images, int32_t images_on_device, const int32_t* num_gt,
+                                const float* gt_boxes_vuvu, const float* gt_classes, float min_positive_iou,
+                                float max_negative_iou, uint64_t seed, uint32_t first_image_id, int32_t reg_kind,
+                                float label_smoothing, float w_cls, float w_reg, float l2_rate, float learning_rate,
+                                int32_t apply_update, double* out6);
+bod_status bod_train_get_targets(bod_handle h, float* cls_targets, float* box_targets, uint8_t* positive_mask,
+                                 uint8_t* negative_mask);
 bod_status bod_train_gradients(bod_handle h, void** device_ptr, int64_t* count);
 bod_status bod_train_apply(bod_handle h, float learning_rate, double* grad_norm);
 bod_status bod_train_get(bod_handle h, const char* layer, int32_t kind, int32_t what, float* out, int64_t n);
@@ -121,6 +128,10 @@ bod_status bod_loss_forward(int32_t device, int32_t B, int32_t A, int32_t C, con
                             const float* covar_params, const float* anchors, const uint8_t* positive_mask,
                             const uint8_t* negative_mask, int32_t do_classification, int32_t reg_kind,
                             float label_smoothing, double* out4);
+bod_status bod_anchor_targets(int32_t device, int32_t A, const float* anchors_vuhw, int32_t B, const int32_t* num_gt,
+                              const float* gt_boxes_vuvu, const float* gt_classes, int32_t C, float min_positive_iou,
+                              float max_negative_iou, float* cls_targets, float* box_targets, uint8_t* positive_mask,
+                              uint8_t* negative_mask, int32_t* best_gt, float* best_iou);
 bod_status bod_loss_backward(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls,
                              const float* cls_targets, const float* box, const float* box_targets,
                              const float* covar_params, const float* anchors, const uint8_t* positive_mask,
