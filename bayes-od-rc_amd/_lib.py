@@ -114,6 +114,10 @@ SIGNATURES = {
                                     C.c_float, C.c_float, C.POINTER(C.c_double), _F, _F, _F]),
     "bod_anchor_targets": (C.c_int, [C.c_int32, C.c_int32, _F, C.c_int32, _I, _F, _F, C.c_int32, C.c_float, C.c_float, _F, _F,
                                      C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _I, _F]),
+    "bod_validation_losses_boxes": (C.c_int, [_H, _I, _F, _F, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, _D]),
+    "bod_get_validation_detections_batch": (C.c_int, [_H, _I, _F, _F]),
+    "bod_validate_boxes": (C.c_int, [_H, C.c_void_p, C.c_int32, _I, _F, _F, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, _D,
+                                     _I, _F, _F]),
     "bod_pdq_corner_heatmaps": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, _I, _F]),
     "bod_pdq_frames": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, _I, _I, _I, _D, _D, _D, _D, _F]),
     "bod_bench_head_conv": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

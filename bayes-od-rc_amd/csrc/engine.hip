@@ -14,6 +14,7 @@
 #include <mutex>
 #include <thread>
 #include <tuple>
+#include <type_traits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -242,6 +243,7 @@ struct bod_context {
     std::map<const void*, size_t> alloc_bytes;
     int64_t device_bytes = 0;
     struct TrainState* train = nullptr;                 // training mode (train_impl.inc)
+    struct ValState* val = nullptr;                     // validation from boxes (validate_impl.inc): allocated by its first call
 
     // geometry
     int sh = 0, sw = 0, ph = 0, pw = 0;                 // stem / pool output
@@ -682,6 +684,7 @@ bod_status train_init(bod_context* h);          // train_impl.inc
 bod_status train_forward_only(bod_context* h, const float* dev, uint64_t seed, uint32_t first_image_id);
 const uint32_t* train_dyn_rng(bod_context* h);
 void train_destroy(bod_context* h);
+void val_destroy(bod_context* h);               // validate_impl.inc
 
 bod_status build_plan(bod_context* h) {
     const bod_config& c = h->cfg;
@@ -1658,6 +1661,19 @@ bod_status run_posterior(bod_context* h, uint64_t seed, uint32_t first_image) {
     return BOD_OK;
 }
 
+// validation_utils.post_process_predictions up to the NMS input, on MC sample 0 of the raw head outputs (bod_validation_post)
+bod_status run_validation_post(bod_context* h) {
+    BODCHK(materialise_raw(h));
+    for (int sidx = 0; sidx < 2; ++sidx)
+        if (h->side_pending[sidx]) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_done[sidx], 0));
+    PostCfg pc = post_cfg(h, 0, 0);
+    PostBuffers pb = h->pb;
+    pb.cls = h->raw[0]; pb.box = h->raw[1]; pb.cov = h->raw[2]; pb.anchors = h->d_anchors;
+    HIPCHK(h, launch_validation_post(pc, pb, h->stream));
+    h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;
+    return BOD_OK;
+}
+
 bod_status run_nms(bod_context* h, hipStream_t st) {
     MarkerRange mr("bod:nms");
     const bod_config& c = h->cfg;
@@ -1859,6 +1875,7 @@ bod_status bod_destroy(bod_handle h) {
     if (h->ev_posterior) hipEventDestroy(h->ev_posterior);
     for (int sidx = 0; sidx < 2; ++sidx) if (h->ev_done[sidx]) hipEventDestroy(h->ev_done[sidx]);
     train_destroy(h);
+    val_destroy(h);
     for (int sidx = 0; sidx < 2; ++sidx) if (h->host_stage[sidx]) hipHostFree(h->host_stage[sidx]);
     if (h->rec_recv && h->rec_recv != h->rec_send) hipFree(h->rec_recv);
     if (h->rec_send) hipFree(h->rec_send);
@@ -2153,15 +2170,7 @@ bod_status bod_validation_post(bod_handle h) {
     if (!h->forward_done) return h->fail(BOD_ERR_NOT_READY, "bod_forward / bod_set_raw has not run");
     if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    BODCHK(materialise_raw(h));
-    for (int sidx = 0; sidx < 2; ++sidx)
-        if (h->side_pending[sidx]) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_done[sidx], 0));
-    PostCfg pc = post_cfg(h, 0, 0);
-    PostBuffers pb = h->pb;
-    pb.cls = h->raw[0]; pb.box = h->raw[1]; pb.cov = h->raw[2]; pb.anchors = h->d_anchors;
-    HIPCHK(h, launch_validation_post(pc, pb, h->stream));
-    h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;
-    return BOD_OK;
+    return run_validation_post(h);
 }
 
 bod_status bod_get_num_kept(bod_handle h, int32_t* out) {
@@ -3156,4 +3165,5 @@ bod_status bod_profile_end(bod_handle h, double* head_ms, int64_t* head_launches
 
 }  // extern "C"
 
+#include "validate_impl.inc"
 #include "train_impl.inc"

@@ -249,6 +249,20 @@ struct NmsArgs {
 };
 hipError_t launch_nms(const NmsArgs& a, hipStream_t s);
 
+// Records of the validation path: score rows and corners (y1, x1, y2, x2) of every image's selected candidates, in soft-NMS order
+struct ValGatherArgs {
+    int32_t B, A, C, max_out;
+    const int32_t* num_kept;      // [B]
+    const int32_t* selected;      // [B,max_out] indices into the image's compacted candidates
+    const int32_t* num_selected;  // [B]
+    const float* score;           // [B,A,C]
+    const float* corners;         // [B,A,4]
+    float* out_scores;            // [B,max_out,C]; rows beyond the image's count are zero
+    float* out_corners;           // [B,max_out,4]
+    int32_t* out_num;             // [B]
+};
+hipError_t launch_validation_gather(const ValGatherArgs& a, hipStream_t s);
+
 struct ClusterArgs {
     int32_t B, A, C, max_out;
     const int32_t* num_kept;
@@ -300,6 +314,10 @@ struct LossArgs {
 };
 hipError_t launch_loss(const LossArgs& a, float* partial, int nblocks, hipStream_t s);
 hipError_t launch_loss_reduce(const float* partial, int nblocks, float* sums4, hipStream_t s);
+// Per-frame sums (validation from boxes): grid.y = frame; partial [B][ceil(A / 256)][4], then sums [B][4] in double, one block
+// per frame, fixed order -- a frame's four sums do not depend on the batch around it
+hipError_t launch_loss_frames(const LossArgs& a, float* partial, hipStream_t s);
+hipError_t launch_loss_frames_reduce(const float* partial, int frames, int nblocks, double* sums, hipStream_t s);
 hipError_t launch_loss_backward(const LossArgs& a, const float* sums4, float w_cls, float w_reg, float* dcls, float* dbox, float* dcov,
                                 hipStream_t s);
 

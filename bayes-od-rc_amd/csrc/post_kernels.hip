@@ -767,6 +767,28 @@ hipError_t launch_validation_post(const PostCfg& c, const PostBuffers& b, hipStr
     return hipGetLastError();
 }
 
+// The records validation writes out (validation_utils.py:62-77: tf.gather of the class rows and the corners by the NMS indices):
+// one thread per (image, output row).  An index outside the image's candidates (never produced by nms_kernel) yields a zero row.
+__global__ __launch_bounds__(128) void val_gather_kernel(ValGatherArgs a) {
+    const int k = blockIdx.x * 128 + threadIdx.x;
+    const int b = blockIdx.y;
+    if (k >= a.max_out) return;
+    const int n = min(max(a.num_selected[b], 0), a.max_out);
+    if (k == 0) a.out_num[b] = n;
+    const size_t o = (size_t)b * a.max_out + k;
+    const int src = k < n ? a.selected[o] : -1;
+    const bool ok = src >= 0 && src < min(a.num_kept[b], a.A);
+    const size_t i = (size_t)b * a.A + (ok ? src : 0);
+    for (int j = 0; j < a.C; ++j) a.out_scores[o * a.C + j] = ok ? a.score[i * a.C + j] : 0.f;
+    reinterpret_cast<float4*>(a.out_corners)[o] = ok ? reinterpret_cast<const float4*>(a.corners)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+hipError_t launch_validation_gather(const ValGatherArgs& a, hipStream_t s) {
+    if (a.B < 1 || a.B > 65535 || a.A < 1 || a.C < 1 || a.max_out < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(val_gather_kernel, dim3((unsigned)((a.max_out + 127) / 128), (unsigned)a.B), dim3(128), 0, s, a);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // joint-entropy ranking (:169-200): min-max normalised information gains, one block per image
 // ------------------------------------------------------------------------------------------------

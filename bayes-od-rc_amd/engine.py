@@ -332,6 +332,56 @@ class Engine(object):
         """validation_utils.post_process_predictions up to the NMS input (softmax, background filter, ranking)."""
         self._chk(self.lib.bod_validation_post(self.h))
 
+    # -- validation from ground-truth boxes (run_validation.py:230-260 + validation_utils.py:10-77) -------------
+    def _chk_val(self, st):
+        """Status of a validation entry point: a stage-order violation (no anchors, no forward, no NMS yet) is a RuntimeError,
+        a refused argument or handle a ValueError."""
+        if st == _lib.BOD_ERR_NOT_READY:
+            msg = self.lib.bod_last_error(self.h)
+            raise RuntimeError(msg.decode() if msg else "not ready")
+        self._chk(st)
+
+    def validation_losses_boxes(self, gt_boxes, gt_classes, min_positive_iou=0.5, max_negative_iou=0.4, do_classification=True,
+                                reg_kind=3, label_smoothing=0.001):
+        """Per-frame loss sums of the handle's current raw outputs (``bod_validation_losses_boxes``): [B,4] float64 rows
+        (sum of masked focal terms, sum of positive regression terms, sum of positive 0.5 sum(log D) terms, positives).
+        Ground truth as in train_step_boxes; the dense targets are assigned on the device."""
+        ng, boxes, classes = _pack_gt(gt_boxes, gt_classes, self.B, self.Ccls)
+        sums = np.empty((self.B, 4), np.float64)
+        self._chk_val(self.lib.bod_validation_losses_boxes(self.h, iptr(ng), fptr(boxes), fptr(classes), float(min_positive_iou),
+                                                           float(max_negative_iou), int(bool(do_classification)), int(reg_kind),
+                                                           float(label_smoothing), _lib.dptr(sums)))
+        return sums
+
+    def _val_records(self, num, scores, corners):
+        return [(scores[b, :num[b]].copy(), corners[b, :num[b]].copy()) for b in range(self.B)]
+
+    def validation_detections_batch(self):
+        """After validation_post() + nms(): per image (class rows [K,C], corners [K,4] as y1, x1, y2, x2 in network pixels) of
+        the selected candidates in soft-NMS order, gathered on the device (``bod_get_validation_detections_batch``)."""
+        num = np.empty(self.B, np.int32)
+        scores, corners = np.empty((self.B, self.K, self.Ccls), np.float32), np.empty((self.B, self.K, 4), np.float32)
+        self._chk_val(self.lib.bod_get_validation_detections_batch(self.h, iptr(num), fptr(scores), fptr(corners)))
+        return self._val_records(num, scores, corners)
+
+    def validate_boxes(self, images, gt_boxes, gt_classes, min_positive_iou=0.5, max_negative_iou=0.4, do_classification=True,
+                       reg_kind=3, label_smoothing=0.001):
+        """The validation loop body for a batch (``bod_validate_boxes``): forward, per-frame loss sums, validation post,
+        soft-NMS, record gather.  images=None uses the frames uploaded with upload_frames_u8 / upload_images.  Returns
+        (sums [B,4] float64, [(class rows [K,C], corners [K,4])] per image)."""
+        ng, boxes, classes = _pack_gt(gt_boxes, gt_classes, self.B, self.Ccls)
+        if images is None:
+            ptr, on_dev = self.lib.bod_device_images(self.h), 1
+        else:
+            img = self._img(images)
+            ptr, on_dev = img.ctypes.data, 0
+        sums, num = np.empty((self.B, 4), np.float64), np.empty(self.B, np.int32)
+        scores, corners = np.empty((self.B, self.K, self.Ccls), np.float32), np.empty((self.B, self.K, 4), np.float32)
+        self._chk_val(self.lib.bod_validate_boxes(self.h, ptr, on_dev, iptr(ng), fptr(boxes), fptr(classes), float(min_positive_iou),
+                                                  float(max_negative_iou), int(bool(do_classification)), int(reg_kind),
+                                                  float(label_smoothing), _lib.dptr(sums), iptr(num), fptr(scores), fptr(corners)))
+        return sums, self._val_records(num, scores, corners)
+
     def num_kept(self):
         out = np.zeros(self.B, np.int32)
         self._chk(self.lib.bod_get_num_kept(self.h, iptr(out)))

@@ -52,6 +52,7 @@ class RetinaNetModel(object):
         self.image_counter = 0
         self.prediction_dict = None
         self._weights = None
+        self._reg_loss = None
         self._engines = {}
         self._testing_overrides = {}
 
@@ -69,6 +70,7 @@ class RetinaNetModel(object):
                 d.setdefault(layer, {})[field] = z[k]
             weights = d
         self._weights = weights
+        self._reg_loss = None
         for e in self._engines.values():
             e.close()
         self._engines = {}
@@ -175,19 +177,56 @@ class RetinaNetModel(object):
                                   int('classification' in names), kind,
                                   float(losses.get('label_smoothing_epsilon', 0.001)), out)
         _lib.check(lib, None, st)
-        s_cls, s_cmp, s_reg, n_pos = out[0], out[1], out[2], out[3]
-        denom = max(n_pos, 1.0)
-        total, loss_dict = 0.0, {}
+        return loss_from_sums(names, weights, out)
+
+    def loss_kinds(self):
+        """(do_classification, reg_kind) of model_config['losses'] as the loss entry points take them; ValueError as get_loss."""
+        names = list(self.model_config['losses']['loss_names'])
         for n in names:
-            w = float(weights[names.index(n)])
-            if n == 'classification':
-                loss_dict['cls_loss'] = s_cls / denom * w
-                total += loss_dict['cls_loss']
-            elif n == 'regression':
-                loss_dict['reg_loss'] = s_cmp / denom * w
-                total += loss_dict['reg_loss']
-            else:
-                loss_dict['reg_loss'] = s_cmp / denom
-                loss_dict['covariance_loss'] = s_reg / denom
-                total += w * (s_cmp + s_reg) / denom
-        return total, loss_dict
+            if n != 'classification' and n not in self._REG_KIND:
+                raise ValueError('Invalid Loss! Not implemented yet.', n)
+        reg = [n for n in names if n in self._REG_KIND]
+        if len(reg) > 1:
+            raise ValueError("only one regression loss can be active")
+        return 'classification' in names, (self._REG_KIND[reg[0]] if reg else 0)
+
+    def regularization_loss(self):
+        """sum(model.losses) of the reference's val_single_step (run_validation.py:252-258): Keras l2(rate) = rate * sum(w^2)
+        over the kernels the training step regularises -- the head tower convolutions the model calls and ``pyramid_cov``
+        (multitask_headers.py:85-94,196-205,304-314) -- from the loaded fp32 weights, in float64, once per checkpoint."""
+        if self._weights is None:
+            raise ValueError("no weights loaded: call model.load_weights(...)")
+        if self._reg_loss is None:
+            rate = float(self.model_config['header'].get('l2_norm_rate', 1e-6))
+            layers = ['%s_%d' % (head, i) for head, n in _TOWER_CONVS[:3 if self.compute_covar else 2] for i in range(n)]
+            if self.compute_covar:
+                layers.append('pyramid_cov')
+            self._reg_loss = rate * sum(float(np.sum(np.square(np.asarray(self._weights[l]['kernel'], np.float64)))) for l in layers)
+        return self._reg_loss
+
+
+# tower convolutions each header calls (RegHeader builds a fourth one and never calls it: multitask_headers.py:209-230)
+_TOWER_CONVS = (('pyramid_classification', 4), ('pyramid_regression', 3), ('pyramid_cov', 4))
+
+
+def loss_from_sums(loss_names, loss_weights, sums4):
+    """``(total_loss, loss_dict)`` of get_loss (retinanet_model.py:183-323) from the four sums of the loss kernels -- masked
+    focal terms, positive regression terms, positive 0.5 sum(log D) terms, number of positives: the /max(n_pos, 1)
+    normalisation and the yaml loss weights.  One frame's sums give the reference's batch(1) validation losses."""
+    names, weights = list(loss_names), list(loss_weights)
+    s_cls, s_cmp, s_reg, n_pos = (float(v) for v in sums4)
+    denom = max(n_pos, 1.0)
+    total, loss_dict = 0.0, {}
+    for n in names:
+        w = float(weights[names.index(n)])
+        if n == 'classification':
+            loss_dict['cls_loss'] = s_cls / denom * w
+            total += loss_dict['cls_loss']
+        elif n == 'regression':
+            loss_dict['reg_loss'] = s_cmp / denom * w
+            total += loss_dict['reg_loss']
+        else:
+            loss_dict['reg_loss'] = s_cmp / denom
+            loss_dict['covariance_loss'] = s_reg / denom
+            total += w * (s_cmp + s_reg) / denom
+    return total, loss_dict

@@ -2,19 +2,27 @@
 src/retina_net/experiments/run_validation.py:27-228 (loop body :108-204, ``val_single_step`` :230-260):
 
     python -m bayes_od_rc_amd.run_validation --gpu_device 0 --yaml_path <yaml> [--data_split val]
-                                             [--dataset | --synthetic N --image_size H W] [--poll SECONDS]
+                                             [--dataset [--batch B] | --synthetic N --image_size H W] [--poll SECONDS]
 
 For every checkpoint of ``<data_dir>/outputs/<checkpoint_name>/checkpoints`` that ``evaluated_ckpts.txt`` does not list
 yet: one plain forward per frame (``train_val_test='validation'``: no MC dropout), the losses of the frame, the
 validation post-processing (softmax, background filter, soft-NMS on the top score: ``post_process_predictions``,
 validation_utils.py:10-77, on the device) and the predictions in the dataset's format under
 ``predictions/validation/<ckpt_id>/data`` (BDD: one ``predictions.json``; KITTI: one text file per frame), followed by
-the AP report when the frames carry BDD-format labels.  Differences from the reference, on purpose: checkpoints are
+the AP report when the frames carry BDD-format labels.
+
+Two routes.  Samples with dense anchor targets (``--synthetic``, callers of ``validate()`` with such samples) go frame by
+frame through ``val_single_step`` + ``post_process_predictions``.  Samples that carry the ground-truth boxes only
+(``--dataset``: the split is streamed, never held in memory) go ``--batch`` frames at a time through
+``Engine.validate_boxes``: the targets are assigned on the device, the raw head outputs stay there, and a batch comes back as
+per-frame loss sums and detection records.  Both report per-frame losses (the reference validates with ``batch(1)``: every
+frame is normalised by its own positive count); the batched route adds the reference's ``regularization_loss``.  Differences from the reference, on purpose: checkpoints are
 the ``.npz`` files ``run_training`` writes (the TF checkpoint format is ``convert_checkpoint``'s business), losses are
 returned / printed instead of going to TensorBoard, and the process stops after one pass unless ``--poll`` asks for the
 reference's wait-for-new-checkpoints loop.
 """
 import argparse
+import itertools
 import json
 import os
 import time
@@ -23,8 +31,11 @@ import numpy as np
 
 from . import config_utils, constants
 from .inference_utils import post_process_predictions
-from .model import RetinaNetModel
+from .model import RetinaNetModel, loss_from_sums
 from .writers import predictions_to_bdd_format, predictions_to_kitti_format, strip_checkpoint_id
+
+# validation_utils.post_process_predictions' own constants (:47-52), not testing_config.nms_config
+VALIDATION_NMS = {'max_output_size': 100, 'iou_threshold': 0.5, 'soft_nms_sigma': 0.5}
 
 
 def get_evaluated_ckpts(predictions_dir):
@@ -50,15 +61,106 @@ def val_single_step(model, sample_dict):
     return total_loss, loss_dict, prediction_dict
 
 
-def validate_checkpoint(config, checkpoint_path, samples, sample_ids, predictions_dir, categories=None):
-    """One checkpoint over the validation frames.  Returns {'ckpt_id', 'mean_total_loss', 'mean_losses', 'num_frames',
-    'num_detections', 'predictions'} ('predictions' = the BDD records, or None for KITTI)."""
+def _write_kitti(out_dir, sid, boxes, classes):
+    rows = predictions_to_kitti_format(boxes, classes)
+    np.savetxt(os.path.join(out_dir, sid + '.txt'), rows if rows.size else [], newline='\r\n', fmt='%s')
+
+
+def kitti_rescale(corners, net_hw, original_im_size):
+    """Corners in network-input pixels -> the frame's original pixels: the host expression of ``post_process_predictions``
+    (validation_utils.py:66-75)."""
+    orig = np.asarray(original_im_size).reshape(-1)[-3:]
+    n = np.asarray([net_hw[0], net_hw[1]] * 2, np.float32)
+    s = np.asarray([orig[0], orig[1]] * 2, np.float32)
+    return (corners / n) * s
+
+
+def flush_buckets(carry, batch):
+    """The partial buckets ``bucket_minibatches`` leaves behind at the end of a split, as tail batches of at most ``batch``
+    frames of one source size; ``carry`` is emptied."""
+    for key in sorted(carry):
+        rest = carry.pop(key)
+        while rest:
+            yield rest[:batch]
+            rest = rest[batch:]
+
+
+def validate_batch(model, config, batch):
+    """``len(batch)`` ground-truth-only samples of one source size through ``Engine.validate_boxes`` on a handle of that batch
+    size.  Returns per frame ``(total_loss, loss_dict, class rows [K,C], corners [K,4])``: the values ``val_single_step`` +
+    ``post_process_predictions`` give for the frame alone, plus the regularisation term (run_validation.py:252-258)."""
+    dataset_config = config['dataset_config']
+    first = batch[0][constants.IMAGE_NORMALIZED_KEY]
+    on_device_resize = first is None                       # KITTI: the pixels are produced on the device
+    hw = tuple(int(v) for v in dataset_config['kitti']['resize_shape']) if on_device_resize else tuple(first.shape[:2])
+    eng = model.engine_for(hw, batch=len(batch), mc_samples=1, nms_config=VALIDATION_NMS)
+    if not eng._anchors_set:
+        eng.set_anchors(np.asarray(batch[0][constants.ANCHORS_KEY], np.float32))
+    if 'image_uint8' in batch[0]:
+        eng.upload_frames_u8(np.stack([s['image_uint8'] for s in batch]),
+                             constants.MEANS_DICT[dataset_config.get('im_normalization', 'ImageNet')], aspect_resize=on_device_resize)
+        images = None
+    else:
+        images = np.stack([s[constants.IMAGE_NORMALIZED_KEY] for s in batch]).astype(np.float32)
+    anchor_config = dataset_config['anchor_generator']
+    losses = config['model_config']['losses']
+    do_cls, reg_kind = model.loss_kinds()
+    sums, detections = eng.validate_boxes(
+        images, [s[constants.BOXES_2D_GT_KEY] for s in batch], [s[constants.BOXES_CLASS_GT_KEY] for s in batch],
+        float(anchor_config['min_positive_iou']), float(anchor_config['max_negative_iou']), do_classification=do_cls,
+        reg_kind=reg_kind, label_smoothing=float(losses.get('label_smoothing_epsilon', 0.001)))
+    reg_loss = model.regularization_loss()
+    out = []
+    for b, sample in enumerate(batch):
+        total, loss_dict = loss_from_sums(losses['loss_names'], losses['loss_weights'], sums[b])
+        loss_dict['regularization_loss'] = reg_loss
+        classes, corners = detections[b]
+        if dataset_config['dataset'] == 'kitti':
+            corners = kitti_rescale(corners, hw, sample[constants.ORIGINAL_IM_SIZE_KEY])
+        out.append((total + reg_loss, loss_dict, classes, corners))
+    return out
+
+
+def _validate_batched(model, config, samples, sample_ids, out_dir, categories, batch):
+    """The batched route over an iterable of ground-truth-only samples, walked once and lazily: never more than one batch of
+    samples plus the partial size buckets alive.  Returns (records in dataset order, per-frame totals, loss sums, detections)."""
+    from .run_training import bucket_minibatches
     dataset = config['dataset_config']['dataset']
-    ckpt_id = strip_checkpoint_id(checkpoint_path[:-4] if checkpoint_path.endswith('.npz') else checkpoint_path)
-    out_dir = os.path.join(predictions_dir, 'validation', str(ckpt_id), 'data')
-    os.makedirs(out_dir, exist_ok=True)
-    model = RetinaNetModel(config['model_config'])
-    model.load_weights(checkpoint_path)
+    index_of, carry = {}, {}                              # id(sample) -> position in the dataset, for the samples alive
+
+    def indexed():
+        for i, sample in enumerate(samples):
+            index_of[id(sample)] = i
+            yield sample
+            del sample
+    per_frame, totals, sums, ndet = {}, {}, {}, 0
+
+    def run(frames):
+        nonlocal ndet
+        for sample, (total, loss_dict, classes, corners) in zip(frames, validate_batch(model, config, frames)):
+            i = index_of.pop(id(sample))
+            totals[i] = float(total)
+            for k, v in loss_dict.items():
+                sums[k] = sums.get(k, 0.0) + float(v)
+            ndet += len(corners)
+            if dataset == 'kitti':
+                _write_kitti(out_dir, sample_ids[i], corners, classes)
+            else:
+                per_frame[i] = predictions_to_bdd_format(corners, classes, sample_ids[i], category_list=categories)
+    stream = bucket_minibatches(indexed(), batch, carry)
+    for frames in stream:
+        run(frames)
+        frames = None                                     # (released before the stream reads on)
+    for frames in flush_buckets(carry, batch):
+        run(frames)
+        frames = None
+    records = [r for i in sorted(per_frame) for r in per_frame[i]]
+    return records, [totals[i] for i in sorted(totals)], sums, ndet
+
+
+def _validate_per_frame(model, config, samples, sample_ids, out_dir, categories, batch=1):
+    """The dense route: one frame at a time through ``val_single_step`` and ``post_process_predictions``."""
+    dataset = config['dataset_config']['dataset']
     records, totals, sums, ndet = [], [], {}, 0
     for sample, sid in zip(samples, sample_ids):
         total_loss, loss_dict, prediction_dict = val_single_step(model, sample)
@@ -70,11 +172,35 @@ def validate_checkpoint(config, checkpoint_path, samples, sample_ids, prediction
         classes, boxes = post_process_predictions(batched, prediction_dict, dataset_name=dataset)
         ndet += len(boxes)
         if dataset == 'kitti':
-            rows = predictions_to_kitti_format(boxes, classes)
-            path = os.path.join(out_dir, sid + '.txt')
-            np.savetxt(path, rows if rows.size else [], newline='\r\n', fmt='%s')
+            _write_kitti(out_dir, sid, boxes, classes)
         else:
             records.extend(predictions_to_bdd_format(boxes, classes, sid, category_list=categories))
+    return records, totals, sums, ndet
+
+
+def _put_back(head, rest):
+    """``head`` (a list, emptied) in front of the iterator ``rest``, keeping no reference to what has been handed out."""
+    while head:
+        yield head.pop(0)
+    yield from rest
+
+
+def validate_checkpoint(config, checkpoint_path, samples, sample_ids, predictions_dir, categories=None, batch=8):
+    """One checkpoint over the validation frames.  Returns {'ckpt_id', 'mean_total_loss', 'mean_losses', 'num_frames',
+    'num_detections', 'predictions'} ('predictions' = the BDD records, or None for KITTI).  ``samples``: an iterable of
+    sample dicts, or a callable that returns one (a streamed split is read once per checkpoint).  Samples without dense
+    targets take the batched route, ``batch`` frames per call."""
+    dataset = config['dataset_config']['dataset']
+    ckpt_id = strip_checkpoint_id(checkpoint_path[:-4] if checkpoint_path.endswith('.npz') else checkpoint_path)
+    out_dir = os.path.join(predictions_dir, 'validation', str(ckpt_id), 'data')
+    os.makedirs(out_dir, exist_ok=True)
+    model = RetinaNetModel(config['model_config'])
+    model.load_weights(checkpoint_path)
+    stream = iter(samples() if callable(samples) else samples)
+    head = list(itertools.islice(stream, 1))
+    batched = bool(head) and constants.ANCHORS_CLASS_TARGETS_KEY not in head[0]        # the test Trainer.train_single_step uses
+    route = _validate_batched if batched else _validate_per_frame
+    records, totals, sums, ndet = route(model, config, _put_back(head, stream), sample_ids, out_dir, categories, int(batch))
     if dataset != 'kitti':
         with open(os.path.join(out_dir, 'predictions.json'), 'w') as fp:
             json.dump(records, fp, indent=4, separators=(',', ': '))
@@ -93,9 +219,10 @@ def list_checkpoints(checkpoint_dir):
     return sorted(found)
 
 
-def validate(config, samples, sample_ids, categories=None, gt_records=None, poll_seconds=None, max_polls=None):
+def validate(config, samples, sample_ids, categories=None, gt_records=None, poll_seconds=None, max_polls=None, batch=8):
     """The loop of run_validation.py:86-228: every checkpoint not yet listed in evaluated_ckpts.txt, in id order; with
-    ``poll_seconds`` keep waiting for new ones (``max_polls`` bounds the waiting, for tests)."""
+    ``poll_seconds`` keep waiting for new ones (``max_polls`` bounds the waiting, for tests).  ``samples`` / ``batch``: see
+    ``validate_checkpoint``."""
     root = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'])
     checkpoint_dir = os.path.join(root, 'checkpoints')
     predictions_dir = os.path.join(root, 'predictions')
@@ -109,7 +236,7 @@ def validate(config, samples, sample_ids, categories=None, gt_records=None, poll
             if ckpt_id in done or ckpt_id <= last_id:
                 continue
             print('\nRunning checkpoint ' + str(ckpt_id) + '\n')
-            r = validate_checkpoint(config, path, samples, sample_ids, predictions_dir, categories)
+            r = validate_checkpoint(config, path, samples, sample_ids, predictions_dir, categories, batch=batch)
             if gt_records is not None and r['predictions'] is not None:
                 from .offline_eval import ap_report
                 r['ap'] = ap_report(gt_records, r['predictions']) if r['predictions'] else None
@@ -136,14 +263,19 @@ def main(argv=None):
     ap.add_argument('--image_size', type=int, nargs=2, default=[256, 256])
     ap.add_argument('--poll', type=int, default=0, help='seconds between scans for new checkpoints (0: one pass)')
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--batch', type=int, default=8, help='frames per call on the --dataset route (frames are bucketed by source size)')
     args = ap.parse_args(argv)
+    if args.batch < 1:
+        ap.error('--batch must be at least 1')
     config = config_utils.setup(config_utils.load_yaml(args.yaml_path), args)
     dataset_config = config['dataset_config']
     categories = None
     if args.dataset:
         from . import datasets
+        # the split is streamed, once per checkpoint: samples carry the GT boxes only (the targets are assigned on the device)
         handler = datasets.build_dataset(dataset_config, args.data_split)
-        samples, sample_ids = list(handler.create_dataset()), list(handler.sample_ids)
+        handler.dense_targets = False
+        samples, sample_ids = handler.create_dataset, list(handler.sample_ids)
         categories = handler.training_data_config['categories'] if dataset_config['dataset'] == 'bdd' else None
     else:
         from .run_training import synthetic_samples
@@ -151,7 +283,7 @@ def main(argv=None):
         samples = synthetic_samples(args.synthetic, args.image_size, dataset_config['anchor_generator'], num_classes, seed=args.seed)
         sample_ids = ['synthetic_%04d.jpg' % i for i in range(len(samples))]
         categories = ['car', 'truck', 'bus', 'person', 'rider', 'bike', 'motor'][:num_classes]
-    return validate(config, samples, sample_ids, categories=categories, poll_seconds=args.poll or None)
+    return validate(config, samples, sample_ids, categories=categories, poll_seconds=args.poll or None, batch=args.batch)
 
 
 if __name__ == '__main__':

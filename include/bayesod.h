@@ -359,6 +359,36 @@ bod_status bod_anchor_targets(int32_t device, int32_t A, const float* anchors_vu
                               float max_negative_iou, float* cls_targets, float* box_targets, uint8_t* positive_mask,
                               uint8_t* negative_mask, int32_t* best_gt, float* best_iou);
 
+/* ---- validation from ground-truth boxes (src/retina_net/experiments/run_validation.py:230-260 val_single_step, followed by
+ * validation_utils.post_process_predictions, :10-77), for `batch` frames of an inference handle with mc_samples = 1; the raw head
+ * outputs, the dense targets and the candidates never leave the device.  The three calls return BOD_ERR_INVALID_ARG for a
+ * training handle, mc_samples != 1, reg_kind >= 2 without the covariance head, a class count other than 4 or 8 and
+ * num_gt[b] < 1, and BOD_ERR_NOT_READY for missing anchors, a missing forward or a missing bod_nms.
+ *
+ * model.get_loss(sample_dict, prediction_dict) of val_single_step (:247-258) per frame: stage entry on the handle's current raw
+ * outputs (after bod_forward or bod_set_raw; MC sample 0).  The ground truth is given as to bod_train_step_boxes: num_gt[b] >= 1
+ * rows per frame (the placeholder row [0,0,1,1] with the background class for a frame without boxes), gt_boxes_vuvu [sum G,4],
+ * gt_classes [sum G,C].  The dense targets are assigned on the device by the kernel of bod_anchor_targets into buffers the handle
+ * allocates on its first validation call; the loss terms are those of bod_loss_forward (do_classification, reg_kind and
+ * label_smoothing as there), summed per frame: sums4 [batch][4] = {sum of masked focal terms, sum of positive regression terms,
+ * sum of positive 0.5*sum(log D) terms, number of positives}.  Block partials are added in double in a fixed order: a frame's four
+ * sums are bitwise independent of the batch it sits in and of its position there. */
+bod_status bod_validation_losses_boxes(bod_handle h, const int32_t* num_gt, const float* gt_boxes_vuvu, const float* gt_classes,
+                                       float min_positive_iou, float max_negative_iou, int32_t do_classification,
+                                       int32_t reg_kind, float label_smoothing, double* sums4);
+/* The return value of validation_utils.post_process_predictions (:62-77) for every image, after bod_validation_post and bod_nms:
+ * the class rows and the corners (y1, x1, y2, x2; network-input pixels) of the selected candidates in soft-NMS order, gathered on
+ * the device and copied with one copy per array and one synchronise.  num_detections [batch]; scores [batch,max_detections,C];
+ * corners [batch,max_detections,4]; rows >= num_detections[b] are zero.  NULLs skipped. */
+bod_status bod_get_validation_detections_batch(bod_handle h, int32_t* num_detections, float* scores, float* corners);
+/* The loop body of run_validation.py:108-204 for `batch` frames -- val_single_step, then post_process_predictions: forward, loss
+ * sums, validation post, NMS, record gather on one stream, no host round trip until the final copies.  images as in bod_forward;
+ * the other arguments and the results as in the two calls above, which it equals bit for bit. */
+bod_status bod_validate_boxes(bod_handle h, const float* images, int32_t images_on_device, const int32_t* num_gt,
+                              const float* gt_boxes_vuvu, const float* gt_classes, float min_positive_iou,
+                              float max_negative_iou, int32_t do_classification, int32_t reg_kind, float label_smoothing,
+                              double* sums4, int32_t* num_detections, float* scores, float* corners);
+
 /* Gradient of  total = w_cls * S_cls / max(n_pos,1) + w_reg * (S_cmp + S_reg) / max(n_pos,1)  (the reference's
  * total_loss before the L2 term, retinanet_model.py:183-323) with respect to the raw head outputs: dcls [B,A,C],
  * dbox [B,A,4], dcov [B,A,10] (NULL = not wanted).  Arguments as bod_loss_forward; out4 receives the same sums.

@@ -132,6 +132,14 @@ bod_status bod_anchor_targets(int32_t device, int32_t A, const float* anchors_vu
                               const float* gt_boxes_vuvu, const float* gt_classes, int32_t C, float min_positive_iou,
                               float max_negative_iou, float* cls_targets, float* box_targets, uint8_t* positive_mask,
                               uint8_t* negative_mask, int32_t* best_gt, float* best_iou);
+bod_status bod_validation_losses_boxes(bod_handle h, const int32_t* num_gt, const float* gt_boxes_vuvu, const float* gt_classes,
+                                       float min_positive_iou, float max_negative_iou, int32_t do_classification,
+                                       int32_t reg_kind, float label_smoothing, double* sums4);
+bod_status bod_get_validation_detections_batch(bod_handle h, int32_t* num_detections, float* scores, float* corners);
+bod_status bod_validate_boxes(bod_handle h, const float* images, int32_t images_on_device, const int32_t* num_gt,
+                              const float* gt_boxes_vuvu, const float* gt_classes, float min_positive_iou,
+                              float max_negative_iou, int32_t do_classification, int32_t reg_kind, float label_smoothing,
+                              double* sums4, int32_t* num_detections, float* scores, float* corners);
 bod_status bod_loss_backward(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls,
                              const float* cls_targets, const float* box, const float* box_targets,
                              const float* covar_params, const float* anchors, const uint8_t* positive_mask,
