@@ -749,9 +749,7 @@ hipError_t launch_stem_conv(const float* img, const float* w, const float* bias,
     const int segs = (ow + ST_SEG - 1) / ST_SEG;
     const int ntasks = B * oh * segs;
     const int grid = ntasks < 1024 ? ntasks : 1024;
-    static const bool f32_stem = getenv("BOD_STEM_F32") && atoi(getenv("BOD_STEM_F32")) == 1;     // A/B aid: the exact-fp32 kernel in bf16 mode
     if (out_f32) hipLaunchKernelGGL(stem_conv_kernel<true>, dim3(grid), dim3(256), 0, s, img, w, bias, out, B, H, W, oh, ow);
-    else if (f32_stem) hipLaunchKernelGGL(stem_conv_kernel<false>, dim3(grid), dim3(256), 0, s, img, w, bias, out, B, H, W, oh, ow);
     else {
         static const bool old_stem = getenv("BOD_STEM_SEG64") && atoi(getenv("BOD_STEM_SEG64")) == 1;   // A/B aid: the 64-pixel-task kernel (bit-identical outputs)
         if (old_stem || (W & 3) || (reinterpret_cast<uintptr_t>(img) & 15)) {            // (16-byte row loads: rows of W*3 floats from a 16-byte aligned base)

@@ -907,7 +907,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
             // weight offsets of the K-tiles one and two ahead: K-tile t is tap t % 9 of channel chunk t / 9
             int wo1 = a.cin * 2, tap1 = 1, wo2 = 2 * a.cin * 2, tap2 = 2;
             auto w_advance = [&](int& wo, int& tap) { if (++tap == 9) { tap = 0; wo += BK * 2 - 8 * a.cin * 2; } else wo += a.cin * 2; };
-            // ConvArgs.mx_loader == 1 (round 5, A/B switch BOD_TOWER_LOADER): the lower four waves -- one per SIMD -- issue the weight pieces of
+            // ConvArgs.mx_loader == 1 (round 5; the engine plans it on f16mx launches only): the lower four waves -- one per SIMD -- issue the weight pieces of
             // both waves of their SIMD (their own 8 rows of a piece and the rows + 32 of wave + 4), the upper four none (f16mx loop: -0.9 %)
             const bool w_pair = a.mx_loader == 1;
             auto dma_w = [&](int piece, int wo, int stage_) {
@@ -2016,7 +2016,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
                 const uint4 vh = *reinterpret_cast<const uint4*>(prow + (((ch ^ lr) & (CPR2 - 1)) << 4));
                 const uint4 vl = *reinterpret_cast<const uint4*>(prow + ((((ch + 4) ^ lr) & (CPR2 - 1)) << 4));
                 const size_t e = ((size_t)off + (size_t)n * a.fan_stride) * a.out_cstride + bc0 * 2 + ch * 8;
-                if (MXK != 0 && (a.flags & CONV_NT_OUT)) {        // f16mx towers, BOD_NT_STORES bits 3 / 4: streaming stores (A/B switch)
+                if (MXK != 0 && (a.flags & CONV_NT_OUT)) {        // f16mx towers: streaming stores (no effect measured; launch_conv_igemm never sets the flag on mx launches)
                     __builtin_nontemporal_store(u32x4{vh.x, vh.y, vh.z, vh.w}, reinterpret_cast<u32x4*>(out16 + e));
                     __builtin_nontemporal_store(u32x4{vl.x, vl.y, vl.z, vl.w}, reinterpret_cast<u32x4*>(out16 + e + 32));
                     continue;
@@ -2615,7 +2615,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
             const int c16 = (cp ^ pixl) & (CPR - 1);
             const size_t e = ((size_t)off + (size_t)n * a.fan_stride) * a.out_cstride + bc0 + c16 * 8;
             if (ABL == 30) { if (v.x == 0x12345678u && e == 0) *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(G.out)) = v; continue; }
-            // (variant 86, BOD_NT_STORES=1: non-temporal stores for the generic kernel's outputs -- A/B)
+            // (non-temporal stores for the generic kernel's outputs: launch_conv_igemm sets the flag on the fan-out launch alone)
             if (nt_out) __builtin_nontemporal_store(u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4*>(reinterpret_cast<uint16_t*>(G.out) + e));
             else *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(G.out) + e) = v;
             if (CAN_RES && G.out_relu) {
@@ -2966,26 +2966,15 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvArgs 
 // (measured on the stage-4 / FPN layers: 128 big tiles for 256 CUs).
 // The N-way dropout fan-out layer takes the big tile too (from 1 024 tiles on) since its epilogue keeps the tile in
 // registers across the samples (1.9-2.0 ms on 256x256 tiles vs 2.2 ms on 128x128 at 64 frames; the older epilogue, an
-// LDS round trip and two barriers per sample, preferred two co-resident 128x128 workgroups).  BOD_FAN_SMALL=1: A/B aid.
-static bool fan_out_small_tile() {
-    static const bool small = getenv("BOD_FAN_SMALL") && atoi(getenv("BOD_FAN_SMALL")) == 1;
-    return small;
-}
-
+// LDS round trip and two barriers per sample, preferred two co-resident 128x128 workgroups).
 static bool conv_big_tile_pays(const ConvArgs& a) {
     // fp32 accumulate-in-place launches (training: input gradients) take the big tile from 96 tiles on (measured on the
-    // training step, batch 8 and 32); other fp32-output launches never do.  BOD_F32_BIG_TILES=0 disables, =n moves the threshold
-    static const int f32_min_tiles = getenv("BOD_F32_BIG_TILES") ? atoi(getenv("BOD_F32_BIG_TILES")) : 96;
+    // training step, batch 8 and 32); other fp32-output launches never do
+    constexpr long kF32MinBigTiles = 96;
     if (a.cout_pad % 256 != 0) return false;
-    static const bool old_rule = getenv("BOD_TILE_RULE_OLD") != nullptr;          // A/B aid
-    if (old_rule) return a.M >= 16384 && !(a.flags & CONV_OUT_F32);
     const long tiles = (long)((a.M + 255) / 256) * (a.cout_pad / 256) * (a.groups > 0 ? a.groups : 1);
-    if (a.flags & CONV_OUT_F32) return (a.flags & CONV_ACCUM) && f32_min_tiles > 0 && tiles >= f32_min_tiles;
+    if (a.flags & CONV_OUT_F32) return (a.flags & CONV_ACCUM) && tiles >= kF32MinBigTiles;
     if (a.fan_count > 1) return tiles >= 1024;        // (fan-out layer: -1 % at 513 tiles, +0.5 % from 1 026 on)
-    // BOD_SMALL_TILE_MAXK=k (A/B aid): layers whose reduction is at most k (taps * cin: the memory-bound 1x1 layers of res2 / res3
-    // have 64 / 128) take the 128x128 tile, two workgroups per CU, whatever their tile count
-    static const int small_maxk = getenv("BOD_SMALL_TILE_MAXK") ? atoi(getenv("BOD_SMALL_TILE_MAXK")) : 0;
-    if (small_maxk > 0 && a.taps > 0 && a.cin > 0 && a.taps * a.cin <= small_maxk && !a.xreuse && a.fan_count <= 1) return false;
     return tiles >= 384;
 }
 
@@ -3002,7 +2991,6 @@ bool conv_igemm_uses_full_cout_tile(const ConvArgs& a) {
     // overrides the size heuristic (tests exercise both configurations on small inputs)
     static const int forced = [] { const char* e = getenv("BOD_FORCE_CONV_TILE"); return e ? atoi(e) : 0; }();
     bool big = conv_big_tile_pays(a);
-    if (a.fan_count > 1 && fan_out_small_tile()) big = false;
     if (forced == 256) big = a.cout_pad % 256 == 0 && !(a.flags & CONV_OUT_F32);
     if (forced == 128) big = false;
     return big && a.cout_pad == 256;
@@ -3012,27 +3000,18 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     ConvArgs a_local = a_in;
     // a threshold of 0 keeps every element (rate < 2^-16): the packed keep-mask needs threshold >= 1, so run without dropout
     if ((a_local.flags & CONV_DROPOUT) && a_local.drop_threshold == 0) a_local.flags &= ~CONV_DROPOUT;
-    // BOD_RES_REGISTER=1: residuals read from global memory in the accumulator layout instead of through the LDS tile (A/B aid)
-    static const bool res_register = getenv("BOD_RES_REGISTER") && atoi(getenv("BOD_RES_REGISTER")) == 1;
-    if (res_register && a_local.variant == 0 && !a_local.xreuse && !a_local.split && a_local.ksplit <= 1) a_local.variant = 82;
-    // BOD_NT_STORES (default 4; 0 = plain stores everywhere): bit 0 = non-temporal output stores in the generic kernel (backbone / FPN), bit 1 = in
-    // the row-reuse kernels (head towers, fan-out launch).  Measured on one box, 256 frames: backbone -0.35 ms with bit 0, the tower
-    // launches +0.5 ms beside it (net 0); bit 1 costs the towers 1 % and the fan-out launch 4 %: the outputs are re-read by the next
-    // launch's neighbouring tiles through L2 after all.  Kept as an A/B switch.
-    static const int nt_stores = getenv("BOD_NT_STORES") ? atoi(getenv("BOD_NT_STORES")) : 4;      // (round 5: bit 2 on -- the fan-out launch, 13.5 -> 13.2 ms per 512 frames in two same-box A/B pairs)
-    // bit 2 (round 5): the fan-out launch ALONE -- its ten masked copies (42.9 GB per 512 frames) are what pushes the three heads' weights
-    // and the shared pyramid rows out of L2 (11.2 GB fetched for 1.4 GB algorithmic, profiles/round4_head_conv_pmc.json launch 0)
-    if (!(a_local.flags & CONV_OUT_F32) && !a_local.split && a_local.ksplit <= 1 &&
-        (((nt_stores & 1) && !a_local.xreuse) || ((nt_stores & 2) && a_local.xreuse) || ((nt_stores & 4) && a_local.xreuse && a_local.fan_count > 1)))
+    // Non-temporal output stores for the bf16 fan-out launch ALONE (13.5 -> 13.2 ms per 512 frames in two same-box A/B pairs): its ten
+    // masked copies (42.9 GB per 512 frames) are what pushes the three heads' weights and the shared pyramid rows out of L2 (11.2 GB
+    // fetched for 1.4 GB algorithmic, profiles/round4_head_conv_pmc.json launch 0).  Anywhere else they measured no gain or a loss
+    // (256 frames, one box: in the generic kernel backbone -0.35 ms but the tower launches +0.5 ms beside it; on every row-reuse launch
+    // the towers +1 %: their outputs are re-read by the next launch's neighbouring tiles through L2 after all; f16mx towers: no effect).
+    if (!(a_local.flags & CONV_OUT_F32) && !a_local.split && a_local.ksplit <= 1 && a_local.xreuse && a_local.fan_count > 1)
         a_local.flags |= CONV_NT_OUT;
-    // bits 3 / 4 (f16mx towers): the per-sample tower layers' hx outputs / the first layer's ten-fold hx outputs
-    if (a_local.mx && (((nt_stores & 8) && a_local.fan_count <= 1) || ((nt_stores & 16) && a_local.fan_count > 1))) a_local.flags |= CONV_NT_OUT;
-    {   // Work-item order of the fan-out launch (kernels.h ConvArgs.fan_chunk). Measured round 6 (profiles/round6_mx_ablations.txt,
-        // "fan-out work-item order"): chunks of 8..64 tiles are 0.9 % faster than the interleaved order (12.62 against 12.73 ms at
-        // 512 frames), all the same within noise; 16 is the default, BOD_FAN_CHUNK=0 gives the interleaved order back.
-        static const int fan_chunk = getenv("BOD_FAN_CHUNK") ? atoi(getenv("BOD_FAN_CHUNK")) : 16;
-        a_local.fan_chunk = (a_local.fan_count > 1 && a_local.groups > 1 && !a_local.mx && !a_local.split) ? fan_chunk : 0;
-    }
+    // Work-item order of the fan-out launch (kernels.h ConvArgs.fan_chunk). Measured round 6 (profiles/round6_mx_ablations.txt,
+    // "fan-out work-item order"): chunks of 8..64 tiles are 0.9 % faster than the interleaved order (12.62 against 12.73 ms at
+    // 512 frames), all the same within noise
+    constexpr int kFanChunk = 16;
+    a_local.fan_chunk = (a_local.fan_count > 1 && a_local.groups > 1 && !a_local.mx && !a_local.split) ? kFanChunk : 0;
     const ConvArgs& a = a_local;
     if (a.M <= 0) return hipSuccess;
     if (a.tile_count && (a.mx || a.split || !a.xreuse || a.ksplit > 1)) return hipErrorInvalidValue;       // (the bf16 row-reuse loop only)
@@ -3059,13 +3038,12 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     return hipErrorInvalidValue;
 #else
     static const int forced = [] { const char* e = getenv("BOD_FORCE_CONV_TILE"); return e ? atoi(e) : 0; }();
-    if (!forced && !(a.flags & CONV_NT_OUT) && conv_pointwise_eligible(a)) return launch_conv_pointwise(a, s);   // streaming 1x1 kernel (bit-identical)
-    if (!forced && !(a.flags & CONV_NT_OUT) && conv_slide3x3_eligible(a)) return launch_conv_slide3x3(a, s);     // sliding-window 3x3, 64 -> 64 (bit-identical)
+    if (!forced && conv_pointwise_eligible(a)) return launch_conv_pointwise(a, s);   // streaming 1x1 kernel (bit-identical)
+    if (!forced && conv_slide3x3_eligible(a)) return launch_conv_slide3x3(a, s);     // sliding-window 3x3, 64 -> 64 (bit-identical)
     // a fused "next block's 2a" (ch_w3 without the chain's ch_w2) exists only in the pointwise kernel: a plan that carries one must
     // never fall through to the generic kernel, which would run the expansion and silently skip the reduction
     if (a.g[0].ch_w3 && !a.g[0].ch_w2) return hipErrorInvalidValue;
     bool big = conv_big_tile_pays(a);
-    if (a.fan_count > 1 && fan_out_small_tile()) big = false;
     if (forced == 256) big = a.cout_pad % 256 == 0 && !(a.flags & CONV_OUT_F32);
     if (forced == 128) big = false;
     for (int g = 0; g < a.groups; ++g)

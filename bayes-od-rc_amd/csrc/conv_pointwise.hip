@@ -285,9 +285,8 @@ bool conv_pointwise_eligible(const ConvArgs& a) {
     // (512-channel reductions WITH shortcut need two output buffers and fit one workgroup per CU only: +0.55 ms per 256-frame step
     //  against the generic kernel, not kept)
     // 512-channel reductions WITHOUT shortcut (stage 3's `2a`, stage 4's first block, the C3 lateral of the FPN): 128 weight registers,
-    // 32-pixel tiles and a single output buffer keep two workgroups on a CU; -0.1 ms per 256-frame step (BOD_PW_K512=0: generic)
-    static const bool k512 = [] { const char* e = getenv("BOD_PW_K512"); return !e || atoi(e) != 0; }();
-    if (a.cin != 64 && a.cin != 128 && a.cin != 256 && !(k512 && a.cin == 512 && !g.res)) return false;
+    // 32-pixel tiles and a single output buffer keep two workgroups on a CU; -0.1 ms per 256-frame step against the generic kernel
+    if (a.cin != 64 && a.cin != 128 && a.cin != 256 && !(a.cin == 512 && !g.res)) return false;
     // (64-channel cout tiles -- stage 2's `2a` reductions -- measured on this kernel: no difference to the generic 64x128 tiles, three
     //  workgroups per CU, that run them now; not kept)
     if (a.cout_pad % 128 != 0 || a.cout_valid != a.cout_pad) return false;
@@ -321,10 +320,10 @@ hipError_t launch_conv_pointwise(const ConvArgs& a, hipStream_t s) {
 // 576 k) live in registers; four waves = 2 cout halves x 2 pixel fragments.  Same MFMA (32x32x16), same k order (taps outer, 16-
 // channel steps inner within the single 64-channel chunk) and epilogue as the generic kernel: bit-identical.
 // ------------------------------------------------------------------------------------------------------------------------------
-template <int LEAD>
 __global__ __launch_bounds__(256, 2) void slide3x3_c64_kernel(const ConvArgs a, int nstrips, int xsegs) {
     constexpr int SLOT = 66 * 128;                // bytes per ring slot: 64 + 2 halo pixels x 64 channels
-    constexpr int RING = LEAD == 1 ? 4 : 6;       // rows y .. y+2 in use + LEAD rows landing / in flight (a power of two for one row ahead)
+    constexpr int LEAD = 1;                       // rows of prefetch (a named constant: the expressions below compile to the measured code as spelled)
+    constexpr int RING = 4;                       // rows y .. y+2 in use + LEAD rows landing / in flight (a power of two)
     constexpr int OB = 64 * 128;                  // one output row tile [64 px][64 ch] bf16
     extern __shared__ __attribute__((aligned(16))) char sl_smem[];
     char* const ring = sl_smem;                   // [RING][SLOT]
@@ -374,22 +373,16 @@ __global__ __launch_bounds__(256, 2) void slide3x3_c64_kernel(const ConvArgs a, 
         };
         __syncthreads();                          // the previous strip's last reads of the ring / output tiles are done
         issue_row(0); issue_row(1); issue_row(2);
-        if (LEAD == 2 && H >= 2) issue_row(3);
         for (int y = 0; y < H; ++y) {
             const bool pre = y + LEAD < H;        // row y+2+LEAD exists (the padded plane has H+2 rows)
             if (pre) issue_row(y + 2 + LEAD);
             asm volatile("" ::: "memory");
             // rows y .. y+2 have landed once at most the instructions issued BEHIND row y+2's pieces are outstanding (vmcnt retires in
-            // issue order): the pieces of rows y+3 and y+4 (D each: 3 on wave 0, 2 elsewhere) and the two stores of each of the last
-            // two output rows.  The last two rows of a strip wait for everything.
+            // issue order): the pieces of row y+3 (3 on wave 0, 2 elsewhere) and the two stores of the previous output row.  The last
+            // row of a strip waits for everything.
             if (!pre) pw_wait_vm<0>();
-            else if (LEAD == 2) {
-                if (wave == 0) { if (y == 0) pw_wait_vm<6>(); else if (y == 1) pw_wait_vm<8>(); else pw_wait_vm<10>(); }
-                else { if (y == 0) pw_wait_vm<4>(); else if (y == 1) pw_wait_vm<6>(); else pw_wait_vm<8>(); }
-            } else {
-                if (wave == 0) { if (y == 0) pw_wait_vm<3>(); else pw_wait_vm<5>(); }
-                else { if (y == 0) pw_wait_vm<2>(); else pw_wait_vm<4>(); }
-            }
+            else if (wave == 0) { if (y == 0) pw_wait_vm<3>(); else pw_wait_vm<5>(); }
+            else { if (y == 0) pw_wait_vm<2>(); else pw_wait_vm<4>(); }
             __syncthreads();
             pw_f32x16 acc;
 #pragma unroll
@@ -617,24 +610,20 @@ hipError_t launch_conv_slide3x3(const ConvArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(slide3x3_c128_kernel, dim3(std::min(nstrips, launch_cus(a))), dim3(512), LDS128, s, a, nstrips, xsegs);
         return hipGetLastError();
     }
-    constexpr int LDS = 6 * 66 * 128 + 2 * 64 * 128;
+    constexpr int LDS = 4 * 66 * 128 + 2 * 64 * 128;
     static PerDeviceOnce once;
     bool& attr_set = *once.slot();
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(slide3x3_c64_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(slide3x3_c64_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(slide3x3_c64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         if (e != hipSuccess) return e;
         attr_set = true;
     }
     const int xsegs = (a.plane_w + 63) / 64;
     const int nstrips = a.M / (a.plane_h * a.plane_w) * xsegs;
-    // rows of prefetch: one (default) or two (BOD_SLIDE_LEAD=2).  Measured per 256-frame step, same box: backbone 22.96 ms with one row
-    // ahead, 23.11-23.17 with two (a sixth ring slot and longer wait chains for nothing: the row in flight is not what a row waits for),
-    // 23.69 on the generic kernel
-    static const int lead = [] { const char* e = getenv("BOD_SLIDE_LEAD"); return e ? atoi(e) : 1; }();
+    // one row of prefetch.  Measured per 256-frame step, same box: backbone 22.96 ms with one row ahead, 23.11-23.17 with two (a sixth
+    // ring slot and longer wait chains for nothing: the row in flight is not what a row waits for), 23.69 on the generic kernel
     const int wgs = std::min(nstrips, 2 * launch_cus(a));             // two workgroups per compute unit; the rest of the strips in further rounds
-    if (lead == 2) hipLaunchKernelGGL(slide3x3_c64_kernel<2>, dim3(wgs), dim3(256), LDS, s, a, nstrips, xsegs);
-    else hipLaunchKernelGGL(slide3x3_c64_kernel<1>, dim3(wgs), dim3(256), 4 * 66 * 128 + 2 * 64 * 128, s, a, nstrips, xsegs);
+    hipLaunchKernelGGL(slide3x3_c64_kernel, dim3(wgs), dim3(256), LDS, s, a, nstrips, xsegs);
     return hipGetLastError();
 }
 
@@ -643,9 +632,7 @@ hipError_t launch_conv_slide3x3(const ConvArgs& a, hipStream_t s) {
 bool conv_pointwise_can_fuse_next(const ConvArgs& a) {
     static const bool on = [] { const char* e = getenv("BOD_PW_FUSE_NEXT"); return !e || atoi(e) != 0; }();
     static const bool forced = [] { const char* e = getenv("BOD_FORCE_CONV_TILE"); return e && atoi(e) != 0; }();
-    static const bool nt = [] { const char* e = getenv("BOD_NT_STORES"); return e && (atoi(e) & 1); }();
-    static const bool res_reg = [] { const char* e = getenv("BOD_RES_REGISTER"); return e && atoi(e) == 1; }();   // (sends the launch to a variant build)
-    if (!on || forced || nt || res_reg) return false;
+    if (!on || forced) return false;
     return a.cin == 64 && a.cout_pad == 256 && a.g[0].res && conv_pointwise_eligible(a);
 }
 
@@ -653,8 +640,6 @@ bool conv_pointwise_can_fuse_next(const ConvArgs& a) {
 bool conv_pointwise_can_fuse_dual(const ConvArgs& a) {
     static const bool on = [] { const char* e = getenv("BOD_PW_FUSE_DUAL"); return !e || atoi(e) != 0; }();
     static const bool forced = [] { const char* e = getenv("BOD_FORCE_CONV_TILE"); return e && atoi(e) != 0; }();
-    static const bool nt = [] { const char* e = getenv("BOD_NT_STORES"); return e && (atoi(e) & 1); }();
-    static const bool res_reg = [] { const char* e = getenv("BOD_RES_REGISTER"); return e && atoi(e) == 1; }();
-    if (!on || forced || nt || res_reg) return false;
+    if (!on || forced) return false;
     return a.cin == 64 && a.cout_pad == 256 && !a.g[0].res && !(a.flags & CONV_RELU) && conv_pointwise_eligible(a);
 }

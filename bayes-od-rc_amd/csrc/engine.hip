@@ -292,7 +292,6 @@ struct bod_context {
     // kept anchor only; their statistics [agg[1], agg[2]] then exist for the anchors kept at (keep_seed, keep_first) alone.
     bool plan_sparse = false;
     bool plan_halo = false;                              // ... and box layer 1 / covariance layer 2 over the tail's 3x3 halo
-    int dense_plain_tiles = 0;                           // (BOD_SPARSE_STATS)
     SparseTailArgs sparse{};
     bool agg_sparse = false;                             // the last forward's agg[1] / agg[2] are sparse
     bool keep_ready = false;                             // pb.keep / d_counts / block_counts / num_kept hold the keep stage's output
@@ -964,13 +963,11 @@ bod_status build_plan(bod_context* h) {
         return BOD_OK;
     };
     if (xreuse) BODCHK(make_xr_tiles(t2, &d2x, &dext, &m2x));
-    h->dense_plain_tiles = m2x / 256;
     // the first tower layer (one convolution per image, N-way dropout fan-out epilogue) takes the row-reuse loop too once
     // its launch is on the 256x256 tile (conv_igemm.hip: from 1 024 tiles on): activation reads x4.5 -> x1.2 of the
-    // algorithmic bytes (profiles/round1_head_conv_pmc.json, launch 0).  BOD_FAN_XREUSE=0: A/B aid.
+    // algorithmic bytes (profiles/round1_head_conv_pmc.json, launch 0).
     RowEnt* d1x = nullptr; int2* dext1 = nullptr; int m1x = 0;
     bool xreuse0 = xreuse;          // (N = 1: no fan-out, a plain three-head launch over the pyramid -- on the same loop since round 4: 1.07 -> 1.23 PFLOP/s)
-    if (const char* e = getenv("BOD_FAN_XREUSE")) xreuse0 = xreuse0 && atoi(e) != 0;
     {
         ConvArgs probe{};
         probe.M = B * h->P; probe.cout_pad = 256; probe.fan_count = N; probe.flags = CONV_RELU | CONV_DROPOUT; probe.groups = c.has_covar_head ? 3 : 2;
@@ -1028,14 +1025,13 @@ bod_status build_plan(bod_context* h) {
     } else {
         BODCHK(ensure_raw(h));                 // the ops below reference the raw tensors directly
     }
-    static const bool split_on = [] { const char* e = getenv("BOD_SPLIT_AGG_LAUNCH"); return !e || atoi(e) != 0; }();     // (=0: one launch per layer on the aggregated tiling, A/B aid)
     // ---- Sparse tail: only the classification head's statistics decide which anchors are kept (post_sample_kernel), and everything
     // behind the filter reads the box and covariance statistics of kept anchors only (post_fuse_kernel, through anchor_index) -- about
     // 2 % of them at the reference's operating point.  So the launch of the heads that end at layer 2 (box regression) and at layer 3
     // (covariance) moves behind the classification head's last layer and the keep flags, and runs over the pixels with a kept anchor
     // (SparseTailArgs): the same rows, products and epilogue as the dense launch, for those pixels.  BOD_SPARSE_TAIL=0: the dense plan.
     // (Not on pipeline_overlap handles, the experimental CU-partitioned mode: they keep the dense plan.)
-    bool sparse = agg && split_on && h->es == 2 && !h->split && !mx_plan && !c.pipeline_overlap && h->A == h->P * c.anchors_per_location &&
+    bool sparse = agg && h->es == 2 && !h->split && !mx_plan && !c.pipeline_overlap && h->A == h->P * c.anchors_per_location &&
                   h->P <= 65536;
     if (const char* e = getenv("BOD_SPARSE_TAIL")) sparse = sparse && atoi(e) != 0;
     // ---- Sparse halo: the tail's 3x3 windows read box layer 1's and covariance layer 2's outputs only around the tail's pixels, and
@@ -1103,7 +1099,7 @@ bod_status build_plan(bod_context* h) {
     for (int fpass = 0; fpass < 2; ++fpass)
     for (int part = 0; part < 2; ++part)
     for (int flav = (agg && layer >= 2) ? FLAVOUR_RAW : FLAVOUR_BOTH; flav <= ((agg && layer >= 2) ? FLAVOUR_AGG : FLAVOUR_BOTH); ++flav) {
-        const bool split_launch = agg && layer >= 2 && split_on;       // part 0: heads that continue, part 1: heads that end at this layer
+        const bool split_launch = agg && layer >= 2;       // part 0: heads that continue, part 1: heads that end at this layer
         if (fpass == 1 && (!mixed || layer == 0)) continue;
         const int lfmt = !mx_plan ? 0 : layer == 0 ? pyr_fmt : mixed ? (fpass == 0 ? 2 : 1) : mxf;       // row format this launch READS
         if (!split_launch && part == 1) continue;
@@ -1198,17 +1194,14 @@ bod_status build_plan(bod_context* h) {
             a.drop_threshold = thr; a.drop_scale = dscale;
             a.mx = mx_plan ? ((layer == 0 && !mx_l0) ? 2 : (lfmt == 2 ? 3 : 1)) : 0;
             op.hx_pyramid = mx_l0 && layer == 0;
-            {   // BOD_MX_LOADER=0|1|2: which waves of the f16mx loop issue the weight pieces (conv_igemm.hip: all / lower four / upper four)
-                // (same-box A/B at 256 frames, two rounds each: towers 198.0 / 196.2 / 199.7 ms with 0 / 1 / 2)
-                static const int mx_loader = getenv("BOD_MX_LOADER") ? atoi(getenv("BOD_MX_LOADER")) : 1;
-                // BOD_TOWER_LOADER=1: the same pairing in the bf16 tower loop (A/B switch; measured 0.8 % SLOWER there: 211.6 against 209.9 ms per 512 frames)
-                static const int tower_loader = getenv("BOD_TOWER_LOADER") ? atoi(getenv("BOD_TOWER_LOADER")) : 0;
-                a.mx_loader = mx_plan ? mx_loader : ((h->es == 2 && layer > 0) ? tower_loader : 0);
-            }
+            // which waves of the f16mx loop issue the weight pieces (conv_igemm.hip: 0 all / 1 lower four / 2 upper four; same-box A/B at
+            // 256 frames, two rounds each: towers 198.0 / 196.2 / 199.7 ms).  The bf16 tower loop keeps 0: the same pairing measured
+            // 0.8 % SLOWER there (211.6 against 209.9 ms per 512 frames)
+            a.mx_loader = mx_plan ? 1 : 0;
             if (xreuse0 && layer == 0) { a.rows = d1x; a.M = m1x; a.ext = dext1; a.xreuse = 2; }
             if (xreuse && layer > 0) {
                 a.rows = d2x; a.M = m2x; a.ext = dext;
-                if (agg && layer >= 2 && !(split_launch && part == 0)) { a.rows = d2a; a.M = m2a; a.ext = dexta; }       // sample-complete tiles (both flavours)
+                if (split_launch && part == 1) { a.rows = d2a; a.M = m2a; a.ext = dexta; }       // sample-complete tiles (both flavours)
                 a.xreuse = 2;       // 32-bit activation offsets against the tile's first extended row: any buffer size
             }
             op.conv = a;
@@ -1231,7 +1224,6 @@ bod_status build_plan(bod_context* h) {
             a.fan_count = 1; a.fan_stride = (int32_t)h->Ppad;
             a.drop_threshold = thr; a.drop_scale = dscale;
             a.ext = sa.halo_ext; a.xreuse = 2; a.tile_count = sa.tile_count + 1;
-            a.mx_loader = getenv("BOD_TOWER_LOADER") ? atoi(getenv("BOD_TOWER_LOADER")) : 0;
             halo_op.conv = a;
             halo_op.name = "head_tower_layer_2(halo)";
             h->ops.push_back(halo_op);
@@ -1243,7 +1235,6 @@ bod_status build_plan(bod_context* h) {
         a.fan_count = 1; a.fan_stride = (int32_t)h->Ppad;
         a.drop_threshold = thr; a.drop_scale = dscale;
         a.ext = sa.ext; a.xreuse = 2; a.tile_count = sa.tile_count;
-        a.mx_loader = getenv("BOD_TOWER_LOADER") ? atoi(getenv("BOD_TOWER_LOADER")) : 0;      // (as the dense launches of the towers)
         sparse_op.conv = a;
         sparse_op.name = "head_tower_layer_3(sparse)";
         h->ops.push_back(sparse_op);
@@ -1345,50 +1336,6 @@ PostCfg post_cfg(bod_context* h, uint64_t seed, uint32_t first_image) {
     p.kitti_sh = c.kitti_scale_h; p.kitti_sw = c.kitti_scale_w;
     p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32); p.image_base = first_image;
     return p;
-}
-
-// BOD_SPARSE_STATS=1 (development aid): after each keep stage, the tile counts of the tail and halo tables against the dense plain
-// table's, and the share of each pyramid level's pixels in each table (the flags replayed on the host with the kernel's rules), on
-// stderr.  Synchronises the stream.
-bod_status sparse_stats(bod_context* h, hipStream_t st) {
-    const SparseTailArgs& sa = h->sparse;
-    int32_t cnt[2] = {0, 0};
-    std::vector<uint8_t> keep((size_t)sa.B * sa.P * sa.apl);
-    HIPCHK(h, hipMemcpyAsync(cnt, sa.tile_count, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(keep.data(), h->pb.keep, keep.size(), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    const SparseLevels& lv = sa.lv;
-    std::vector<uint8_t> f((size_t)sa.P);
-    std::vector<double> share[3];
-    for (auto& v : share) v.assign(lv.n + 1, 0.0);
-    for (int b = 0; b < sa.B; ++b) {
-        for (int p = 0; p < sa.P; ++p) {
-            uint8_t k = 0;
-            for (int a = 0; a < sa.apl; ++a) k |= keep[((size_t)b * sa.P + p) * sa.apl + a];
-            f[p] = k ? ST_KEPT : 0;
-        }
-        for (int p = 0; p < sa.P; ++p) if (st_member(f.data(), lv, p, ST_KEPT)) f[p] |= ST_TAIL;
-        for (int p = 0; p < sa.P; ++p) if (st_dilated(f.data(), lv, p)) f[p] |= ST_DIL;
-        for (int p = 0; p < sa.P; ++p) if (st_member(f.data(), lv, p, ST_DIL)) f[p] |= ST_HALO;
-        for (int p = 0; p < sa.P; ++p) {
-            int l, y, x;
-            st_level_x(lv, p, l, y, x);
-            const uint8_t bits[3] = {ST_KEPT, ST_TAIL, ST_HALO};
-            for (int t = 0; t < 3; ++t) if (f[p] & bits[t]) { share[t][l] += 1; share[t][lv.n] += 1; }
-        }
-    }
-    fprintf(stderr, "# sparse tables: B %d N %d P %d  tail tiles %d  halo tiles %d  dense plain tiles %d  f = %.4f  tail / dense %.4f\n",
-            sa.B, sa.N, sa.P, cnt[0], cnt[1], h->dense_plain_tiles, (double)cnt[1] / h->dense_plain_tiles, (double)cnt[0] / h->dense_plain_tiles);
-    const char* what[3] = {"kept", "tail", "halo"};
-    for (int t = 0; t < 3; ++t) {
-        fprintf(stderr, "# sparse tables: %s pixel share per level", what[t]);
-        for (int l = 0; l <= lv.n; ++l) {
-            const double pix = l < lv.n ? (double)sa.B * lv.lw[l] * lv.lh[l] : (double)sa.B * sa.P;
-            fprintf(stderr, " %s%.4f", l < lv.n ? "" : "all ", share[t][l] / pix);
-        }
-        fprintf(stderr, "\n");
-    }
-    return BOD_OK;
 }
 
 // flavour: FLAVOUR_RAW = per-sample head outputs into raw[] (RetinaNetModel.call's tensors), FLAVOUR_AGG = MC statistics
@@ -1544,8 +1491,6 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
                 sa.keep = h->pb.keep;
                 HIPCHK(h, launch_sparse_tail_rows(sa, st));
                 h->keep_ready = true; h->keep_seed = seed; h->keep_first = first_image;
-                static const bool stats = [] { const char* e = getenv("BOD_SPARSE_STATS"); return e && atoi(e) != 0; }();
-                if (stats) BODCHK(sparse_stats(h, st));          // (development aid: synchronises; never inside a timed region)
                 break;
             }
             case Op::POOL:
@@ -1567,10 +1512,6 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
                     HIPCHK(h, hipEventRecord(e0, st));
                 }
                 op.conv.n_cu = is_front ? cus_front : cus_back;          // compute units this launch may fill (planner: workgroups vs CUs)
-                {   // fan-out launch: CU de-phasing (conv_igemm.hip); BOD_FAN_STAGGER_US=t: quarter-tile delay in microseconds (0 = off)
-                    static const int stagger_us = getenv("BOD_FAN_STAGGER_US") ? atoi(getenv("BOD_FAN_STAGGER_US")) : 0;
-                    op.conv.stagger_ticks = (op.conv.fan_count > 1 && op.conv.xreuse) ? stagger_us * 100 : 0;
-                }
                 if (par != 0) {                                  // the second pyramid buffer of an overlap handle
                     ConvArgs a = op.conv;
                     for (int g = 0; g < a.groups; ++g) {
@@ -1791,11 +1732,7 @@ bod_status bod_create(const bod_config* cfg, bod_handle* out) {
     //   BOD_FORWARD_OPS=lo:hi    bod_forward runs ops [lo, hi) of the plan only (a company of chosen kernels; the outputs are garbage).
     if (const char* e = getenv("BOD_FORWARD_OPS")) { int lo = 0, hi = 0; if (sscanf(e, "%d:%d", &lo, &hi) == 2 && lo >= 0 && hi > lo) { h->dev_op_lo = lo; h->dev_op_hi = hi; } }
     bool masked_main = false;
-    // (BOD_MAIN_CUS_PER_XCD=k, the older spelling: slots [0, k))
-    const std::string mask_env = getenv("BOD_CU_MASK_SLOTS") ? std::string(getenv("BOD_CU_MASK_SLOTS")) :
-                                 getenv("BOD_MAIN_CUS_PER_XCD") ? "0:" + std::to_string(std::max(1, std::min(32, atoi(getenv("BOD_MAIN_CUS_PER_XCD"))))) : std::string();
-    if (!mask_env.empty()) {
-        const char* e = mask_env.c_str();
+    if (const char* e = getenv("BOD_CU_MASK_SLOTS")) {
         int lo = 0, hi = 0;
         hipDeviceProp_t prop;
         if (sscanf(e, "%d:%d", &lo, &hi) == 2 && hipGetDeviceProperties(&prop, c.device) == hipSuccess && prop.multiProcessorCount % 8 == 0 &&
@@ -1813,9 +1750,9 @@ bod_status bod_create(const bod_config* cfg, bod_handle* out) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c.device) != hipSuccess) return bail(h->fail(BOD_ERR_HIP, "hipGetDeviceProperties failed"));
         h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        // pipeline overlap: BOD_OVERLAP=0 forces it off, =1 on (CU-masked streams), =2 on with two plain streams (A/B aid);
-        // BOD_OVERLAP_FRONT_SLOTS=k: CU slots per XCD the front owns (default 4; the workgroup dispatcher balances over the four
-        // shader engines of an XCD, so only multiples of 4 change anything: tests/tools/cu_mask_probe.hip)
+        // pipeline overlap: BOD_OVERLAP=0 forces it off, =1 on (CU-masked streams), =2 on with two plain streams (A/B aid).
+        // The front owns 4 CU slots per XCD (the workgroup dispatcher balances over the four shader engines of an XCD, so only
+        // multiples of 4 change anything: tests/tools/cu_mask_probe.hip)
         int want = c.pipeline_overlap ? 1 : 0;
         if (const char* e = getenv("BOD_OVERLAP")) want = atoi(e);
         if (c.training) want = 0;
@@ -1826,8 +1763,7 @@ bod_status bod_create(const bod_config* cfg, bod_handle* out) {
                                                      "DESIGN.md 8.3-8.4): set BOD_OVERLAP_EXPERIMENTAL=1 to create such a handle"));
         if (want) {
             const int slots = h->n_cu / 8;
-            int fs = getenv("BOD_OVERLAP_FRONT_SLOTS") ? atoi(getenv("BOD_OVERLAP_FRONT_SLOTS")) : 4;
-            fs = std::max(1, std::min(fs, slots - 1));
+            const int fs = std::max(1, std::min(4, slots - 1));
             const bool masks = want == 1 && h->n_cu % 8 == 0 && slots >= 8 && slots <= 32;
             if (masks) {
                 uint32_t mf[8], mb[8];
@@ -2709,13 +2645,9 @@ bod_status bod_stage_conv_wgrad(int32_t device, const float* x, int32_t B, int32
         uint16_t* d_dyt = nullptr; uint16_t* d_xct = nullptr;
         BODCHK(h->dalloc(&d_dyt, (size_t)cout_pad * Kpad));                 // zero-filled: rows >= Cout stay 0
         BODCHK(h->dalloc(&d_xct, (size_t)N * Kpad, false));
-        const bool trace = getenv("BOD_TRACE_WGRAD") != nullptr;     // development aid: device time of the two phases
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        if (trace) { for (auto& e : ev) HIPCHK(h, hipEventCreate(&e)); HIPCHK(h, hipEventRecord(ev[0], h->stream)); }
         HIPCHK(h, launch_gather_transpose(d_dy, nullptr, d_dyt, M, Kpad, Cout, Cout, 1, 1, false, h->stream));
         HIPCHK(h, launch_gather_transpose(in.d, d_rows, d_xct, M, Kpad, Cin, Cin, taps, KW, true, h->stream));
         // ---- the forward kernel as a plain GEMM: "pixels" = rows of Xcol^T, "weights" = dY^T, reduction = pixels
-        if (trace) HIPCHK(h, hipEventRecord(ev[1], h->stream));
         std::vector<RowEnt> grow((size_t)N);
         for (int n = 0; n < N; ++n) { RowEnt e{}; e.in_off = n; e.out_off = n; grow[n] = e; }
         RowEnt* d_grow = nullptr;
@@ -2735,16 +2667,6 @@ bod_status bod_stage_conv_wgrad(int32_t device, const float* x, int32_t B, int32
             a.partial = d_part;
         }
         HIPCHK(h, launch_conv_igemm(a, h->stream));
-        if (trace) {
-            HIPCHK(h, hipEventRecord(ev[2], h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            float t0 = 0, t1 = 0;
-            hipEventElapsedTime(&t0, ev[0], ev[1]); hipEventElapsedTime(&t1, ev[1], ev[2]);
-            const double fl = 2.0 * M * (double)taps * Cin * Cout;
-            fprintf(stderr, "# wgrad M=%d K=%dx%d Cout=%d S=%d: transposes %.3f ms, GEMM+reduce %.3f ms (%.1f TFLOP/s)\n",
-                    M, taps, Cin, Cout, S, t0, t1, fl / (t1 * 1e-3) / 1e12);
-            for (auto& e : ev) hipEventDestroy(e);
-        }
         std::vector<float> ho((size_t)N * Cout);
         HIPCHK(h, hipMemcpyAsync(ho.data(), d_out, ho.size() * 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2960,14 +2882,6 @@ bod_status bod_bench_head_conv(bod_handle h, int32_t layer, int32_t variant, int
     if (!op) return h->fail(BOD_ERR_INVALID_ARG, "no head launch %d", layer);
     ConvArgs a = op->conv;
     a.variant = variant;
-    // BOD_BENCH_ZERO=1: time the identical launch on zero-filled activations (DVFS / power-limit probe: the matrix
-    // pipe toggles far less on zeros, so any speed-up is clock, not work).  Destroys the head buffers' contents.
-    if (const char* z = getenv("BOD_BENCH_ZERO")) {
-        if (atoi(z) != 0 && layer > 0) {
-            const size_t bytes = (size_t)h->cfg.batch * h->cfg.mc_samples * h->Ppad * 256 * h->es;
-            for (int g = 0; g < a.groups; ++g) HIPCHK(h, hipMemsetAsync(const_cast<void*>(a.g[g].in), 0, bytes, h->stream));
-        }
-    }
     hipEvent_t e0, e1;
     HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
     HIPCHK(h, launch_conv_igemm(a, h->stream));            // warm-up

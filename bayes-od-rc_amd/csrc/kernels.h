@@ -63,7 +63,7 @@ enum : int32_t { AGG_NONE = 0, AGG_CLS = 1, AGG_BOX = 2, AGG_COV = 3 };
 
 enum : int32_t { CONV_RELU = 1, CONV_DROPOUT = 2, CONV_OUT_F32 = 4,
                  CONV_ACCUM = 8,       // with CONV_OUT_F32: out += result (input gradients of 1x1 layers accumulate in place)
-                 CONV_NT_OUT = 16 };   // bf16 outputs stored non-temporally (set by launch_conv_igemm, BOD_NT_STORES)
+                 CONV_NT_OUT = 16 };   // bf16 outputs stored non-temporally (set by launch_conv_igemm: the bf16 fan-out launch)
 
 struct ConvArgs {
     ConvGroup g[3];
@@ -117,9 +117,8 @@ struct ConvArgs {
     // late, so that the ten-fold store bursts of the CUs' epilogues interleave with other CUs' main loops instead of all hitting HBM
     // at once (conv_igemm.hip).  0 = off.
     int32_t stagger_ticks;
-    // Fan-out launch, order of the (pixel tile, head) work items inside an XCD's range (round 6, BOD_FAN_CHUNK=T, A/B): 0 = interleaved
-    // (tile 0 heads 0 1 2, tile 1 ...: the three heads of a tile share its input rows through L2); T > 0 = chunks of T tiles, head-major
-    // inside a chunk (T tiles of head 0, the same T tiles of head 1, ...: one head's weights at a time in L2)
+    // Fan-out launch, order of the (pixel tile, head) work items in an XCD's range (set by launch_conv_igemm): 0 = interleaved (tile 0 heads
+    // 0 1 2, tile 1 ...: a tile's heads share its input rows through L2); T > 0 = chunks of T tiles, head-major (one head's weights at a time in L2)
     int32_t fan_chunk;
     // f16mx precision, head towers on the row-reuse loop (with `split`: same slot counts, same 1 KiB pixel rows): 1 = activations and
     // weights in the hx format, one f16 product + half a block-scaled e2m3 (fp6) product (the two cross terms) per multiplication; 2 = (hi, lo)

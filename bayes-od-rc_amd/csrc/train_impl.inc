@@ -70,9 +70,8 @@ struct SideWorker {
 };
 
 struct TrainState {
-    static constexpr int WS = 4;                          // dZ^T slots (and weight-gradient streams) at most
-    int nslots = 2;                                       // in use (BOD_TRAIN_WGRAD_SLOTS)
-    SideWorker worker; bool use_worker = false; long slot_job[WS] = {0, 0, 0, 0};
+    static constexpr int WS = 2;                          // dZ^T slots (and weight-gradient streams)
+    SideWorker worker; bool use_worker = false; long slot_job[WS] = {0, 0};
     std::vector<TrainConv> convs;
     std::map<std::string, int> index;                     // conv name -> convs[]
     size_t arena_n = 0;
@@ -81,17 +80,17 @@ struct TrainState {
     std::map<const void*, size_t> grad_elems;
     float* act_grad_arena = nullptr; size_t act_grad_n = 0;   // all activation-gradient planes, zeroed by one memset per step
     // scratch (sized for the largest layer)
-    uint16_t *dz = nullptr, *dyt2[WS] = {nullptr, nullptr, nullptr, nullptr};
+    uint16_t *dz = nullptr, *dyt2[WS] = {nullptr, nullptr};
     std::map<std::tuple<const RowEnt*, long, int>, uint16_t*> dzp_of;   // (row table, plane bytes, group) -> dZ plane
     // weight gradients run on a second stream (they feed nothing downstream): dZ^T is double-buffered between the streams
-    // (BOD_TRAIN_WGRAD_SLOTS = 3 / 4 slots and streams measured: 10.8 / 10.9 / 10.9 ms at three ResNet-101 frames -- the main stream
+    // (3 / 4 slots and streams measured: 10.8 / 10.9 / 10.9 ms at three ResNet-101 frames -- the main stream
     // does not wait for slots; what the weight-gradient work costs the step (1.9 ms) is its share of the chip)
     // slot k of the dZ^T double buffer owns scratch set k and, for small minibatches, its own stream: consecutive layers'
     // weight gradients then overlap (8.3 -> 7.8 ms at 3 frames, 14.6 -> 13.8 at 8, 23.8 -> 22.9 at 16); at 32 frames of
     // 512x512 the kernels fill the chip by themselves and the extra concurrency costs 3 % (42.8 -> 44.3 ms): one stream
-    hipStream_t wstreams[WS] = {nullptr, nullptr, nullptr, nullptr}; bool two_wgrad_streams = true;
-    uint16_t* xct2[WS] = {nullptr, nullptr, nullptr, nullptr}; float *partial2[WS] = {nullptr, nullptr, nullptr, nullptr}, *dwp2[WS] = {nullptr, nullptr, nullptr, nullptr}, *dot2[WS] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_ready[WS] = {nullptr, nullptr, nullptr, nullptr}, ev_done[WS] = {nullptr, nullptr, nullptr, nullptr}; bool pending[WS] = {false, false, false, false}; int flip = 0;
+    hipStream_t wstreams[WS] = {nullptr, nullptr}; bool two_wgrad_streams = true;
+    uint16_t* xct2[WS] = {nullptr, nullptr}; float *partial2[WS] = {nullptr, nullptr}, *dwp2[WS] = {nullptr, nullptr}, *dot2[WS] = {nullptr, nullptr};
+    hipEvent_t ev_ready[WS] = {nullptr, nullptr}, ev_done[WS] = {nullptr, nullptr}; bool pending[WS] = {false, false}; int flip = 0;
     float *dxcol = nullptr, *zero_bias = nullptr;
     float* dgrad_partial = nullptr; size_t dgrad_partial_n = 0;   // split-K partials of the input-gradient launches (main stream)
     bool f32 = false; const float* cur_images = nullptr;   // fp32 handle: element size 4 everywhere; this step's device frames (stem weight gradient)
@@ -262,20 +261,19 @@ bod_status train_init(bod_context* h) {
                 uint16_t*& plane = t->dzp_of[std::make_tuple(o.conv.rows, (long)it->second, g)];
                 if (!plane) BODCHK(h->dalloc(reinterpret_cast<char**>(&plane), it->second));
             }
-    if (const char* e = getenv("BOD_TRAIN_WGRAD_SLOTS")) t->nslots = std::min(std::max(atoi(e), 2), (int)TrainState::WS);
     BODCHK(h->dalloc(&t->dz, dz_e * em));
-    for (int k = 0; k < t->nslots; ++k) BODCHK(h->dalloc(&t->dyt2[k], dyt_e * em));
+    for (int k = 0; k < TrainState::WS; ++k) BODCHK(h->dalloc(&t->dyt2[k], dyt_e * em));
     t->two_wgrad_streams = (size_t)c.batch * c.image_h * c.image_w <= (size_t)20 * 512 * 512;
     if (const char* e = getenv("BOD_TRAIN_WGRAD_STREAMS")) t->two_wgrad_streams = atoi(e) >= 2;
-    for (int k = 0; k < t->nslots; ++k) {
+    for (int k = 0; k < TrainState::WS; ++k) {
         BODCHK(h->dalloc(&t->xct2[k], xct_e * em));
         HIPCHK(h, hipStreamCreateWithFlags(&t->wstreams[k], hipStreamNonBlocking));
     }
-    for (int k = 0; k < t->nslots; ++k) {
+    for (int k = 0; k < TrainState::WS; ++k) {
         HIPCHK(h, hipEventCreateWithFlags(&t->ev_ready[k], hipEventDisableTiming));
         HIPCHK(h, hipEventCreateWithFlags(&t->ev_done[k], hipEventDisableTiming));
     }
-    for (int k = 0; k < t->nslots; ++k) { BODCHK(h->dalloc(&t->partial2[k], part_e)); BODCHK(h->dalloc(&t->dwp2[k], max_nk_cout)); BODCHK(h->dalloc(&t->dot2[k], 4096)); }
+    for (int k = 0; k < TrainState::WS; ++k) { BODCHK(h->dalloc(&t->partial2[k], part_e)); BODCHK(h->dalloc(&t->dwp2[k], max_nk_cout)); BODCHK(h->dalloc(&t->dot2[k], 4096)); }
     BODCHK(h->dalloc(&t->dxcol, std::max<size_t>(dxcol_e, 1)));
     BODCHK(h->dalloc(&t->zero_bias, std::max(max_cout_pad, max_n + 64)));
     t->iota_n = std::max(max_m, max_n);
@@ -384,7 +382,7 @@ bod_status train_fold_all(bod_context* h) {
 struct WgradSlot { int k, S, Kpad; uint16_t* dzt; };
 bod_status train_wgrad_slot(bod_context* h, const TrainConv& tc, int M, WgradSlot* slot) {
     TrainState* t = h->train;
-    slot->k = t->flip; t->flip = (t->flip + 1) % t->nslots;
+    slot->k = t->flip; t->flip = (t->flip + 1) % TrainState::WS;
     slot->S = wgrad_splits((size_t)M, (size_t)(tc.taps * tc.cin + 1), (size_t)tc.cout_pad, t->f32);
     slot->Kpad = (M + 64 * slot->S - 1) / (64 * slot->S) * (64 * slot->S);
     slot->dzt = t->dyt2[slot->k];
@@ -444,10 +442,9 @@ bod_status train_backward(bod_context* h) {
     const bod_config& c = h->cfg;
     const bool f32 = t->f32;
     const size_t es = h->es;
-    static const bool dsplit_on = [] { const char* e = getenv("BOD_TRAIN_DGRAD_SPLITK"); return !e || atoi(e) != 0; }();   // A/B aid
     auto gemm = [&](ConvArgs d) {
         if (f32) return launch_conv_igemm_f32(d, h->stream);
-        if (dsplit_on && t->dgrad_partial && d.cout_pad % 64 == 0 && d.cin % 64 == 0) {
+        if (t->dgrad_partial && d.cout_pad % 64 == 0 && d.cin % 64 == 0) {
             const int S = dgrad_splits(d.M, d.cin, d.taps, d.cout_pad, d.groups);
             if (S > 1 && (size_t)S * d.groups * d.M * d.cout_pad <= t->dgrad_partial_n) { d.ksplit = S; d.partial = t->dgrad_partial; }
         }
@@ -557,7 +554,7 @@ bod_status train_backward(bod_context* h) {
         }
     }
     // join: every weight gradient is in the arena before the optimizer reads it
-    for (int k = 0; k < t->nslots; ++k)
+    for (int k = 0; k < TrainState::WS; ++k)
         if (t->pending[k]) {
             if (t->slot_job[k]) t->worker.wait_for(t->slot_job[k]);
             HIPCHK(h, hipStreamWaitEvent(h->stream, t->ev_done[k], 0));
