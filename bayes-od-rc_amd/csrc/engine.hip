@@ -272,6 +272,18 @@ struct bod_context {
     hipEvent_t ev_img_ready[2] = {nullptr, nullptr}, ev_img_free[2] = {nullptr, nullptr};
     bool img_ready_pending[2] = {false, false}, img_free_pending[2] = {false, false};
     int cur_img_buf = -1;
+    // ragged uploads (bod_upload_frames_u8_ragged[_async]): one table per route -- [batch] PreprocFrame records, then [batch][2] KITTI
+    // factors -- filled on the host and copied on the upload's stream ahead of its kernel (plain hipMalloc on first use; the batch
+    // fixes its size).  kscale_src[k]: where the factors of the frames in image buffer k lie (nullptr: uniform frames, the handle's
+    // scalars apply).  The forward that consumes buffer k copies them into kscale_cur[i] on the stream of its stem, in front of
+    // ev_img_free[k]: the copy stream may rewrite the table from then on, and the posterior reads the snapshot only.  Two
+    // snapshots, alternated: at most two batches are in flight (bod_infer_async).
+    struct RaggedTable { std::vector<char> host; char* dev = nullptr; };
+    RaggedTable rag_sync, rag_b[2];
+    hipEvent_t ev_tab[2] = {nullptr, nullptr};          // the copy of rag_b[k].host has left the host (its next rewrite waits for it)
+    const float* kscale_src[2] = {nullptr, nullptr};
+    float* kscale_cur[2] = {nullptr, nullptr}; int kscale_i = 0;
+    const float* kscale_now = nullptr;                  // snapshot of the batch the current call works on (nullptr: none)
     char* stem_out = nullptr;
     int es = 2;                                          // bytes per activation / weight CHANNEL (2 = bf16; 4 = fp32, or a (hi, lo) bf16 pair)
     bool split = false;                                  // bf16x3 precision: (hi, lo) bf16 pairs, three MFMA products (conv_igemm.hip)
@@ -1334,6 +1346,7 @@ PostCfg post_cfg(bod_context* h, uint64_t seed, uint32_t first_image) {
     p.use_full_covar = c.use_full_covar; p.has_covar = c.has_covar_head; p.dirichlet = c.dirichlet_non_informative;
     p.gaussian_iso = c.gaussian_isotropic; p.ranking_method = c.ranking_method; p.iso_var = c.isotropic_variance;
     p.kitti_sh = c.kitti_scale_h; p.kitti_sw = c.kitti_scale_w;
+    p.kitti_frame = c.kitti_scale_h > 0.f ? h->kscale_now : nullptr;
     p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32); p.image_base = first_image;
     return p;
 }
@@ -1647,6 +1660,7 @@ bod_status stage_images(bod_context* h, const float* images, int on_device, cons
     if (!images) return h->fail(BOD_ERR_INVALID_ARG, "images is NULL");
     if (!st) st = h->stream;                            // the stream the stem will run on
     h->cur_img_buf = -1;
+    h->kscale_now = nullptr;
     if (on_device) {
         for (int k = 0; k < 2; ++k)
             if (images == h->d_images_b[k] && h->d_images_b[k]) {
@@ -1655,10 +1669,17 @@ bod_status stage_images(bod_context* h, const float* images, int on_device, cons
                     HIPCHK(h, hipStreamWaitEvent(st, h->ev_img_ready[k], 0));
                     h->img_ready_pending[k] = false;
                 }
+                if (h->kscale_src[k]) {                  // frames of a ragged upload: their factors become this call's (see kscale_src)
+                    float* cur = h->kscale_cur[h->kscale_i];
+                    h->kscale_i ^= 1;
+                    HIPCHK(h, hipMemcpyAsync(cur, h->kscale_src[k], (size_t)h->cfg.batch * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+                    h->kscale_now = cur;
+                }
             }
         *dev = images;
         return BOD_OK;
     }
+    h->kscale_src[0] = nullptr;                         // host float frames replace whatever buffer 0 held
     const size_t bytes = (size_t)h->cfg.batch * h->cfg.image_h * h->cfg.image_w * 3 * sizeof(float);
     HIPCHK(h, hipMemcpyAsync(h->d_images, images, bytes, hipMemcpyHostToDevice, st));
     *dev = h->d_images;
@@ -1820,6 +1841,8 @@ bod_status bod_destroy(bod_handle h) {
     if (h->iou_scratch) hipFree(h->iou_scratch);
     if (h->affinity) hipFree(h->affinity);
     if (h->d_frames_u8) hipFree(h->d_frames_u8);
+    if (h->rag_sync.dev) hipFree(h->rag_sync.dev);
+    for (int k = 0; k < 2; ++k) { if (h->rag_b[k].dev) hipFree(h->rag_b[k].dev); if (h->ev_tab[k]) hipEventDestroy(h->ev_tab[k]); if (h->kscale_cur[k]) hipFree(h->kscale_cur[k]); }
     if (h->copy) { hipStreamSynchronize(h->copy); hipStreamDestroy(h->copy); }
     for (int k = 0; k < 2; ++k) {
         if (h->d_u8_b[k]) hipFree(h->d_u8_b[k]);
@@ -1907,13 +1930,15 @@ bod_status bod_upload_images(bod_handle h, const float* host_images) {
     const size_t bytes = (size_t)h->cfg.batch * h->cfg.image_h * h->cfg.image_w * 3 * sizeof(float);
     HIPCHK(h, hipMemcpyAsync(h->d_images, host_images, bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->kscale_src[0] = nullptr;
     return BOD_OK;
 }
 
-static bod_status preproc_geometry(bod_handle h, int32_t src_h, int32_t src_w, const float* rgb_means, int32_t aspect_resize, PreprocArgs* out) {
-    const bod_config& c = h->cfg;
-    PreprocArgs a{};
-    a.B = c.batch; a.sh = src_h; a.sw = src_w; a.H = c.image_h; a.W = c.image_w; a.resize = aspect_resize ? 1 : 0;
+// Resize / crop / pad geometry of ONE frame (both upload routes).  0 = ok; 1 = the resize degenerates (g->rh, g->rw say how);
+// 2 = no resize asked for and the frame is not at the network size.
+static int frame_geometry(const bod_config& c, int32_t src_h, int32_t src_w, int32_t aspect_resize, PreprocFrame* g) {
+    PreprocFrame a{};
+    a.sh = src_h; a.sw = src_w;
     a.rh = src_h; a.rw = src_w;
     if (aspect_resize) {
         // tf.image.resize(..., preserve_aspect_ratio=True): scale = min(H/sh, W/sw) in float32, size = round(s * in)
@@ -1921,10 +1946,9 @@ static bod_status preproc_geometry(bod_handle h, int32_t src_h, int32_t src_w, c
         const float sc = fh < fw ? fh : fw;
         a.rh = (int32_t)std::nearbyint(sc * (float)src_h);
         a.rw = (int32_t)std::nearbyint(sc * (float)src_w);
-        if (a.rh < 1 || a.rw < 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_upload_frames_u8: degenerate resize %dx%d", a.rh, a.rw);
+        if (a.rh < 1 || a.rw < 1) { *g = a; return 1; }
     } else if (src_h != c.image_h || src_w != c.image_w) {
-        return h->fail(BOD_ERR_INVALID_ARG, "bod_upload_frames_u8: frames are %dx%d but the handle expects %dx%d (pass aspect_resize=1 for "
-                       "the KITTI-style resize + crop/pad)", src_h, src_w, c.image_h, c.image_w);
+        return 2;
     }
     a.scale_y = (float)src_h / (float)a.rh; a.scale_x = (float)src_w / (float)a.rw;
     const int dh = c.image_h - a.rh, dw = c.image_w - a.rw;                 // resize_with_crop_or_pad (floor division like Python)
@@ -1932,9 +1956,79 @@ static bod_status preproc_geometry(bod_handle h, int32_t src_h, int32_t src_w, c
     a.crop_y = std::max(fdiv2(-dh), 0); a.crop_x = std::max(fdiv2(-dw), 0);
     a.pad_y = std::max(fdiv2(dh), 0); a.pad_x = std::max(fdiv2(dw), 0);
     a.vis_h = std::min(a.rh, c.image_h); a.vis_w = std::min(a.rw, c.image_w);
+    *g = a;
+    return 0;
+}
+
+static bod_status preproc_geometry(bod_handle h, int32_t src_h, int32_t src_w, const float* rgb_means, int32_t aspect_resize, PreprocArgs* out) {
+    const bod_config& c = h->cfg;
+    PreprocFrame g{};
+    const int bad = frame_geometry(c, src_h, src_w, aspect_resize, &g);
+    if (bad == 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_upload_frames_u8: degenerate resize %dx%d", g.rh, g.rw);
+    if (bad == 2)
+        return h->fail(BOD_ERR_INVALID_ARG, "bod_upload_frames_u8: frames are %dx%d but the handle expects %dx%d (pass aspect_resize=1 for "
+                       "the KITTI-style resize + crop/pad)", src_h, src_w, c.image_h, c.image_w);
+    PreprocArgs a{};
+    a.B = c.batch; a.sh = g.sh; a.sw = g.sw; a.H = c.image_h; a.W = c.image_w; a.resize = aspect_resize ? 1 : 0;
+    a.rh = g.rh; a.rw = g.rw; a.scale_y = g.scale_y; a.scale_x = g.scale_x;
+    a.crop_y = g.crop_y; a.crop_x = g.crop_x; a.pad_y = g.pad_y; a.pad_x = g.pad_x; a.vis_h = g.vis_h; a.vis_w = g.vis_w;
     for (int k = 0; k < 3; ++k) a.mean[k] = rgb_means[k];
     *out = a;
     return BOD_OK;
+}
+
+// A ragged batch's table on the host (PreprocFrame records, then the [batch][2] factors) and its packed byte count.  Nothing of the
+// handle's upload state has changed when this fails.
+static bod_status ragged_table(bod_handle h, const char* who, const int32_t* src_hw, int32_t aspect_resize, bod_context::RaggedTable* t,
+                               size_t* bytes, bool* with_factors) {
+    const bod_config& c = h->cfg;
+    const size_t B = (size_t)c.batch;
+    t->host.resize(B * (sizeof(PreprocFrame) + 2 * sizeof(float)));
+    PreprocFrame* fr = reinterpret_cast<PreprocFrame*>(t->host.data());
+    float* fac = reinterpret_cast<float*>(t->host.data() + B * sizeof(PreprocFrame));
+    int64_t off = 0;
+    for (int b = 0; b < c.batch; ++b) {
+        const int32_t sh = src_hw[2 * b], sw = src_hw[2 * b + 1];
+        if (sh < 1 || sw < 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: frame %d has size %dx%d", who, b, sh, sw);
+        PreprocFrame g{};
+        const int bad = frame_geometry(c, sh, sw, aspect_resize, &g);
+        if (bad == 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: frame %d (%dx%d): degenerate resize %dx%d", who, b, sh, sw, g.rh, g.rw);
+        if (bad == 2)
+            return h->fail(BOD_ERR_INVALID_ARG, "%s: frame %d is %dx%d but the handle expects %dx%d (pass aspect_resize=1 for the "
+                           "KITTI-style resize + crop/pad)", who, b, sh, sw, c.image_h, c.image_w);
+        g.offset = off;
+        off += (int64_t)3 * sh * sw;
+        fr[b] = g;
+        // S = orig / net per sample (inference_utils.py:147-167), rounded as make_config rounds the handle's pair
+        fac[2 * b] = (float)((double)sh / (double)c.image_h);
+        fac[2 * b + 1] = (float)((double)sw / (double)c.image_w);
+    }
+    *bytes = (size_t)off;
+    *with_factors = aspect_resize && c.kitti_scale_h > 0.f;
+    return BOD_OK;
+}
+
+// Device side of a route's table and the two snapshots, on first use.
+static bod_status ragged_alloc(bod_handle h, const char* who, bod_context::RaggedTable* t) {
+    const size_t n = t->host.size(), fb = (size_t)h->cfg.batch * 2 * sizeof(float);
+    if (!t->dev && hipMalloc(reinterpret_cast<void**>(&t->dev), n) != hipSuccess) { t->dev = nullptr; return h->fail(BOD_ERR_OOM, "%s: %zu bytes of frame table", who, n); }
+    for (int k = 0; k < 2; ++k)
+        if (!h->kscale_cur[k] && hipMalloc(reinterpret_cast<void**>(&h->kscale_cur[k]), fb) != hipSuccess) {
+            h->kscale_cur[k] = nullptr;
+            return h->fail(BOD_ERR_OOM, "%s: %zu bytes of frame factors", who, fb);
+        }
+    return BOD_OK;
+}
+
+static PreprocRaggedArgs ragged_args(bod_handle h, const bod_context::RaggedTable& t, const float* rgb_means, int32_t aspect_resize) {
+    PreprocRaggedArgs a{};
+    a.frames = reinterpret_cast<const PreprocFrame*>(t.dev);
+    a.B = h->cfg.batch; a.H = h->cfg.image_h; a.W = h->cfg.image_w; a.resize = aspect_resize ? 1 : 0;
+    for (int k = 0; k < 3; ++k) a.mean[k] = rgb_means[k];
+    return a;
+}
+static const float* ragged_factors(bod_handle h, const bod_context::RaggedTable& t) {
+    return reinterpret_cast<const float*>(t.dev + (size_t)h->cfg.batch * sizeof(PreprocFrame));
 }
 
 bod_status bod_upload_frames_u8(bod_handle h, const uint8_t* rgb, int32_t src_h, int32_t src_w, const float* rgb_means,
@@ -1957,6 +2051,35 @@ bod_status bod_upload_frames_u8(bod_handle h, const uint8_t* rgb, int32_t src_h,
     HIPCHK(h, hipMemcpyAsync(h->d_frames_u8, rgb, bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, launch_preprocess(a, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));       // the caller may reuse `rgb` on return
+    h->kscale_src[0] = nullptr;
+    return BOD_OK;
+}
+
+bod_status bod_upload_frames_u8_ragged(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw, const float* rgb_means,
+                                       int32_t aspect_resize) {
+    MarkerRange mr_api("bod:upload");
+    if (!h || !rgb_packed || !src_hw || !rgb_means) return BOD_ERR_INVALID_ARG;
+    static const char* who = "bod_upload_frames_u8_ragged";
+    BODCHK(join_overlap(h));
+    const bod_config& c = h->cfg;
+    HIPCHK(h, hipSetDevice(c.device));
+    // (the table of the previous ragged upload has been copied: that call synchronized the stream)
+    size_t bytes = 0; bool with_factors = false;
+    BODCHK(ragged_table(h, who, src_hw, aspect_resize, &h->rag_sync, &bytes, &with_factors));
+    BODCHK(ragged_alloc(h, who, &h->rag_sync));
+    if (bytes > h->frames_u8_cap) {
+        if (h->d_frames_u8) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(h->d_frames_u8); h->d_frames_u8 = nullptr; h->frames_u8_cap = 0; }
+        if (hipMalloc(reinterpret_cast<void**>(&h->d_frames_u8), bytes) != hipSuccess)
+            return h->fail(BOD_ERR_OOM, "%s: %zu bytes of staging", who, bytes);
+        h->frames_u8_cap = bytes;
+    }
+    PreprocRaggedArgs a = ragged_args(h, h->rag_sync, rgb_means, aspect_resize);
+    a.src = h->d_frames_u8; a.dst = h->d_images;
+    HIPCHK(h, hipMemcpyAsync(h->rag_sync.dev, h->rag_sync.host.data(), h->rag_sync.host.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_frames_u8, rgb_packed, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, launch_preprocess_ragged(a, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));       // the caller may reuse `rgb_packed` on return
+    h->kscale_src[0] = with_factors ? ragged_factors(h, h->rag_sync) : nullptr;
     return BOD_OK;
 }
 
@@ -1999,6 +2122,58 @@ bod_status bod_upload_frames_u8_async(bod_handle h, const uint8_t* rgb, int32_t 
     HIPCHK(h, launch_preprocess(a, h->copy));
     HIPCHK(h, hipEventRecord(h->ev_img_ready[buffer], h->copy));
     h->img_ready_pending[buffer] = true;
+    h->kscale_src[buffer] = nullptr;
+    return BOD_OK;
+}
+
+bod_status bod_upload_frames_u8_ragged_async(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw, const float* rgb_means,
+                                             int32_t aspect_resize, int32_t buffer) {
+    MarkerRange mr_api("bod:upload");
+    if (!h || !rgb_packed || !src_hw || !rgb_means) return BOD_ERR_INVALID_ARG;
+    static const char* who = "bod_upload_frames_u8_ragged_async";
+    if (buffer < 0 || buffer > 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: buffer must be 0 or 1", who);
+    const bod_config& c = h->cfg;
+    HIPCHK(h, hipSetDevice(c.device));
+    bod_context::RaggedTable& t = h->rag_b[buffer];
+    // the host side of the table is rewritten below: the copy of this buffer's previous one (two uploads back) must have left it
+    if (h->ev_tab[buffer]) HIPCHK(h, hipEventSynchronize(h->ev_tab[buffer]));
+    size_t bytes = 0; bool with_factors = false;
+    BODCHK(ragged_table(h, who, src_hw, aspect_resize, &t, &bytes, &with_factors));
+    BODCHK(ragged_alloc(h, who, &t));
+    if (!h->copy) {
+        HIPCHK(h, hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking));
+        for (int k = 0; k < 2; ++k) {
+            HIPCHK(h, hipEventCreateWithFlags(&h->ev_img_ready[k], hipEventDisableTiming));
+            HIPCHK(h, hipEventCreateWithFlags(&h->ev_img_free[k], hipEventDisableTiming));
+        }
+    }
+    // (no zero fill: see bod_upload_frames_u8_async)
+    if (!h->d_images_b[buffer]) BODCHK(h->dalloc(&h->d_images_b[buffer], (size_t)c.batch * c.image_h * c.image_w * 3, false));
+    if (bytes > h->u8_cap_b[buffer]) {
+        HIPCHK(h, hipStreamSynchronize(h->copy));
+        if (h->d_u8_b[buffer]) hipFree(h->d_u8_b[buffer]);
+        h->d_u8_b[buffer] = nullptr; h->u8_cap_b[buffer] = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&h->d_u8_b[buffer]), bytes) != hipSuccess)
+            return h->fail(BOD_ERR_OOM, "%s: %zu bytes of staging", who, bytes);
+        h->u8_cap_b[buffer] = bytes;
+    }
+    // the frames AND the table of this buffer stay until the forward that reads them has passed its stem (it snapshots the factors
+    // in front of ev_img_free: stage_images)
+    if (h->img_free_pending[buffer]) { HIPCHK(h, hipStreamWaitEvent(h->copy, h->ev_img_free[buffer], 0)); h->img_free_pending[buffer] = false; }
+    else if (buffer == 0) {                                                   // buffer 0 doubles as the synchronous d_images
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->front) HIPCHK(h, hipStreamSynchronize(h->front));
+    }
+    PreprocRaggedArgs a = ragged_args(h, t, rgb_means, aspect_resize);
+    a.src = h->d_u8_b[buffer]; a.dst = h->d_images_b[buffer];
+    HIPCHK(h, hipMemcpyAsync(t.dev, t.host.data(), t.host.size(), hipMemcpyHostToDevice, h->copy));
+    if (!h->ev_tab[buffer]) HIPCHK(h, hipEventCreateWithFlags(&h->ev_tab[buffer], hipEventDisableTiming));
+    HIPCHK(h, hipEventRecord(h->ev_tab[buffer], h->copy));
+    HIPCHK(h, hipMemcpyAsync(h->d_u8_b[buffer], rgb_packed, bytes, hipMemcpyHostToDevice, h->copy));
+    HIPCHK(h, launch_preprocess_ragged(a, h->copy));
+    HIPCHK(h, hipEventRecord(h->ev_img_ready[buffer], h->copy));
+    h->img_ready_pending[buffer] = true;
+    h->kscale_src[buffer] = with_factors ? ragged_factors(h, t) : nullptr;
     return BOD_OK;
 }
 
@@ -2055,6 +2230,7 @@ bod_status bod_set_raw(bod_handle h, const float* cls, const float* box, const f
     BODCHK(ensure_raw(h));
     const bod_config& c = h->cfg;
     const size_t n = (size_t)c.batch * c.mc_samples * h->A;
+    h->kscale_now = nullptr;                            // outputs from outside: no ragged batch's factors belong to them
     if (cls) HIPCHK(h, hipMemcpyAsync(h->raw[0], cls, n * c.num_classes * 4, hipMemcpyHostToDevice, h->stream));
     if (box) HIPCHK(h, hipMemcpyAsync(h->raw[1], box, n * 16, hipMemcpyHostToDevice, h->stream));
     if (cov && c.has_covar_head) HIPCHK(h, hipMemcpyAsync(h->raw[2], cov, n * 40, hipMemcpyHostToDevice, h->stream));
@@ -2291,7 +2467,7 @@ bod_status bod_device_raw(bod_handle h, void** p, int32_t mark_ready) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (mark_ready) BODCHK(ensure_raw(h)); else BODCHK(materialise_raw(h));
     p[0] = h->raw[0]; p[1] = h->raw[1]; p[2] = h->cfg.has_covar_head ? h->raw[2] : nullptr;
-    if (mark_ready) { h->forward_done = true; h->posterior_done = h->nms_done = h->cluster_done = false; h->affinity_img = -1; h->raw_valid = true; h->agg_valid = false; }
+    if (mark_ready) { h->kscale_now = nullptr; h->forward_done = true; h->posterior_done = h->nms_done = h->cluster_done = false; h->affinity_img = -1; h->raw_valid = true; h->agg_valid = false; }
     return BOD_OK;
 }
 

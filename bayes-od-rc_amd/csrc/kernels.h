@@ -174,6 +174,7 @@ struct PostCfg {
     int32_t use_full_covar, has_covar, dirichlet, gaussian_iso, ranking_method;
     float iso_var;
     float kitti_sh, kitti_sw;       // 0 => off
+    const float* kitti_frame;       // [B][2] (sh, sw) of every frame (a ragged upload's frames), used in place of the two scalars; nullptr => the scalars
     uint32_t seed_lo, seed_hi, image_base;
     int32_t aggregated;             // 1: the MC statistics come from the conv epilogue (PostBuffers.agg_*), not from raw [B,N,A,.]
 };
@@ -296,6 +297,24 @@ struct PreprocArgs {
     float mean[3];             // RGB order
 };
 hipError_t launch_preprocess(const PreprocArgs& a, hipStream_t s);
+
+// Ragged form: frame b of the batch has its own source size and resize / pad geometry (one record of a device table), the frames
+// lie back to back in one packed uint8 buffer.
+struct PreprocFrame {
+    int64_t offset;            // first byte of the frame in the packed buffer: 3 * sum of h_i * w_i over the frames in front of it
+    int32_t sh, sw, rh, rw;    // as PreprocArgs, of this frame
+    float scale_y, scale_x;
+    int32_t crop_y, crop_x, pad_y, pad_x, vis_h, vis_w;
+};
+struct PreprocRaggedArgs {
+    const uint8_t* src;              // packed uint8 RGB frames
+    float* dst;                      // [B, H, W, 3] fp32 BGR, mean-subtracted
+    const PreprocFrame* frames;      // [B], device memory
+    int32_t B, H, W;
+    int32_t resize;
+    float mean[3];                   // RGB order, shared by the batch
+};
+hipError_t launch_preprocess_ragged(const PreprocRaggedArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // Loss forward (loss_kernels.hip)

@@ -434,7 +434,9 @@ __device__ POST_FUSE_INLINE void post_fuse_anchor(const PostCfg& c, const PostBu
         for (int i = 0; i < 4; ++i) pm[i] = mu[i];
     }
     if (c.kitti_sh > 0.f) {                                       // (:147-167) S mu, S Sigma S^T
-        const float sc[4] = {c.kitti_sh, c.kitti_sw, c.kitti_sh, c.kitti_sw};
+        float ksh = c.kitti_sh, ksw = c.kitti_sw;
+        if (c.kitti_frame) { ksh = c.kitti_frame[2 * b]; ksw = c.kitti_frame[2 * b + 1]; }      // the frame's own S = orig / net
+        const float sc[4] = {ksh, ksw, ksh, ksw};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             pm[i] *= sc[i];
@@ -1295,30 +1297,30 @@ hipError_t launch_iou_matrix(const float* corners, int M, float* out, hipStream_
 // One thread per output pixel; fp32 operation order identical to oracle/preprocess.py (this file is built
 // with -ffp-contract=off), so results are bit-exact.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void preprocess_kernel(PreprocArgs a) {
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    const int y = blockIdx.y, b = blockIdx.z;
-    if (x >= a.W) return;
-    const int ry = y - a.pad_y + a.crop_y, rx = x - a.pad_x + a.crop_x;     // coordinates in the (resized) source
+// One output pixel (y, x) of a frame whose source starts at `src`: the geometry fields are PreprocArgs' / PreprocFrame's.
+__device__ __forceinline__ void preprocess_pixel(const uint8_t* src, float* o, const int y, const int x, const int sh, const int sw,
+                                                 const int rh, const int rw, const int crop_y, const int crop_x, const int pad_y,
+                                                 const int pad_x, const int vis_h, const int vis_w, const int resize,
+                                                 const float scale_y, const float scale_x, const float* mean) {
+    const int ry = y - pad_y + crop_y, rx = x - pad_x + crop_x;             // coordinates in the (resized) source
     float v[3] = {0.f, 0.f, 0.f};                                            // zero padding (before mean subtraction)
-    const bool inside = y >= a.pad_y && x >= a.pad_x && ry < a.rh && rx < a.rw && ry >= 0 && rx >= 0 &&
-                        y - a.pad_y < a.vis_h && x - a.pad_x < a.vis_w;
+    const bool inside = y >= pad_y && x >= pad_x && ry < rh && rx < rw && ry >= 0 && rx >= 0 &&
+                        y - pad_y < vis_h && x - pad_x < vis_w;
     if (inside) {
-        const uint8_t* src = a.src + (size_t)b * a.sh * a.sw * 3;
-        if (!a.resize) {
-            const uint8_t* p = src + ((size_t)ry * a.sw + rx) * 3;
+        if (!resize) {
+            const uint8_t* p = src + ((size_t)ry * sw + rx) * 3;
             v[0] = (float)p[0]; v[1] = (float)p[1]; v[2] = (float)p[2];
         } else {
-            const float fy = ((float)ry + 0.5f) * a.scale_y - 0.5f;
-            const float fx = ((float)rx + 0.5f) * a.scale_x - 0.5f;
+            const float fy = ((float)ry + 0.5f) * scale_y - 0.5f;
+            const float fx = ((float)rx + 0.5f) * scale_x - 0.5f;
             const float fy0 = floorf(fy), fx0 = floorf(fx);
             const float ly = fy - fy0, lx = fx - fx0;
-            const int y0 = min(max((int)fy0, 0), a.sh - 1), y1 = min(max((int)ceilf(fy), 0), a.sh - 1);
-            const int x0 = min(max((int)fx0, 0), a.sw - 1), x1 = min(max((int)ceilf(fx), 0), a.sw - 1);
-            const uint8_t* p00 = src + ((size_t)y0 * a.sw + x0) * 3;
-            const uint8_t* p01 = src + ((size_t)y0 * a.sw + x1) * 3;
-            const uint8_t* p10 = src + ((size_t)y1 * a.sw + x0) * 3;
-            const uint8_t* p11 = src + ((size_t)y1 * a.sw + x1) * 3;
+            const int y0 = min(max((int)fy0, 0), sh - 1), y1 = min(max((int)ceilf(fy), 0), sh - 1);
+            const int x0 = min(max((int)fx0, 0), sw - 1), x1 = min(max((int)ceilf(fx), 0), sw - 1);
+            const uint8_t* p00 = src + ((size_t)y0 * sw + x0) * 3;
+            const uint8_t* p01 = src + ((size_t)y0 * sw + x1) * 3;
+            const uint8_t* p10 = src + ((size_t)y1 * sw + x0) * 3;
+            const uint8_t* p11 = src + ((size_t)y1 * sw + x1) * 3;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float tl = (float)p00[c], tr = (float)p01[c], bl = (float)p10[c], br = (float)p11[c];
@@ -1328,11 +1330,34 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreprocArgs a) {
             }
         }
     }
-    float* o = a.dst + (((size_t)b * a.H + y) * a.W + x) * 3;
-    o[0] = v[2] - a.mean[2]; o[1] = v[1] - a.mean[1]; o[2] = v[0] - a.mean[0];
+    o[0] = v[2] - mean[2]; o[1] = v[1] - mean[1]; o[2] = v[0] - mean[0];
+}
+
+__global__ __launch_bounds__(256) void preprocess_kernel(PreprocArgs a) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y, b = blockIdx.z;
+    if (x >= a.W) return;
+    preprocess_pixel(a.src + (size_t)b * a.sh * a.sw * 3, a.dst + (((size_t)b * a.H + y) * a.W + x) * 3, y, x, a.sh, a.sw, a.rh, a.rw,
+                     a.crop_y, a.crop_x, a.pad_y, a.pad_x, a.vis_h, a.vis_w, a.resize, a.scale_y, a.scale_x, a.mean);
 }
 
 hipError_t launch_preprocess(const PreprocArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(preprocess_kernel, dim3((a.W + 255) / 256, a.H, a.B), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// The same pixel for a batch of frames of mixed source sizes: grid z = frame, whose record of the geometry table gives its
+// 64-bit offset into the packed buffer and its own resize / crop / pad.  Same fp32 operations in the same order as above.
+__global__ __launch_bounds__(256) void preprocess_ragged_kernel(PreprocRaggedArgs a) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y, b = blockIdx.z;
+    if (x >= a.W) return;
+    const PreprocFrame f = a.frames[b];
+    preprocess_pixel(a.src + f.offset, a.dst + (((size_t)b * a.H + y) * a.W + x) * 3, y, x, f.sh, f.sw, f.rh, f.rw,
+                     f.crop_y, f.crop_x, f.pad_y, f.pad_x, f.vis_h, f.vis_w, a.resize, f.scale_y, f.scale_x, a.mean);
+}
+
+hipError_t launch_preprocess_ragged(const PreprocRaggedArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(preprocess_ragged_kernel, dim3((a.W + 255) / 256, a.H, a.B), dim3(256), 0, s, a);
     return hipGetLastError();
 }

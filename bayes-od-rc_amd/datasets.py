@@ -198,7 +198,11 @@ class KittiDatasetHandler(DatasetHandler):
 
 def normalized_on_device(engine, frames_u8, im_normalization='ImageNet', aspect_resize=False):
     """uint8 RGB frames [B,h,w,3] -> the reference's 'image_normalized' tensors [B,H,W,3], computed by the device
-    preprocessing kernel and left resident in the engine's image buffer (forward(None) / infer(None) use them)."""
+    preprocessing kernel and left resident in the engine's image buffer (forward(None) / infer(None) use them).  A list of
+    [h,w,3] frames may mix source sizes (``Engine.upload_frames_u8_ragged``)."""
+    if isinstance(frames_u8, (list, tuple)):
+        engine.upload_frames_u8_ragged(list(frames_u8), constants.MEANS_DICT[im_normalization], aspect_resize=aspect_resize)
+        return engine.get_images()
     engine.upload_frames_u8(frames_u8, constants.MEANS_DICT[im_normalization], aspect_resize=aspect_resize)
     return engine.get_images()
 

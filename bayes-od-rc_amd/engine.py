@@ -158,6 +158,29 @@ class Engine(object):
         self._chk(self.lib.bod_upload_frames_u8_async(self.h, a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[2],
                                                       fptr(m), int(bool(aspect_resize)), int(buffer)))
 
+    def upload_frames_u8_ragged(self, frames, means=None, aspect_resize=True):
+        """``upload_frames_u8`` for ``batch`` frames of mixed source sizes (``bod_upload_frames_u8_ragged``): ``frames`` is a
+        list of uint8 [h,w,3] arrays.  Every frame is resized / padded by its own geometry; on a handle made with
+        ``dataset_name='kitti'`` and ``aspect_resize=True`` the next forward on these frames rescales every frame's boxes by that
+        frame's own ``orig / net`` factors instead of the handle's ``orig_size``."""
+        from . import constants
+        buf, sizes = pack_ragged(frames, self.B)
+        m = np.ascontiguousarray(constants.MEANS_DICT['ImageNet'] if means is None else means, dtype=np.float32)
+        self._chk(self.lib.bod_upload_frames_u8_ragged(self.h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), iptr(sizes), fptr(m),
+                                                       int(bool(aspect_resize))))
+
+    def upload_frames_u8_ragged_async(self, frames, buffer, means=None, aspect_resize=True):
+        """Pipelined form (``bod_upload_frames_u8_ragged_async``), used like ``upload_frames_u8_async``.  The packed copy of the
+        frames is kept alive by the engine until the next upload into the same buffer."""
+        from . import constants
+        buf, sizes = pack_ragged(frames, self.B)
+        m = np.ascontiguousarray(constants.MEANS_DICT['ImageNet'] if means is None else means, dtype=np.float32)
+        self._chk(self.lib.bod_upload_frames_u8_ragged_async(self.h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), iptr(sizes), fptr(m),
+                                                             int(bool(aspect_resize)), int(buffer)))
+        if not hasattr(self, "_ragged_keep"):
+            self._ragged_keep = {}
+        self._ragged_keep[int(buffer)] = buf
+
     def _device_images(self, image_buffer):
         ptr = self.lib.bod_device_images(self.h) if image_buffer is None else self.lib.bod_device_images_buffer(self.h, int(image_buffer))
         if not ptr:
@@ -526,6 +549,28 @@ class Engine(object):
         self._chk(self.lib.bod_profile_end(self.h, C.byref(hm), C.byref(hl), C.byref(fl), C.byref(pm), C.byref(pl)))
         return {"head_conv_ms": hm.value, "head_conv_launches": hl.value, "head_conv_flops": fl.value,
                 "posterior_ms": pm.value, "posterior_launches": pl.value}
+
+
+def pack_ragged(frames, batch=None):
+    """Frames of mixed sizes as the ragged uploads take them: (packed uint8 buffer -- the frames back to back, frame b at byte
+    3 * sum of h_i * w_i over i < b -- and sizes [n,2] int32 (h, w)).  ``frames``: a sequence of uint8 [h,w,3] arrays, ``batch``
+    of them when given."""
+    frames = list(frames)
+    if batch is not None and len(frames) != int(batch):
+        raise ValueError("expected %d frames, got %d" % (int(batch), len(frames)))
+    if not frames:
+        raise ValueError("no frames to pack")
+    for i, f in enumerate(frames):
+        if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape[0] < 1 or f.shape[1] < 1:
+            raise ValueError("frame %d: expected a uint8 array of shape (h, w, 3), got %s %s" %
+                             (i, getattr(f, "dtype", type(f).__name__), getattr(f, "shape", "")))
+    sizes = np.asarray([f.shape[:2] for f in frames], np.int32)
+    buf = np.empty(3 * int(np.sum(sizes[:, 0].astype(np.int64) * sizes[:, 1])), np.uint8)
+    off = 0
+    for f in frames:
+        buf[off:off + f.size] = f.reshape(-1)
+        off += f.size
+    return buf, sizes
 
 
 def _pack_gt(gt_boxes, gt_classes, batch, num_classes=None):

@@ -166,6 +166,12 @@ class BayesOdPipeline(object):
         self.engine = self.model.engine_for(self._hw, batch=self._batch, mc_samples=self.model.mc_dropout_samples, **self._kw)
         return self.engine
 
+    def upload_mixed(self, frames, means, aspect_resize=True):
+        """``batch`` uint8 frames of mixed source sizes into the engine, for ``__call__(None, ...)``: every frame is rescaled by
+        its own S = orig / net (inference_utils.py:147-167 takes it per sample), so no ``bind(orig_size=...)`` per size."""
+        self.bind()
+        self.engine.upload_frames_u8_ragged(frames, means, aspect_resize=aspect_resize)
+
     def __call__(self, images=None, seed=0, first_image_id=0):
         """images [B,H,W,3] (or None to reuse the uploaded device batch).  Returns, per image,
         (output_classes [K,C], output_boxes_vuhw [K,4], output_covs [K,4,4], output_counts [K,C])."""

@@ -5,7 +5,9 @@
 
 ``--dataset`` reads the yaml's BDD / KITTI tree through ``datasets.build_dataset`` (the reference's default,
 run_inference.py:60-72): frames are decoded on the host, uploaded as uint8 and normalised / resized on the GPU
-(``bod_upload_frames_u8``); frames of one batch must share a size.  Otherwise frames come from an .npy of
+(``bod_upload_frames_u8``); frames of one batch must share a size, so a batch ends where the size changes.  With
+``--mixed_sizes`` batches are formed in dataset order whatever the sizes (``bod_upload_frames_u8_ragged``: every frame
+is resized and its boxes rescaled by its own size).  Otherwise frames come from an .npy of
 normalised BGR images or are synthetic.  Weights: an .npz with Keras layer names (the TF-checkpoint converter is
 SURVEY.md section 8 f3).
 """
@@ -96,8 +98,36 @@ def _test_model_on_dataset(config, args, model):
     gen = FpnAnchorGenerator(dataset_config['anchor_generator'])
     pipes = {}
     pending = []
+    mixed = bool(getattr(args, 'mixed_sizes', False))
+
+    def emit(dets):
+        for (name, _, _), (classes, boxes_vuhw, covs, counts) in zip(pending, dets):
+            boxes = box_utils.vuhw_to_vuvu_np(boxes_vuhw) if boxes_vuhw.size else boxes_vuhw
+            mapped = classes
+            if training_dataset != test_dataset and boxes.size > 0:
+                mapped = inference_utils.map_dataset_classes(training_dataset, test_dataset, classes)
+            writer.write(name, boxes, mapped, boxes_vuhw, covs, classes, counts, categories)
+        del pending[:]
+
+    def flush_mixed():
+        """--mixed_sizes: one handle per batch count (the full batch, the tail); the frames' own sizes travel with the upload."""
+        if not pending:
+            return
+        hw = tuple(handler.resize_shape) if kitti else pending[0][1].shape[:2]
+        key = ('mixed', len(pending))
+        if key not in pipes:
+            # orig_size only switches the KITTI rescale on: the ragged upload gives every frame its own factors
+            pipes[key] = inference_utils.BayesOdPipeline(
+                model, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
+                use_full_covar=test_config['use_full_covar'], dataset_name=test_dataset, orig_size=hw,
+                anchors=gen.generate_all((hw[0], hw[1], 3)))
+        pipe = pipes[key]
+        pipe.upload_mixed([p[1] for p in pending], constants.MEANS_DICT[handler.im_normalization], aspect_resize=kitti)
+        emit(pipe(None, seed=args.seed, first_image_id=pending[0][2]))
 
     def flush():
+        if mixed:
+            return flush_mixed()
         if not pending:
             return
         frames = np.stack([p[1] for p in pending])
@@ -112,20 +142,13 @@ def _test_model_on_dataset(config, args, model):
         pipe = pipes[key]
         pipe.bind(orig_size=src_hw)      # the handle may be shared with a pipe of another source size: re-apply the KITTI scale
         pipe.engine.upload_frames_u8(frames, constants.MEANS_DICT[handler.im_normalization], aspect_resize=kitti)
-        dets = pipe(None, seed=args.seed, first_image_id=pending[0][2])
-        for (name, _, _), (classes, boxes_vuhw, covs, counts) in zip(pending, dets):
-            boxes = box_utils.vuhw_to_vuvu_np(boxes_vuhw) if boxes_vuhw.size else boxes_vuhw
-            mapped = classes
-            if training_dataset != test_dataset and boxes.size > 0:
-                mapped = inference_utils.map_dataset_classes(training_dataset, test_dataset, classes)
-            writer.write(name, boxes, mapped, boxes_vuhw, covs, classes, counts, categories)
-        del pending[:]
+        emit(pipe(None, seed=args.seed, first_image_id=pending[0][2]))
 
     start, n_done = time.time(), 0
     for idx, sample in enumerate(handler.create_dataset()):
         rgb = sample[datasets.IMAGE_UINT8_KEY]
         name = os.path.splitext(os.path.basename(handler.im_paths[idx]))[0]
-        if pending and (pending[0][1].shape != rgb.shape or len(pending) == args.batch):
+        if pending and ((not mixed and pending[0][1].shape != rgb.shape) or len(pending) == args.batch):
             flush()
         pending.append((name, rgb, idx))
         n_done += 1
@@ -149,6 +172,8 @@ def main(argv=None):
     ap.add_argument('--orig_size', type=int, nargs=2, default=None)
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--mixed_sizes', action='store_true', help='with --dataset: batches in dataset order whatever the frame sizes '
+                    '(default: a batch ends where the source size changes)')
     args = ap.parse_args(argv)
     config = config_utils.load_yaml(args.yaml_path)
     config = config_utils.setup(config, args)

@@ -78,8 +78,11 @@ class Trainer(object):
         """Samples that carry the ground truth only (``dense_targets=False``): the targets are assigned on the device.  KITTI
         samples have no host image (IMAGE_NORMALIZED_KEY is None): their uint8 frames are resized and normalised on the device."""
         if sample_dicts[0][constants.IMAGE_NORMALIZED_KEY] is None:
-            frames = np.stack([s['image_uint8'] for s in sample_dicts])
-            self.engine.upload_frames_u8(frames, constants.MEANS_DICT[self.im_normalization], aspect_resize=True)
+            frames = [s['image_uint8'] for s in sample_dicts]
+            if len(set(f.shape for f in frames)) > 1:                  # --mixed_sizes: a minibatch in the handler's order
+                self.engine.upload_frames_u8_ragged(frames, constants.MEANS_DICT[self.im_normalization], aspect_resize=True)
+            else:
+                self.engine.upload_frames_u8(np.stack(frames), constants.MEANS_DICT[self.im_normalization], aspect_resize=True)
             imgs = None
         else:
             imgs = np.stack([s[constants.IMAGE_NORMALIZED_KEY] for s in sample_dicts]).astype(np.float32)
@@ -185,10 +188,25 @@ def bucket_minibatches(samples, minibatch_size, carry):
             yield carry.pop(key)
 
 
-def stream_minibatches(handler, minibatch_size):
+def ordered_minibatches(samples, minibatch_size, carry):
+    """``bucket_minibatches`` without buckets (``--mixed_sizes``): full minibatches in the order of ``samples`` whatever the
+    source sizes, as the reference forms them.  ``carry`` (a list) holds the partial last minibatch; the caller passes the same
+    list for the next epoch, so no frame is dropped."""
+    for sample in samples:
+        carry.append(sample)
+        del sample
+        if len(carry) == minibatch_size:
+            full = carry[:]
+            del carry[:]
+            yield full
+
+
+def stream_minibatches(handler, minibatch_size, mixed_sizes=False):
     """Endless generator of minibatches over ``handler.create_dataset()``: one pass per epoch, restarted at its end, never more
-    than the current minibatch and the partial buckets in memory."""
-    carry = {}
+    than the current minibatch and the partial buckets in memory.  ``mixed_sizes``: in the handler's (shuffled) order instead of
+    bucketed by source size."""
+    carry = [] if mixed_sizes else {}
+    form = ordered_minibatches if mixed_sizes else bucket_minibatches
     while True:
         seen = [0]
 
@@ -197,7 +215,7 @@ def stream_minibatches(handler, minibatch_size):
                 seen[0] += 1
                 yield sample
                 del sample
-        yield from bucket_minibatches(counted(handler.create_dataset()), minibatch_size, carry)
+        yield from form(counted(handler.create_dataset()), minibatch_size, carry)
         if not seen[0]:
             raise ValueError('the data split is empty')
 
@@ -213,7 +231,7 @@ def train(config, args):
         # one minibatch at a time
         handler = datasets.build_dataset(dataset_config, 'train')
         handler.dense_targets = False
-        stream = stream_minibatches(handler, mb)
+        stream = stream_minibatches(handler, mb, mixed_sizes=bool(getattr(args, 'mixed_sizes', False)))
         pending = next(stream)                                        # the first minibatch also tells the frame size
         first = pending[0][constants.IMAGE_NORMALIZED_KEY]
         hw = tuple(handler.resize_shape) if first is None else first.shape[:2]
@@ -353,6 +371,8 @@ def main(argv=None):
     ap.add_argument('--image_size', type=int, nargs=2, default=[256, 256])
     ap.add_argument('--steps', type=int, default=0)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--mixed_sizes', action='store_true', help='with --dataset: minibatches in the handler\'s shuffled order whatever '
+                    'the frame sizes (default: bucketed by source size)')
     ap.add_argument('--no_resume', action='store_true', help='start from scratch: existing checkpoints of this run are not restored; they are moved to '
                     'checkpoints/superseded-<time>/ (never deleted) once the trainer has been built')
     args = ap.parse_args(argv)

@@ -2,7 +2,7 @@
 src/retina_net/experiments/run_validation.py:27-228 (loop body :108-204, ``val_single_step`` :230-260):
 
     python -m bayes_od_rc_amd.run_validation --gpu_device 0 --yaml_path <yaml> [--data_split val]
-                                             [--dataset [--batch B] | --synthetic N --image_size H W] [--poll SECONDS]
+                                             [--dataset [--batch B] [--mixed_sizes] | --synthetic N --image_size H W] [--poll SECONDS]
 
 For every checkpoint of ``<data_dir>/outputs/<checkpoint_name>/checkpoints`` that ``evaluated_ckpts.txt`` does not list
 yet: one plain forward per frame (``train_val_test='validation'``: no MC dropout), the losses of the frame, the
@@ -85,9 +85,9 @@ def flush_buckets(carry, batch):
             rest = rest[batch:]
 
 
-def validate_batch(model, config, batch):
-    """``len(batch)`` ground-truth-only samples of one source size through ``Engine.validate_boxes`` on a handle of that batch
-    size.  Returns per frame ``(total_loss, loss_dict, class rows [K,C], corners [K,4])``: the values ``val_single_step`` +
+def validate_batch(model, config, batch, mixed_sizes=False):
+    """``len(batch)`` ground-truth-only samples of one source size (``mixed_sizes``: of any sizes, uploaded ragged) through
+    ``Engine.validate_boxes`` on a handle of that batch size.  Returns per frame ``(total_loss, loss_dict, class rows [K,C], corners [K,4])``: the values ``val_single_step`` +
     ``post_process_predictions`` give for the frame alone, plus the regularisation term (run_validation.py:252-258)."""
     dataset_config = config['dataset_config']
     first = batch[0][constants.IMAGE_NORMALIZED_KEY]
@@ -97,8 +97,11 @@ def validate_batch(model, config, batch):
     if not eng._anchors_set:
         eng.set_anchors(np.asarray(batch[0][constants.ANCHORS_KEY], np.float32))
     if 'image_uint8' in batch[0]:
-        eng.upload_frames_u8(np.stack([s['image_uint8'] for s in batch]),
-                             constants.MEANS_DICT[dataset_config.get('im_normalization', 'ImageNet')], aspect_resize=on_device_resize)
+        means = constants.MEANS_DICT[dataset_config.get('im_normalization', 'ImageNet')]
+        if mixed_sizes:
+            eng.upload_frames_u8_ragged([s['image_uint8'] for s in batch], means, aspect_resize=on_device_resize)
+        else:
+            eng.upload_frames_u8(np.stack([s['image_uint8'] for s in batch]), means, aspect_resize=on_device_resize)
         images = None
     else:
         images = np.stack([s[constants.IMAGE_NORMALIZED_KEY] for s in batch]).astype(np.float32)
@@ -158,6 +161,30 @@ def _validate_batched(model, config, samples, sample_ids, out_dir, categories, b
     return records, [totals[i] for i in sorted(totals)], sums, ndet
 
 
+def _validate_mixed(model, config, samples, sample_ids, out_dir, categories, batch):
+    """``--mixed_sizes``: the batched route without buckets -- one pass in dataset order, ``batch`` frames of whatever source
+    sizes per call, one tail batch.  Same return value as ``_validate_batched``."""
+    dataset = config['dataset_config']['dataset']
+    records, totals, sums, ndet = [], [], {}, 0
+    stream = iter(samples)
+    while True:
+        frames = list(itertools.islice(stream, batch))
+        if not frames:
+            break
+        first = len(totals)
+        for j, (total, loss_dict, classes, corners) in enumerate(validate_batch(model, config, frames, mixed_sizes=True)):
+            totals.append(float(total))
+            for k, v in loss_dict.items():
+                sums[k] = sums.get(k, 0.0) + float(v)
+            ndet += len(corners)
+            if dataset == 'kitti':
+                _write_kitti(out_dir, sample_ids[first + j], corners, classes)
+            else:
+                records.extend(predictions_to_bdd_format(corners, classes, sample_ids[first + j], category_list=categories))
+        frames = None
+    return records, totals, sums, ndet
+
+
 def _validate_per_frame(model, config, samples, sample_ids, out_dir, categories, batch=1):
     """The dense route: one frame at a time through ``val_single_step`` and ``post_process_predictions``."""
     dataset = config['dataset_config']['dataset']
@@ -185,11 +212,11 @@ def _put_back(head, rest):
     yield from rest
 
 
-def validate_checkpoint(config, checkpoint_path, samples, sample_ids, predictions_dir, categories=None, batch=8):
+def validate_checkpoint(config, checkpoint_path, samples, sample_ids, predictions_dir, categories=None, batch=8, mixed_sizes=False):
     """One checkpoint over the validation frames.  Returns {'ckpt_id', 'mean_total_loss', 'mean_losses', 'num_frames',
     'num_detections', 'predictions'} ('predictions' = the BDD records, or None for KITTI).  ``samples``: an iterable of
     sample dicts, or a callable that returns one (a streamed split is read once per checkpoint).  Samples without dense
-    targets take the batched route, ``batch`` frames per call."""
+    targets take the batched route, ``batch`` frames per call: bucketed by source size, or with ``mixed_sizes`` in dataset order."""
     dataset = config['dataset_config']['dataset']
     ckpt_id = strip_checkpoint_id(checkpoint_path[:-4] if checkpoint_path.endswith('.npz') else checkpoint_path)
     out_dir = os.path.join(predictions_dir, 'validation', str(ckpt_id), 'data')
@@ -199,7 +226,7 @@ def validate_checkpoint(config, checkpoint_path, samples, sample_ids, prediction
     stream = iter(samples() if callable(samples) else samples)
     head = list(itertools.islice(stream, 1))
     batched = bool(head) and constants.ANCHORS_CLASS_TARGETS_KEY not in head[0]        # the test Trainer.train_single_step uses
-    route = _validate_batched if batched else _validate_per_frame
+    route = (_validate_mixed if mixed_sizes else _validate_batched) if batched else _validate_per_frame
     records, totals, sums, ndet = route(model, config, _put_back(head, stream), sample_ids, out_dir, categories, int(batch))
     if dataset != 'kitti':
         with open(os.path.join(out_dir, 'predictions.json'), 'w') as fp:
@@ -219,9 +246,10 @@ def list_checkpoints(checkpoint_dir):
     return sorted(found)
 
 
-def validate(config, samples, sample_ids, categories=None, gt_records=None, poll_seconds=None, max_polls=None, batch=8):
+def validate(config, samples, sample_ids, categories=None, gt_records=None, poll_seconds=None, max_polls=None, batch=8,
+             mixed_sizes=False):
     """The loop of run_validation.py:86-228: every checkpoint not yet listed in evaluated_ckpts.txt, in id order; with
-    ``poll_seconds`` keep waiting for new ones (``max_polls`` bounds the waiting, for tests).  ``samples`` / ``batch``: see
+    ``poll_seconds`` keep waiting for new ones (``max_polls`` bounds the waiting, for tests).  ``samples`` / ``batch`` / ``mixed_sizes``: see
     ``validate_checkpoint``."""
     root = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'])
     checkpoint_dir = os.path.join(root, 'checkpoints')
@@ -236,7 +264,7 @@ def validate(config, samples, sample_ids, categories=None, gt_records=None, poll
             if ckpt_id in done or ckpt_id <= last_id:
                 continue
             print('\nRunning checkpoint ' + str(ckpt_id) + '\n')
-            r = validate_checkpoint(config, path, samples, sample_ids, predictions_dir, categories, batch=batch)
+            r = validate_checkpoint(config, path, samples, sample_ids, predictions_dir, categories, batch=batch, mixed_sizes=mixed_sizes)
             if gt_records is not None and r['predictions'] is not None:
                 from .offline_eval import ap_report
                 r['ap'] = ap_report(gt_records, r['predictions']) if r['predictions'] else None
@@ -264,6 +292,8 @@ def main(argv=None):
     ap.add_argument('--poll', type=int, default=0, help='seconds between scans for new checkpoints (0: one pass)')
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--batch', type=int, default=8, help='frames per call on the --dataset route (frames are bucketed by source size)')
+    ap.add_argument('--mixed_sizes', action='store_true', help='with --dataset: one pass in dataset order, frames of any source sizes in '
+                    'one batch (default: bucketed by source size)')
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error('--batch must be at least 1')
@@ -283,7 +313,8 @@ def main(argv=None):
         samples = synthetic_samples(args.synthetic, args.image_size, dataset_config['anchor_generator'], num_classes, seed=args.seed)
         sample_ids = ['synthetic_%04d.jpg' % i for i in range(len(samples))]
         categories = ['car', 'truck', 'bus', 'person', 'rider', 'bike', 'motor'][:num_classes]
-    return validate(config, samples, sample_ids, categories=categories, poll_seconds=args.poll or None, batch=args.batch)
+    return validate(config, samples, sample_ids, categories=categories, poll_seconds=args.poll or None, batch=args.batch,
+                    mixed_sizes=bool(args.mixed_sizes and args.dataset))
 
 
 if __name__ == '__main__':

@@ -255,6 +255,21 @@ bod_status bod_upload_frames_u8(bod_handle h, const uint8_t* rgb, int32_t src_h,
  * has completed (bod_synchronize, or a later bod_collect of that batch).  Buffer 0 is bod_device_images(). */
 bod_status bod_upload_frames_u8_async(bod_handle h, const uint8_t* rgb, int32_t src_h, int32_t src_w,
                                       const float* rgb_means, int32_t aspect_resize, int32_t buffer);
+/* The same two uploads for a batch whose frames differ in source size (KITTI: 370x1224 .. 376x1241 interleaved through every
+ * split).  `rgb_packed` holds the frames back to back -- frame b starts at byte 3 * sum of h_i * w_i over i < b -- and
+ * src_hw[batch][2] their (h, w).  Every frame gets the resize / crop / pad geometry of its own size and comes out as
+ * bod_upload_frames_u8 of that size gives it, bit for bit; rgb_means are shared by the batch.  With aspect_resize != 0 on a
+ * handle whose kitti_scale_h > 0, frame b also gets its own rescale factors float(h_b / image_h), float(w_b / image_w): they
+ * belong to the image buffer filled, and the forward that consumes that buffer applies them in its posterior
+ * (inference_utils.py:147-167, S = orig / net per sample) in place of kitti_scale_h / kitti_scale_w.  A uniform upload,
+ * bod_upload_images or host float images into that buffer bring the handle's two scalars back.  BOD_ERR_INVALID_ARG, naming
+ * the frame, for a size below 1, a degenerate resize, or aspect_resize == 0 with a frame not at the network size; the
+ * handle and the frames it held stay as they were.  Staging, streams and the lifetime of `rgb_packed` as for the uniform
+ * pair (src_hw is read before the call returns). */
+bod_status bod_upload_frames_u8_ragged(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw,
+                                       const float* rgb_means, int32_t aspect_resize);
+bod_status bod_upload_frames_u8_ragged_async(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw,
+                                             const float* rgb_means, int32_t aspect_resize, int32_t buffer);
 const float* bod_device_images_buffer(bod_handle h, int32_t buffer);
 const float* bod_device_images(bod_handle h);
 bod_status bod_synchronize(bod_handle h);
