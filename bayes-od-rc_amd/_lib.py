@@ -35,7 +35,8 @@ class BodConfig(C.Structure):
         ("training", C.c_int32),
         ("backbone_depth", C.c_int32),
         ("pipeline_overlap", C.c_int32),
-        ("reserved", C.c_int32 * 2),
+        ("mc_statistics", C.c_int32),
+        ("reserved", C.c_int32 * 1),
     ]
 
 
@@ -127,6 +128,14 @@ SIGNATURES = {
     "bod_profile_select": (C.c_int, [_H, C.c_int32]),
     "bod_plan_info": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "bod_plan_info_n": (C.c_int, [_H, C.POINTER(C.c_int32), C.c_int32]),
+    "bod_stat_reset": (C.c_int, [_H]),
+    "bod_stat_forward": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32]),
+    "bod_stat_merge_from": (C.c_int, [_H, _H]),
+    "bod_stat_merge": (C.c_int, [_H, C.POINTER(C.c_void_p), C.c_int32]),
+    "bod_stat_device": (C.c_int, [_H, C.POINTER(C.c_void_p), _I]),
+    "bod_stat_get": (C.c_int, [_H, _F, _F, _F, _I]),
+    "bod_stat_set": (C.c_int, [_H, _F, _F, _F, C.c_int32]),
+    "bod_stat_posterior": (C.c_int, [_H, C.c_uint64, C.c_uint32]),
     "bod_record_width": (C.c_int32, [_H]),
     "bod_gather_detections": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
     "bod_profile_end": (C.c_int, [_H, C.POINTER(C.c_double), C.POINTER(C.c_int64),

@@ -306,9 +306,16 @@ struct bod_context {
     bool plan_halo = false;                              // ... and box layer 1 / covariance layer 2 over the tail's 3x3 halo
     SparseTailArgs sparse{};
     bool agg_sparse = false;                             // the last forward's agg[1] / agg[2] are sparse
+    // Statistics handles (bod_config.mc_statistics): the accumulator of the bod_stat_* entry points -- a second set of the three
+    // agg[] arrays holding the merged statistics of stat_k samples.  agg[] itself receives every bod_stat_forward's fresh record (from
+    // the aggregating flavour, or from raw[] through stat_from_raw_kernel on plans without one) and is the merge's source.
+    float* stat_acc[3] = {nullptr};
+    int stat_k = 0;
+    hipEvent_t ev_stat = nullptr;                        // bod_stat_merge_from: orders the two handles' streams
     bool keep_ready = false;                             // pb.keep / d_counts / block_counts / num_kept hold the keep stage's output
     uint64_t keep_seed = 0; uint32_t keep_first = 0;
     uint64_t last_seed = 0; uint32_t last_first_image = 0;
+    int32_t last_sample_base = 0;                        // mc_sample_base of the last forward (bod_stat_forward passes its own): materialise_raw re-runs with it
     std::map<std::string, RowEnt*> tables;
     struct XrTable { RowEnt* rows = nullptr; int2* ext = nullptr; int m = 0; };
     std::map<std::string, XrTable> xr_tables;          // row-reuse tilings of plane -> plane 3x3 layers (add_conv)
@@ -697,6 +704,18 @@ const uint32_t* train_dyn_rng(bod_context* h);
 void train_destroy(bod_context* h);
 void val_destroy(bod_context* h);               // validate_impl.inc
 
+// The accumulator of a statistics handle (34 floats per anchor and image): with the plan, or on the first bod_stat_* call of a
+// handle that never gets weights (a merge-and-posterior handle, like the raw buffers of such a handle: ensure_raw)
+bod_status ensure_stat(bod_context* h) {
+    if (h->stat_acc[0]) return BOD_OK;
+    const bod_config& c = h->cfg;
+    const size_t BA = (size_t)c.batch * h->A;
+    BODCHK(h->dalloc(&h->stat_acc[0], BA * c.num_classes));
+    BODCHK(h->dalloc(&h->stat_acc[1], BA * 16));
+    if (c.has_covar_head) BODCHK(h->dalloc(&h->stat_acc[2], BA * 10));
+    return BOD_OK;
+}
+
 bod_status build_plan(bod_context* h) {
     const bod_config& c = h->cfg;
     const int B = c.batch, N = c.mc_samples;
@@ -1015,7 +1034,7 @@ bod_status build_plan(bod_context* h) {
     // :220-244): a tile of those layers must hold ALL N samples of its pixels, so they get their own row table -- tiles of
     // Q <= 256 / N pixel slots, row = slot * N + sample, made of runs of x-adjacent pixels whose extended rows (run + 2,
     // once per sample) fit the 320 staged rows.  BOD_FUSE_AGGREGATION=0 keeps the raw tensors + the posterior's own loops.
-    bool agg = xreuse && fuse_out && N >= 2 && 256 / N >= 1 && 320 / N - 2 >= 1 && c.mc_ensemble_size <= N;
+    bool agg = xreuse && fuse_out && N >= 2 && 256 / N >= 1 && 320 / N - 2 >= 1 && (c.mc_ensemble_size <= N || c.mc_statistics);      // (a statistics handle's record is one part of a larger ensemble's by design)
     if (const char* e = getenv("BOD_FUSE_AGGREGATION")) agg = agg && atoi(e) != 0;
     RowEnt* d2a = nullptr; int2* dexta = nullptr; int m2a = 0;
     if (agg) {
@@ -1037,14 +1056,22 @@ bod_status build_plan(bod_context* h) {
     } else {
         BODCHK(ensure_raw(h));                 // the ops below reference the raw tensors directly
     }
+    if (c.mc_statistics) {                     // the accumulator and, on plans without the aggregating flavour, stat_from_raw_kernel's output
+        const size_t BA = (size_t)B * h->A;
+        const size_t per[3] = {(size_t)c.num_classes, 16, 10};
+        for (int k = 0; k < (c.has_covar_head ? 3 : 2); ++k)
+            if (!h->agg[k]) BODCHK(h->dalloc(&h->agg[k], BA * per[k]));
+        BODCHK(ensure_stat(h));
+    }
     // ---- Sparse tail: only the classification head's statistics decide which anchors are kept (post_sample_kernel), and everything
     // behind the filter reads the box and covariance statistics of kept anchors only (post_fuse_kernel, through anchor_index) -- about
     // 2 % of them at the reference's operating point.  So the launch of the heads that end at layer 2 (box regression) and at layer 3
     // (covariance) moves behind the classification head's last layer and the keep flags, and runs over the pixels with a kept anchor
     // (SparseTailArgs): the same rows, products and epilogue as the dense launch, for those pixels.  BOD_SPARSE_TAIL=0: the dense plan.
     // (Not on pipeline_overlap handles, the experimental CU-partitioned mode: they keep the dense plan.)
-    bool sparse = agg && h->es == 2 && !h->split && !mx_plan && !c.pipeline_overlap && h->A == h->P * c.anchors_per_location &&
-                  h->P <= 65536;
+    // (Nor on statistics handles: the kept set depends on the MERGED class statistics, so every anchor's record must exist.)
+    bool sparse = agg && h->es == 2 && !h->split && !mx_plan && !c.pipeline_overlap && !c.mc_statistics &&
+                  h->A == h->P * c.anchors_per_location && h->P <= 65536;
     if (const char* e = getenv("BOD_SPARSE_TAIL")) sparse = sparse && atoi(e) != 0;
     // ---- Sparse halo: the tail's 3x3 windows read box layer 1's and covariance layer 2's outputs only around the tail's pixels, and
     // nothing else reads them in an aggregating forward.  So in aggregating forwards those two convs leave the dense launches of
@@ -1562,6 +1589,7 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
     }
     h->forward_done = true; h->posterior_done = h->nms_done = h->cluster_done = false; h->affinity_img = -1;
     h->last_seed = seed; h->last_first_image = first_image;
+    if (!only_flavoured) h->last_sample_base = c.mc_sample_base;
     if (flavour == FLAVOUR_AGG) { h->agg_valid = true; h->raw_valid = false; h->agg_sparse = h->plan_sparse; }
     else { h->raw_valid = true; if (!only_flavoured) h->agg_valid = false; }
     return BOD_OK;
@@ -1577,7 +1605,10 @@ bod_status materialise_raw(bod_context* h) {
     h->profiling = false;
     const bool fd = h->forward_done, pd = h->posterior_done, nd = h->nms_done, cd = h->cluster_done;
     const int aff = h->affinity_img;
+    const int32_t base = h->cfg.mc_sample_base;
+    h->cfg.mc_sample_base = h->last_sample_base;
     const bod_status st = run_forward(h, h->cur_images, h->last_seed, h->last_first_image, FLAVOUR_RAW, true);
+    h->cfg.mc_sample_base = base;
     h->profiling = prof;
     h->forward_done = fd; h->posterior_done = pd; h->nms_done = nd; h->cluster_done = cd; h->affinity_img = aff;
     return st;
@@ -1744,6 +1775,10 @@ bod_status bod_create(const bod_config* cfg, bod_handle* out) {
     if (c.nms_max_output_size < 1 || c.nms_max_output_size > 512) return bail(h->fail(BOD_ERR_INVALID_ARG, "nms_max_output_size must be in [1,512]"));
     if (c.precision != BOD_PRECISION_BF16 && c.precision != BOD_PRECISION_FP32 && c.precision != BOD_PRECISION_BF16X3 && c.precision != BOD_PRECISION_F16MX && c.precision != BOD_PRECISION_F16MX4)
         return bail(h->fail(BOD_ERR_INVALID_ARG, "precision must be BOD_PRECISION_BF16 (0), BOD_PRECISION_FP32 (1), BOD_PRECISION_BF16X3 (2), BOD_PRECISION_F16MX (3) or BOD_PRECISION_F16MX4 (4)"));
+    if (c.mc_statistics != 0 && c.mc_statistics != 1) return bail(h->fail(BOD_ERR_INVALID_ARG, "mc_statistics must be 0 or 1, got %d", c.mc_statistics));
+    if (c.mc_statistics && (c.training || c.pipeline_overlap))
+        return bail(h->fail(BOD_ERR_INVALID_ARG, "mc_statistics: statistics handles are inference handles on one stream (%s = 1 refused)",
+                            c.training ? "training" : "pipeline_overlap"));
     h->es = c.precision == BOD_PRECISION_BF16 ? 2 : 4;
     h->split = c.precision == BOD_PRECISION_BF16X3 || c.precision == BOD_PRECISION_F16MX || c.precision == BOD_PRECISION_F16MX4;
     h->mx = c.precision == BOD_PRECISION_F16MX ? 1 : c.precision == BOD_PRECISION_F16MX4 ? 2 : 0;
@@ -1809,6 +1844,8 @@ bod_status bod_create(const bod_config* cfg, bod_handle* out) {
         hipEventCreateWithFlags(&h->ev_done[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_done[1], hipEventDisableTiming) != hipSuccess)
         return bail(h->fail(BOD_ERR_HIP, "hipEventCreate failed"));
+    if (c.mc_statistics && hipEventCreateWithFlags(&h->ev_stat, hipEventDisableTiming) != hipSuccess)
+        return bail(h->fail(BOD_ERR_HIP, "hipEventCreate failed"));
     bod_status s = build_geometry(h.get());
     if (s != BOD_OK) return bail(s);
     if ((int64_t)c.batch * c.mc_samples * h->Ppad >= (1LL << 31))
@@ -1830,6 +1867,7 @@ bod_status bod_destroy(bod_handle h) {
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->side) { hipStreamSynchronize(h->side); hipStreamDestroy(h->side); }
     if (h->ev_posterior) hipEventDestroy(h->ev_posterior);
+    if (h->ev_stat) hipEventDestroy(h->ev_stat);
     for (int sidx = 0; sidx < 2; ++sidx) if (h->ev_done[sidx]) hipEventDestroy(h->ev_done[sidx]);
     train_destroy(h);
     val_destroy(h);
@@ -1873,7 +1911,7 @@ bod_status bod_update_config(bod_handle h, const bod_config* cfg) {
         cfg->mc_samples != o.mc_samples || cfg->num_classes != o.num_classes ||
         cfg->anchors_per_location != o.anchors_per_location || cfg->min_level != o.min_level ||
         cfg->max_level != o.max_level || cfg->has_covar_head != o.has_covar_head || cfg->dropout_rate != o.dropout_rate ||
-        cfg->precision != o.precision || cfg->training != o.training || cfg->backbone_depth != o.backbone_depth || cfg->pipeline_overlap != o.pipeline_overlap || (std::max(cfg->mc_ensemble_size, cfg->mc_samples) > 1) != (std::max(o.mc_ensemble_size, o.mc_samples) > 1))
+        cfg->precision != o.precision || cfg->training != o.training || cfg->backbone_depth != o.backbone_depth || cfg->pipeline_overlap != o.pipeline_overlap || cfg->mc_statistics != o.mc_statistics || (std::max(cfg->mc_ensemble_size, cfg->mc_samples) > 1) != (std::max(o.mc_ensemble_size, o.mc_samples) > 1))
         return h->fail(BOD_ERR_INVALID_ARG, "bod_update_config: geometry / model fields cannot change on a live handle");
     if (cfg->nms_max_output_size != o.nms_max_output_size)
         return h->fail(BOD_ERR_INVALID_ARG, "bod_update_config: nms_max_output_size sizes device buffers and cannot change");
@@ -3227,6 +3265,153 @@ bod_status bod_plan_info_n(bod_handle h, int32_t* info, int32_t n) {
     BODCHK(bod_plan_info(h, all));
     all[8] = h->plan_halo;
     for (int i = 0; i < n && i < 9; ++i) info[i] = all[i];
+    return BOD_OK;
+}
+
+// ---- mergeable MC statistics (include/bayesod.h): handles created with mc_statistics = 1
+static bod_status stat_handle(bod_handle h, const char* who) {
+    if (!h->cfg.mc_statistics) return h->fail(BOD_ERR_INVALID_ARG, "%s: the handle was not created with mc_statistics = 1", who);
+    BODCHK(join_overlap(h));
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return ensure_stat(h);
+}
+
+// accumulator (+)= {cls_sum, box_moments, cov_sum} of kb samples, on the handle's stream
+static bod_status stat_fold(bod_handle h, const char* who, const float* cls, const float* box, const float* cov, int kb) {
+    if (kb < 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: a record of %d samples", who, kb);
+    if (h->stat_k > (1 << 24) - kb) return h->fail(BOD_ERR_INVALID_ARG, "%s: more than 2^24 samples in one accumulator", who);
+    StatMergeArgs m{};
+    m.BA = (int64_t)h->cfg.batch * h->A; m.C = h->cfg.num_classes; m.ka = h->stat_k; m.kb = kb;
+    m.acc_cls = h->stat_acc[0]; m.acc_box = h->stat_acc[1]; m.acc_cov = h->stat_acc[2];
+    m.src_cls = cls; m.src_box = box; m.src_cov = h->cfg.has_covar_head ? cov : nullptr;
+    if (!cls || !box || (h->cfg.has_covar_head && !cov)) return h->fail(BOD_ERR_INVALID_ARG, "%s: NULL statistics array", who);
+    if (cls == m.acc_cls || box == m.acc_box) return h->fail(BOD_ERR_INVALID_ARG, "%s: the source is the accumulator itself", who);
+    if (((uintptr_t)cls | (uintptr_t)box | (uintptr_t)m.src_cov) & 15u) return h->fail(BOD_ERR_INVALID_ARG, "%s: statistics arrays must be 16-byte aligned", who);
+    HIPCHK(h, launch_stat_merge(m, h->stream));
+    h->stat_k += kb;
+    return BOD_OK;
+}
+
+bod_status bod_stat_reset(bod_handle h) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(stat_handle(h, "bod_stat_reset"));
+    h->stat_k = 0;
+    return BOD_OK;
+}
+
+bod_status bod_stat_forward(bod_handle h, const float* images, int32_t on_device, uint64_t seed, uint32_t first_image_id, int32_t sample_base) {
+    MarkerRange mr_api("bod:stat_forward");
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(stat_handle(h, "bod_stat_forward"));
+    if (!h->weights_ready) return h->fail(BOD_ERR_NOT_READY, "weights not finalized");
+    if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called (the box statistics are those of the decoded boxes)");
+    const bod_config& c = h->cfg;
+    const int n = c.mc_samples;
+    if (sample_base < 0 || sample_base + n > 65535 || (c.mc_ensemble_size > 0 && sample_base + n > c.mc_ensemble_size))
+        return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_forward: sample_base=%d / mc_samples=%d / mc_ensemble_size=%d inconsistent", sample_base, n,
+                       c.mc_ensemble_size);
+    if (h->stat_k > (1 << 24) - n) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_forward: more than 2^24 samples in one accumulator");
+    const float* dev = nullptr;
+    BODCHK(stage_images(h, images, on_device, &dev));
+    h->cur_images = dev;
+    const int flavour = h->agg_plan ? FLAVOUR_AGG : FLAVOUR_RAW;
+    const int32_t base = c.mc_sample_base;
+    h->cfg.mc_sample_base = sample_base;                  // (the forward reads it per launch: ConvArgs.sample_base)
+    const bod_status st = run_forward(h, dev, seed, first_image_id, flavour);
+    h->cfg.mc_sample_base = base;
+    BODCHK(st);
+    if (flavour == FLAVOUR_RAW) {                          // no aggregating plan (n = 1, small geometries, fp32): the same reduction from raw[]
+        StatRawArgs r{};
+        r.B = c.batch; r.N = n; r.A = h->A; r.C = c.num_classes;
+        r.cls = h->raw[0]; r.box = h->raw[1]; r.cov = c.has_covar_head ? h->raw[2] : nullptr; r.anchors = h->d_anchors;
+        r.cls_sum = h->agg[0]; r.box_moments = h->agg[1]; r.cov_sum = c.has_covar_head ? h->agg[2] : nullptr;
+        HIPCHK(h, launch_stat_from_raw(r, h->stream));
+    }
+    return stat_fold(h, "bod_stat_forward", h->agg[0], h->agg[1], h->agg[2], n);
+}
+
+bod_status bod_stat_merge_from(bod_handle dst, bod_handle src) {
+    if (!dst) return BOD_ERR_INVALID_ARG;
+    if (!src) return dst->fail(BOD_ERR_INVALID_ARG, "bod_stat_merge_from: src is NULL");
+    if (src == dst) return dst->fail(BOD_ERR_INVALID_ARG, "bod_stat_merge_from: src and dst are the same handle");
+    if (!src->cfg.mc_statistics) return dst->fail(BOD_ERR_INVALID_ARG, "bod_stat_merge_from: src was not created with mc_statistics = 1");
+    const bod_config& a = dst->cfg; const bod_config& b = src->cfg;
+    const char* field = a.device != b.device ? "device" : a.batch != b.batch ? "batch" : dst->A != src->A ? "num_anchors" :
+                        a.num_classes != b.num_classes ? "num_classes" : a.has_covar_head != b.has_covar_head ? "has_covar_head" : nullptr;
+    if (field) return dst->fail(BOD_ERR_INVALID_ARG, "bod_stat_merge_from: the handles differ in %s", field);
+    BODCHK(stat_handle(dst, "bod_stat_merge_from"));
+    if (src->stat_k == 0) return BOD_OK;
+    if (stat_handle(src, "bod_stat_merge_from") != BOD_OK) return dst->fail(BOD_ERR_HIP, "bod_stat_merge_from: src: %s", src->err.c_str());
+    HIPCHK(dst, hipEventRecord(src->ev_stat, src->stream));              // src's accumulator is complete ...
+    HIPCHK(dst, hipStreamWaitEvent(dst->stream, src->ev_stat, 0));
+    BODCHK(stat_fold(dst, "bod_stat_merge_from", src->stat_acc[0], src->stat_acc[1], src->stat_acc[2], src->stat_k));
+    HIPCHK(dst, hipEventRecord(dst->ev_stat, dst->stream));              // ... and is not rewritten before the merge has read it
+    HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev_stat, 0));
+    return BOD_OK;
+}
+
+bod_status bod_stat_merge(bod_handle h, const void* const* ptrs3, int32_t samples) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(stat_handle(h, "bod_stat_merge"));
+    if (!ptrs3) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_merge: ptrs3 is NULL");
+    return stat_fold(h, "bod_stat_merge", static_cast<const float*>(ptrs3[0]), static_cast<const float*>(ptrs3[1]),
+                     static_cast<const float*>(ptrs3[2]), samples);
+}
+
+bod_status bod_stat_device(bod_handle h, void** ptrs3, int32_t* samples) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(stat_handle(h, "bod_stat_device"));
+    if (ptrs3) { ptrs3[0] = h->stat_acc[0]; ptrs3[1] = h->stat_acc[1]; ptrs3[2] = h->cfg.has_covar_head ? h->stat_acc[2] : nullptr; }
+    if (samples) *samples = h->stat_k;
+    return BOD_OK;
+}
+
+bod_status bod_stat_get(bod_handle h, float* cls_sum, float* box_moments, float* cov_sum, int32_t* samples) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(stat_handle(h, "bod_stat_get"));
+    if (cov_sum && !h->cfg.has_covar_head) return h->fail(BOD_ERR_INVALID_ARG, "model has no covariance head");
+    const size_t BA = (size_t)h->cfg.batch * h->A;
+    BODCHK(d2h(h, cls_sum, h->stat_acc[0], BA * h->cfg.num_classes));
+    BODCHK(d2h(h, box_moments, h->stat_acc[1], BA * 16));
+    BODCHK(d2h(h, cov_sum, h->stat_acc[2], BA * 10));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (samples) *samples = h->stat_k;
+    return BOD_OK;
+}
+
+bod_status bod_stat_set(bod_handle h, const float* cls_sum, const float* box_moments, const float* cov_sum, int32_t samples) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(stat_handle(h, "bod_stat_set"));
+    if (samples < 0 || samples > (1 << 24)) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_set: samples = %d", samples);
+    if (cov_sum && !h->cfg.has_covar_head) return h->fail(BOD_ERR_INVALID_ARG, "model has no covariance head");
+    const size_t BA = (size_t)h->cfg.batch * h->A;
+    if (cls_sum) HIPCHK(h, hipMemcpyAsync(h->stat_acc[0], cls_sum, BA * h->cfg.num_classes * 4, hipMemcpyHostToDevice, h->stream));
+    if (box_moments) HIPCHK(h, hipMemcpyAsync(h->stat_acc[1], box_moments, BA * 64, hipMemcpyHostToDevice, h->stream));
+    if (cov_sum) HIPCHK(h, hipMemcpyAsync(h->stat_acc[2], cov_sum, BA * 40, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->stat_k = samples;
+    return BOD_OK;
+}
+
+bod_status bod_stat_posterior(bod_handle h, uint64_t seed, uint32_t first_image_id) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(stat_handle(h, "bod_stat_posterior"));
+    if (h->stat_k < 2) return h->fail(BOD_ERR_NOT_READY, "bod_stat_posterior: the accumulator holds %d samples; bayes_od needs >= 2 (sample covariance divides by N-1)", h->stat_k);
+    if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called");
+    for (int sidx = 0; sidx < 2; ++sidx)
+        if (h->side_pending[sidx]) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_done[sidx], 0));
+    MarkerRange mr("bod:posterior");
+    PostCfg pc = post_cfg(h, seed, first_image_id);
+    pc.N = h->stat_k;                                    // the merged sample count
+    pc.aggregated = 1;
+    PostBuffers pb = h->pb;
+    pb.cls = nullptr; pb.box = nullptr; pb.cov = nullptr; pb.anchors = h->d_anchors;
+    pb.agg_cls = h->stat_acc[0]; pb.agg_box = h->stat_acc[1]; pb.agg_cov = h->stat_acc[2];
+    h->keep_ready = false;                               // the keep flags are rewritten
+    HIPCHK(h, launch_posterior(pc, pb, h->stream));
+    if (h->cfg.ranking_method == BOD_RANK_JOINT_ENTROPY && h->cfg.gaussian_isotropic && h->cfg.dirichlet_non_informative)
+        HIPCHK(h, launch_joint_entropy_rank(pc, pb, h->stream));
+    h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;
     return BOD_OK;
 }
 

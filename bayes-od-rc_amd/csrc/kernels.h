@@ -356,6 +356,25 @@ struct TargetArgs {
 hipError_t launch_anchor_targets(const TargetArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
+// Mergeable MC statistics (stat_kernels.hip; record layout: include/bayesod.h): the three per-anchor arrays of the fused
+// epilogues (ConvGroup.agg_kind) from raw head outputs of n >= 1 samples, and the fold of one set of them into another
+struct StatRawArgs {
+    int32_t B, N, A, C;
+    const float* cls; const float* box; const float* cov;      // raw [B,N,A,C], [B,N,A,4], [B,N,A,10] (cov: nullptr without the head)
+    const float* anchors;                                       // [A,4] (v, u, h, w)
+    float* cls_sum; float* box_moments; float* cov_sum;         // [B,A,C], [B,A,16], [B,A,10] (nullptr with cov)
+};
+hipError_t launch_stat_from_raw(const StatRawArgs& a, hipStream_t s);
+struct StatMergeArgs {
+    int64_t BA;                                                 // images * anchors
+    int32_t C;
+    int32_t ka, kb;                                             // samples in the accumulator (0: copy the source) / in the source (>= 1)
+    float* acc_cls; float* acc_box; float* acc_cov;             // 16-byte aligned; acc_cov / src_cov both nullptr without the head
+    const float* src_cls; const float* src_box; const float* src_cov;
+};
+hipError_t launch_stat_merge(const StatMergeArgs& a, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // Streaming pointwise (1x1) convolution for reductions of <= 256 channels (conv_pointwise.hip); launch_conv_igemm routes eligible
 // launches there (BOD_POINTWISE=0: off)
 bool conv_pointwise_eligible(const ConvArgs& a);

@@ -1,0 +1,182 @@
+// MC statistics that can be accumulated and merged (include/bayesod.h, "statistics handles"): the per-anchor record the last
+// tower layers' epilogues reduce over the samples of ONE forward (conv_igemm.hip agg_reduce_cls / agg_reduce_box / agg_reduce_cov)
+//
+//   cls_sum     [B,A,C]   sum over samples of softmax(logits)
+//   box_moments [B,A,16]  Welford mean[4] of the decoded boxes, lower triangle of the co-moment sums M2 row-major [10], 0, 0
+//   cov_sum     [B,A,10]  sum over samples of the raw covariance parameters (absent without the covariance head)
+//
+// produced from raw [B,n,A,.] head outputs (stat_from_raw_kernel: handles without an aggregating plan) and folded into an
+// accumulator of ka samples (stat_merge_kernel).  The file is built with -ffp-contract=off, the correctly rounded division and the
+// library expf: stat_from_raw_kernel's results are compared with the fused epilogues' for equality, stat_merge_kernel's with a
+// float64 statement of the same formula.
+#include "kernels.h"
+#include <math.h>
+#include <algorithm>
+
+#define STAT_BLOCK 256
+#define STAT_MAX_GRID 2048          // memory-bound: grid-stride beyond 8 blocks per compute unit
+
+// One thread per (image, anchor); the same operations in the same order as agg_reduce_cls / agg_reduce_box / agg_reduce_cov, whose
+// tile holds the n samples of a pixel as LDS rows -- here they are rows of the raw tensors.
+template <int C>
+__global__ __launch_bounds__(STAT_BLOCK) void stat_from_raw_kernel(StatRawArgs a) {
+    const size_t BA = (size_t)a.B * a.A;
+    for (size_t idx = (size_t)blockIdx.x * STAT_BLOCK + threadIdx.x; idx < BA; idx += (size_t)gridDim.x * STAT_BLOCK) {
+        const size_t b = idx / (size_t)a.A, an = idx - b * (size_t)a.A;
+        const size_t row0 = b * (size_t)a.N * a.A + an;                  // sample 0; sample n at row0 + n * A
+        {   // sum_n softmax(logits)
+            float mp[C];
+#pragma unroll
+            for (int j = 0; j < C; ++j) mp[j] = 0.f;
+            for (int n = 0; n < a.N; ++n) {
+                const float* l = a.cls + (row0 + (size_t)n * a.A) * C;
+                float v[C];
+#pragma unroll
+                for (int k = 0; k < C / 4; ++k) {
+                    const float4 t = reinterpret_cast<const float4*>(l)[k];
+                    v[4 * k] = t.x; v[4 * k + 1] = t.y; v[4 * k + 2] = t.z; v[4 * k + 3] = t.w;
+                }
+                float mx = v[0];
+#pragma unroll
+                for (int j = 1; j < C; ++j) mx = fmaxf(mx, v[j]);
+                float sden = 0.f;
+#pragma unroll
+                for (int j = 0; j < C; ++j) { v[j] = expf(v[j] - mx); sden += v[j]; }
+#pragma unroll
+                for (int j = 0; j < C; ++j) mp[j] += v[j] / sden;
+            }
+            float* o = a.cls_sum + idx * C;
+#pragma unroll
+            for (int k = 0; k < C / 4; ++k) reinterpret_cast<float4*>(o)[k] = make_float4(mp[4 * k], mp[4 * k + 1], mp[4 * k + 2], mp[4 * k + 3]);
+        }
+        {   // Welford mean and co-moment sums of the decoded boxes
+            const float4 anc = reinterpret_cast<const float4*>(a.anchors)[an];
+            float mean[4] = {0.f, 0.f, 0.f, 0.f}, m2[10];
+#pragma unroll
+            for (int k = 0; k < 10; ++k) m2[k] = 0.f;
+            for (int n = 0; n < a.N; ++n) {
+                const float4 t = reinterpret_cast<const float4*>(a.box)[row0 + (size_t)n * a.A];
+                float x[4];
+                x[0] = anc.z * t.x / 10.0f + anc.x;
+                x[1] = anc.w * t.y / 10.0f + anc.y;
+                x[2] = anc.z * fminf(fmaxf(expf(t.z / 5.0f), 1e-4f), 1e4f);
+                x[3] = anc.w * fminf(fmaxf(expf(t.w / 5.0f), 1e-4f), 1e4f);
+                const float inv = 1.0f / (float)(n + 1);
+                float d[4], e[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { d[i] = x[i] - mean[i]; mean[i] += d[i] * inv; e[i] = x[i] - mean[i]; }
+                int k = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j <= i; ++j) m2[k++] += d[i] * e[j];
+            }
+            float4* o = reinterpret_cast<float4*>(a.box_moments + idx * 16);
+            o[0] = make_float4(mean[0], mean[1], mean[2], mean[3]);
+            o[1] = make_float4(m2[0], m2[1], m2[2], m2[3]);
+            o[2] = make_float4(m2[4], m2[5], m2[6], m2[7]);
+            o[3] = make_float4(m2[8], m2[9], 0.f, 0.f);
+        }
+        if (a.cov) {   // sum_n of the covariance parameters (rows of 10 floats: 8-byte aligned)
+            float acc[10];
+#pragma unroll
+            for (int k = 0; k < 10; ++k) acc[k] = 0.f;
+            for (int n = 0; n < a.N; ++n) {
+                const float2* p = reinterpret_cast<const float2*>(a.cov + (row0 + (size_t)n * a.A) * 10);
+#pragma unroll
+                for (int k = 0; k < 5; ++k) { const float2 t = p[k]; acc[2 * k] += t.x; acc[2 * k + 1] += t.y; }
+            }
+            float2* o = reinterpret_cast<float2*>(a.cov_sum + idx * 10);
+#pragma unroll
+            for (int k = 0; k < 5; ++k) o[k] = make_float2(acc[2 * k], acc[2 * k + 1]);
+        }
+    }
+}
+
+hipError_t launch_stat_from_raw(const StatRawArgs& a, hipStream_t s) {
+    if (a.B < 1 || a.N < 1 || a.A < 1 || (a.C != 4 && a.C != 8) || !a.cls || !a.box || !a.anchors || !a.cls_sum || !a.box_moments ||
+        ((a.cov != nullptr) != (a.cov_sum != nullptr)))
+        return hipErrorInvalidValue;
+    const size_t BA = (size_t)a.B * a.A;
+    const unsigned grid = (unsigned)std::min<size_t>((BA + STAT_BLOCK - 1) / STAT_BLOCK, STAT_MAX_GRID);
+    if (a.C == 8) hipLaunchKernelGGL(stat_from_raw_kernel<8>, dim3(grid), dim3(STAT_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL(stat_from_raw_kernel<4>, dim3(grid), dim3(STAT_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// accumulator (ka samples) <- accumulator (+) source (kb samples), one pass, 16-byte loads and stores, no atomics.  The work items
+// of the three arrays are laid end to end: [0, BA) one box record each, then the float4s of cls_sum, then those of cov_sum (whose
+// last item may be a partial one: B*A*10 need not be a multiple of 4).  Operation order, per (image, anchor):
+//   cls_sum, cov_sum:  acc = acc + src
+//   d_i   = mean_b,i - mean_a,i            w = kb / (ka + kb)            kw = ka * w
+//   mean_i = mean_a,i + d_i * w
+//   M2_ij  = (M2a_ij + M2b_ij) + (d_i * d_j) * kw          for the 10 stored entries, i >= j
+//   pads   = 0
+// ka == 0: every array is a copy of the source (the accumulator's old contents are not read).
+template <int C>
+__global__ __launch_bounds__(STAT_BLOCK) void stat_merge_kernel(StatMergeArgs a) {
+    const size_t n_box = a.BA, n_cls = a.BA * (C / 4), cov_f = a.acc_cov ? a.BA * 10 : 0, n_cov = (cov_f + 3) / 4;
+    const size_t total = n_box + n_cls + n_cov;
+    const bool copy = a.ka == 0;
+    const float fka = (float)a.ka, fkb = (float)a.kb;
+    const float w = fkb / (fka + fkb);
+    const float kw = fka * w;
+    for (size_t it = (size_t)blockIdx.x * STAT_BLOCK + threadIdx.x; it < total; it += (size_t)gridDim.x * STAT_BLOCK) {
+        if (it < n_box) {
+            const float4* sb = reinterpret_cast<const float4*>(a.src_box) + it * 4;
+            float4* ab = reinterpret_cast<float4*>(a.acc_box) + it * 4;
+            const float4 s0 = sb[0], s1 = sb[1], s2 = sb[2], s3 = sb[3];
+            if (copy) {
+                ab[0] = s0; ab[1] = s1; ab[2] = s2; ab[3] = make_float4(s3.x, s3.y, 0.f, 0.f);
+                continue;
+            }
+            const float4 a0 = ab[0], a1 = ab[1], a2 = ab[2], a3 = ab[3];
+            const float ma[4] = {a0.x, a0.y, a0.z, a0.w}, mb[4] = {s0.x, s0.y, s0.z, s0.w};
+            const float qa[10] = {a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w, a3.x, a3.y};
+            const float qb[10] = {s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w, s3.x, s3.y};
+            float d[4], m[4], q[10];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { d[i] = mb[i] - ma[i]; m[i] = ma[i] + d[i] * w; }
+            int k = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j <= i; ++j) { q[k] = (qa[k] + qb[k]) + (d[i] * d[j]) * kw; ++k; }
+            ab[0] = make_float4(m[0], m[1], m[2], m[3]);
+            ab[1] = make_float4(q[0], q[1], q[2], q[3]);
+            ab[2] = make_float4(q[4], q[5], q[6], q[7]);
+            ab[3] = make_float4(q[8], q[9], 0.f, 0.f);
+            continue;
+        }
+        size_t j = it - n_box;
+        const float* src = a.src_cls;
+        float* acc = a.acc_cls;
+        size_t floats = n_cls * 4;
+        if (j >= n_cls) { j -= n_cls; src = a.src_cov; acc = a.acc_cov; floats = cov_f; }
+        if (j * 4 + 4 <= floats) {
+            const float4 sv = reinterpret_cast<const float4*>(src)[j];
+            float4 r = sv;
+            if (!copy) {
+                const float4 av = reinterpret_cast<const float4*>(acc)[j];
+                r = make_float4(av.x + sv.x, av.y + sv.y, av.z + sv.z, av.w + sv.w);
+            }
+            reinterpret_cast<float4*>(acc)[j] = r;
+        } else {
+            for (size_t e = j * 4; e < floats; ++e) acc[e] = copy ? src[e] : acc[e] + src[e];
+        }
+    }
+}
+
+hipError_t launch_stat_merge(const StatMergeArgs& a, hipStream_t s) {
+    if (a.BA < 1 || (a.C != 4 && a.C != 8) || a.ka < 0 || a.kb < 1 || !a.acc_cls || !a.acc_box || !a.src_cls || !a.src_box ||
+        ((a.acc_cov != nullptr) != (a.src_cov != nullptr)))
+        return hipErrorInvalidValue;
+    const void* p[6] = {a.acc_cls, a.acc_box, a.acc_cov, a.src_cls, a.src_box, a.src_cov};
+    for (const void* q : p)
+        if ((reinterpret_cast<uintptr_t>(q) & 15u) != 0) return hipErrorInvalidValue;          // 16-byte loads and stores
+    const size_t total = a.BA + a.BA * (size_t)a.C / 4 + (a.acc_cov ? (a.BA * 10 + 3) / 4 : 0);
+    const unsigned grid = (unsigned)std::min<size_t>((total + STAT_BLOCK - 1) / STAT_BLOCK, STAT_MAX_GRID);
+    if (a.C == 8) hipLaunchKernelGGL(stat_merge_kernel<8>, dim3(grid), dim3(STAT_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL(stat_merge_kernel<4>, dim3(grid), dim3(STAT_BLOCK), 0, s, a);
+    return hipGetLastError();
+}

@@ -168,6 +168,120 @@ class SampleShardedEngine(object):
 
 
 # ---------------------------------------------------------------------------------------------------
+# Sample sharding on statistics (include/bayesod.h, mc_statistics): every rank reduces its n samples to the per-anchor
+# statistics record -- 34 floats per anchor and image whatever n is, against 22 per anchor AND sample of the raw exchange --
+# ONE all-gather moves the records, and every rank folds the W records in rank order with the merge kernel, so all ranks
+# hold the same bits.  The fold re-associates the Welford sums (Chan's update): results agree with the single-handle run to
+# fp32 round-off, not bit for bit -- SampleShardedEngine stays the bit-identical mode.
+# ---------------------------------------------------------------------------------------------------
+def stat_views(engine):
+    """torch tensors aliasing a statistics handle's accumulator: cls [B,A,C], box [B,A,16], cov [B,A,10] (with the head)."""
+    ptrs = engine.stat_device_pointers()
+    dev = torch.device("cuda", engine.cfg.device)
+    b, a = engine.B, engine.A
+    shapes = {"cls": (b, a, engine.Ccls), "box": (b, a, 16), "cov": (b, a, 10)}
+    return {k: torch.as_tensor(DeviceArray(p, shapes[k], "<f4"), device=dev)
+            for k, p in zip(("cls", "box", "cov"), ptrs) if p}
+
+
+def _stat_order(stats):
+    return [k for k in ("cls", "box", "cov") if k in stats]
+
+
+def all_gather_statistics(local, group=None):
+    """local {'cls': [B,A,C], 'box': [B,A,16], 'cov': [B,A,10]} of every rank (torch, host or device) -> a list over the ranks of
+    such dicts, on every rank, with ONE all-gather of the records laid end to end (cls, box, cov: every part starts on a
+    16-byte boundary of its rank's own buffer, as ``bod_stat_merge`` wants)."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    names = _stat_order(local)
+    flat = torch.cat([local[k].reshape(-1) for k in names])
+    if world == 1:
+        bufs = [flat]
+    elif flat.is_cuda and dist.get_backend(group) == "gloo":
+        # gloo moves device tensors through the host anyway; used by the one-GPU test of this mode (RCCL in production)
+        host = [torch.empty(flat.shape, dtype=flat.dtype) for _ in range(world)]
+        dist.all_gather(host, flat.cpu(), group=group)
+        bufs = [h.to(flat.device) for h in host]
+    else:
+        bufs = [torch.empty_like(flat) for _ in range(world)]
+        dist.all_gather(bufs, flat, group=group)
+    out = []
+    for buf in bufs:
+        d, off = {}, 0
+        for k in names:
+            n = local[k].numel()
+            d[k] = buf[off:off + n].view(local[k].shape)
+            off += n
+        out.append(d)
+    return out
+
+
+def merge_statistics_np(a, b, ka, kb, dtype=np.float64):
+    """The merge of two statistics records on the host, as include/bayesod.h states it: a, b = (cls_sum [...,C], box_moments
+    [...,16], cov_sum [...,10] or None) of ka and kb samples; returns the record of ka + kb samples in ``dtype`` (float64: the
+    statement the tests compare the kernel with; float32: the kernel's own operation order).  Used by nothing in the product path."""
+    t = np.dtype(dtype).type
+    cls_a, box_a, cov_a = a
+    cls_b, box_b, cov_b = b
+    if int(ka) == 0:
+        box = np.array(box_b, dtype=t)
+        box[..., 14:] = 0
+        return np.array(cls_b, dtype=t), box, (None if cov_b is None else np.array(cov_b, dtype=t))
+    box_a, box_b = np.asarray(box_a, dtype=t), np.asarray(box_b, dtype=t)
+    w = t(kb) / (t(ka) + t(kb))
+    kw = t(ka) * w
+    d = box_b[..., :4] - box_a[..., :4]
+    box = np.zeros(box_a.shape, dtype=t)
+    box[..., :4] = box_a[..., :4] + d * w
+    k = 4
+    for i in range(4):
+        for j in range(i + 1):
+            box[..., k] = (box_a[..., k] + box_b[..., k]) + (d[..., i] * d[..., j]) * kw
+            k += 1
+    cls = np.asarray(cls_a, dtype=t) + np.asarray(cls_b, dtype=t)
+    cov = None if cov_a is None or cov_b is None else np.asarray(cov_a, dtype=t) + np.asarray(cov_b, dtype=t)
+    return cls, box, cov
+
+
+class StatShardedEngine(object):
+    """The sample-sharded mode on statistics: ONE statistics handle per rank computes its n = N / world samples
+    (``stat_forward`` with sample base rank * n), one all-gather exchanges the 34-float records, every rank resets and folds
+    the W records in rank order (identical bits on all ranks), and posterior / soft-NMS / cluster-fuse run replicated.
+    ``make_config_kwargs`` are those of engine.make_config for the FULL ensemble."""
+
+    def __init__(self, image_hw, weights, anchors, mc_samples, device=0, batch=1, group=None, **make_config_kwargs):
+        from .engine import Engine, make_config
+        self.group = group
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        self.base, self.n = sample_shard(mc_samples, self.world, self.rank)
+        self.engine = Engine(make_config(image_hw, batch=batch, mc_samples=self.n, device=device, mc_ensemble_size=mc_samples,
+                                         mc_statistics=True, **make_config_kwargs))
+        self.engine.load_weights(weights)
+        self.engine.set_anchors(anchors)
+        self._local = stat_views(self.engine)
+        self._gathered = None                     # kept alive until the folds that read it have run
+
+    def infer(self, images, seed=0, first_image_id=0):
+        """images: [B,H,W,3] float32 (the same on every rank).  Returns this rank's copy of the detections (list over images of
+        (scores, means, covs, counts)); identical on all ranks."""
+        eng = self.engine
+        eng.stat_reset()
+        eng.stat_forward(images, seed=seed, first_image_id=first_image_id, sample_base=self.base)
+        eng.synchronize()                         # the collective runs on torch's stream, not the engine's
+        self._gathered = all_gather_statistics(self._local, self.group)
+        torch.cuda.synchronize(self._local["cls"].device)
+        eng.stat_reset()
+        for rec in self._gathered:                # rank order on every rank
+            eng.stat_merge([rec[k].data_ptr() if k in rec else None for k in ("cls", "box", "cov")], self.n)
+        eng.stat_posterior(seed=seed, first_image_id=first_image_id)
+        eng.nms()
+        eng.cluster_fuse()
+        out = [eng.get_detections(i) for i in range(eng.B)]
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # Data-parallel training: every rank runs bod_train_step(apply_update=False) on its own minibatch; the gradients of
 # all ~260 tensors sit in ONE contiguous fp32 arena, so the step needs a single all-reduce (39 M floats = 156 MB; a
 # ring over 7 xGMI links) instead of per-tensor buckets; the update then runs on the mean gradient (the usual

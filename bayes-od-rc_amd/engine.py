@@ -19,7 +19,7 @@ def make_config(image_hw, batch=1, mc_samples=10, num_classes=8, anchors_per_loc
                 dropout_rate=0.3, use_full_covar=True, bayes_od_config=None, nms_config=None,
                 has_covar_head=True, dataset_name='bdd', orig_size=None, nms_variant='A',
                 num_categorical_draws=30, layers=(3, 4, 5, 6, 7), precision='bf16', mc_sample_base=0,
-                mc_ensemble_size=0, training=False, backbone_depth=50, pipeline_overlap=False):
+                mc_ensemble_size=0, training=False, backbone_depth=50, pipeline_overlap=False, mc_statistics=False):
     """Translates the reference's yaml dictionaries (configs/retinanet_bdd_covar.yaml:61-143)
     into a ``bod_config``."""
     bo = bayes_od_config or {'ranking_method': 'score', 'dirichlet_prior': {'type': 'non_informative'},
@@ -56,6 +56,10 @@ def make_config(image_hw, batch=1, mc_samples=10, num_classes=8, anchors_per_loc
     cfg.backbone_depth = int(backbone_depth)
     # infer_async overlaps the front (stem / backbone / FPN) of batch i+1 with the towers of batch i on CU-partitioned streams
     cfg.pipeline_overlap = int(bool(pipeline_overlap))
+    # a statistics handle (include/bayesod.h): mergeable MC statistics beside the forward's own -- ensembles, passes, sample shards
+    cfg.mc_statistics = int(bool(mc_statistics))
+    if cfg.mc_statistics and (cfg.training or cfg.pipeline_overlap):
+        raise ValueError("mc_statistics handles are inference handles on one stream: training / pipeline_overlap cannot be combined with it")
     if dataset_name == 'kitti':
         if orig_size is None:
             raise ValueError("dataset_name='kitti' needs orig_size (sample_dict['im_size'])")
@@ -497,6 +501,70 @@ class Engine(object):
         shapes = [(b,), (b, k, c), (b, k, 4), (b, k, 16), (b, k, c)]
         names = ["num", "scores", "means", "covs", "counts"]
         return {n: (int(p), s) for n, p, s in zip(names, ptrs, shapes)}
+
+    # -- mergeable MC statistics (handles made with make_config(mc_statistics=True); include/bayesod.h) ----------
+    def stat_reset(self):
+        """Empty the accumulator (K = 0)."""
+        self._chk(self.lib.bod_stat_reset(self.h))
+
+    def stat_forward(self, images=None, seed=0, first_image_id=0, sample_base=0, image_buffer=None, device_images=None):
+        """Forward of this handle's n samples as samples ``sample_base .. sample_base + n - 1`` of the dropout streams, reduced to
+        the statistics record and folded into the accumulator (``bod_stat_forward``).  images as in forward();
+        ``device_images``: the address of a [B,H,W,3] float32 batch already on this device (another handle's image buffer,
+        complete before the call) in place of this handle's own."""
+        if images is None:
+            ptr = self._device_images(image_buffer) if device_images is None else int(device_images)
+            self._chk(self.lib.bod_stat_forward(self.h, ptr, 1, seed, first_image_id, int(sample_base)))
+        else:
+            a = self._img(images)
+            self._chk(self.lib.bod_stat_forward(self.h, a.ctypes.data, 0, seed, first_image_id, int(sample_base)))
+
+    def stat_merge_from(self, other):
+        """Fold ``other``'s accumulator into this one's (``bod_stat_merge_from``); ``other`` is unchanged."""
+        self._chk(self.lib.bod_stat_merge_from(self.h, other.h))
+
+    def stat_merge(self, ptrs, samples):
+        """Fold a record of ``samples`` samples given as device addresses (cls_sum, box_moments, cov_sum or None)."""
+        p = (C.c_void_p * 3)(*[int(x) if x else None for x in (list(ptrs) + [None])[:3]])
+        self._chk(self.lib.bod_stat_merge(self.h, p, int(samples)))
+
+    def stat_device_pointers(self):
+        """Device addresses [cls_sum [B,A,C], box_moments [B,A,16], cov_sum [B,A,10] or None] of the accumulator."""
+        ptrs = (C.c_void_p * 3)()
+        self._chk(self.lib.bod_stat_device(self.h, ptrs, None))
+        return [ptrs[i] for i in range(3)]
+
+    @property
+    def stat_samples(self):
+        """K: the number of MC samples the accumulator holds."""
+        k = C.c_int32(0)
+        self._chk(self.lib.bod_stat_device(self.h, None, C.byref(k)))
+        return int(k.value)
+
+    def get_statistics(self):
+        """(cls_sum [B,A,C], box_moments [B,A,16], cov_sum [B,A,10] or None, samples) of the accumulator, on the host."""
+        n = (self.B, self.A)
+        cls = np.empty(n + (self.Ccls,), np.float32)
+        box = np.empty(n + (16,), np.float32)
+        cov = np.empty(n + (10,), np.float32) if self.cfg.has_covar_head else None
+        k = C.c_int32(0)
+        self._chk(self.lib.bod_stat_get(self.h, fptr(cls), fptr(box), fptr(cov), C.byref(k)))
+        return cls, box, cov, int(k.value)
+
+    def set_statistics(self, cls_sum, box_moments, cov_sum=None, samples=0):
+        """Replace the accumulator (``bod_stat_set``): arrays as get_statistics returns them (None: left as it is), K = samples."""
+        n = (self.B, self.A)
+        arrs = []
+        for a, w in ((cls_sum, self.Ccls), (box_moments, 16), (cov_sum, 10)):
+            a = as_f32(a) if a is not None else None
+            if a is not None and a.shape != n + (w,):
+                raise ValueError("statistics array of shape %s, expected %s" % (a.shape, n + (w,)))
+            arrs.append(a)
+        self._chk(self.lib.bod_stat_set(self.h, fptr(arrs[0]), fptr(arrs[1]), fptr(arrs[2]), int(samples)))
+
+    def stat_posterior(self, seed=0, first_image_id=0):
+        """posterior() on the accumulator with N = stat_samples (``bod_stat_posterior``); nms() / cluster_fuse() follow."""
+        self._chk(self.lib.bod_stat_posterior(self.h, seed, first_image_id))
 
     def bench_head_conv(self, layer=1, variant=0, iters=10):
         ms, fl = C.c_double(0), C.c_double(0)

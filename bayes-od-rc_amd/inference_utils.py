@@ -180,6 +180,92 @@ class BayesOdPipeline(object):
         return [self.engine.get_detections(b) for b in range(self.engine.B)]
 
 
+class EnsemblePipeline(object):
+    """``BayesOdPipeline`` for an ensemble: ONE posterior per image from the MC samples of several weight sets and / or several
+    passes of one handle (deep / checkpoint ensembles; more samples than one forward holds).  ``models``: RetinaNetModel
+    instances with loaded weights and the same heads; every member runs ``passes`` forwards of ``samples_per_member`` samples on
+    a statistics handle of its own (``make_config(mc_statistics=True)``) -- member m, pass p draws the dropout samples
+    ``(m * passes + p) * n ..`` -- and the per-anchor statistics (34 floats per anchor, whatever the sample count) are folded
+    into member 0's accumulator in member order; posterior, soft-NMS and cluster-and-fuse run there with N = the total.  A list
+    of one model with ``passes = k`` is "N = k * n on one handle".  Same call and return shape as ``BayesOdPipeline``."""
+
+    def __init__(self, models, image_hw, batch, bayes_od_config, nms_config, samples_per_member, passes=1, use_full_covar=True,
+                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None):
+        from .engine import Engine, make_config
+        models = list(models)
+        if not models:
+            raise ValueError("EnsemblePipeline needs at least one model")
+        n, passes = int(samples_per_member), int(passes)
+        if n < 1 or passes < 1:
+            raise ValueError("samples_per_member and passes must be >= 1")
+        self.total = len(models) * passes * n
+        if self.total < 2:
+            raise ValueError("bayes_od needs at least 2 samples in all: the sample covariance divides by N-1 "
+                             "(inference_utils.py:241-242)")
+        first = models[0]
+        for m in models:
+            if m._weights is None:
+                raise ValueError("no weights loaded: call model.load_weights(...) on every ensemble member")
+            if (m.num_classes, m.anchors_per_location, m.compute_covar) != (first.num_classes, first.anchors_per_location,
+                                                                            first.compute_covar):
+                raise ValueError("ensemble members must share num_classes, anchors_per_location and the covariance head")
+        self.models, self.n, self.passes = models, n, passes
+        self._hw, self._batch = tuple(image_hw), int(batch)
+        self._kw = dict(bayes_od_config=bayes_od_config, nms_config=nms_config, use_full_covar=use_full_covar,
+                        dataset_name=dataset_name, nms_variant=nms_variant, orig_size=orig_size)
+        self.engines = []
+        for m in models:
+            eng = Engine(self._config(m))
+            eng.load_weights(m._weights)
+            self.engines.append(eng)
+        self.engine = self.engines[0]             # uploads, the merged accumulator and the Bayesian stages live here
+        if anchors is not None:
+            self.set_anchors(anchors)
+
+    def _config(self, m):
+        from .engine import make_config
+        return make_config(self._hw, batch=self._batch, mc_samples=self.n, num_classes=m.num_classes + 1,
+                           anchors_per_location=m.anchors_per_location, device=m.device, dropout_rate=m.dropout_rate,
+                           has_covar_head=m.compute_covar, precision=m.precision, backbone_depth=m.backbone_depth,
+                           mc_ensemble_size=self.total, mc_statistics=True, **self._kw)
+
+    def set_anchors(self, anchors):
+        for eng in self.engines:
+            eng.set_anchors(anchors)
+
+    def bind(self, orig_size=None):
+        """Re-apply the testing configuration (a new ``orig_size``: KITTI's per-size rescale) to every member's handle."""
+        if orig_size is not None:
+            self._kw['orig_size'] = tuple(orig_size)
+            for m, eng in zip(self.models, self.engines):
+                eng.update_config(self._config(m))
+        return self.engine
+
+    def upload_mixed(self, frames, means, aspect_resize=True):
+        self.engine.upload_frames_u8_ragged(frames, means, aspect_resize=aspect_resize)
+
+    def __call__(self, images=None, seed=0, first_image_id=0):
+        """images [B,H,W,3], or None to run every member on the batch uploaded into member 0's handle."""
+        shared = None
+        if images is None:
+            shared = self.engine._device_images(None)
+            self.engine.synchronize()             # the upload is complete before another handle's stream reads it
+        for m, eng in enumerate(self.engines):
+            eng.stat_reset()
+            for p in range(self.passes):
+                base = (m * self.passes + p) * self.n
+                if images is None and m > 0:
+                    eng.stat_forward(None, seed=seed, first_image_id=first_image_id, sample_base=base, device_images=shared)
+                else:
+                    eng.stat_forward(images, seed=seed, first_image_id=first_image_id, sample_base=base)
+        for eng in self.engines[1:]:
+            self.engine.stat_merge_from(eng)
+        self.engine.stat_posterior(seed=seed, first_image_id=first_image_id)
+        self.engine.nms()
+        self.engine.cluster_fuse()
+        return [self.engine.get_detections(b) for b in range(self.engine.B)]
+
+
 def post_process_predictions(sample_dict, prediction_dict, dataset_name='bdd', engine=None, nms_config=None):
     """Validation post-processing with the reference's signature and return value
     (src/retina_net/experiments/validation_utils.py:10-77): ``(predicted_boxes_classes [K,C],

@@ -32,7 +32,9 @@ def test_model(config, args):
     test_dataset = test_config['test_dataset']
     nms_config = test_config['nms_config']
     model = RetinaNetModel(config['model_config'], device=int(args.gpu_device), seed=args.seed)
-    if args.weights:
+    if getattr(args, 'ensemble', None):
+        model = _ensemble_members(config, args)
+    elif args.weights:
         if not os.path.exists(args.weights):
             raise ValueError('%s must exist (no checkpoint entry)' % args.weights)
         model.load_weights(args.weights)
@@ -54,9 +56,9 @@ def test_model(config, args):
 
     def pipe_for(b):                      # the tail (len(frames) % batch frames) runs through a smaller-batch handle
         if b not in pipes:
-            pipes[b] = inference_utils.BayesOdPipeline(model, hw, b, test_config['bayes_od_config'], nms_config,
-                                                       use_full_covar=test_config['use_full_covar'],
-                                                       dataset_name=test_dataset, orig_size=orig, anchors=anchors)
+            pipes[b] = _make_pipeline(model, args, hw, b, test_config['bayes_od_config'], nms_config,
+                                      use_full_covar=test_config['use_full_covar'],
+                                      dataset_name=test_dataset, orig_size=orig, anchors=anchors)
         return pipes[b]
     predictions_dir = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'], 'predictions')
     writer = writers.PredictionWriter(predictions_dir, test_dataset, test_config['ckpt_idx'],
@@ -80,6 +82,27 @@ def test_model(config, args):
     elapsed = time.time() - start
     print("\nMean frame rate: " + str(n_done / max(elapsed, 1e-9)))
     return writer.root
+
+
+def _ensemble_members(config, args):
+    """--ensemble w0.npz w1.npz ...: one model per weight file (a deep / checkpoint ensemble)."""
+    members = []
+    for path in args.ensemble:
+        if not os.path.exists(path):
+            raise ValueError('%s must exist (no checkpoint entry)' % path)
+        m = RetinaNetModel(config['model_config'], device=int(args.gpu_device), seed=args.seed)
+        m.load_weights(path)
+        members.append(m)
+    return members
+
+
+def _make_pipeline(model, args, hw, batch, bayes_od_config, nms_config, **kw):
+    """BayesOdPipeline of the one model, or -- ``model`` a list (--ensemble) -- EnsemblePipeline with the yaml's
+    mc_dropout_samples per member and --mc_passes passes each."""
+    if isinstance(model, list):
+        return inference_utils.EnsemblePipeline(model, hw, batch, bayes_od_config, nms_config, model[0].mc_dropout_samples,
+                                                passes=int(getattr(args, 'mc_passes', 1) or 1), **kw)
+    return inference_utils.BayesOdPipeline(model, hw, batch, bayes_od_config, nms_config, **kw)
 
 
 def _test_model_on_dataset(config, args, model):
@@ -117,8 +140,8 @@ def _test_model_on_dataset(config, args, model):
         key = ('mixed', len(pending))
         if key not in pipes:
             # orig_size only switches the KITTI rescale on: the ragged upload gives every frame its own factors
-            pipes[key] = inference_utils.BayesOdPipeline(
-                model, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
+            pipes[key] = _make_pipeline(
+                model, args, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
                 use_full_covar=test_config['use_full_covar'], dataset_name=test_dataset, orig_size=hw,
                 anchors=gen.generate_all((hw[0], hw[1], 3)))
         pipe = pipes[key]
@@ -135,8 +158,8 @@ def _test_model_on_dataset(config, args, model):
         hw = tuple(handler.resize_shape) if kitti else src_hw
         key = (src_hw, len(pending))
         if key not in pipes:
-            pipes[key] = inference_utils.BayesOdPipeline(
-                model, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
+            pipes[key] = _make_pipeline(
+                model, args, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
                 use_full_covar=test_config['use_full_covar'], dataset_name=test_dataset, orig_size=src_hw,
                 anchors=gen.generate_all((hw[0], hw[1], 3)))
         pipe = pipes[key]
@@ -174,6 +197,10 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--mixed_sizes', action='store_true', help='with --dataset: batches in dataset order whatever the frame sizes '
                     '(default: a batch ends where the source size changes)')
+    ap.add_argument('--ensemble', type=str, nargs='+', default=None, help='weight files of an ensemble: every member runs the '
+                    'yaml\'s mc_dropout_samples samples and ONE posterior is formed from all of them (overrides --weights)')
+    ap.add_argument('--mc_passes', type=int, default=1, help='with --ensemble: forwards per member (k passes of n samples = k * n '
+                    'samples per member; one weight file with --mc_passes k is N = k * n on one handle)')
     args = ap.parse_args(argv)
     config = config_utils.load_yaml(args.yaml_path)
     config = config_utils.setup(config, args)

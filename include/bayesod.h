@@ -107,7 +107,14 @@ typedef struct {
                                     mode unless BOD_OVERLAP_EXPERIMENTAL=1 is set in the environment.  Every other entry point
                                     keeps the whole chip.  Inference handles only.  0 (default): one stream: no kernel of the
                                     library runs beside another.                                                  */
-    int32_t reserved[2];
+    int32_t mc_statistics;       /* 1: a STATISTICS handle (inference only; training / pipeline_overlap are refused): the handle owns
+                                    an accumulator of mergeable per-anchor MC statistics beside the ones of its last forward, and a
+                                    sample count K -- the bod_stat_* entry points below.  Its aggregating plan, where the conditions
+                                    for one hold (also with mc_ensemble_size > mc_samples), is the DENSE one: no keep stage, no
+                                    sparse tail or halo, because the kept set depends on the merged class statistics and every
+                                    anchor's box / covariance statistics must exist before the merge.  0 (default): plans, kernels,
+                                    buffers and results exactly as without the field.                                    */
+    int32_t reserved[1];
 } bod_config;
 
 /* Sizes the caller needs to allocate host buffers. */
@@ -489,6 +496,48 @@ bod_status bod_plan_info(bod_handle h, int32_t* info8);
 /* bod_plan_info with more slots: fills info[0 .. min(n, 9) - 1]; [0..7] as above, [8] = 1 when box layer 1 and covariance layer 2
  * also run only over the 3x3 dilation of the sparse tail's pixels (the sparse halo; BOD_SPARSE_HALO=0: dense, as before). */
 bod_status bod_plan_info_n(bod_handle h, int32_t* info, int32_t n);
+
+/* ---- mergeable MC statistics (handles created with mc_statistics = 1): ensembles of several weight sets, more samples than one
+ * forward holds, sample sharding at 34 floats per anchor instead of 22 per anchor AND sample.  Every call below returns
+ * BOD_ERR_INVALID_ARG for a handle without mc_statistics and BOD_ERR_NOT_READY for a stage-order violation.
+ *
+ * The statistics record of `samples` MC samples, fp32, per image b and anchor a (what the last tower layers' epilogues reduce
+ * over the samples of one forward, and what bayes_od_inference needs of them, inference_utils.py:31-60, :220-244):
+ *   cls_sum     [B,A,C]   sum over the samples of softmax(class logits)
+ *   box_moments [B,A,16]  mean[4] of the decoded boxes (v,u,h,w); the lower triangle, row-major, of the co-moment sums
+ *                         M2_ij = sum (x_i - mean_i)(x_j - mean_j): (0,0) (1,0) (1,1) (2,0) (2,1) (2,2) (3,0) .. (3,3) [10]; 0; 0
+ *   cov_sum     [B,A,10]  sum over the samples of the raw covariance parameters (pre fill_triangular); absent (NULL) without
+ *                         the covariance head
+ * Two records of ka and kb samples merge (Chan's pairwise update; fp32, no fused multiply-add, in this order):
+ *   cls_sum = a + b;  cov_sum = a + b;  d = mean_b - mean_a;  w = kb / (ka + kb);  mean = mean_a + d * w;
+ *   M2_ij = (M2a_ij + M2b_ij) + (d_i * d_j) * (ka * w);  the two pad floats stay 0;  ka = 0 copies b.
+ * The merge uses no atomics: the same calls in the same order give the same bits. */
+/* K = 0: the accumulator is empty (its contents are not read by the next merge). */
+bod_status bod_stat_reset(bod_handle h);
+/* bod_forward for this handle's n = mc_samples samples with the ABSOLUTE sample indices sample_base .. sample_base + n - 1 in the
+ * dropout streams (mc_sample_base of the call; the handle's own value is untouched), reduced to a statistics record -- inside the
+ * last tower layers' tiles where the plan aggregates, else by a kernel over the raw head outputs (same operations in the same
+ * order: identical bits) -- and folded into the accumulator: K += n.  One stream, no host round trip.  sample_base + n must not
+ * exceed mc_ensemble_size when that is set.  Needs the weights and the anchors (the boxes are decoded). */
+bod_status bod_stat_forward(bod_handle h, const float* images, int32_t images_on_device, uint64_t seed, uint32_t first_image_id,
+                            int32_t sample_base);
+/* dst's accumulator (+)= src's; src is unchanged.  Both handles on the same device with the same batch, anchors, classes and
+ * covariance head (BOD_ERR_INVALID_ARG names the field).  dst's stream is ordered behind src's and src's next write behind the
+ * merge.  An empty src (K = 0) is a no-op. */
+bod_status bod_stat_merge_from(bod_handle dst, bod_handle src);
+/* The same from device pointers {cls_sum, box_moments, cov_sum or NULL} of a record of `samples` >= 1 samples (buffers that
+ * arrived through a collective; 16-byte aligned).  The caller orders its writes before the call as for bod_device_raw. */
+bod_status bod_stat_merge(bod_handle h, const void* const* ptrs3, int32_t samples);
+/* Device addresses of the accumulator (order as above; [2] = NULL without the covariance head) and K, for zero-copy exchange.
+ * Valid until bod_destroy; the contents are complete after bod_synchronize.  Either output may be NULL. */
+bod_status bod_stat_device(bod_handle h, void** ptrs3, int32_t* samples);
+/* Host copies of the accumulator out and in (stage-level test hooks, like bod_get_raw / bod_set_raw).  NULL arrays are skipped;
+ * bod_stat_set sets K = samples >= 0. */
+bod_status bod_stat_get(bod_handle h, float* cls_sum, float* box_moments, float* cov_sum, int32_t* samples);
+bod_status bod_stat_set(bod_handle h, const float* cls_sum, const float* box_moments, const float* cov_sum, int32_t samples);
+/* bod_posterior on the accumulator with N = K (BOD_ERR_NOT_READY for K < 2: the sample covariance divides by N - 1); bod_nms,
+ * bod_cluster_fuse, bod_get_posterior and bod_get_detections* follow as after bod_posterior.  Needs the anchors. */
+bod_status bod_stat_posterior(bod_handle h, uint64_t seed, uint32_t first_image_id);
 
 #ifdef __cplusplus
 }

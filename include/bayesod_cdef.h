@@ -40,7 +40,8 @@ typedef struct {
     int32_t training;
     int32_t backbone_depth;
     int32_t pipeline_overlap;
-    int32_t reserved[2];
+    int32_t mc_statistics;
+    int32_t reserved[1];
 } bod_config;
 typedef struct {
     int32_t num_pixels;
@@ -166,3 +167,12 @@ bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, in
                                  float* gathered_host, float** gathered_device);
 bod_status bod_plan_info(bod_handle h, int32_t* info8);
 bod_status bod_plan_info_n(bod_handle h, int32_t* info, int32_t n);
+bod_status bod_stat_reset(bod_handle h);
+bod_status bod_stat_forward(bod_handle h, const float* images, int32_t images_on_device, uint64_t seed, uint32_t first_image_id,
+                            int32_t sample_base);
+bod_status bod_stat_merge_from(bod_handle dst, bod_handle src);
+bod_status bod_stat_merge(bod_handle h, const void* const* ptrs3, int32_t samples);
+bod_status bod_stat_device(bod_handle h, void** ptrs3, int32_t* samples);
+bod_status bod_stat_get(bod_handle h, float* cls_sum, float* box_moments, float* cov_sum, int32_t* samples);
+bod_status bod_stat_set(bod_handle h, const float* cls_sum, const float* box_moments, const float* cov_sum, int32_t samples);
+bod_status bod_stat_posterior(bod_handle h, uint64_t seed, uint32_t first_image_id);
