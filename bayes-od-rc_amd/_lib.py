@@ -40,6 +40,12 @@ class BodConfig(C.Structure):
     ]
 
 
+class BodAugment(C.Structure):
+    """bod_augment: one frame's augmentation record (``engine.AUGMENT_DTYPE`` is the same layout as a NumPy dtype)."""
+    _fields_ = [("flip", C.c_int32), ("scale", C.c_float), ("off_y", C.c_float), ("off_x", C.c_float),
+                ("gain", C.c_float), ("bias", C.c_float)]
+
+
 class BodSizes(C.Structure):
     _fields_ = [
         ("num_pixels", C.c_int32), ("num_anchors", C.c_int32), ("level_h", C.c_int32 * 8),
@@ -91,6 +97,10 @@ SIGNATURES = {
     "bod_upload_frames_u8_async": (C.c_int, [_H, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, _F, C.c_int32, C.c_int32]),
     "bod_upload_frames_u8_ragged": (C.c_int, [_H, C.POINTER(C.c_uint8), _I, _F, C.c_int32]),
     "bod_upload_frames_u8_ragged_async": (C.c_int, [_H, C.POINTER(C.c_uint8), _I, _F, C.c_int32, C.c_int32]),
+    "bod_upload_frames_u8_augmented": (C.c_int, [_H, C.POINTER(C.c_uint8), _I, _F, C.c_int32, C.POINTER(BodAugment)]),
+    "bod_upload_frames_u8_augmented_async": (C.c_int, [_H, C.POINTER(C.c_uint8), _I, _F, C.c_int32, C.POINTER(BodAugment), C.c_int32]),
+    "bod_augment_boxes": (C.c_int, [C.c_int32, _I, C.c_int32, C.c_int32, C.c_int32, C.POINTER(BodAugment), _I, _F, _F, C.c_int32,
+                                    C.c_float, _I, _F, _F]),
     "bod_device_images_buffer": (C.c_void_p, [_H, C.c_int32]),
     "bod_device_images": (C.c_void_p, [_H]),
     "bod_synchronize": (C.c_int, [_H]),

@@ -280,6 +280,7 @@ struct bod_context {
     // snapshots, alternated: at most two batches are in flight (bod_infer_async).
     struct RaggedTable { std::vector<char> host; char* dev = nullptr; };
     RaggedTable rag_sync, rag_b[2];
+    RaggedTable aug_sync, aug_b[2];       // the augmented uploads' own (their records are PreprocAugFrame, without factors)
     hipEvent_t ev_tab[2] = {nullptr, nullptr};          // the copy of rag_b[k].host has left the host (its next rewrite waits for it)
     const float* kscale_src[2] = {nullptr, nullptr};
     float* kscale_cur[2] = {nullptr, nullptr}; int kscale_i = 0;
@@ -1880,6 +1881,8 @@ bod_status bod_destroy(bod_handle h) {
     if (h->affinity) hipFree(h->affinity);
     if (h->d_frames_u8) hipFree(h->d_frames_u8);
     if (h->rag_sync.dev) hipFree(h->rag_sync.dev);
+    if (h->aug_sync.dev) hipFree(h->aug_sync.dev);
+    for (int k = 0; k < 2; ++k) if (h->aug_b[k].dev) hipFree(h->aug_b[k].dev);
     for (int k = 0; k < 2; ++k) { if (h->rag_b[k].dev) hipFree(h->rag_b[k].dev); if (h->ev_tab[k]) hipEventDestroy(h->ev_tab[k]); if (h->kscale_cur[k]) hipFree(h->kscale_cur[k]); }
     if (h->copy) { hipStreamSynchronize(h->copy); hipStreamDestroy(h->copy); }
     for (int k = 0; k < 2; ++k) {
@@ -1972,28 +1975,47 @@ bod_status bod_upload_images(bod_handle h, const float* host_images) {
     return BOD_OK;
 }
 
-// Resize / crop / pad geometry of ONE frame (both upload routes).  0 = ok; 1 = the resize degenerates (g->rh, g->rw say how);
-// 2 = no resize asked for and the frame is not at the network size.
-static int frame_geometry(const bod_config& c, int32_t src_h, int32_t src_w, int32_t aspect_resize, PreprocFrame* g) {
+// Resize / crop / pad geometry of ONE frame for a network input of H x W (every upload route, and bod_augment_boxes).  0 = ok;
+// 1 = the resize degenerates (g->rh, g->rw say how); 2 = no resize asked for and the frame is not at the network size.
+// scale / off_y / off_x are the augmented route's (bayesod.h, bod_augment): the resize target grows by `scale`, and the crop or the
+// pad of an axis takes the share `off` of the size difference.  Their defaults are every other route's: the target is the network
+// size and floor(0.5 * d) is the centred d / 2 of tf.image.resize_with_crop_or_pad.
+static int frame_geometry(int32_t H, int32_t W, int32_t src_h, int32_t src_w, int32_t aspect_resize, PreprocFrame* g,
+                          float scale = 1.f, float off_y = 0.5f, float off_x = 0.5f) {
     PreprocFrame a{};
     a.sh = src_h; a.sw = src_w;
     a.rh = src_h; a.rw = src_w;
+    const double kMaxSide = 1048576.0;                                      // (a resized side beyond 2^20 pixels is no resize any more)
+    auto scaled = [&](int32_t n, int32_t* out) {
+        const double t = std::max(1.0, std::floor((double)scale * (double)n + 0.5));
+        *out = t <= kMaxSide ? (int32_t)t : -1;
+        return t <= kMaxSide;
+    };
     if (aspect_resize) {
         // tf.image.resize(..., preserve_aspect_ratio=True): scale = min(H/sh, W/sw) in float32, size = round(s * in)
-        const float fh = (float)c.image_h / (float)src_h, fw = (float)c.image_w / (float)src_w;
+        int32_t th = 0, tw = 0;
+        if (!scaled(H, &th) || !scaled(W, &tw)) { a.rh = th; a.rw = tw; *g = a; return 1; }
+        const float fh = (float)th / (float)src_h, fw = (float)tw / (float)src_w;
         const float sc = fh < fw ? fh : fw;
-        a.rh = (int32_t)std::nearbyint(sc * (float)src_h);
-        a.rw = (int32_t)std::nearbyint(sc * (float)src_w);
+        const float nh = std::nearbyint(sc * (float)src_h), nw = std::nearbyint(sc * (float)src_w);
+        a.rh = nh <= (float)kMaxSide ? (int32_t)nh : -1;
+        a.rw = nw <= (float)kMaxSide ? (int32_t)nw : -1;
         if (a.rh < 1 || a.rw < 1) { *g = a; return 1; }
-    } else if (src_h != c.image_h || src_w != c.image_w) {
+    } else if (src_h != H || src_w != W) {
         return 2;
+    } else if (!scaled(src_h, &a.rh) || !scaled(src_w, &a.rw)) {
+        *g = a;
+        return 1;
     }
     a.scale_y = (float)src_h / (float)a.rh; a.scale_x = (float)src_w / (float)a.rw;
-    const int dh = c.image_h - a.rh, dw = c.image_w - a.rw;                 // resize_with_crop_or_pad (floor division like Python)
-    auto fdiv2 = [](int v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); };
-    a.crop_y = std::max(fdiv2(-dh), 0); a.crop_x = std::max(fdiv2(-dw), 0);
-    a.pad_y = std::max(fdiv2(dh), 0); a.pad_x = std::max(fdiv2(dw), 0);
-    a.vis_h = std::min(a.rh, c.image_h); a.vis_w = std::min(a.rw, c.image_w);
+    // resize_with_crop_or_pad, the offsets at the share `off` of the difference (0.5: its centred floor division)
+    auto place = [](int d, float off, int32_t* crop, int32_t* pad) {
+        *crop = d > 0 ? (int32_t)std::floor((double)off * (double)d) : 0;
+        *pad = d < 0 ? (int32_t)std::floor((double)off * (double)-d) : 0;
+    };
+    place(a.rh - H, off_y, &a.crop_y, &a.pad_y);
+    place(a.rw - W, off_x, &a.crop_x, &a.pad_x);
+    a.vis_h = std::min(a.rh, H); a.vis_w = std::min(a.rw, W);
     *g = a;
     return 0;
 }
@@ -2001,7 +2023,7 @@ static int frame_geometry(const bod_config& c, int32_t src_h, int32_t src_w, int
 static bod_status preproc_geometry(bod_handle h, int32_t src_h, int32_t src_w, const float* rgb_means, int32_t aspect_resize, PreprocArgs* out) {
     const bod_config& c = h->cfg;
     PreprocFrame g{};
-    const int bad = frame_geometry(c, src_h, src_w, aspect_resize, &g);
+    const int bad = frame_geometry(c.image_h, c.image_w, src_h, src_w, aspect_resize, &g);
     if (bad == 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_upload_frames_u8: degenerate resize %dx%d", g.rh, g.rw);
     if (bad == 2)
         return h->fail(BOD_ERR_INVALID_ARG, "bod_upload_frames_u8: frames are %dx%d but the handle expects %dx%d (pass aspect_resize=1 for "
@@ -2029,7 +2051,7 @@ static bod_status ragged_table(bod_handle h, const char* who, const int32_t* src
         const int32_t sh = src_hw[2 * b], sw = src_hw[2 * b + 1];
         if (sh < 1 || sw < 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: frame %d has size %dx%d", who, b, sh, sw);
         PreprocFrame g{};
-        const int bad = frame_geometry(c, sh, sw, aspect_resize, &g);
+        const int bad = frame_geometry(c.image_h, c.image_w, sh, sw, aspect_resize, &g);
         if (bad == 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: frame %d (%dx%d): degenerate resize %dx%d", who, b, sh, sw, g.rh, g.rw);
         if (bad == 2)
             return h->fail(BOD_ERR_INVALID_ARG, "%s: frame %d is %dx%d but the handle expects %dx%d (pass aspect_resize=1 for the "
@@ -2043,6 +2065,44 @@ static bod_status ragged_table(bod_handle h, const char* who, const int32_t* src
     }
     *bytes = (size_t)off;
     *with_factors = aspect_resize && c.kitti_scale_h > 0.f;
+    return BOD_OK;
+}
+
+// What is wrong with an augmentation record (nullptr: nothing).
+static const char* augment_bad(const bod_augment& a) {
+    if (a.flip != 0 && a.flip != 1) return "flip must be 0 or 1";
+    if (!std::isfinite(a.scale) || !(a.scale > 0.f)) return "scale must be finite and positive";
+    if (!(a.off_y >= 0.f && a.off_y <= 1.f) || !(a.off_x >= 0.f && a.off_x <= 1.f)) return "off_y and off_x must lie in [0, 1]";
+    if (!std::isfinite(a.gain) || !std::isfinite(a.bias)) return "gain and bias must be finite";
+    return nullptr;
+}
+
+// The augmented route's table: [batch] PreprocAugFrame records, no factors (a KITTI handle's own two scalars apply).  As
+// ragged_table, nothing of the handle's upload state has changed when this fails.
+static bod_status augment_table(bod_handle h, const char* who, const int32_t* src_hw, int32_t aspect_resize, const bod_augment* aug,
+                                bod_context::RaggedTable* t, size_t* bytes) {
+    const bod_config& c = h->cfg;
+    t->host.resize((size_t)c.batch * sizeof(PreprocAugFrame));
+    PreprocAugFrame* fr = reinterpret_cast<PreprocAugFrame*>(t->host.data());
+    int64_t off = 0;
+    for (int b = 0; b < c.batch; ++b) {
+        const int32_t sh = src_hw[2 * b], sw = src_hw[2 * b + 1];
+        if (sh < 1 || sw < 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: frame %d has size %dx%d", who, b, sh, sw);
+        if (const char* why = augment_bad(aug[b])) return h->fail(BOD_ERR_INVALID_ARG, "%s: frame %d: %s", who, b, why);
+        PreprocAugFrame r{};
+        const int bad = frame_geometry(c.image_h, c.image_w, sh, sw, aspect_resize, &r.g, aug[b].scale, aug[b].off_y, aug[b].off_x);
+        if (bad == 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: frame %d (%dx%d): degenerate resize %dx%d", who, b, sh, sw, r.g.rh, r.g.rw);
+        if (bad == 2)
+            return h->fail(BOD_ERR_INVALID_ARG, "%s: frame %d is %dx%d but the handle expects %dx%d (pass aspect_resize=1 for the "
+                           "KITTI-style resize + crop/pad)", who, b, sh, sw, c.image_h, c.image_w);
+        r.g.offset = off;
+        off += (int64_t)3 * sh * sw;
+        r.flip = aug[b].flip;
+        r.resize = (aspect_resize || r.g.rh != sh || r.g.rw != sw) ? 1 : 0;
+        r.gain = aug[b].gain; r.bias = aug[b].bias;
+        fr[b] = r;
+    }
+    *bytes = (size_t)off;
     return BOD_OK;
 }
 
@@ -2062,6 +2122,13 @@ static PreprocRaggedArgs ragged_args(bod_handle h, const bod_context::RaggedTabl
     PreprocRaggedArgs a{};
     a.frames = reinterpret_cast<const PreprocFrame*>(t.dev);
     a.B = h->cfg.batch; a.H = h->cfg.image_h; a.W = h->cfg.image_w; a.resize = aspect_resize ? 1 : 0;
+    for (int k = 0; k < 3; ++k) a.mean[k] = rgb_means[k];
+    return a;
+}
+static PreprocAugArgs augment_args(bod_handle h, const bod_context::RaggedTable& t, const float* rgb_means) {
+    PreprocAugArgs a{};
+    a.frames = reinterpret_cast<const PreprocAugFrame*>(t.dev);
+    a.B = h->cfg.batch; a.H = h->cfg.image_h; a.W = h->cfg.image_w;
     for (int k = 0; k < 3; ++k) a.mean[k] = rgb_means[k];
     return a;
 }
@@ -2093,32 +2160,52 @@ bod_status bod_upload_frames_u8(bod_handle h, const uint8_t* rgb, int32_t src_h,
     return BOD_OK;
 }
 
-bod_status bod_upload_frames_u8_ragged(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw, const float* rgb_means,
-                                       int32_t aspect_resize) {
+// The synchronous upload of a packed batch: the ragged route (aug == nullptr) or the augmented one, which differ in their table and
+// their kernel only.
+static bod_status upload_packed(bod_handle h, const char* who, const uint8_t* rgb_packed, const int32_t* src_hw, const float* rgb_means,
+                                int32_t aspect_resize, const bod_augment* aug) {
     MarkerRange mr_api("bod:upload");
-    if (!h || !rgb_packed || !src_hw || !rgb_means) return BOD_ERR_INVALID_ARG;
-    static const char* who = "bod_upload_frames_u8_ragged";
     BODCHK(join_overlap(h));
     const bod_config& c = h->cfg;
     HIPCHK(h, hipSetDevice(c.device));
-    // (the table of the previous ragged upload has been copied: that call synchronized the stream)
+    // (the table of the previous upload of this kind has been copied: that call synchronized the stream)
     size_t bytes = 0; bool with_factors = false;
-    BODCHK(ragged_table(h, who, src_hw, aspect_resize, &h->rag_sync, &bytes, &with_factors));
-    BODCHK(ragged_alloc(h, who, &h->rag_sync));
+    bod_context::RaggedTable& t = aug ? h->aug_sync : h->rag_sync;
+    if (aug) BODCHK(augment_table(h, who, src_hw, aspect_resize, aug, &t, &bytes));
+    else BODCHK(ragged_table(h, who, src_hw, aspect_resize, &t, &bytes, &with_factors));
+    BODCHK(ragged_alloc(h, who, &t));
     if (bytes > h->frames_u8_cap) {
         if (h->d_frames_u8) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(h->d_frames_u8); h->d_frames_u8 = nullptr; h->frames_u8_cap = 0; }
         if (hipMalloc(reinterpret_cast<void**>(&h->d_frames_u8), bytes) != hipSuccess)
             return h->fail(BOD_ERR_OOM, "%s: %zu bytes of staging", who, bytes);
         h->frames_u8_cap = bytes;
     }
-    PreprocRaggedArgs a = ragged_args(h, h->rag_sync, rgb_means, aspect_resize);
-    a.src = h->d_frames_u8; a.dst = h->d_images;
-    HIPCHK(h, hipMemcpyAsync(h->rag_sync.dev, h->rag_sync.host.data(), h->rag_sync.host.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(t.dev, t.host.data(), t.host.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_frames_u8, rgb_packed, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, launch_preprocess_ragged(a, h->stream));
+    if (aug) {
+        PreprocAugArgs a = augment_args(h, t, rgb_means);
+        a.src = h->d_frames_u8; a.dst = h->d_images;
+        HIPCHK(h, launch_preprocess_augment(a, h->stream));
+    } else {
+        PreprocRaggedArgs a = ragged_args(h, t, rgb_means, aspect_resize);
+        a.src = h->d_frames_u8; a.dst = h->d_images;
+        HIPCHK(h, launch_preprocess_ragged(a, h->stream));
+    }
     HIPCHK(h, hipStreamSynchronize(h->stream));       // the caller may reuse `rgb_packed` on return
-    h->kscale_src[0] = with_factors ? ragged_factors(h, h->rag_sync) : nullptr;
+    h->kscale_src[0] = with_factors ? ragged_factors(h, t) : nullptr;
     return BOD_OK;
+}
+
+bod_status bod_upload_frames_u8_ragged(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw, const float* rgb_means,
+                                       int32_t aspect_resize) {
+    if (!h || !rgb_packed || !src_hw || !rgb_means) return BOD_ERR_INVALID_ARG;
+    return upload_packed(h, "bod_upload_frames_u8_ragged", rgb_packed, src_hw, rgb_means, aspect_resize, nullptr);
+}
+
+bod_status bod_upload_frames_u8_augmented(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw, const float* rgb_means,
+                                          int32_t aspect_resize, const bod_augment* aug) {
+    if (!h || !rgb_packed || !src_hw || !rgb_means || !aug) return BOD_ERR_INVALID_ARG;
+    return upload_packed(h, "bod_upload_frames_u8_augmented", rgb_packed, src_hw, rgb_means, aspect_resize, aug);
 }
 
 bod_status bod_upload_frames_u8_async(bod_handle h, const uint8_t* rgb, int32_t src_h, int32_t src_w, const float* rgb_means,
@@ -2164,19 +2251,20 @@ bod_status bod_upload_frames_u8_async(bod_handle h, const uint8_t* rgb, int32_t 
     return BOD_OK;
 }
 
-bod_status bod_upload_frames_u8_ragged_async(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw, const float* rgb_means,
-                                             int32_t aspect_resize, int32_t buffer) {
+// The pipelined upload of a packed batch, ragged (aug == nullptr) or augmented.
+static bod_status upload_packed_async(bod_handle h, const char* who, const uint8_t* rgb_packed, const int32_t* src_hw,
+                                      const float* rgb_means, int32_t aspect_resize, const bod_augment* aug, int32_t buffer) {
     MarkerRange mr_api("bod:upload");
-    if (!h || !rgb_packed || !src_hw || !rgb_means) return BOD_ERR_INVALID_ARG;
-    static const char* who = "bod_upload_frames_u8_ragged_async";
     if (buffer < 0 || buffer > 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: buffer must be 0 or 1", who);
     const bod_config& c = h->cfg;
     HIPCHK(h, hipSetDevice(c.device));
-    bod_context::RaggedTable& t = h->rag_b[buffer];
+    bod_context::RaggedTable& t = aug ? h->aug_b[buffer] : h->rag_b[buffer];
     // the host side of the table is rewritten below: the copy of this buffer's previous one (two uploads back) must have left it
+    // (one event per buffer for both kinds of table: they are copied on the one copy stream, so the latest copy is the last to end)
     if (h->ev_tab[buffer]) HIPCHK(h, hipEventSynchronize(h->ev_tab[buffer]));
     size_t bytes = 0; bool with_factors = false;
-    BODCHK(ragged_table(h, who, src_hw, aspect_resize, &t, &bytes, &with_factors));
+    if (aug) BODCHK(augment_table(h, who, src_hw, aspect_resize, aug, &t, &bytes));
+    else BODCHK(ragged_table(h, who, src_hw, aspect_resize, &t, &bytes, &with_factors));
     BODCHK(ragged_alloc(h, who, &t));
     if (!h->copy) {
         HIPCHK(h, hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking));
@@ -2202,16 +2290,96 @@ bod_status bod_upload_frames_u8_ragged_async(bod_handle h, const uint8_t* rgb_pa
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if (h->front) HIPCHK(h, hipStreamSynchronize(h->front));
     }
-    PreprocRaggedArgs a = ragged_args(h, t, rgb_means, aspect_resize);
-    a.src = h->d_u8_b[buffer]; a.dst = h->d_images_b[buffer];
     HIPCHK(h, hipMemcpyAsync(t.dev, t.host.data(), t.host.size(), hipMemcpyHostToDevice, h->copy));
     if (!h->ev_tab[buffer]) HIPCHK(h, hipEventCreateWithFlags(&h->ev_tab[buffer], hipEventDisableTiming));
     HIPCHK(h, hipEventRecord(h->ev_tab[buffer], h->copy));
     HIPCHK(h, hipMemcpyAsync(h->d_u8_b[buffer], rgb_packed, bytes, hipMemcpyHostToDevice, h->copy));
-    HIPCHK(h, launch_preprocess_ragged(a, h->copy));
+    if (aug) {
+        PreprocAugArgs a = augment_args(h, t, rgb_means);
+        a.src = h->d_u8_b[buffer]; a.dst = h->d_images_b[buffer];
+        HIPCHK(h, launch_preprocess_augment(a, h->copy));
+    } else {
+        PreprocRaggedArgs a = ragged_args(h, t, rgb_means, aspect_resize);
+        a.src = h->d_u8_b[buffer]; a.dst = h->d_images_b[buffer];
+        HIPCHK(h, launch_preprocess_ragged(a, h->copy));
+    }
     HIPCHK(h, hipEventRecord(h->ev_img_ready[buffer], h->copy));
     h->img_ready_pending[buffer] = true;
     h->kscale_src[buffer] = with_factors ? ragged_factors(h, t) : nullptr;
+    return BOD_OK;
+}
+
+bod_status bod_upload_frames_u8_ragged_async(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw, const float* rgb_means,
+                                             int32_t aspect_resize, int32_t buffer) {
+    if (!h || !rgb_packed || !src_hw || !rgb_means) return BOD_ERR_INVALID_ARG;
+    return upload_packed_async(h, "bod_upload_frames_u8_ragged_async", rgb_packed, src_hw, rgb_means, aspect_resize, nullptr, buffer);
+}
+
+bod_status bod_upload_frames_u8_augmented_async(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw, const float* rgb_means,
+                                                int32_t aspect_resize, const bod_augment* aug, int32_t buffer) {
+    if (!h || !rgb_packed || !src_hw || !rgb_means || !aug) return BOD_ERR_INVALID_ARG;
+    return upload_packed_async(h, "bod_upload_frames_u8_augmented_async", rgb_packed, src_hw, rgb_means, aspect_resize, aug, buffer);
+}
+
+// Ground truth through an augmented frame's geometry (bayesod.h): host arithmetic only, in fp32, no device call.
+bod_status bod_augment_boxes(int32_t B, const int32_t* src_hw, int32_t net_h, int32_t net_w, int32_t aspect_resize, const bod_augment* aug,
+                             const int32_t* num_gt, const float* gt_boxes_vuvu_src, const float* gt_classes, int32_t C, float min_visible,
+                             int32_t* num_out, float* boxes_out, float* classes_out) {
+#pragma clang fp contract(off)                          // multiply, then add: the float32 restatement of the tests rounds twice
+    auto fail = [](const char* fmt, auto... args) {
+        char buf[512];
+        snprintf(buf, sizeof(buf), fmt, args...);
+        g_create_error = buf;
+        return BOD_ERR_INVALID_ARG;
+    };
+    static const char* who = "bod_augment_boxes";
+    if (B < 1 || net_h < 1 || net_w < 1 || C < 2 || !std::isfinite(min_visible))
+        return fail("%s: bad argument (B = %d, network %dx%d, C = %d >= 2, min_visible finite)", who, B, net_h, net_w, C);
+    if (!src_hw || !aug || !num_gt || !gt_boxes_vuvu_src || !gt_classes || !num_out || !boxes_out || !classes_out)
+        return fail("%s: a required array is NULL", who);
+    // everything is checked before the first output is written
+    std::vector<PreprocFrame> geo((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const int32_t sh = src_hw[2 * b], sw = src_hw[2 * b + 1];
+        if (sh < 1 || sw < 1) return fail("%s: frame %d has size %dx%d", who, b, sh, sw);
+        if (num_gt[b] < 0) return fail("%s: frame %d has %d ground-truth rows", who, b, num_gt[b]);
+        if (const char* why = augment_bad(aug[b])) return fail("%s: frame %d: %s", who, b, why);
+        const int bad = frame_geometry(net_h, net_w, sh, sw, aspect_resize, &geo[b], aug[b].scale, aug[b].off_y, aug[b].off_x);
+        if (bad == 1) return fail("%s: frame %d (%dx%d): degenerate resize %dx%d", who, b, sh, sw, geo[b].rh, geo[b].rw);
+        if (bad == 2) return fail("%s: frame %d is %dx%d but the network size is %dx%d (pass aspect_resize=1 for the KITTI-style "
+                                  "resize + crop/pad)", who, b, sh, sw, net_h, net_w);
+    }
+    size_t in = 0, out = 0;
+    for (int b = 0; b < B; ++b) {
+        const PreprocFrame& g = geo[b];
+        const float ky = (float)((double)g.rh / (double)g.sh), kx = (float)((double)g.rw / (double)g.sw);
+        const float dy = (float)(g.pad_y - g.crop_y), dx = (float)(g.pad_x - g.crop_x);
+        const float ymax = (float)(net_h - 1), xmax = (float)(net_w - 1), wm1 = (float)(g.sw - 1);
+        int32_t kept = 0;
+        for (int i = 0; i < num_gt[b]; ++i, ++in) {
+            const float* q = gt_boxes_vuvu_src + 4 * in;
+            float x1 = q[1], x2 = q[3];
+            if (aug[b].flip) { const float t = wm1 - x2; x2 = wm1 - x1; x1 = t; }
+            const float ty1 = q[0] * ky + dy, tx1 = x1 * kx + dx, ty2 = q[2] * ky + dy, tx2 = x2 * kx + dx;
+            const float cy1 = std::min(std::max(ty1, 0.f), ymax), cx1 = std::min(std::max(tx1, 0.f), xmax);
+            const float cy2 = std::min(std::max(ty2, 0.f), ymax), cx2 = std::min(std::max(tx2, 0.f), xmax);
+            const float ch = cy2 - cy1, cw = cx2 - cx1;
+            const float full = (ty2 - ty1) * (tx2 - tx1);
+            if (!(ch >= 1.f) || !(cw >= 1.f) || ch * cw < min_visible * full) continue;
+            float* o = boxes_out + 4 * out;
+            o[0] = cy1; o[1] = cx1; o[2] = cy2; o[3] = cx2;
+            std::copy(gt_classes + (size_t)C * in, gt_classes + (size_t)C * (in + 1), classes_out + (size_t)C * out);
+            ++out; ++kept;
+        }
+        if (!kept) {                                    // the dataset handlers' row for a frame without ground truth
+            float* o = boxes_out + 4 * out;
+            o[0] = 0.f; o[1] = 0.f; o[2] = 1.f; o[3] = 1.f;
+            std::fill(classes_out + (size_t)C * out, classes_out + (size_t)C * (out + 1), 0.f);
+            classes_out[(size_t)C * out + C - 1] = 1.f;
+            ++out; kept = 1;
+        }
+        num_out[b] = kept;
+    }
     return BOD_OK;
 }
 

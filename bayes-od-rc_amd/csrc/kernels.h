@@ -316,6 +316,25 @@ struct PreprocRaggedArgs {
 };
 hipError_t launch_preprocess_ragged(const PreprocRaggedArgs& a, hipStream_t s);
 
+// Augmented form (training only): the ragged record drawn at random on the host -- crop / pad no longer centred, the resize target
+// scaled -- plus a mirror bit and two photometric scalars.  flip mirrors the SOURCE frame (every source column c read becomes
+// sw - 1 - c); gain / bias act on the interpolated 0..255 value inside the visible region, v' = clamp(gain * v + bias, 0, 255) as two
+// fp32 operations; padding stays 0.  flip = 0, gain = 1, bias = 0 on a centred record is preprocess_ragged_kernel bit for bit.
+struct PreprocAugFrame {
+    PreprocFrame g;
+    int32_t flip;              // 0 or 1
+    int32_t resize;            // per frame: without aspect_resize a frame is resized only when its scale moves it off its source size
+    float gain, bias;
+};
+struct PreprocAugArgs {
+    const uint8_t* src;              // packed uint8 RGB frames
+    float* dst;                      // [B, H, W, 3] fp32 BGR, mean-subtracted
+    const PreprocAugFrame* frames;   // [B], device memory
+    int32_t B, H, W;
+    float mean[3];                   // RGB order, shared by the batch
+};
+hipError_t launch_preprocess_augment(const PreprocAugArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------------
 // Loss forward (loss_kernels.hip)
 // ------------------------------------------------------------------------------------------------

@@ -1298,17 +1298,21 @@ hipError_t launch_iou_matrix(const float* corners, int M, float* out, hipStream_
 // with -ffp-contract=off), so results are bit-exact.
 // ------------------------------------------------------------------------------------------------
 // One output pixel (y, x) of a frame whose source starts at `src`: the geometry fields are PreprocArgs' / PreprocFrame's.
+// kAug (preprocess_augment_kernel only) adds the mirror of the source columns and the photometric step; without it flip, gain and
+// bias are not read and the code is what the two plain kernels have always run.
+template <bool kAug>
 __device__ __forceinline__ void preprocess_pixel(const uint8_t* src, float* o, const int y, const int x, const int sh, const int sw,
                                                  const int rh, const int rw, const int crop_y, const int crop_x, const int pad_y,
                                                  const int pad_x, const int vis_h, const int vis_w, const int resize,
-                                                 const float scale_y, const float scale_x, const float* mean) {
+                                                 const float scale_y, const float scale_x, const float* mean, const int flip = 0,
+                                                 const float gain = 1.f, const float bias = 0.f) {
     const int ry = y - pad_y + crop_y, rx = x - pad_x + crop_x;             // coordinates in the (resized) source
     float v[3] = {0.f, 0.f, 0.f};                                            // zero padding (before mean subtraction)
     const bool inside = y >= pad_y && x >= pad_x && ry < rh && rx < rw && ry >= 0 && rx >= 0 &&
                         y - pad_y < vis_h && x - pad_x < vis_w;
     if (inside) {
         if (!resize) {
-            const uint8_t* p = src + ((size_t)ry * sw + rx) * 3;
+            const uint8_t* p = src + ((size_t)ry * sw + (kAug && flip ? sw - 1 - rx : rx)) * 3;
             v[0] = (float)p[0]; v[1] = (float)p[1]; v[2] = (float)p[2];
         } else {
             const float fy = ((float)ry + 0.5f) * scale_y - 0.5f;
@@ -1316,7 +1320,8 @@ __device__ __forceinline__ void preprocess_pixel(const uint8_t* src, float* o, c
             const float fy0 = floorf(fy), fx0 = floorf(fx);
             const float ly = fy - fy0, lx = fx - fx0;
             const int y0 = min(max((int)fy0, 0), sh - 1), y1 = min(max((int)ceilf(fy), 0), sh - 1);
-            const int x0 = min(max((int)fx0, 0), sw - 1), x1 = min(max((int)ceilf(fx), 0), sw - 1);
+            int x0 = min(max((int)fx0, 0), sw - 1), x1 = min(max((int)ceilf(fx), 0), sw - 1);
+            if (kAug && flip) { x0 = sw - 1 - x0; x1 = sw - 1 - x1; }      // the taps keep their roles in the lerp: lx is unchanged
             const uint8_t* p00 = src + ((size_t)y0 * sw + x0) * 3;
             const uint8_t* p01 = src + ((size_t)y0 * sw + x1) * 3;
             const uint8_t* p10 = src + ((size_t)y1 * sw + x0) * 3;
@@ -1329,6 +1334,14 @@ __device__ __forceinline__ void preprocess_pixel(const uint8_t* src, float* o, c
                 v[c] = top + (bot - top) * ly;
             }
         }
+        if (kAug) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float t = gain * v[c];
+                t = t + bias;
+                v[c] = fminf(fmaxf(t, 0.f), 255.f);
+            }
+        }
     }
     o[0] = v[2] - mean[2]; o[1] = v[1] - mean[1]; o[2] = v[0] - mean[0];
 }
@@ -1337,8 +1350,8 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreprocArgs a) {
     const int x = blockIdx.x * 256 + threadIdx.x;
     const int y = blockIdx.y, b = blockIdx.z;
     if (x >= a.W) return;
-    preprocess_pixel(a.src + (size_t)b * a.sh * a.sw * 3, a.dst + (((size_t)b * a.H + y) * a.W + x) * 3, y, x, a.sh, a.sw, a.rh, a.rw,
-                     a.crop_y, a.crop_x, a.pad_y, a.pad_x, a.vis_h, a.vis_w, a.resize, a.scale_y, a.scale_x, a.mean);
+    preprocess_pixel<false>(a.src + (size_t)b * a.sh * a.sw * 3, a.dst + (((size_t)b * a.H + y) * a.W + x) * 3, y, x, a.sh, a.sw, a.rh,
+                            a.rw, a.crop_y, a.crop_x, a.pad_y, a.pad_x, a.vis_h, a.vis_w, a.resize, a.scale_y, a.scale_x, a.mean);
 }
 
 hipError_t launch_preprocess(const PreprocArgs& a, hipStream_t s) {
@@ -1353,11 +1366,29 @@ __global__ __launch_bounds__(256) void preprocess_ragged_kernel(PreprocRaggedArg
     const int y = blockIdx.y, b = blockIdx.z;
     if (x >= a.W) return;
     const PreprocFrame f = a.frames[b];
-    preprocess_pixel(a.src + f.offset, a.dst + (((size_t)b * a.H + y) * a.W + x) * 3, y, x, f.sh, f.sw, f.rh, f.rw,
+    preprocess_pixel<false>(a.src + f.offset, a.dst + (((size_t)b * a.H + y) * a.W + x) * 3, y, x, f.sh, f.sw, f.rh, f.rw,
                      f.crop_y, f.crop_x, f.pad_y, f.pad_x, f.vis_h, f.vis_w, a.resize, f.scale_y, f.scale_x, a.mean);
 }
 
 hipError_t launch_preprocess_ragged(const PreprocRaggedArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(preprocess_ragged_kernel, dim3((a.W + 255) / 256, a.H, a.B), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// The same pixel of a training frame shown in a random form: the record adds a per-frame resize switch, the mirror bit and the
+// photometric pair (PreprocAugFrame).  The record is uniform over a workgroup (grid z = frame), so its loads are scalar.
+__global__ __launch_bounds__(256) void preprocess_augment_kernel(PreprocAugArgs a) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y, b = blockIdx.z;
+    if (x >= a.W) return;
+    const PreprocAugFrame r = a.frames[b];
+    const PreprocFrame& f = r.g;
+    preprocess_pixel<true>(a.src + f.offset, a.dst + (((size_t)b * a.H + y) * a.W + x) * 3, y, x, f.sh, f.sw, f.rh, f.rw,
+                           f.crop_y, f.crop_x, f.pad_y, f.pad_x, f.vis_h, f.vis_w, r.resize, f.scale_y, f.scale_x, a.mean, r.flip,
+                           r.gain, r.bias);
+}
+
+hipError_t launch_preprocess_augment(const PreprocAugArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(preprocess_augment_kernel, dim3((a.W + 255) / 256, a.H, a.B), dim3(256), 0, s, a);
     return hipGetLastError();
 }

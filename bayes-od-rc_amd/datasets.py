@@ -25,6 +25,8 @@ KITTI_DIFF_DICTS = {            # src/core/constants.py:5-9
     'hard': {'min_height': 25, 'max_occlusion': 2, 'max_truncation': 0.50},
     'all': {'min_height': 0, 'max_occlusion': 3, 'max_truncation': 1.0}}
 IMAGE_UINT8_KEY = 'image_uint8'
+# KITTI: the ground-truth boxes in SOURCE pixels, beside the ratio-scaled BOXES_2D_GT_KEY (run_training --augment maps them itself)
+BOXES_2D_GT_SOURCE_KEY = 'boxes_2d_gt_source'
 
 
 def check_data_dirs(folders):
@@ -183,6 +185,7 @@ class KittiDatasetHandler(DatasetHandler):
         cls_gt, box_gt, _ = self._read_labels(label_path)
         oh, ow = rgb.shape[:2]
         nh, nw = self.resize_shape
+        box_gt_source = box_gt
         box_gt = (box_gt / np.array([oh, ow, oh, ow], np.float32)) * np.array([nh, nw, nh, nw], np.float32)
         placeholder = np.zeros((nh, nw, 3), np.float32)       # shape carrier: the pixels are produced on the device
         sample = create_sample_dict(placeholder, self.anchor_gen_config, box_gt, cls_gt, is_testing=self.is_testing,
@@ -190,6 +193,7 @@ class KittiDatasetHandler(DatasetHandler):
         sample[constants.IMAGE_NORMALIZED_KEY] = None
         sample[constants.ORIGINAL_IM_SIZE_KEY] = np.asarray(rgb.shape, dtype=np.int32)
         sample[IMAGE_UINT8_KEY] = rgb
+        sample[BOXES_2D_GT_SOURCE_KEY] = box_gt_source
         return sample
 
     def create_dataset(self):

@@ -185,17 +185,42 @@ class Engine(object):
             self._ragged_keep = {}
         self._ragged_keep[int(buffer)] = buf
 
+    def upload_frames_u8_augmented(self, frames, aug, means=None, aspect_resize=True):
+        """``upload_frames_u8_ragged`` with every frame shown in a form of its own (``bod_upload_frames_u8_augmented``, training
+        only): ``aug`` holds one record per frame -- an ``AUGMENT_DTYPE`` array or a list of dicts with its field names, missing
+        ones meaning "none" -- as ``draw_augmentation`` returns them.  ``augment_boxes`` maps the ground truth the same way."""
+        from . import constants
+        buf, sizes = pack_ragged(frames, self.B)
+        rec = augment_records(aug, self.B)
+        m = np.ascontiguousarray(constants.MEANS_DICT['ImageNet'] if means is None else means, dtype=np.float32)
+        self._chk(self.lib.bod_upload_frames_u8_augmented(self.h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), iptr(sizes), fptr(m),
+                                                          int(bool(aspect_resize)), rec.ctypes.data_as(C.POINTER(_lib.BodAugment))))
+
+    def upload_frames_u8_augmented_async(self, frames, aug, buffer, means=None, aspect_resize=True):
+        """Pipelined form (``bod_upload_frames_u8_augmented_async``), used like ``upload_frames_u8_ragged_async``."""
+        from . import constants
+        buf, sizes = pack_ragged(frames, self.B)
+        rec = augment_records(aug, self.B)
+        m = np.ascontiguousarray(constants.MEANS_DICT['ImageNet'] if means is None else means, dtype=np.float32)
+        self._chk(self.lib.bod_upload_frames_u8_augmented_async(self.h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), iptr(sizes), fptr(m),
+                                                                int(bool(aspect_resize)), rec.ctypes.data_as(C.POINTER(_lib.BodAugment)),
+                                                                int(buffer)))
+        if not hasattr(self, "_ragged_keep"):
+            self._ragged_keep = {}
+        self._ragged_keep[int(buffer)] = buf
+
     def _device_images(self, image_buffer):
         ptr = self.lib.bod_device_images(self.h) if image_buffer is None else self.lib.bod_device_images_buffer(self.h, int(image_buffer))
         if not ptr:
             raise ValueError("image buffer %r has not been filled" % (image_buffer,))
         return ptr
 
-    def get_images(self):
-        """The device image buffer [B,H,W,3] float32 (normalised BGR) copied to the host."""
+    def get_images(self, image_buffer=None):
+        """The device image buffer [B,H,W,3] float32 (normalised BGR) copied to the host; ``image_buffer`` 0 / 1: that buffer of
+        the pipelined uploads, once its upload has completed (``synchronize()``)."""
         import torch
         from .distributed import DeviceArray
-        ptr = self.lib.bod_device_images(self.h)
+        ptr = self._device_images(image_buffer)
         t = torch.as_tensor(DeviceArray(ptr, (self.B, self.cfg.image_h, self.cfg.image_w, 3), "<f4"),
                             device=torch.device("cuda", self.cfg.device))
         return t.cpu().numpy()
@@ -639,6 +664,112 @@ def pack_ragged(frames, batch=None):
         buf[off:off + f.size] = f.reshape(-1)
         off += f.size
     return buf, sizes
+
+
+# bod_augment as a NumPy record: what the augmented uploads and augment_boxes take
+AUGMENT_DTYPE = np.dtype([("flip", "<i4"), ("scale", "<f4"), ("off_y", "<f4"), ("off_x", "<f4"), ("gain", "<f4"), ("bias", "<f4")])
+AUGMENT_IDENTITY = {"flip": 0, "scale": 1.0, "off_y": 0.5, "off_x": 0.5, "gain": 1.0, "bias": 0.0}
+# training_config['augmentation'] of the yaml: keys and (mild) defaults
+AUGMENT_DEFAULTS = {"flip_probability": 0.5, "scale_range": [0.8, 1.25], "random_placement": True, "gain_range": [0.8, 1.2],
+                    "bias_range": [-20.0, 20.0], "min_visible": 0.25}
+
+
+def augment_records(aug, batch=None):
+    """``aug`` -- an ``AUGMENT_DTYPE`` array or a sequence of dicts (missing fields: no augmentation) -- as one C-contiguous
+    ``AUGMENT_DTYPE`` array of ``batch`` records."""
+    if isinstance(aug, np.ndarray):
+        if aug.dtype != AUGMENT_DTYPE:
+            raise ValueError("augmentation records must have dtype AUGMENT_DTYPE, got %s" % (aug.dtype,))
+        rec = np.ascontiguousarray(aug).reshape(-1)
+    else:
+        rec = np.empty(len(aug), AUGMENT_DTYPE)
+        for i, d in enumerate(aug):
+            unknown = set(d) - set(AUGMENT_IDENTITY)
+            if unknown:
+                raise ValueError("frame %d: unknown augmentation field(s) %s" % (i, sorted(unknown)))
+            rec[i] = tuple(d.get(k, v) for k, v in AUGMENT_IDENTITY.items())
+    if batch is not None and rec.shape[0] != int(batch):
+        raise ValueError("expected %d augmentation records, got %d" % (int(batch), rec.shape[0]))
+    return rec
+
+
+def augment_config(cfg=None):
+    """``AUGMENT_DEFAULTS`` overridden by ``cfg`` (``training_config['augmentation']``); an unknown key is an error."""
+    out = dict(AUGMENT_DEFAULTS)
+    unknown = set(cfg or {}) - set(out)
+    if unknown:
+        raise ValueError("unknown augmentation setting(s) %s (known: %s)" % (sorted(unknown), sorted(out)))
+    out.update(cfg or {})
+    return out
+
+
+def _f32_in(x, lo, hi):
+    """x in [lo, hi] as a float32 that is still in [lo, hi] (rounding to float32 may step over a bound by one ulp)."""
+    v = np.float32(x)
+    if float(v) > hi:
+        v = np.nextafter(v, np.float32(-np.inf))
+    elif float(v) < lo:
+        v = np.nextafter(v, np.float32(np.inf))
+    return v
+
+
+def draw_augmentation(cfg, seed, image_ids):
+    """One record per frame (``AUGMENT_DTYPE``), drawn from ``numpy.random.Generator(numpy.random.Philox(key=[seed, image_id]))``:
+    a frame's record depends on (seed, image id) alone -- not on the batch it sits in, the step a run was resumed at or the rank
+    that draws it.  Six doubles are drawn per frame, always and in this order, whatever ``cfg`` switches off:
+
+      1. ``random()`` -> flip = 1 when below ``flip_probability``;
+      2. ``random()`` -> scale = exp(log lo + u (log hi - log lo)) over ``scale_range`` (log-uniform);
+      3. ``random()`` -> off_y, 4. ``random()`` -> off_x: the draw itself with ``random_placement``, else 0.5;
+      5. ``random()`` -> gain = lo + u (hi - lo) over ``gain_range``;
+      6. ``random()`` -> bias = lo + u (hi - lo) over ``bias_range``.
+
+    ``cfg``: ``AUGMENT_DEFAULTS`` keys (None: the defaults); ``min_visible`` is ``augment_boxes``' business, not a record field."""
+    cfg = augment_config(cfg)
+    ids = [int(i) for i in np.asarray(image_ids).reshape(-1)]
+    rec = np.empty(len(ids), AUGMENT_DTYPE)
+    (s_lo, s_hi), (g_lo, g_hi), (b_lo, b_hi) = cfg["scale_range"], cfg["gain_range"], cfg["bias_range"]
+    if not (0.0 < s_lo <= s_hi) or g_lo > g_hi or b_lo > b_hi or not (0.0 <= cfg["flip_probability"] <= 1.0):
+        raise ValueError("bad augmentation ranges: %r" % (cfg,))
+    for k, image_id in enumerate(ids):
+        u = np.random.Generator(np.random.Philox(key=[int(seed), image_id])).random(6)
+        placed = bool(cfg["random_placement"])
+        rec[k] = (int(u[0] < cfg["flip_probability"]),
+                  _f32_in(np.exp(np.log(s_lo) + u[1] * (np.log(s_hi) - np.log(s_lo))), s_lo, s_hi),
+                  np.float32(u[2]) if placed else 0.5, np.float32(u[3]) if placed else 0.5,
+                  _f32_in(g_lo + u[4] * (g_hi - g_lo), g_lo, g_hi), _f32_in(b_lo + u[5] * (b_hi - b_lo), b_lo, b_hi))
+    return rec
+
+
+def augment_boxes(src_hw, net_hw, aug, gt_boxes, gt_classes, aspect_resize=True, min_visible=0.25):
+    """Ground truth of augmented frames (``bod_augment_boxes``; host arithmetic, no device): ``src_hw`` [B,2] source sizes, ``gt_boxes``
+    / ``gt_classes`` per-frame lists of [G_b,4] corners (y1,x1,y2,x2) in SOURCE pixels and [G_b,C] class rows.  Returns the two
+    lists in network pixels of the augmented frames: boxes flipped, scaled, shifted by pad - crop and clipped; a box of which less
+    than ``min_visible`` stays visible is dropped; a frame left without a box gets the row [0,0,1,1] of the background class."""
+    lib = _lib.load()
+    sizes = np.ascontiguousarray(src_hw, dtype=np.int32).reshape(-1, 2)
+    b = sizes.shape[0]
+    rec = augment_records(aug, b)
+    if len(gt_boxes) != b or len(gt_classes) != b:
+        raise ValueError("expected ground truth for %d frames, got %d box and %d class arrays" % (b, len(gt_boxes), len(gt_classes)))
+    boxes = [as_f32(x).reshape(-1, 4) for x in gt_boxes]
+    classes = [as_f32(c) for c in gt_classes]
+    width = max([c.shape[-1] for c in classes if c.ndim == 2] + [c.size // x.shape[0] for x, c in zip(boxes, classes) if x.shape[0]])
+    for i, (x, c) in enumerate(zip(boxes, classes)):
+        if c.size != x.shape[0] * width:
+            raise ValueError("frame %d: class rows of shape %s do not match %d boxes x %d classes" % (i, c.shape, x.shape[0], width))
+    ng = np.asarray([x.shape[0] for x in boxes], np.int32)
+    # (one spare row: a pointer to an empty array may be NULL)
+    allb = as_f32(np.concatenate(boxes + [np.zeros((1, 4), np.float32)], axis=0))
+    allc = as_f32(np.concatenate([c.reshape(-1, width) for c in classes] + [np.zeros((1, width), np.float32)], axis=0))
+    rows = int(np.maximum(ng, 1).sum())
+    num_out, bo, co = np.empty(b, np.int32), np.empty((rows, 4), np.float32), np.empty((rows, width), np.float32)
+    st = lib.bod_augment_boxes(b, iptr(sizes), int(net_hw[0]), int(net_hw[1]), int(bool(aspect_resize)),
+                               rec.ctypes.data_as(C.POINTER(_lib.BodAugment)), iptr(ng), fptr(allb), fptr(allc), width,
+                               float(min_visible), iptr(num_out), fptr(bo), fptr(co))
+    _lib.check(lib, None, st)
+    ends = np.cumsum(num_out)
+    return ([bo[e - n:e].copy() for n, e in zip(num_out, ends)], [co[e - n:e].copy() for n, e in zip(num_out, ends)])
 
 
 def _pack_gt(gt_boxes, gt_classes, batch, num_classes=None):

@@ -7,7 +7,8 @@ The step itself -- forward in training mode, losses, backward, global-norm clipp
 ``bod_train_step``; this file keeps what the reference keeps on the host: the piecewise-constant learning-rate
 schedule (:48-61), the batching of the dataset handler's sample dictionaries, the summary print and the checkpoint
 cadence.  With ``--dataset`` the split is streamed one minibatch at a time and the anchor targets are assigned on the GPU from
-the frames' ground-truth boxes (``bod_train_step_boxes``); KITTI frames are resized there too.  Checkpoints are ``.npz``
+the frames' ground-truth boxes (``bod_train_step_boxes``); KITTI frames are resized there too, and with ``--augment`` every frame
+is mirrored / rescaled / placed / brightened at random in the same kernel.  Checkpoints are ``.npz``
 files in the schema ``RetinaNetModel.load_weights`` reads (the TF-checkpoint
 format is the converter's business, convert_checkpoint.py)."""
 import argparse
@@ -23,7 +24,7 @@ import numpy as np
 
 from . import config_utils, constants, synthetic
 from .anchor_generator import FpnAnchorGenerator
-from .engine import Engine, make_config
+from .engine import Engine, augment_boxes, augment_config, draw_augmentation, make_config
 from .sample_builder import create_sample_dict
 
 _REG_KIND = {'regression': 1, 'regression_var': 2, 'regression_covar': 3}
@@ -48,7 +49,7 @@ class Trainer(object):
     """Holds the training handle; ``train_single_step(sample_dicts)`` mirrors run_training.train_single_step (:208-247)
     and returns ``(total_loss, loss_dict)`` with the reference's keys."""
 
-    def __init__(self, config, image_hw, weights, device=0, seed=0):
+    def __init__(self, config, image_hw, weights, device=0, seed=0, augmentation=None):
         model_config = config['model_config']
         header = model_config['header']
         losses = model_config['losses']
@@ -64,6 +65,8 @@ class Trainer(object):
         self.batch = int(config['training_config']['minibatch_size'])
         self.seed = seed
         self.step = 0
+        self.image_hw = (int(image_hw[0]), int(image_hw[1]))
+        self.augmentation = None if augmentation is None else augment_config(augmentation)     # --augment: the settings
         self.engine = Engine(make_config(image_hw, batch=self.batch, mc_samples=1, num_classes=int(header['num_classes']) + 1,
                                          anchors_per_location=int(header['anchors_per_location']), device=device,
                                          dropout_rate=float(header['dropout_rate']),
@@ -77,6 +80,8 @@ class Trainer(object):
     def _train_step_from_boxes(self, sample_dicts, learning_rate):
         """Samples that carry the ground truth only (``dense_targets=False``): the targets are assigned on the device.  KITTI
         samples have no host image (IMAGE_NORMALIZED_KEY is None): their uint8 frames are resized and normalised on the device."""
+        if self.augmentation is not None:
+            return self._train_step_augmented(sample_dicts, learning_rate)
         if sample_dicts[0][constants.IMAGE_NORMALIZED_KEY] is None:
             frames = [s['image_uint8'] for s in sample_dicts]
             if len(set(f.shape for f in frames)) > 1:                  # --mixed_sizes: a minibatch in the handler's order
@@ -90,6 +95,25 @@ class Trainer(object):
             imgs, [s[constants.BOXES_2D_GT_KEY] for s in sample_dicts], [s[constants.BOXES_CLASS_GT_KEY] for s in sample_dicts],
             float(self.anchor_config['min_positive_iou']), float(self.anchor_config['max_negative_iou']),
             seed=self.seed, first_image_id=self.step * self.batch, reg_kind=self.reg_kind, label_smoothing=self.label_smoothing,
+            w_cls=self.w_cls, w_reg=self.w_reg, l2_rate=self.l2_rate, learning_rate=learning_rate)
+
+    def _train_step_augmented(self, sample_dicts, learning_rate):
+        """``--augment``: frame i of the step is shown in the form drawn for image id ``step * batch + i`` (the id its dropout
+        streams are keyed by), so a resumed run draws what an uninterrupted one would.  The uint8 frames -- KITTI's of equal or
+        mixed sizes, BDD's at the network size -- go up through the augmented entry point and the ground truth, kept in source
+        pixels, is mapped by the same geometry on the host."""
+        kitti = sample_dicts[0][constants.IMAGE_NORMALIZED_KEY] is None
+        frames = [s['image_uint8'] for s in sample_dicts]
+        first = self.step * self.batch
+        aug = draw_augmentation(self.augmentation, self.seed, [first + i for i in range(len(frames))])
+        self.engine.upload_frames_u8_augmented(frames, aug, constants.MEANS_DICT[self.im_normalization], aspect_resize=kitti)
+        boxes, classes = augment_boxes(
+            [f.shape[:2] for f in frames], self.image_hw, aug,
+            [s['boxes_2d_gt_source'] if kitti else s[constants.BOXES_2D_GT_KEY] for s in sample_dicts],
+            [s[constants.BOXES_CLASS_GT_KEY] for s in sample_dicts], aspect_resize=kitti, min_visible=float(self.augmentation['min_visible']))
+        return self.engine.train_step_boxes(
+            None, boxes, classes, float(self.anchor_config['min_positive_iou']), float(self.anchor_config['max_negative_iou']),
+            seed=self.seed, first_image_id=first, reg_kind=self.reg_kind, label_smoothing=self.label_smoothing,
             w_cls=self.w_cls, w_reg=self.w_reg, l2_rate=self.l2_rate, learning_rate=learning_rate)
 
     def train_single_step(self, sample_dicts, learning_rate):
@@ -225,13 +249,20 @@ def train(config, args):
     dataset_config = config['dataset_config']
     num_classes = int(config['model_config']['header']['num_classes'])
     mb = int(training_config['minibatch_size'])
+    augmentation = None
+    if getattr(args, 'augment', False):
+        if not args.dataset:
+            raise ValueError('--augment needs --dataset: only frames streamed from a data split are augmented (synthetic samples '
+                             'carry dense targets computed for the frame as it is)')
+        augmentation = augment_config(training_config.get('augmentation'))
     if args.dataset:
         from . import datasets
         # the split is streamed: samples carry the GT boxes only (the step assigns the dense targets on the device) and are read
         # one minibatch at a time
         handler = datasets.build_dataset(dataset_config, 'train')
         handler.dense_targets = False
-        stream = stream_minibatches(handler, mb, mixed_sizes=bool(getattr(args, 'mixed_sizes', False)))
+        # (the augmented upload takes equal and mixed sizes alike: no buckets needed)
+        stream = stream_minibatches(handler, mb, mixed_sizes=bool(getattr(args, 'mixed_sizes', False)) or augmentation is not None)
         pending = next(stream)                                        # the first minibatch also tells the frame size
         first = pending[0][constants.IMAGE_NORMALIZED_KEY]
         hw = tuple(handler.resize_shape) if first is None else first.shape[:2]
@@ -281,7 +312,7 @@ def train(config, args):
         print('Restored from {}'.format(restored))
     else:
         print('Initializing from scratch.')
-    trainer = Trainer(config, hw, weights, device=int(args.gpu_device), seed=args.seed)
+    trainer = Trainer(config, hw, weights, device=int(args.gpu_device), seed=args.seed, augmentation=augmentation)
     if opt_state:
         trainer.restore_optimizer_state(opt_state)
     if superseded:
@@ -373,6 +404,8 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--mixed_sizes', action='store_true', help='with --dataset: minibatches in the handler\'s shuffled order whatever '
                     'the frame sizes (default: bucketed by source size)')
+    ap.add_argument('--augment', action='store_true', help='with --dataset: random horizontal flip, scale jitter, placement and gain / bias '
+                    'per frame, on the device (training_config[\'augmentation\'] of the yaml, else mild defaults)')
     ap.add_argument('--no_resume', action='store_true', help='start from scratch: existing checkpoints of this run are not restored; they are moved to '
                     'checkpoints/superseded-<time>/ (never deleted) once the trainer has been built')
     args = ap.parse_args(argv)

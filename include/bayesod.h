@@ -277,6 +277,48 @@ bod_status bod_upload_frames_u8_ragged(bod_handle h, const uint8_t* rgb_packed, 
                                        const float* rgb_means, int32_t aspect_resize);
 bod_status bod_upload_frames_u8_ragged_async(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw,
                                              const float* rgb_means, int32_t aspect_resize, int32_t buffer);
+/* Training-time augmentation of the same upload: every frame of the packed batch is shown in a form of its own -- mirrored,
+ * resized by `scale`, placed off-centre in the network frame, its brightness / contrast changed.  The default routes above do
+ * not change; this one is opt-in (run_training --augment).
+ * Geometry of frame b (the function the two other upload routes take their centred geometry from):
+ *   aspect_resize != 0: the resize target is (max(1, floor(scale*image_h + 0.5)), max(1, floor(scale*image_w + 0.5))), in double,
+ *     in place of (image_h, image_w); (rh, rw) is the aspect-preserving size for that target by the rule above.
+ *   aspect_resize == 0: the frame must be at the network size; (rh, rw) = (max(1, floor(scale*h + 0.5)), max(1, floor(scale*w + 0.5)))
+ *     and the frame is resized by the same bilinear when that differs from (h, w).
+ *   per axis, d = rh - image_h:  d > 0: crop = floor(off*d), no pad;  d < 0: pad = floor(off*(-d)), no crop (off widened to double).
+ *     off = 0.5 is the centred d / 2 of every other upload.
+ * Then, per output pixel: flip mirrors the SOURCE frame (the result is bit for bit the upload of the mirrored frame with flip = 0);
+ * inside the visible region v' = min(max(gain*v + bias, 0), 255) on the interpolated 0..255 value, two fp32 operations; padding
+ * stays 0 (so -mean after normalisation).  flip 0, scale 1, off 0.5, gain 1, bias 0 is bod_upload_frames_u8_ragged bit for bit.
+ * On a handle whose kitti_scale_h > 0 the handle's two scalars apply, as after a uniform upload (detections of an augmented frame
+ * are not mapped back to its source).  BOD_ERR_INVALID_ARG, naming the frame, for flip outside {0, 1}, a scale that is not finite
+ * and positive, an off outside [0, 1], a gain or bias that is not finite, and the ragged uploads' errors; the handle and the
+ * frames it held stay as they were.  Packing, staging, streams and lifetimes as for the ragged pair (aug is read before return). */
+typedef struct bod_augment {   /* one per frame */
+    int32_t flip;              /* 0 or 1 */
+    float   scale;             /* > 0, finite; 1 = none */
+    float   off_y, off_x;      /* in [0,1]; 0.5 = centred, as every other upload */
+    float   gain, bias;        /* finite; 1, 0 = none */
+} bod_augment;
+bod_status bod_upload_frames_u8_augmented(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw,
+                                          const float* rgb_means, int32_t aspect_resize, const bod_augment* aug);
+bod_status bod_upload_frames_u8_augmented_async(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw,
+                                                const float* rgb_means, int32_t aspect_resize, const bod_augment* aug,
+                                                int32_t buffer);
+/* Ground truth of B augmented frames, mapped through the same geometry: pure host code, no handle and no device.  gt_boxes_vuvu_src
+ * holds sum(num_gt) rows (y1, x1, y2, x2) in SOURCE pixels, frame after frame, gt_classes the matching [.., C] rows.  In fp32, in
+ * this order: flip (x1' = (w-1) - x2, x2' = (w-1) - x1); multiply by float(rh / h), float(rw / w); add pad - crop; clip to
+ * [0, net_h-1] x [0, net_w-1].  A box is dropped when its clipped area is below min_visible times its unclipped transformed area or
+ * its clipped height or width is below 1.  A frame left without a box gets the dataset handlers' placeholder row [0, 0, 1, 1] with
+ * the background class (the last of C), so num_out[b] >= 1.  Outputs: num_out[B]; boxes_out / classes_out sized for
+ * sum(max(num_gt[b], 1)) rows, packed frame after frame.
+ * NOTE: this map differs on purpose from the KITTI handler's box * (net / orig) ratio (kitti_dataset_handler.py:132-135), which
+ * ignores the pad of the aspect-preserving resize; that ratio stays what the non-augmented route uses.
+ * Errors are reported through bod_last_error(NULL). */
+bod_status bod_augment_boxes(int32_t B, const int32_t* src_hw, int32_t net_h, int32_t net_w, int32_t aspect_resize,
+                             const bod_augment* aug, const int32_t* num_gt, const float* gt_boxes_vuvu_src,
+                             const float* gt_classes, int32_t C, float min_visible,
+                             int32_t* num_out, float* boxes_out, float* classes_out);
 const float* bod_device_images_buffer(bod_handle h, int32_t buffer);
 const float* bod_device_images(bod_handle h);
 bod_status bod_synchronize(bod_handle h);

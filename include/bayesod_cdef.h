@@ -100,6 +100,21 @@ bod_status bod_upload_frames_u8_ragged(bod_handle h, const uint8_t* rgb_packed, 
                                        const float* rgb_means, int32_t aspect_resize);
 bod_status bod_upload_frames_u8_ragged_async(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw,
                                              const float* rgb_means, int32_t aspect_resize, int32_t buffer);
+typedef struct bod_augment {
+    int32_t flip;
+    float   scale;
+    float   off_y, off_x;
+    float   gain, bias;
+} bod_augment;
+bod_status bod_upload_frames_u8_augmented(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw,
+                                          const float* rgb_means, int32_t aspect_resize, const bod_augment* aug);
+bod_status bod_upload_frames_u8_augmented_async(bod_handle h, const uint8_t* rgb_packed, const int32_t* src_hw,
+                                                const float* rgb_means, int32_t aspect_resize, const bod_augment* aug,
+                                                int32_t buffer);
+bod_status bod_augment_boxes(int32_t B, const int32_t* src_hw, int32_t net_h, int32_t net_w, int32_t aspect_resize,
+                             const bod_augment* aug, const int32_t* num_gt, const float* gt_boxes_vuvu_src,
+                             const float* gt_classes, int32_t C, float min_visible,
+                             int32_t* num_out, float* boxes_out, float* classes_out);
 const float* bod_device_images_buffer(bod_handle h, int32_t buffer);
 const float* bod_device_images(bod_handle h);
 bod_status bod_synchronize(bod_handle h);
