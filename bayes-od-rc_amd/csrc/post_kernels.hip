@@ -929,6 +929,7 @@ __global__ __launch_bounds__(64) void nms_kernel(NmsArgs a) {
     const float scale = a.sigma > 0.f ? -0.5f / a.sigma : 0.f;
     const bool soft = a.sigma > 0.f;
     const bool always_soft = a.variant == 1 && soft;
+    const bool hard_drop = a.variant == 1 && !soft;      // TF >= 2.3 without soft-NMS: a box over the IoU threshold is dropped, never re-queued
     const float NEG_INF = -INFINITY;
 
     // score[] is padded to a multiple of 64*8 with -inf; a candidate that leaves the queue is marked by
@@ -972,14 +973,18 @@ __global__ __launch_bounds__(64) void nms_kernel(NmsArgs a) {
         // selected boxes at a time with lane l <-> j = hi-1-l; a factor of exactly 1.0f (no overlap) leaves
         // the product bit-identical, so only the lanes with w != 1 enter the serial chain.
         float s = original;
+        bool dropped = false;
         for (int hi = nsel; hi > beg; hi -= 64) {
             const int j = hi - 1 - lane;
             float w = 1.0f;
+            bool over = false;
             if (j >= beg) {
                 const float sim = nms_iou(cb, s_selbox[j]);
                 if (sim != 0.f) w = (float)exp((double)(scale * (sim * sim)));
                 if (!always_soft && !(sim <= a.iou_thr)) w = 0.f;
+                over = sim > a.iou_thr;
             }
+            if (hard_drop && __ballot(over)) dropped = true;
             unsigned long long m = __ballot(w != 1.0f);
             while (m) {
                 const int l = __builtin_ctzll(m);
@@ -988,7 +993,9 @@ __global__ __launch_bounds__(64) void nms_kernel(NmsArgs a) {
             }
         }
         const bool owner = (idx & 63) == lane;
-        if (s == original) {
+        if (dropped) {
+            if (owner) score[idx] = NEG_INF;
+        } else if (s == original) {
             if (lane == 0) { sel[nsel] = idx; s_selbox[nsel] = cb; }
             if (owner) score[idx] = NEG_INF;
             ++nsel;

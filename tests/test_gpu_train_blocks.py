@@ -77,8 +77,9 @@ def test_dgrad_is_the_forward_kernel_on_flipped_weights(b, h, w, cin, cout, k):
     assert rel_err(dx, ref_dx, floor=float(np.sqrt((ref_dx ** 2).mean()))) < 1e-3
 
 
-def _torch_loss(cls, cls_t, box, box_t, cov, anchors, pos, neg, reg_kind, eps, w_cls, w_reg):
-    """The reference's total loss (retinanet_model.py:183-323, core/losses.py:30-61) in torch float64."""
+def _torch_loss(cls, cls_t, box, box_t, cov, anchors, pos, neg, reg_kind, eps, w_cls, w_reg, do_cls=1):
+    """The reference's total loss (retinanet_model.py:183-323, core/losses.py:30-61) in torch float64; do_cls = 0 / reg_kind = 0
+    leave the classification / regression loss out of loss_names."""
     import torch
     t = lambda x: torch.tensor(np.asarray(x), dtype=torch.float64)
     cls, box, cov = t(cls).requires_grad_(True), t(box).requires_grad_(True), t(cov).requires_grad_(True)
@@ -91,14 +92,16 @@ def _torch_loss(cls, cls_t, box, box_t, cov, anchors, pos, neg, reg_kind, eps, w
     ce = -(q * ls).sum(-1)
     pt = (torch.softmax(cls, -1) * cls_t).sum(-1)
     focal = 0.5 * (1 - pt) ** 2 * ce
-    total = w_cls * (focal * (posm + negm)).sum() / npos
+    total = w_cls * (focal * (posm + negm)).sum() / npos if do_cls else 0.0 * cls.sum()
 
     def decode(tg):
         return torch.stack([anc[:, 2] * tg[..., 0] / 10 + anc[:, 0], anc[:, 3] * tg[..., 1] / 10 + anc[:, 1],
                             anc[:, 2] * torch.clamp(torch.exp(tg[..., 2] / 5), 1e-4, 1e4),
                             anc[:, 3] * torch.clamp(torch.exp(tg[..., 3] / 5), 1e-4, 1e4)], -1)
     hub = torch.nn.functional.huber_loss
-    if reg_kind == 1:
+    if reg_kind == 0:
+        pass
+    elif reg_kind == 1:
         l = hub(box, box_t, reduction="none", delta=1.0).mean(-1)
         total = total + w_reg * (l * posm).sum() / npos
     else:
@@ -145,3 +148,97 @@ def test_loss_backward_matches_autograd(reg_kind):
             assert not got.any(), name
         else:
             assert rel_err(got, ref, floor=rms) < 1e-4, name
+
+
+# ------------------------------------------------------------------------------------------------ loss backward at the edges
+def _loss_backward(p, reg_kind, do_cls, eps, pos=None, want=(True, True, True), w_cls=5.0, w_reg=1.0):
+    """bod_loss_backward on a tests/test_gpu_loss.py edge_problem: (dcls, dbox, dcov, out4), None where not wanted (NULL)."""
+    import ctypes as C
+    from bayes_od_rc_amd import _lib
+    lib = _lib.load()
+    pos = np.ascontiguousarray(p["pos"] if pos is None else pos, dtype=np.uint8)
+    out4 = (C.c_double * 4)()
+    grads = [np.full_like(p[k], np.nan) if w else None for k, w in zip(("cls", "box", "cov"), want)]
+    u8 = C.POINTER(C.c_uint8)
+    st = lib.bod_loss_backward(0, p["b"], p["a"], p["c"], _lib.fptr(p["cls"]), _lib.fptr(p["cls_t"]), _lib.fptr(p["box"]),
+                               _lib.fptr(p["box_t"]), _lib.fptr(p["cov"]), _lib.fptr(p["anchors"]), pos.ctypes.data_as(u8),
+                               p["neg"].ctypes.data_as(u8), int(do_cls), int(reg_kind), float(eps), w_cls, w_reg, out4,
+                               _lib.fptr(grads[0]), _lib.fptr(grads[1]), _lib.fptr(grads[2]))
+    _lib.check(lib, None, st)
+    return grads + [np.array(list(out4))]
+
+
+@pytest.mark.parametrize("c", [4, 8])
+@pytest.mark.parametrize("b,a", [(1, 1), (1, 255), (1, 256), (1, 257), (3, 171), (2, 3069)])
+def test_loss_backward_at_the_edges(b, a, c):
+    """bod_loss_backward element-wise against float64 autograd on the edge problems of tests/test_gpu_loss.py (both clamps of the
+    decode, the Huber switch, saturated logits, extreme log-variances, a frame and a call without positives, shapes on the block
+    edges) for every (reg_kind, do_cls, label_smoothing), and with each of dcls / dbox / dcov not wanted in turn.
+
+    rel_err(got, ref, floor = rms of ref) < 1e-4 on each gradient as a whole.  The planted anchors' gradients are up to 1e9 times
+    the others' and would own that rms, so the anchors without a plant are also compared among themselves (their own rms), and
+    every planted anchor against its own row's rms.  Where exp(z / 5) is clamped dbox[2:4] is exactly 0 (clip_by_value passes
+    no gradient outside), and out4 is bod_loss_forward's, bit for bit."""
+    from test_gpu_loss import device_loss_sums, edge_problem, loss_modes
+    p = edge_problem(b, a, c)
+    n = b * a
+    planted = np.zeros(n, bool)
+    planted[[i for _, i in p["plants"]]] = True
+    clamped = [i for kind, i in p["plants"] if kind in ("box_above_clamp", "box_below_clamp")]
+    assert clamped
+    worst = 0.0
+
+    def compare(got, ref, what):
+        nonlocal worst
+        for g, r, name in zip(got[:3], ref, ("cls", "box", "cov")):
+            if g is None:
+                continue
+            assert np.isfinite(g).all(), (what, name)
+            g2, r2 = g.reshape(n, -1).astype(np.float64), r.reshape(n, -1)
+            for rows in (np.ones(n, bool), ~planted):
+                if not rows.any():
+                    continue
+                rms = float(np.sqrt((r2[rows] ** 2).mean()))
+                if rms == 0.0:
+                    assert not g2[rows].any(), (what, name)
+                else:
+                    e = rel_err(g2[rows], r2[rows], floor=rms)
+                    worst = max(worst, e)
+                    assert e < 1e-4, (what, name, e)
+            for i in np.nonzero(planted)[0]:
+                rms = float(np.sqrt((r2[i] ** 2).mean()))
+                if rms == 0.0:
+                    assert not g2[i].any(), (what, name, i)
+                else:
+                    e = rel_err(g2[i], r2[i], floor=rms)
+                    worst = max(worst, e)
+                    assert e < 1e-4, (what, name, i, e)
+
+    def reference(rk, dc, eps, pos):
+        if not rk and not dc:
+            return np.zeros(p["cls"].shape), np.zeros(p["box"].shape), np.zeros(p["cov"].shape)
+        return _torch_loss(p["cls"], p["cls_t"], p["box"], p["box_t"], p["cov"], p["anchors"], pos, p["neg"], rk, eps, 5.0, 1.0, do_cls=dc)
+
+    for rk, dc, eps in loss_modes():
+        got = _loss_backward(p, rk, dc, eps)
+        assert np.array_equal(got[3], device_loss_sums(p, rk, dc, eps)), (rk, dc, eps)
+        compare(got, reference(rk, dc, eps, p["pos"]), (rk, dc, eps))
+        if rk >= 2:
+            for i in clamped:
+                assert np.all(got[1].reshape(n, 4)[i, 2:] == 0.0), (rk, i)
+                assert np.all(got[1].reshape(n, 4)[i, :2] != 0.0), (rk, i)
+    # a call without any positive: max(n_pos, 1) = 1, only the focal term of the negatives is left
+    nopos = np.zeros_like(p["pos"])
+    got = _loss_backward(p, 3, 1, 0.001, pos=nopos)
+    assert got[3][3] == 0.0 and not got[1].any() and not got[2].any()
+    compare(got, reference(3, 1, 0.001, nopos), "no positive")
+    # each gradient not wanted (NULL) in turn: the others are what the full call returns
+    full = _loss_backward(p, 3, 1, 0.001)
+    for skip in range(3):
+        want = tuple(k != skip for k in range(3))
+        part = _loss_backward(p, 3, 1, 0.001, want=want)
+        assert part[skip] is None and np.array_equal(part[3], full[3])
+        for k in range(3):
+            if k != skip:
+                assert np.array_equal(part[k], full[k]), (skip, k)
+    print("loss backward (%d,%d) C=%d: worst error %.2e of the rms (bound 1e-4)" % (b, a, c, worst))
