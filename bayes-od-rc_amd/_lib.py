@@ -17,6 +17,7 @@ if os.environ.get("BOD_LIB_OVERRIDE"):
     LIB_PATH = os.path.abspath(os.environ["BOD_LIB_OVERRIDE"])
 
 BOD_OK, BOD_ERR_INVALID_ARG, BOD_ERR_HIP, BOD_ERR_OOM, BOD_ERR_NOT_READY, BOD_ERR_NO_DEVICE = range(6)
+BOD_VIEW_IDENTITY, BOD_VIEW_HFLIP = 0, 1          # views of a statistics handle (bod_stat_forward_view / bod_stat_merge_view)
 
 
 class BodConfig(C.Structure):
@@ -146,6 +147,8 @@ SIGNATURES = {
     "bod_stat_get": (C.c_int, [_H, _F, _F, _F, _I]),
     "bod_stat_set": (C.c_int, [_H, _F, _F, _F, C.c_int32]),
     "bod_stat_posterior": (C.c_int, [_H, C.c_uint64, C.c_uint32]),
+    "bod_stat_forward_view": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32]),
+    "bod_stat_merge_view": (C.c_int, [_H, C.POINTER(C.c_void_p), C.c_int32, C.c_int32]),
     "bod_record_width": (C.c_int32, [_H]),
     "bod_gather_detections": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
     "bod_profile_end": (C.c_int, [_H, C.POINTER(C.c_double), C.POINTER(C.c_int64),

@@ -313,6 +313,11 @@ struct bod_context {
     float* stat_acc[3] = {nullptr};
     int stat_k = 0;
     hipEvent_t ev_stat = nullptr;                        // bod_stat_merge_from: orders the two handles' streams
+    // Mirrored views (bod_stat_forward_view / bod_stat_merge_view): the frames mirrored left-right, allocated by the first mirrored
+    // forward, and the outcome of the host check that the uploaded anchors are mirror-symmetric (-1: not checked since
+    // bod_set_anchors, 1: symmetric, 0: level mirror_bad_level is not)
+    float* d_mirror = nullptr;
+    int mirror_sym = -1, mirror_bad_level = 0;
     bool keep_ready = false;                             // pb.keep / d_counts / block_counts / num_kept hold the keep stage's output
     uint64_t keep_seed = 0; uint32_t keep_first = 0;
     uint64_t last_seed = 0; uint32_t last_first_image = 0;
@@ -1961,6 +1966,7 @@ bod_status bod_set_anchors(bod_handle h, const float* anchors, int32_t n) {
     HIPCHK(h, hipMemcpyAsync(h->d_anchors, anchors, (size_t)n * 16, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->anchors_ready = true;
+    h->mirror_sym = -1;
     return BOD_OK;
 }
 
@@ -3444,8 +3450,44 @@ static bod_status stat_handle(bod_handle h, const char* who) {
     return ensure_stat(h);
 }
 
-// accumulator (+)= {cls_sum, box_moments, cov_sum} of kb samples, on the handle's stream
-static bod_status stat_fold(bod_handle h, const char* who, const float* cls, const float* box, const float* cov, int kb) {
+// Mirrored views need mirror-symmetric anchors (include/bayesod.h): checked on the host once per bod_set_anchors
+static bod_status stat_view_ready(bod_handle h, const char* who, int32_t view) {
+    if (view != BOD_VIEW_IDENTITY && view != BOD_VIEW_HFLIP)
+        return h->fail(BOD_ERR_INVALID_ARG, "%s: view must be BOD_VIEW_IDENTITY (0) or BOD_VIEW_HFLIP (1), got %d", who, view);
+    if (view == BOD_VIEW_IDENTITY) return BOD_OK;
+    if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "%s: bod_set_anchors has not been called (a mirrored view maps every anchor to its partner)", who);
+    const bod_config& c = h->cfg;
+    const int K = c.anchors_per_location;
+    if (h->mirror_sym < 0) {
+        std::vector<float> an((size_t)h->A * 4);
+        HIPCHK(h, hipMemcpyAsync(an.data(), h->d_anchors, an.size() * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        const float fw = (float)c.image_w;
+        int bad = -1;
+        for (int l = 0; l < h->nlev && bad < 0; ++l) {
+            const size_t off = (size_t)h->lvl_p0[l] * K;
+            const int W = h->lw[l];
+            for (int y = 0; y < h->lh[l] && bad < 0; ++y)
+                for (int x = 0; x < W && bad < 0; ++x)
+                    for (int k = 0; k < K; ++k) {
+                        const float* s = &an[(off + ((size_t)y * W + x) * K + k) * 4];
+                        const float* p = &an[(off + ((size_t)y * W + (W - 1 - x)) * K + k) * 4];
+                        const float want[4] = {s[0], fw - s[1], s[2], s[3]};
+                        if (memcmp(p, want, 16) != 0) { bad = l; break; }
+                    }
+        }
+        h->mirror_sym = bad < 0; h->mirror_bad_level = bad < 0 ? 0 : c.min_level + bad;
+    }
+    if (!h->mirror_sym)
+        return h->fail(BOD_ERR_INVALID_ARG, "%s: the anchors of pyramid level %d are not mirror-symmetric about image_w / 2 for a %dx%d image "
+                       "(BOD_VIEW_HFLIP needs image_w to be a multiple of 2^max_level = %d)", who, h->mirror_bad_level, c.image_h, c.image_w,
+                       1 << c.max_level);
+    return BOD_OK;
+}
+
+// accumulator (+)= {cls_sum, box_moments, cov_sum} of kb samples, on the handle's stream; view = BOD_VIEW_HFLIP (checked by
+// stat_view_ready): the record is that of the mirrored frames and is read through the mirror map
+static bod_status stat_fold(bod_handle h, const char* who, const float* cls, const float* box, const float* cov, int kb, int32_t view = BOD_VIEW_IDENTITY) {
     if (kb < 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: a record of %d samples", who, kb);
     if (h->stat_k > (1 << 24) - kb) return h->fail(BOD_ERR_INVALID_ARG, "%s: more than 2^24 samples in one accumulator", who);
     StatMergeArgs m{};
@@ -3455,7 +3497,16 @@ static bod_status stat_fold(bod_handle h, const char* who, const float* cls, con
     if (!cls || !box || (h->cfg.has_covar_head && !cov)) return h->fail(BOD_ERR_INVALID_ARG, "%s: NULL statistics array", who);
     if (cls == m.acc_cls || box == m.acc_box) return h->fail(BOD_ERR_INVALID_ARG, "%s: the source is the accumulator itself", who);
     if (((uintptr_t)cls | (uintptr_t)box | (uintptr_t)m.src_cov) & 15u) return h->fail(BOD_ERR_INVALID_ARG, "%s: statistics arrays must be 16-byte aligned", who);
-    HIPCHK(h, launch_stat_merge(m, h->stream));
+    if (view == BOD_VIEW_HFLIP) {
+        StatMirrorArgs mm{};
+        mm.m = m; mm.A = h->A; mm.K = h->cfg.anchors_per_location; mm.nlev = h->nlev;
+        for (int l = 0; l < h->nlev; ++l) { mm.lvl_off[l] = (int32_t)h->lvl_p0[l] * mm.K; mm.lvl_w[l] = h->lw[l]; }
+        mm.lvl_off[h->nlev] = h->A;
+        mm.u_flip = (float)(h->cfg.image_w - 1);
+        HIPCHK(h, launch_stat_merge_mirror(mm, h->stream));
+    } else {
+        HIPCHK(h, launch_stat_merge(m, h->stream));
+    }
     h->stat_k += kb;
     return BOD_OK;
 }
@@ -3467,20 +3518,27 @@ bod_status bod_stat_reset(bod_handle h) {
     return BOD_OK;
 }
 
-bod_status bod_stat_forward(bod_handle h, const float* images, int32_t on_device, uint64_t seed, uint32_t first_image_id, int32_t sample_base) {
+static bod_status stat_forward_view(bod_handle h, const char* who, const float* images, int32_t on_device, uint64_t seed, uint32_t first_image_id,
+                                    int32_t sample_base, int32_t view) {
     MarkerRange mr_api("bod:stat_forward");
     if (!h) return BOD_ERR_INVALID_ARG;
-    BODCHK(stat_handle(h, "bod_stat_forward"));
+    BODCHK(stat_handle(h, who));
     if (!h->weights_ready) return h->fail(BOD_ERR_NOT_READY, "weights not finalized");
     if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called (the box statistics are those of the decoded boxes)");
     const bod_config& c = h->cfg;
     const int n = c.mc_samples;
     if (sample_base < 0 || sample_base + n > 65535 || (c.mc_ensemble_size > 0 && sample_base + n > c.mc_ensemble_size))
-        return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_forward: sample_base=%d / mc_samples=%d / mc_ensemble_size=%d inconsistent", sample_base, n,
+        return h->fail(BOD_ERR_INVALID_ARG, "%s: sample_base=%d / mc_samples=%d / mc_ensemble_size=%d inconsistent", who, sample_base, n,
                        c.mc_ensemble_size);
-    if (h->stat_k > (1 << 24) - n) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_forward: more than 2^24 samples in one accumulator");
+    if (h->stat_k > (1 << 24) - n) return h->fail(BOD_ERR_INVALID_ARG, "%s: more than 2^24 samples in one accumulator", who);
+    BODCHK(stat_view_ready(h, who, view));
+    if (view == BOD_VIEW_HFLIP && !h->d_mirror) BODCHK(h->dalloc(&h->d_mirror, (size_t)c.batch * c.image_h * c.image_w * 3, false));
     const float* dev = nullptr;
     BODCHK(stage_images(h, images, on_device, &dev));
+    if (view == BOD_VIEW_HFLIP) {                          // the source buffer stays as it is; a ragged upload's factors (kscale_now) stay in force
+        HIPCHK(h, launch_mirror_images(dev, h->d_mirror, c.batch, c.image_h, c.image_w, h->stream));
+        dev = h->d_mirror;
+    }
     h->cur_images = dev;
     const int flavour = h->agg_plan ? FLAVOUR_AGG : FLAVOUR_RAW;
     const int32_t base = c.mc_sample_base;
@@ -3495,7 +3553,16 @@ bod_status bod_stat_forward(bod_handle h, const float* images, int32_t on_device
         r.cls_sum = h->agg[0]; r.box_moments = h->agg[1]; r.cov_sum = c.has_covar_head ? h->agg[2] : nullptr;
         HIPCHK(h, launch_stat_from_raw(r, h->stream));
     }
-    return stat_fold(h, "bod_stat_forward", h->agg[0], h->agg[1], h->agg[2], n);
+    return stat_fold(h, who, h->agg[0], h->agg[1], h->agg[2], n, view);
+}
+
+bod_status bod_stat_forward(bod_handle h, const float* images, int32_t on_device, uint64_t seed, uint32_t first_image_id, int32_t sample_base) {
+    return stat_forward_view(h, "bod_stat_forward", images, on_device, seed, first_image_id, sample_base, BOD_VIEW_IDENTITY);
+}
+
+bod_status bod_stat_forward_view(bod_handle h, const float* images, int32_t on_device, uint64_t seed, uint32_t first_image_id, int32_t sample_base,
+                                 int32_t view) {
+    return stat_forward_view(h, "bod_stat_forward_view", images, on_device, seed, first_image_id, sample_base, view);
 }
 
 bod_status bod_stat_merge_from(bod_handle dst, bod_handle src) {
@@ -3524,6 +3591,15 @@ bod_status bod_stat_merge(bod_handle h, const void* const* ptrs3, int32_t sample
     if (!ptrs3) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_merge: ptrs3 is NULL");
     return stat_fold(h, "bod_stat_merge", static_cast<const float*>(ptrs3[0]), static_cast<const float*>(ptrs3[1]),
                      static_cast<const float*>(ptrs3[2]), samples);
+}
+
+bod_status bod_stat_merge_view(bod_handle h, const void* const* ptrs3, int32_t samples, int32_t view) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(stat_handle(h, "bod_stat_merge_view"));
+    if (!ptrs3) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_merge_view: ptrs3 is NULL");
+    BODCHK(stat_view_ready(h, "bod_stat_merge_view", view));
+    return stat_fold(h, "bod_stat_merge_view", static_cast<const float*>(ptrs3[0]), static_cast<const float*>(ptrs3[1]),
+                     static_cast<const float*>(ptrs3[2]), samples, view);
 }
 
 bod_status bod_stat_device(bod_handle h, void** ptrs3, int32_t* samples) {

@@ -392,6 +392,17 @@ struct StatMergeArgs {
     const float* src_cls; const float* src_box; const float* src_cov;
 };
 hipError_t launch_stat_merge(const StatMergeArgs& a, hipStream_t s);
+// The same fold with the source read through the mirror map of a record (stat_kernels.hip header): horizontal-flip views
+struct StatMirrorArgs {
+    StatMergeArgs m;
+    int32_t A, K, nlev;                                         // anchors per image, anchors per location, pyramid levels (<= 8)
+    int32_t lvl_off[9];                                         // first anchor of every level; lvl_off[nlev] = A
+    int32_t lvl_w[8];                                           // columns of every level
+    float u_flip;                                               // float(image_w - 1): u' = u_flip - u
+};
+hipError_t launch_stat_merge_mirror(const StatMirrorArgs& a, hipStream_t s);
+// out[b,y,x,:] = in[b,y,W-1-x,:], fp32 [B,H,W,3]; in != out
+hipError_t launch_mirror_images(const float* in, float* out, int B, int H, int W, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // Streaming pointwise (1x1) convolution for reductions of <= 256 channels (conv_pointwise.hip); launch_conv_igemm routes eligible

@@ -243,6 +243,63 @@ def merge_statistics_np(a, b, ka, kb, dtype=np.float64):
     return cls, box, cov
 
 
+def mirror_anchor_index(level_hw, K):
+    """partner[a] of every anchor a = off_l + (y * W_l + x) * K + k (the order of ``FpnAnchorGenerator.generate_all``): the anchor
+    at column W_l - 1 - x of the same pyramid row.  ``level_hw``: [(H_l, W_l), ...] (``Engine.levels``).  An involution."""
+    parts, off = [], 0
+    for h, w in level_hw:
+        h, w = int(h), int(w)
+        idx = off + np.arange(h * w * K, dtype=np.int64).reshape(h, w, K)
+        parts.append(idx[:, ::-1, :].reshape(-1))
+        off += h * w * K
+    return np.concatenate(parts)
+
+
+_M2_FLIP = (5, 8, 11)           # box_moments[4 + k] for the stored M2 positions k = 1, 4, 7: (1,0), (2,1), (3,1)
+_COV_FLIP = (8, 6, 2)           # the parameters model.fill_triangular_4 places at (1,0), (2,1), (3,1)
+
+
+def mirror_statistics_np(cls_sum, box_moments, cov_sum, level_hw, K, image_w):
+    """The mirror map of a statistics record on the host, as include/bayesod.h states it: the record [..., A, .] of a forward of
+    the frames mirrored left-right -> the record of the frames as given.  Anchors move to their partner (``mirror_anchor_index``),
+    the ``u`` mean becomes ``(image_w - 1) - u`` (one subtraction in the arrays' dtype), the co-moments with exactly one index
+    equal to 1 and the covariance parameters 8, 6, 2 change sign; everything else is copied.  ``cov_sum`` may be None."""
+    perm = mirror_anchor_index(level_hw, K)
+    if np.shape(box_moments)[-2] != perm.shape[0] or np.shape(cls_sum)[-2] != perm.shape[0]:
+        raise ValueError("the level table holds %d anchors, the record %d" % (perm.shape[0], np.shape(box_moments)[-2]))
+    cls = np.array(np.asarray(cls_sum)[..., perm, :])
+    box = np.array(np.asarray(box_moments)[..., perm, :])
+    box[..., 1] = box.dtype.type(image_w - 1) - box[..., 1]
+    for k in _M2_FLIP:
+        box[..., k] = -box[..., k]
+    cov = None
+    if cov_sum is not None:
+        cov = np.array(np.asarray(cov_sum)[..., perm, :])
+        for k in _COV_FLIP:
+            cov[..., k] = -cov[..., k]
+    return cls, box, cov
+
+
+def anchors_mirror_symmetric(anchors, level_hw, K, image_w, min_level=3):
+    """(ok, first_bad_level): is ``anchors[partner[a]]`` equal to ``(v, float(image_w) - u, h, w)`` of ``anchors[a]`` bit for bit,
+    for every anchor?  This is what a mirrored view needs (``bod_stat_forward_view``); for the FPN grid it holds when image_w is a
+    multiple of 2^max_level.  first_bad_level: the pyramid level (``min_level`` + index) of the first level that fails, else None."""
+    a = np.ascontiguousarray(anchors, dtype=np.float32).reshape(-1, 4)
+    perm = mirror_anchor_index(level_hw, K)
+    if a.shape[0] != perm.shape[0]:
+        raise ValueError("the level table holds %d anchors, got %d" % (perm.shape[0], a.shape[0]))
+    want = a.copy()
+    want[:, 1] = np.float32(image_w) - a[:, 1]
+    same = np.all(a[perm].view(np.uint32) == want.view(np.uint32), axis=1)
+    off = 0
+    for l, (h, w) in enumerate(level_hw):
+        n = int(h) * int(w) * K
+        if not same[off:off + n].all():
+            return False, min_level + l
+        off += n
+    return True, None
+
+
 class StatShardedEngine(object):
     """The sample-sharded mode on statistics: ONE statistics handle per rank computes its n = N / world samples
     (``stat_forward`` with sample base rank * n), one all-gather exchanges the 34-float records, every rank resets and folds

@@ -13,6 +13,7 @@ _KINDS = {"kernel": 0, "bias": 1, "gamma": 2, "beta": 3, "mean": 4, "var": 5}
 # bod_config.precision (include/bayesod.h): bf16 = throughput path; fp32 = exact-fp32 MFMA; bf16x3 = (hi, lo) bf16 pairs with
 # three MFMA products, the 1e-3 end-to-end parity mode on the bf16 matrix pipe
 PRECISIONS = {"bf16": 0, "fp32": 1, "bf16x3": 2, "f16mx": 3, "f16mx4": 4}
+VIEWS = {"identity": _lib.BOD_VIEW_IDENTITY, "hflip": _lib.BOD_VIEW_HFLIP}      # test-time views of a statistics handle
 
 
 def make_config(image_hw, batch=1, mc_samples=10, num_classes=8, anchors_per_location=9, device=0,
@@ -532,26 +533,45 @@ class Engine(object):
         """Empty the accumulator (K = 0)."""
         self._chk(self.lib.bod_stat_reset(self.h))
 
-    def stat_forward(self, images=None, seed=0, first_image_id=0, sample_base=0, image_buffer=None, device_images=None):
+    @staticmethod
+    def _view(view):
+        """'identity' / 'hflip' or 0 / 1 -> BOD_VIEW_*; any other int goes to the library, which refuses it."""
+        if isinstance(view, str):
+            if view not in VIEWS:
+                raise ValueError("view must be one of %s or 0 / 1, got %r" % (sorted(VIEWS), view))
+            return VIEWS[view]
+        return int(view)
+
+    def stat_forward(self, images=None, seed=0, first_image_id=0, sample_base=0, image_buffer=None, device_images=None, view=0):
         """Forward of this handle's n samples as samples ``sample_base .. sample_base + n - 1`` of the dropout streams, reduced to
         the statistics record and folded into the accumulator (``bod_stat_forward``).  images as in forward();
         ``device_images``: the address of a [B,H,W,3] float32 batch already on this device (another handle's image buffer,
-        complete before the call) in place of this handle's own."""
+        complete before the call) in place of this handle's own.  ``view='hflip'`` (or 1): the forward sees the frames mirrored
+        left-right and its record is mapped back to the anchors of the frames as given (``bod_stat_forward_view``)."""
+        v = self._view(view)
         if images is None:
-            ptr = self._device_images(image_buffer) if device_images is None else int(device_images)
-            self._chk(self.lib.bod_stat_forward(self.h, ptr, 1, seed, first_image_id, int(sample_base)))
+            ptr, on_device = (self._device_images(image_buffer) if device_images is None else int(device_images)), 1
         else:
             a = self._img(images)
-            self._chk(self.lib.bod_stat_forward(self.h, a.ctypes.data, 0, seed, first_image_id, int(sample_base)))
+            ptr, on_device = a.ctypes.data, 0
+        if v == _lib.BOD_VIEW_IDENTITY:
+            self._chk(self.lib.bod_stat_forward(self.h, ptr, on_device, seed, first_image_id, int(sample_base)))
+        else:
+            self._chk(self.lib.bod_stat_forward_view(self.h, ptr, on_device, seed, first_image_id, int(sample_base), v))
 
     def stat_merge_from(self, other):
         """Fold ``other``'s accumulator into this one's (``bod_stat_merge_from``); ``other`` is unchanged."""
         self._chk(self.lib.bod_stat_merge_from(self.h, other.h))
 
-    def stat_merge(self, ptrs, samples):
-        """Fold a record of ``samples`` samples given as device addresses (cls_sum, box_moments, cov_sum or None)."""
+    def stat_merge(self, ptrs, samples, view=0):
+        """Fold a record of ``samples`` samples given as device addresses (cls_sum, box_moments, cov_sum or None); ``view='hflip'``:
+        the record is that of a mirrored forward and is mapped back while it is folded (``bod_stat_merge_view``)."""
         p = (C.c_void_p * 3)(*[int(x) if x else None for x in (list(ptrs) + [None])[:3]])
-        self._chk(self.lib.bod_stat_merge(self.h, p, int(samples)))
+        v = self._view(view)
+        if v == _lib.BOD_VIEW_IDENTITY:
+            self._chk(self.lib.bod_stat_merge(self.h, p, int(samples)))
+        else:
+            self._chk(self.lib.bod_stat_merge_view(self.h, p, int(samples), v))
 
     def stat_device_pointers(self):
         """Device addresses [cls_sum [B,A,C], box_moments [B,A,16], cov_sum [B,A,10] or None] of the accumulator."""

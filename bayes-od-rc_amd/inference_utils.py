@@ -187,10 +187,13 @@ class EnsemblePipeline(object):
     a statistics handle of its own (``make_config(mc_statistics=True)``) -- member m, pass p draws the dropout samples
     ``(m * passes + p) * n ..`` -- and the per-anchor statistics (34 floats per anchor, whatever the sample count) are folded
     into member 0's accumulator in member order; posterior, soft-NMS and cluster-and-fuse run there with N = the total.  A list
-    of one model with ``passes = k`` is "N = k * n on one handle".  Same call and return shape as ``BayesOdPipeline``."""
+    of one model with ``passes = k`` is "N = k * n on one handle".  Same call and return shape as ``BayesOdPipeline``.
+    ``views``: the test-time views every pass runs, ``'identity'`` and / or ``'hflip'`` (the frames mirrored left-right on the
+    device, the record mapped back to the anchors of the frames as given while it is folded: ``Engine.stat_forward(view=)``);
+    with V views member m, pass p, view index v draws the samples ``((m * passes + p) * V + v) * n ..``."""
 
     def __init__(self, models, image_hw, batch, bayes_od_config, nms_config, samples_per_member, passes=1, use_full_covar=True,
-                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None):
+                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, views=('identity',)):
         from .engine import Engine, make_config
         models = list(models)
         if not models:
@@ -198,7 +201,10 @@ class EnsemblePipeline(object):
         n, passes = int(samples_per_member), int(passes)
         if n < 1 or passes < 1:
             raise ValueError("samples_per_member and passes must be >= 1")
-        self.total = len(models) * passes * n
+        self.views = [Engine._view(v) for v in ([views] if isinstance(views, (str, int)) else views)]
+        if not self.views:
+            raise ValueError("EnsemblePipeline needs at least one view")
+        self.total = len(models) * passes * len(self.views) * n
         if self.total < 2:
             raise ValueError("bayes_od needs at least 2 samples in all: the sample covariance divides by N-1 "
                              "(inference_utils.py:241-242)")
@@ -253,11 +259,12 @@ class EnsemblePipeline(object):
         for m, eng in enumerate(self.engines):
             eng.stat_reset()
             for p in range(self.passes):
-                base = (m * self.passes + p) * self.n
-                if images is None and m > 0:
-                    eng.stat_forward(None, seed=seed, first_image_id=first_image_id, sample_base=base, device_images=shared)
-                else:
-                    eng.stat_forward(images, seed=seed, first_image_id=first_image_id, sample_base=base)
+                for v, view in enumerate(self.views):
+                    base = ((m * self.passes + p) * len(self.views) + v) * self.n
+                    if images is None and m > 0:
+                        eng.stat_forward(None, seed=seed, first_image_id=first_image_id, sample_base=base, device_images=shared, view=view)
+                    else:
+                        eng.stat_forward(images, seed=seed, first_image_id=first_image_id, sample_base=base, view=view)
         for eng in self.engines[1:]:
             self.engine.stat_merge_from(eng)
         self.engine.stat_posterior(seed=seed, first_image_id=first_image_id)

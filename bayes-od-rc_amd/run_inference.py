@@ -98,10 +98,14 @@ def _ensemble_members(config, args):
 
 def _make_pipeline(model, args, hw, batch, bayes_od_config, nms_config, **kw):
     """BayesOdPipeline of the one model, or -- ``model`` a list (--ensemble) -- EnsemblePipeline with the yaml's
-    mc_dropout_samples per member and --mc_passes passes each."""
-    if isinstance(model, list):
-        return inference_utils.EnsemblePipeline(model, hw, batch, bayes_od_config, nms_config, model[0].mc_dropout_samples,
-                                                passes=int(getattr(args, 'mc_passes', 1) or 1), **kw)
+    mc_dropout_samples per member and --mc_passes passes each.  --tta_flip: every pass runs the frames as given and mirrored
+    left-right; without --ensemble that is a one-member EnsemblePipeline of the one model."""
+    tta = bool(getattr(args, 'tta_flip', False))
+    if isinstance(model, list) or tta:
+        members = model if isinstance(model, list) else [model]
+        return inference_utils.EnsemblePipeline(members, hw, batch, bayes_od_config, nms_config, members[0].mc_dropout_samples,
+                                                passes=int(getattr(args, 'mc_passes', 1) or 1),
+                                                views=('identity', 'hflip') if tta else ('identity',), **kw)
     return inference_utils.BayesOdPipeline(model, hw, batch, bayes_od_config, nms_config, **kw)
 
 
@@ -199,12 +203,19 @@ def main(argv=None):
                     '(default: a batch ends where the source size changes)')
     ap.add_argument('--ensemble', type=str, nargs='+', default=None, help='weight files of an ensemble: every member runs the '
                     'yaml\'s mc_dropout_samples samples and ONE posterior is formed from all of them (overrides --weights)')
-    ap.add_argument('--mc_passes', type=int, default=1, help='with --ensemble: forwards per member (k passes of n samples = k * n '
-                    'samples per member; one weight file with --mc_passes k is N = k * n on one handle)')
+    ap.add_argument('--mc_passes', type=int, default=1, help='with --ensemble or --tta_flip: forwards per member (k passes of n '
+                    'samples = k * n samples per member; one weight file with --mc_passes k is N = k * n on one handle)')
+    ap.add_argument('--tta_flip', action='store_true', help='test-time augmentation: every pass also runs the frames mirrored '
+                    'left-right and its samples enter the same posterior (the network width must be a multiple of 2^max_level)')
     args = ap.parse_args(argv)
     config = config_utils.load_yaml(args.yaml_path)
     config = config_utils.setup(config, args)
-    return test_model(config, args)
+    try:
+        return test_model(config, args)
+    except ValueError as e:
+        if args.tta_flip and 'mirror-symmetric' in str(e):
+            sys.exit(str(e))                  # the library's message for a geometry whose anchors have no mirror partners
+        raise
 
 
 if __name__ == '__main__':

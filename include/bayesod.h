@@ -581,6 +581,32 @@ bod_status bod_stat_set(bod_handle h, const float* cls_sum, const float* box_mom
  * bod_cluster_fuse, bod_get_posterior and bod_get_detections* follow as after bod_posterior.  Needs the anchors. */
 bod_status bod_stat_posterior(bod_handle h, uint64_t seed, uint32_t first_image_id);
 
+/* ---- test-time views of a statistics handle: the same frames mirrored left-right, counted in the SAME accumulator.  A forward
+ * of the mirrored frames yields the record of the mirrored anchors; the fold reads it through the mirror map, which is exact in
+ * fp32.  With K = anchors_per_location and the level table of bod_sizes, anchor a = off_l + (y * W_l + x) * K + k has the partner
+ * a' = off_l + (y * W_l + (W_l - 1 - x)) * K + k, and the result at a' from the record at a is
+ *   cls_sum      copied
+ *   box_moments  mean (v, u, h, w) -> (v, float(image_w - 1) - u, h, w) (bod_augment_boxes' flip: x' = (w-1) - x); M2 entries with
+ *                exactly one index equal to 1 -- stored positions 1, 4 and 7 -- negated; the rest and the pads copied
+ *   cov_sum      parameters 8, 6 and 2 (fill_triangular's (1,0), (2,1), (3,1)) negated: Sigma -> S Sigma S^T, S = diag(1,-1,1,1)
+ * and the merge formula above follows, operation for operation.  A mirrored view needs mirror-symmetric anchors: anchors[a']
+ * must equal (v, float(image_w) - u, h, w) of anchors[a] bit for bit, which for the FPN anchor grid means image_w is a multiple of
+ * 2^max_level (512x512, 720x1280, 384x1280; not KITTI's 384x1248, whose levels 6 and 7 overhang the frame).  Checked on the host
+ * on the first mirrored call after bod_set_anchors; BOD_ERR_INVALID_ARG names the first level that fails. */
+enum { BOD_VIEW_IDENTITY = 0, BOD_VIEW_HFLIP = 1 };
+/* bod_stat_forward of a view of the frames.  view = BOD_VIEW_IDENTITY is bod_stat_forward.  BOD_VIEW_HFLIP mirrors the network-input
+ * frames (host floats, either image buffer, a ragged upload: its per-frame factors stay in force) into a scratch buffer of the
+ * handle -- the source is not modified --, runs the same forward with the same seed / sample_base semantics, reduces to a record
+ * and folds it through the mirror map: K += n.  One stream, no host round trip.  The dropout streams do not know about views:
+ * give the mirrored pass a sample_base of its own for independent masks.  BOD_ERR_INVALID_ARG for any other view and for
+ * anchors that are not mirror-symmetric; after a refusal the accumulator and K are as before. */
+bod_status bod_stat_forward_view(bod_handle h, const float* images, int32_t images_on_device, uint64_t seed, uint32_t first_image_id,
+                                 int32_t sample_base, int32_t view);
+/* bod_stat_merge of a record that is still in the frame of `view` (it arrived from a rank that ran mirrored forwards and did not
+ * fold them).  BOD_VIEW_HFLIP needs the anchors (BOD_ERR_NOT_READY).  bod_stat_merge_from has no view: un-mirror where the
+ * forward ran. */
+bod_status bod_stat_merge_view(bod_handle h, const void* const* ptrs3, int32_t samples, int32_t view);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,3 +191,7 @@ bod_status bod_stat_device(bod_handle h, void** ptrs3, int32_t* samples);
 bod_status bod_stat_get(bod_handle h, float* cls_sum, float* box_moments, float* cov_sum, int32_t* samples);
 bod_status bod_stat_set(bod_handle h, const float* cls_sum, const float* box_moments, const float* cov_sum, int32_t samples);
 bod_status bod_stat_posterior(bod_handle h, uint64_t seed, uint32_t first_image_id);
+enum { BOD_VIEW_IDENTITY = 0, BOD_VIEW_HFLIP = 1 };
+bod_status bod_stat_forward_view(bod_handle h, const float* images, int32_t images_on_device, uint64_t seed, uint32_t first_image_id,
+                                 int32_t sample_base, int32_t view);
+bod_status bod_stat_merge_view(bod_handle h, const void* const* ptrs3, int32_t samples, int32_t view);
