@@ -37,7 +37,7 @@ class BodConfig(C.Structure):
         ("backbone_depth", C.c_int32),
         ("pipeline_overlap", C.c_int32),
         ("mc_statistics", C.c_int32),
-        ("reserved", C.c_int32 * 1),
+        ("covariance_parts", C.c_int32),         # (the last reserved int of include/bayesod.h)
     ]
 
 
@@ -150,6 +150,12 @@ SIGNATURES = {
     "bod_stat_forward_view": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32]),
     "bod_stat_merge_view": (C.c_int, [_H, C.POINTER(C.c_void_p), C.c_int32, C.c_int32]),
     "bod_record_width": (C.c_int32, [_H]),
+    "bod_get_posterior_parts": (C.c_int, [_H, C.c_int32, _F]),
+    "bod_set_posterior_parts": (C.c_int, [_H, C.c_int32, C.c_int32, _F]),
+    "bod_get_detection_parts": (C.c_int, [_H, C.c_int32, _F]),
+    "bod_get_detection_parts_batch": (C.c_int, [_H, _F]),
+    "bod_collect_parts": (C.c_int, [_H, C.c_int32, _F]),
+    "bod_device_detection_parts": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
     "bod_gather_detections": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
     "bod_profile_end": (C.c_int, [_H, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

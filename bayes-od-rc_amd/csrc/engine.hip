@@ -340,6 +340,13 @@ struct bod_context {
     int32_t* nms_sel = nullptr; int32_t* nms_nsel = nullptr;          // = current slot
     float* out_scores = nullptr; float* out_means = nullptr; float* out_covs = nullptr; float* out_counts = nullptr;
     int slot = 0;
+    // Covariance parts (bod_config.covariance_parts; nullptr / empty on every other handle): the per-anchor lower triangles behind
+    // pb.covs, the detections' [B,K,3,16] double-buffered with the records.  parts_ok[img]: the image's rows of `parts` belong to its
+    // posterior (false between bod_set_posterior and bod_set_posterior_parts); det_parts_ok[slot][img]: ... at the slot's cluster-fuse.
+    float* parts = nullptr;
+    float* out_parts_s[2] = {nullptr, nullptr}; float* out_parts = nullptr;
+    std::vector<char> parts_ok, det_parts_ok[2];
+    bool parts_staged[2] = {false, false};              // host_stage[slot] holds the parts of a bod_infer_async ticket
     hipStream_t side = nullptr;
     // ---- CU-partitioned pipeline overlap (bod_config.pipeline_overlap; bod_infer_async only).  The memory-bound front of batch i+1
     // (stem, backbone, FPN) runs on its own stream, masked to the last `ov_front_slots` CU slots of every XCD, while the MFMA-bound
@@ -370,6 +377,7 @@ struct bod_context {
         nms_sel = nms_sel_s[sidx]; nms_nsel = nms_nsel_s[sidx];
         out_scores = out_scores_s[sidx]; out_means = out_means_s[sidx];
         out_covs = out_covs_s[sidx]; out_counts = out_counts_s[sidx];
+        out_parts = out_parts_s[sidx];
     }
     float* iou_scratch = nullptr; int64_t iou_cap = 0;
     float* affinity = nullptr; int affinity_img = -1;   // bod_set_affinity: centre columns of a caller-supplied affinity matrix (one-shot)
@@ -1362,9 +1370,15 @@ bod_status alloc_post(bod_context* h) {
         BODCHK(h->dalloc(&h->out_means_s[sidx], BK * 4));
         BODCHK(h->dalloc(&h->out_covs_s[sidx], BK * 16));
         BODCHK(h->dalloc(&h->out_counts_s[sidx], BK * c.num_classes));
-        const size_t stage_bytes = ((size_t)c.batch + BK * (2 * (size_t)c.num_classes + 20)) * 4;
+        if (c.covariance_parts) BODCHK(h->dalloc(&h->out_parts_s[sidx], BK * 48));
+        const size_t stage_bytes = ((size_t)c.batch + BK * (2 * (size_t)c.num_classes + 20 + (c.covariance_parts ? 48 : 0))) * 4;
         if (hipHostMalloc(reinterpret_cast<void**>(&h->host_stage[sidx]), stage_bytes, hipHostMallocDefault) != hipSuccess)
             return h->fail(BOD_ERR_OOM, "pinned host staging buffer (%zu bytes)", stage_bytes);
+    }
+    if (c.covariance_parts) {
+        BODCHK(h->dalloc(&h->parts, BA * BOD_PARTS_TRI));
+        h->parts_ok.assign((size_t)c.batch, 0);
+        for (int sidx = 0; sidx < 2; ++sidx) h->det_parts_ok[sidx].assign((size_t)c.batch, 0);
     }
     h->select_slot(0);
     BODCHK(h->dalloc(&h->d_images, (size_t)c.batch * c.image_h * c.image_w * 3));
@@ -1645,6 +1659,7 @@ bod_status run_posterior(bod_context* h, uint64_t seed, uint32_t first_image) {
         HIPCHK(h, hipEventRecord(e0, h->stream));
     }
     HIPCHK(h, keep_done ? launch_posterior_fuse(pc, pb, h->stream) : launch_posterior(pc, pb, h->stream));
+    if (h->parts) { HIPCHK(h, launch_posterior_parts(pc, pb, h->parts, h->stream)); std::fill(h->parts_ok.begin(), h->parts_ok.end(), 1); }
     if (h->cfg.ranking_method == BOD_RANK_JOINT_ENTROPY && h->cfg.gaussian_isotropic && h->cfg.dirichlet_non_informative)
         HIPCHK(h, launch_joint_entropy_rank(pc, pb, h->stream));
     if (h->profiling) { HIPCHK(h, hipEventRecord(e1, h->stream)); h->ev_post.emplace_back(e0, e1); }
@@ -1661,6 +1676,10 @@ bod_status run_validation_post(bod_context* h) {
     PostBuffers pb = h->pb;
     pb.cls = h->raw[0]; pb.box = h->raw[1]; pb.cov = h->raw[2]; pb.anchors = h->d_anchors;
     HIPCHK(h, launch_validation_post(pc, pb, h->stream));
+    if (h->parts) {                                   // covs = 0: so are the three terms
+        HIPCHK(h, hipMemsetAsync(h->parts, 0, (size_t)h->cfg.batch * h->A * BOD_PARTS_TRI * sizeof(float), h->stream));
+        std::fill(h->parts_ok.begin(), h->parts_ok.end(), 1);
+    }
     h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;
     return BOD_OK;
 }
@@ -1689,6 +1708,7 @@ bod_status run_cluster(bod_context* h, hipStream_t st) {
     h->affinity_img = -1;                         // consumed by this call
     a.out_scores = h->out_scores; a.out_means = h->out_means; a.out_covs = h->out_covs; a.out_counts = h->out_counts;
     HIPCHK(h, launch_cluster_fuse(a, st));
+    if (h->parts) { HIPCHK(h, launch_cluster_parts(a, h->parts, h->out_parts, st)); h->det_parts_ok[h->slot] = h->parts_ok; }
     h->cluster_done = true;
     return BOD_OK;
 }
@@ -1785,6 +1805,9 @@ bod_status bod_create(const bod_config* cfg, bod_handle* out) {
     if (c.mc_statistics && (c.training || c.pipeline_overlap))
         return bail(h->fail(BOD_ERR_INVALID_ARG, "mc_statistics: statistics handles are inference handles on one stream (%s = 1 refused)",
                             c.training ? "training" : "pipeline_overlap"));
+    if (c.covariance_parts != 0 && c.covariance_parts != 1) return bail(h->fail(BOD_ERR_INVALID_ARG, "covariance_parts must be 0 or 1, got %d", c.covariance_parts));
+    if (c.covariance_parts && c.training)
+        return bail(h->fail(BOD_ERR_INVALID_ARG, "covariance_parts: the parts belong to inference and statistics handles (training = 1 refused)"));
     h->es = c.precision == BOD_PRECISION_BF16 ? 2 : 4;
     h->split = c.precision == BOD_PRECISION_BF16X3 || c.precision == BOD_PRECISION_F16MX || c.precision == BOD_PRECISION_F16MX4;
     h->mx = c.precision == BOD_PRECISION_F16MX ? 1 : c.precision == BOD_PRECISION_F16MX4 ? 2 : 0;
@@ -1919,7 +1942,7 @@ bod_status bod_update_config(bod_handle h, const bod_config* cfg) {
         cfg->mc_samples != o.mc_samples || cfg->num_classes != o.num_classes ||
         cfg->anchors_per_location != o.anchors_per_location || cfg->min_level != o.min_level ||
         cfg->max_level != o.max_level || cfg->has_covar_head != o.has_covar_head || cfg->dropout_rate != o.dropout_rate ||
-        cfg->precision != o.precision || cfg->training != o.training || cfg->backbone_depth != o.backbone_depth || cfg->pipeline_overlap != o.pipeline_overlap || cfg->mc_statistics != o.mc_statistics || (std::max(cfg->mc_ensemble_size, cfg->mc_samples) > 1) != (std::max(o.mc_ensemble_size, o.mc_samples) > 1))
+        cfg->precision != o.precision || cfg->training != o.training || cfg->backbone_depth != o.backbone_depth || cfg->pipeline_overlap != o.pipeline_overlap || cfg->mc_statistics != o.mc_statistics || cfg->covariance_parts != o.covariance_parts || (std::max(cfg->mc_ensemble_size, cfg->mc_samples) > 1) != (std::max(o.mc_ensemble_size, o.mc_samples) > 1))
         return h->fail(BOD_ERR_INVALID_ARG, "bod_update_config: geometry / model fields cannot change on a live handle");
     if (cfg->nms_max_output_size != o.nms_max_output_size)
         return h->fail(BOD_ERR_INVALID_ARG, "bod_update_config: nms_max_output_size sizes device buffers and cannot change");
@@ -2552,6 +2575,56 @@ bod_status bod_set_posterior(bod_handle h, int32_t img, int32_t m, const float* 
     HIPCHK(h, hipMemcpyAsync(h->pb.num_kept + img, &m, 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;
+    if (h->parts) h->parts_ok[img] = 0;               // the rows' parts are the previous posterior's until bod_set_posterior_parts
+    return BOD_OK;
+}
+
+static bod_status parts_handle(bod_handle h, const char* who) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    if (!h->parts) return h->fail(BOD_ERR_INVALID_ARG, "%s: the handle was created without bod_config.covariance_parts", who);
+    return BOD_OK;
+}
+
+// lower triangle rows [m][30] (kernels.h) <-> the ABI's [m][3][16]
+static void parts_expand(const float* tri, size_t m, float* full) {
+    for (size_t i = 0; i < m * 3; ++i) {
+        int t = 0;
+        for (int r = 0; r < 4; ++r)
+            for (int q = 0; q <= r; ++q) { full[i * 16 + r * 4 + q] = full[i * 16 + q * 4 + r] = tri[i * 10 + t]; ++t; }
+    }
+}
+
+bod_status bod_get_posterior_parts(bod_handle h, int32_t img, float* parts) {
+    BODCHK(parts_handle(h, "bod_get_posterior_parts"));
+    BODCHK(join_overlap(h));
+    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
+    int32_t m = 0;
+    BODCHK(image_m(h, img, &m));
+    if (!h->parts_ok[img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_posterior_parts: image %d was injected with bod_set_posterior; bod_set_posterior_parts has not followed", img);
+    if (!parts || m == 0) return BOD_OK;
+    std::vector<float> tri((size_t)m * BOD_PARTS_TRI);
+    BODCHK(d2h(h, tri.data(), h->parts + (size_t)img * h->A * BOD_PARTS_TRI, tri.size()));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    parts_expand(tri.data(), (size_t)m, parts);
+    return BOD_OK;
+}
+
+bod_status bod_set_posterior_parts(bod_handle h, int32_t img, int32_t m, const float* parts) {
+    BODCHK(parts_handle(h, "bod_set_posterior_parts"));
+    BODCHK(join_overlap(h));
+    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior / bod_set_posterior has not run");
+    int32_t mm = 0;
+    BODCHK(image_m(h, img, &mm));
+    if (m != mm || (m > 0 && !parts)) return h->fail(BOD_ERR_INVALID_ARG, "bod_set_posterior_parts: got %d rows, image %d has %d", m, img, mm);
+    std::vector<float> tri((size_t)m * BOD_PARTS_TRI);
+    for (size_t i = 0; i < (size_t)m * 3; ++i) {
+        int t = 0;
+        for (int r = 0; r < 4; ++r)
+            for (int q = 0; q <= r; ++q) tri[i * 10 + t++] = parts[i * 16 + r * 4 + q];
+    }
+    if (m > 0) HIPCHK(h, hipMemcpyAsync(h->parts + (size_t)img * h->A * BOD_PARTS_TRI, tri.data(), tri.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->parts_ok[img] = 1; h->cluster_done = false;
     return BOD_OK;
 }
 
@@ -2673,6 +2746,38 @@ bod_status bod_get_detections_batch(bod_handle h, int32_t* num, float* scores, f
     return BOD_OK;
 }
 
+bod_status bod_get_detection_parts(bod_handle h, int32_t img, float* parts) {
+    BODCHK(parts_handle(h, "bod_get_detection_parts"));
+    BODCHK(join_overlap(h));
+    if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+    if (img < 0 || img >= h->cfg.batch) return h->fail(BOD_ERR_INVALID_ARG, "image index out of range");
+    if (!h->det_parts_ok[h->slot][img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_parts: image %d was fused without its posterior's parts (bod_set_posterior_parts)", img);
+    int32_t num = 0;
+    HIPCHK(h, hipMemcpyAsync(&num, h->nms_nsel + img, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    BODCHK(d2h(h, parts, h->out_parts + (size_t)img * h->cfg.nms_max_output_size * 48, (size_t)num * 48));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BOD_OK;
+}
+
+bod_status bod_get_detection_parts_batch(bod_handle h, float* parts) {
+    BODCHK(parts_handle(h, "bod_get_detection_parts_batch"));
+    BODCHK(join_overlap(h));
+    if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+    for (int img = 0; img < h->cfg.batch; ++img)
+        if (!h->det_parts_ok[h->slot][img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_parts_batch: image %d was fused without its posterior's parts (bod_set_posterior_parts)", img);
+    BODCHK(d2h(h, parts, h->out_parts, (size_t)h->cfg.batch * h->cfg.nms_max_output_size * 48));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BOD_OK;
+}
+
+bod_status bod_device_detection_parts(bod_handle h, int32_t sidx, void** p) {
+    BODCHK(parts_handle(h, "bod_device_detection_parts"));
+    if (!p || sidx < 0 || sidx > 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_device_detection_parts: slot %d / NULL", sidx);
+    *p = h->out_parts_s[sidx];
+    return BOD_OK;
+}
+
 bod_status bod_device_raw(bod_handle h, void** p, int32_t mark_ready) {
     if (!h || !p) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
@@ -2757,7 +2862,8 @@ bod_status bod_infer_async(bod_handle h, const float* images, int32_t on_device,
         HIPCHK(h, hipMemcpyAsync(hs, h->out_scores_s[sidx], BK * C * 4, hipMemcpyDeviceToHost, sd)); hs += BK * C * 4;
         HIPCHK(h, hipMemcpyAsync(hs, h->out_means_s[sidx], BK * 16, hipMemcpyDeviceToHost, sd)); hs += BK * 16;
         HIPCHK(h, hipMemcpyAsync(hs, h->out_covs_s[sidx], BK * 64, hipMemcpyDeviceToHost, sd)); hs += BK * 64;
-        HIPCHK(h, hipMemcpyAsync(hs, h->out_counts_s[sidx], BK * C * 4, hipMemcpyDeviceToHost, sd));
+        HIPCHK(h, hipMemcpyAsync(hs, h->out_counts_s[sidx], BK * C * 4, hipMemcpyDeviceToHost, sd)); hs += BK * C * 4;
+        if (h->parts) { HIPCHK(h, hipMemcpyAsync(hs, h->out_parts_s[sidx], BK * 48 * 4, hipMemcpyDeviceToHost, sd)); h->parts_staged[sidx] = true; }
     }
     HIPCHK(h, hipEventRecord(h->ev_done[sidx], sd));
     h->done_stream[sidx] = sd;
@@ -2783,6 +2889,15 @@ bod_status bod_collect(bod_handle h, int32_t sidx, int32_t* num, float* scores, 
     hs += BK * 64;
     if (counts) std::memcpy(counts, hs, BK * C * 4);
     h->side_pending[sidx] = false;
+    return BOD_OK;
+}
+
+bod_status bod_collect_parts(bod_handle h, int32_t sidx, float* parts) {
+    BODCHK(parts_handle(h, "bod_collect_parts"));
+    if (sidx < 0 || sidx > 1 || !h->parts_staged[sidx]) return h->fail(BOD_ERR_NOT_READY, "bod_collect_parts: slot %d holds no batch of bod_infer_async", sidx);
+    const size_t B = (size_t)h->cfg.batch, BK = B * h->cfg.nms_max_output_size, C = h->cfg.num_classes;
+    HIPCHK(h, hipEventSynchronize(h->ev_done[sidx]));
+    if (parts) std::memcpy(parts, h->host_stage[sidx] + (B + BK * (2 * C + 20)) * 4, BK * 48 * 4);
     return BOD_OK;
 }
 
@@ -3344,7 +3459,7 @@ Rccl& rccl() { static Rccl r; return r; }
 }  // namespace
 }  // extern "C++"
 
-int32_t bod_record_width(bod_handle h) { return h ? 21 + 2 * h->cfg.num_classes : 0; }
+int32_t bod_record_width(bod_handle h) { return h ? 21 + 2 * h->cfg.num_classes + (h->parts ? 48 : 0) : 0; }
 
 bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, int32_t world, int32_t rank, int32_t root,
                                  float* gathered_host, float** gathered_device) {
@@ -3355,7 +3470,7 @@ bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, in
     if (!nccl_comm && world != 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_gather_detections: %d ranks need an ncclComm_t", world);
     if (rank != root && (gathered_host || gathered_device)) return h->fail(BOD_ERR_INVALID_ARG, "bod_gather_detections: only the root receives");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int B = h->cfg.batch, K = h->cfg.nms_max_output_size, C = h->cfg.num_classes, W = 21 + 2 * C;
+    const int B = h->cfg.batch, K = h->cfg.nms_max_output_size, C = h->cfg.num_classes, W = bod_record_width(h);
     const size_t block = (size_t)B * K * W;
     // where the records are and which stream finished them
     int sidx = slot;
@@ -3377,6 +3492,8 @@ bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, in
     } else if (slot > 1 || !h->side_pending[slot]) {
         return h->fail(BOD_ERR_NOT_READY, "bod_gather_detections: slot %d has no pending batch", slot);
     }
+    for (int img = 0; h->parts && img < B; ++img)
+        if (!h->det_parts_ok[sidx][img]) return h->fail(BOD_ERR_NOT_READY, "bod_gather_detections: image %d was fused without its posterior's parts (bod_set_posterior_parts)", img);
     if (!h->rec_send && hipMalloc(reinterpret_cast<void**>(&h->rec_send), block * 4) != hipSuccess)
         return h->fail(BOD_ERR_OOM, "bod_gather_detections: %zu bytes", block * 4);
     // rec_send / rec_recv are shared by the ticket gathers (side stream) and the synchronous form (main stream): a gather that goes to
@@ -3384,8 +3501,12 @@ bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, in
     if (h->ev_gather && h->gather_stream && h->gather_stream != st) HIPCHK(h, hipStreamWaitEvent(st, h->ev_gather, 0));
     // (on the side stream: behind the slot's event; on the records' own stream the wait is a no-op)
     if (slot >= 0) HIPCHK(h, hipStreamWaitEvent(st, h->ev_done[slot], 0));
-    HIPCHK(h, launch_pack_records(h->nms_nsel_s[sidx], h->out_scores_s[sidx], h->out_means_s[sidx], h->out_covs_s[sidx],
-                                  h->out_counts_s[sidx], h->rec_send, B, K, C, st));
+    if (h->parts)
+        HIPCHK(h, launch_pack_records_parts(h->nms_nsel_s[sidx], h->out_scores_s[sidx], h->out_means_s[sidx], h->out_covs_s[sidx],
+                                            h->out_counts_s[sidx], h->out_parts_s[sidx], h->rec_send, B, K, C, st));
+    else
+        HIPCHK(h, launch_pack_records(h->nms_nsel_s[sidx], h->out_scores_s[sidx], h->out_means_s[sidx], h->out_covs_s[sidx],
+                                      h->out_counts_s[sidx], h->rec_send, B, K, C, st));
     float* recv = nullptr;
     if (rank == root) {
         if (world == 1 && !nccl_comm) recv = h->rec_send;
@@ -3653,6 +3774,7 @@ bod_status bod_stat_posterior(bod_handle h, uint64_t seed, uint32_t first_image_
     pb.agg_cls = h->stat_acc[0]; pb.agg_box = h->stat_acc[1]; pb.agg_cov = h->stat_acc[2];
     h->keep_ready = false;                               // the keep flags are rewritten
     HIPCHK(h, launch_posterior(pc, pb, h->stream));
+    if (h->parts) { HIPCHK(h, launch_posterior_parts(pc, pb, h->parts, h->stream)); std::fill(h->parts_ok.begin(), h->parts_ok.end(), 1); }
     if (h->cfg.ranking_method == BOD_RANK_JOINT_ENTROPY && h->cfg.gaussian_isotropic && h->cfg.dirichlet_non_informative)
         HIPCHK(h, launch_joint_entropy_rank(pc, pb, h->stream));
     h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;

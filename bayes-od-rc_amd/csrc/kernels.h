@@ -281,9 +281,20 @@ struct ClusterArgs {
 };
 hipError_t launch_cluster_fuse(const ClusterArgs& a, hipStream_t s);
 hipError_t launch_iou_matrix(const float* corners, int M, float* out, hipStream_t s);
+// Covariance parts (bod_config.covariance_parts): every covariance the two fusion steps store, split into what the fused
+// mean inherits from the epistemic noise, from the aleatoric noise and from the prior -- three symmetric 4x4 terms that sum to it.
+//   launch_posterior_parts  behind post_fuse_kernel, one thread per kept slot: parts [B,A,30] = the three lower triangles (row by row:
+//                           00 10 11 20 21 22 30 31 32 33) of epi, ale, pri; writes nothing else
+//   launch_cluster_parts    beside cluster_fuse_kernel (same ClusterArgs, same membership test): out_parts [B,max_out,3,16]
+#define BOD_PARTS_TRI 30
+hipError_t launch_posterior_parts(const PostCfg& c, const PostBuffers& b, float* parts, hipStream_t s);
+hipError_t launch_cluster_parts(const ClusterArgs& a, const float* parts, float* out_parts, hipStream_t s);
 // detection records [B][K][1 + 4 + 16 + 2C] of the multi-GPU gather (zero rows beyond num[b])
 hipError_t launch_pack_records(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
                                float* rec, int B, int K, int C, hipStream_t s);
+// the same rows with the three covariance parts appended behind the counts: [B][K][1 + 4 + 16 + 2C + 48]
+hipError_t launch_pack_records_parts(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
+                                     const float* parts, float* rec, int B, int K, int C, hipStream_t s);
 
 struct PreprocArgs {
     const uint8_t* src;        // [B, sh, sw, 3] uint8 RGB

@@ -560,6 +560,207 @@ hipError_t launch_posterior(const PostCfg& c, const PostBuffers& b, hipStream_t 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Covariance parts, per kept anchor (bod_config.covariance_parts; kernels.h).  post_fuse_anchor mixes
+// lik = (10 A + E) / 11 and fuses the prior iso_var * I: P = (lik^-1 + I / iso_var)^-1.  The posterior mean is linear in the
+// likelihood's mean with gain G = P lik^-1 = (I + lik / iso_var)^-1, so P = G (E / 11) G^T + G (10 A / 11) G^T + P P / iso_var exactly.
+// This kernel runs behind post_fuse_kernel on parts handles only: it rebuilds E and A from the inputs post_fuse_anchor read, with
+// its operations in its order (the two blocks below restate that function's; it is left as it was, so the default handle's bits
+// cannot move) and writes the three lower triangles.
+// ------------------------------------------------------------------------------------------------
+// lower triangle of G X G^T (X symmetric) scaled like the covariance: out[t] = sc_i * (G X G^T)_ij * sc_j
+__device__ __forceinline__ void parts_congruence(const Mat4& g, const Mat4& x, const float sc[4], float* __restrict__ out) {
+    Mat4 t;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s += g.m[i][k] * x.m[k][j];
+            t.m[i][j] = s;
+        }
+    int q = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s += t.m[i][k] * g.m[j][k];
+            out[q++] = sc[i] * s * sc[j];
+        }
+}
+
+__global__ __launch_bounds__(POST_BLOCK) void post_parts_kernel(PostCfg c, PostBuffers pb, float* __restrict__ parts) {
+    const int b = blockIdx.y;
+    const int m = pb.num_kept[b];
+    for (int slot = blockIdx.x * POST_BLOCK + threadIdx.x; slot < m; slot += gridDim.x * POST_BLOCK) {
+        const size_t o = (size_t)b * c.A + slot;
+        const int a = pb.anchor_index[o];
+        const float4 anc = reinterpret_cast<const float4*>(pb.anchors)[a];
+        // ---- E: post_fuse_anchor's epistemic block
+        float mu[4] = {0.f, 0.f, 0.f, 0.f};
+        Mat4 epi;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) epi.m[i][j] = 0.f;
+        const int n_raw = c.aggregated ? 0 : c.N;
+        if (c.aggregated) {
+            const float4* ab = reinterpret_cast<const float4*>(pb.agg_box) + ((size_t)b * c.A + a) * 4;
+            const float4 q0 = ab[1], q1 = ab[2], q2 = ab[3];
+            epi.m[0][0] = q0.x; epi.m[1][0] = q0.y; epi.m[1][1] = q0.z; epi.m[2][0] = q0.w;
+            epi.m[2][1] = q1.x; epi.m[2][2] = q1.y; epi.m[3][0] = q1.z; epi.m[3][1] = q1.w;
+            epi.m[3][2] = q2.x; epi.m[3][3] = q2.y;
+        }
+        for (int n = 0; n < n_raw; ++n) {
+            const float4 t = reinterpret_cast<const float4*>(pb.box)[((size_t)b * c.N + n) * c.A + a];
+            float bx[4];
+            decode_box(anc, t, bx);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) mu[i] += bx[i];
+        }
+        if (!c.aggregated) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) mu[i] = mu[i] / (float)c.N;
+        }
+        for (int n = 0; n < n_raw; ++n) {
+            const float4 t = reinterpret_cast<const float4*>(pb.box)[((size_t)b * c.N + n) * c.A + a];
+            float bx[4];
+            decode_box(anc, t, bx);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) bx[i] -= mu[i];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j <= i; ++j) epi.m[i][j] += bx[i] * bx[j];
+        }
+        const float nm1 = (float)c.N - 1.0f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) { epi.m[i][j] = epi.m[i][j] / nm1; epi.m[j][i] = epi.m[i][j]; }
+        // ---- A: post_fuse_anchor's aleatoric block
+        Mat4 al;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) al.m[i][j] = 0.f;
+        if (c.has_covar) {
+            float x[10];
+#pragma unroll
+            for (int q = 0; q < 10; ++q) x[q] = 0.f;
+            if (c.aggregated) {
+                const float* p = pb.agg_cov + ((size_t)b * c.A + a) * 10;
+#pragma unroll
+                for (int q = 0; q < 5; ++q) {
+                    const float2 t = reinterpret_cast<const float2*>(p)[q];
+                    x[2 * q] = t.x; x[2 * q + 1] = t.y;
+                }
+            }
+            for (int n = 0; n < n_raw; ++n) {
+                const float* p = pb.cov + (((size_t)b * c.N + n) * c.A + a) * 10;
+#pragma unroll
+                for (int q = 0; q < 5; ++q) {
+                    const float2 t = reinterpret_cast<const float2*>(p)[q];
+                    x[2 * q] += t.x; x[2 * q + 1] += t.y;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 10; ++q) x[q] = x[q] / (float)c.N;
+            const float d0 = expf(x[4]), d1 = expf(x[9]), d2 = expf(x[5]), d3 = expf(x[0]);
+            if (c.use_full_covar) {
+                const float l10 = x[8], l20 = x[7], l21 = x[6], l30 = x[3], l31 = x[2], l32 = x[1];
+                float li[4][4];
+                li[0][0] = 1.f; li[0][1] = 0.f; li[0][2] = 0.f; li[0][3] = 0.f;
+                li[1][0] = -l10; li[1][1] = 1.f; li[1][2] = 0.f; li[1][3] = 0.f;
+                li[2][0] = -(l20 * 1.f + l21 * li[1][0]); li[2][1] = -l21; li[2][2] = 1.f; li[2][3] = 0.f;
+                li[3][0] = -(l30 * 1.f + l31 * li[1][0] + l32 * li[2][0]);
+                li[3][1] = -(l31 * 1.f + l32 * li[2][1]);
+                li[3][2] = -l32; li[3][3] = 1.f;
+                const float d[4] = {d0, d1, d2, d3};
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j <= i; ++j) {
+                        float s = 0.f;
+#pragma unroll
+                        for (int k = 0; k <= j; ++k) s += li[i][k] * d[k] * li[j][k];
+                        al.m[i][j] = s; al.m[j][i] = s;
+                    }
+            } else {
+                al.m[0][0] = d0; al.m[1][1] = d1; al.m[2][2] = d2; al.m[3][3] = d3;
+            }
+        }
+        // ---- the two likelihood terms: lik = e + a
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { epi.m[i][j] = epi.m[i][j] / 11.0f; al.m[i][j] = 10.0f * al.m[i][j] / 11.0f; }
+        // ---- the gain G = P lik^-1 = (I + lik / iso_var)^-1 and P = G lik.  I + lik / iso_var is SPD with every eigenvalue >= 1, so this
+        // inverse is well conditioned whatever lik is -- also where lik^-1, and with it the stored P, is beyond fp32 (a rank-deficient
+        // sample covariance without the covariance head) -- which is why P is formed here and not read back (nor unscaled on KITTI)
+        float sc[4] = {1.f, 1.f, 1.f, 1.f};
+        if (c.kitti_sh > 0.f) {
+            float ksh = c.kitti_sh, ksw = c.kitti_sw;
+            if (c.kitti_frame) { ksh = c.kitti_frame[2 * b]; ksw = c.kitti_frame[2 * b + 1]; }
+            sc[0] = ksh; sc[1] = ksw; sc[2] = ksh; sc[3] = ksw;
+        }
+        Mat4 g, pp;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { g.m[i][j] = i == j ? 1.f : 0.f; pp.m[i][j] = 0.f; }
+        if (c.gaussian_iso) {
+            Mat4 lik, t;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { lik.m[i][j] = epi.m[i][j] + al.m[i][j]; t.m[i][j] = g.m[i][j] + lik.m[i][j] / c.iso_var; }
+            g = inv_spd4(t);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s += g.m[i][k] * lik.m[k][j];
+                    t.m[i][j] = s;                                  // P
+                }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j <= i; ++j) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s += t.m[i][k] * t.m[j][k];
+                    pp.m[i][j] = s / c.iso_var; pp.m[j][i] = pp.m[i][j];
+                }
+        }
+        float* out = parts + o * BOD_PARTS_TRI;
+        parts_congruence(g, epi, sc, out);
+        if (c.has_covar) {
+            parts_congruence(g, al, sc, out + 10);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 10; ++q) out[10 + q] = 0.f;
+        }
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) out[20 + q++] = sc[i] * pp.m[i][j] * sc[j];
+    }
+}
+
+hipError_t launch_posterior_parts(const PostCfg& c, const PostBuffers& b, float* parts, hipStream_t s) {
+    if (!parts) return hipErrorInvalidValue;
+    const int nblocks = (c.A + POST_BLOCK - 1) / POST_BLOCK;
+    hipLaunchKernelGGL(post_parts_kernel, dim3(std::min(nblocks, POST_FUSE_BLOCKS), c.B), dim3(POST_BLOCK), 0, s, c, b, parts);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // Sparse tail and halo row tables (kernels.h SparseTailArgs, sparse_tables.h).  One workgroup per image:
 //   1. the pixel flags go to LDS, one phase per flag (kept, tail, 3x3 dilation, halo), all threads;
 //   2. every thread counts the run starts of both tables in its contiguous share of the pixels, a block scan places them, and the
@@ -1251,6 +1452,104 @@ hipError_t launch_cluster_fuse(const ClusterArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// Covariance parts of the fused detections (kernels.h): with P_i the precision of member i and F = (sum P_i)^-1 the
+// fused mean is F sum P_i mu_i, linear in the members' means, so each part X of the fused covariance is 70 F (sum P_i X_i P_i) F
+// and the three sum to 70 F, the covariance cluster_fuse_kernel stores.  Same grid, same membership expression and the same
+// reduction as that kernel: wave butterflies, one LDS exchange, thread 0 finishes.
+__global__ __launch_bounds__(CL_BLOCK) void cluster_parts_kernel(ClusterArgs a, const float* __restrict__ parts, float* __restrict__ out_parts) {
+    __shared__ float red[4 * 40];
+    const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    if (k >= a.num_selected[b]) return;
+    const int M = a.num_kept[b];
+    const int centre = a.selected[(size_t)b * a.max_out + k];
+    const size_t base = (size_t)b * a.A;
+    const float4* boxes = reinterpret_cast<const float4*>(a.corners) + base;
+    const float4 cbox = boxes[centre];
+    float acc[40];                                   // sum P_i X_i P_i: 3 x 10 (lower triangles), then sum P_i: 10
+#pragma unroll
+    for (int q = 0; q < 40; ++q) acc[q] = 0.f;
+    const float* aff = (a.affinity && b == a.affinity_img) ? a.affinity + (size_t)k * a.A : nullptr;
+    for (int i = tid; i < M; i += CL_BLOCK) {
+        if (!((aff ? aff[i] : iou_plus1(boxes[i], cbox)) > a.thr)) continue;
+        Mat4 cv;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) cv.m[r][q] = a.covs[(base + i) * 16 + r * 4 + q];
+        const Mat4 pr = inv_spd4(cv);
+        {
+            int t = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int q = 0; q <= r; ++q) acc[30 + t++] += pr.m[r][q];
+        }
+        const float* x = parts + (base + i) * BOD_PARTS_TRI;
+        const float one[4] = {1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+        for (int part = 0; part < 3; ++part) {
+            Mat4 xm;
+            int t = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int q = 0; q <= r; ++q) { xm.m[r][q] = x[part * 10 + t]; xm.m[q][r] = xm.m[r][q]; ++t; }
+            float pxp[10];
+            parts_congruence(pr, xm, one, pxp);
+#pragma unroll
+            for (int q = 0; q < 10; ++q) acc[part * 10 + q] += pxp[q];
+        }
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int q = 0; q < 40; ++q) {
+        float v = acc[q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) red[wave * 40 + q] = v;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+#pragma unroll
+    for (int q = 0; q < 40; ++q) acc[q] = (red[q] + red[40 + q]) + (red[80 + q] + red[120 + q]);
+    Mat4 ps;
+    {
+        int t = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int q = 0; q <= r; ++q) { ps.m[r][q] = acc[30 + t]; ps.m[q][r] = acc[30 + t]; ++t; }
+    }
+    const Mat4 fc = inv_spd4(ps);
+    const float one[4] = {1.f, 1.f, 1.f, 1.f};
+    float* out = out_parts + ((size_t)b * a.max_out + k) * 48;
+#pragma unroll
+    for (int part = 0; part < 3; ++part) {
+        Mat4 sm;
+        int t = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int q = 0; q <= r; ++q) { sm.m[r][q] = acc[part * 10 + t]; sm.m[q][r] = sm.m[r][q]; ++t; }
+        float fsf[10];
+        parts_congruence(fc, sm, one, fsf);
+        t = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int q = 0; q <= r; ++q) {
+                const float v = fsf[t++] * 70.0f;
+                out[part * 16 + r * 4 + q] = v; out[part * 16 + q * 4 + r] = v;
+            }
+    }
+}
+
+hipError_t launch_cluster_parts(const ClusterArgs& a, const float* parts, float* out_parts, hipStream_t s) {
+    if (!parts || !out_parts) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cluster_parts_kernel, dim3(a.max_out, a.B), dim3(CL_BLOCK), 0, s, a, parts, out_parts);
+    return hipGetLastError();
+}
+
 __global__ void iou_matrix_kernel(const float4* boxes, int M, float* out) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int i = blockIdx.y;
@@ -1287,6 +1586,39 @@ hipError_t launch_pack_records(const int32_t* num, const float* scores, const fl
     const long n = (long)B * K * (21 + 2 * C);
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(pack_records_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, num, scores, means, covs, counts, rec, B, K, C);
+    return hipGetLastError();
+}
+
+// The record rows of a covariance_parts handle: the same row with the 48 floats of the three parts behind the counts
+__global__ __launch_bounds__(256) void pack_records_parts_kernel(const int32_t* __restrict__ num, const float* __restrict__ scores,
+                                                                 const float* __restrict__ means, const float* __restrict__ covs,
+                                                                 const float* __restrict__ counts, const float* __restrict__ parts,
+                                                                 float* __restrict__ rec, int B, int K, int C) {
+    const int W0 = 21 + 2 * C, W = W0 + 48;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * K * W) return;
+    const int w = (int)(i % W);
+    const long row = i / W;                      // b * K + k
+    const int b = (int)(row / K), k = (int)(row % K);
+    float v = 0.f;
+    if (k < num[b]) {
+        if (w == 0) v = 1.f;
+        else if (w < 5) v = means[row * 4 + (w - 1)];
+        else if (w < 21) v = covs[row * 16 + (w - 5)];
+        else if (w < 21 + C) v = scores[row * C + (w - 21)];
+        else if (w < W0) v = counts[row * C + (w - 21 - C)];
+        else v = parts[row * 48 + (w - W0)];
+    }
+    rec[i] = v;
+}
+
+hipError_t launch_pack_records_parts(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
+                                     const float* parts, float* rec, int B, int K, int C, hipStream_t s) {
+    const long n = (long)B * K * (21 + 2 * C + 48);
+    if (n <= 0) return hipSuccess;
+    if (!parts) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pack_records_parts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, num, scores, means, covs, counts, parts,
+                       rec, B, K, C);
     return hipGetLastError();
 }
 

@@ -17,30 +17,40 @@ def shard_range(num_images, world_size, rank):
 
 
 RECORD_EXTRA = 1      # per-detection record = [valid, means 4, covs 16, scores C, counts C]
+RECORD_PARTS = 48     # ... + the three covariance parts (epistemic, aleatoric, prior: 3 x 16) on covariance_parts handles
 
 
-def record_width(num_classes):
-    return RECORD_EXTRA + 4 + 16 + 2 * num_classes
+def record_width(num_classes, cov_parts=False):
+    return RECORD_EXTRA + 4 + 16 + 2 * num_classes + (RECORD_PARTS if cov_parts else 0)
 
 
-def pack_records(num, scores, means, covs, counts):
+def pack_records(num, scores, means, covs, counts, cov_parts=None):
     """Padded per-image arrays -> one float32 tensor [B, K, 1+4+16+2C]; slot 0 flags valid rows.
+    ``cov_parts`` [B,K,3,4,4] (or [B,K,48]): the wide row of a covariance_parts handle, the parts behind the counts.
     Works on torch tensors of any device (device-side pack before the RCCL gather)."""
     b, k, _ = scores.shape
     valid = (torch.arange(k, device=scores.device)[None, :] < num.to(scores.device)[:, None]).to(scores.dtype)
-    rec = torch.cat([valid[:, :, None], means.reshape(b, k, 4), covs.reshape(b, k, 16), scores, counts], dim=2)
+    cols = [valid[:, :, None], means.reshape(b, k, 4), covs.reshape(b, k, 16), scores, counts]
+    if cov_parts is not None:
+        cols.append(cov_parts.reshape(b, k, RECORD_PARTS))
+    rec = torch.cat(cols, dim=2)
     return rec * valid[:, :, None]
 
 
 def unpack_records(rec, num_classes):
-    """[B,K,W] tensor/array -> list of (scores [k,C], means [k,4], covs [k,4,4], counts [k,C]) per image."""
+    """[B,K,W] tensor/array -> list of (scores [k,C], means [k,4], covs [k,4,4], counts [k,C]) per image; rows of the wide
+    form (W = 1+4+16+2C+48) give a fifth element, cov_parts [k,3,4,4]."""
     rec = rec.detach().cpu().numpy() if isinstance(rec, torch.Tensor) else np.asarray(rec)
     out = []
     c = num_classes
+    if rec.shape[-1] not in (record_width(c), record_width(c, True)):
+        raise ValueError("record rows of %d floats: expected %d or %d for %d classes" % (rec.shape[-1], record_width(c), record_width(c, True), c))
+    wide = rec.shape[-1] == record_width(c, True)
     for r in rec:
         k = int(r[:, 0].sum())
         r = r[:k]
-        out.append((r[:, 21:21 + c], r[:, 1:5], r[:, 5:21].reshape(k, 4, 4), r[:, 21 + c:21 + 2 * c]))
+        row = (r[:, 21:21 + c], r[:, 1:5], r[:, 5:21].reshape(k, 4, 4), r[:, 21 + c:21 + 2 * c])
+        out.append(row + (r[:, 21 + 2 * c:].reshape(k, 3, 4, 4),) if wide else row)
     return out
 
 

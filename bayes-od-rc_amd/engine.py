@@ -20,7 +20,8 @@ def make_config(image_hw, batch=1, mc_samples=10, num_classes=8, anchors_per_loc
                 dropout_rate=0.3, use_full_covar=True, bayes_od_config=None, nms_config=None,
                 has_covar_head=True, dataset_name='bdd', orig_size=None, nms_variant='A',
                 num_categorical_draws=30, layers=(3, 4, 5, 6, 7), precision='bf16', mc_sample_base=0,
-                mc_ensemble_size=0, training=False, backbone_depth=50, pipeline_overlap=False, mc_statistics=False):
+                mc_ensemble_size=0, training=False, backbone_depth=50, pipeline_overlap=False, mc_statistics=False,
+                covariance_parts=False):
     """Translates the reference's yaml dictionaries (configs/retinanet_bdd_covar.yaml:61-143)
     into a ``bod_config``."""
     bo = bayes_od_config or {'ranking_method': 'score', 'dirichlet_prior': {'type': 'non_informative'},
@@ -61,6 +62,10 @@ def make_config(image_hw, batch=1, mc_samples=10, num_classes=8, anchors_per_loc
     cfg.mc_statistics = int(bool(mc_statistics))
     if cfg.mc_statistics and (cfg.training or cfg.pipeline_overlap):
         raise ValueError("mc_statistics handles are inference handles on one stream: training / pipeline_overlap cannot be combined with it")
+    # every posterior row and detection also reports the epistemic / aleatoric / prior terms of its covariance (include/bayesod.h)
+    cfg.covariance_parts = int(bool(covariance_parts))
+    if cfg.covariance_parts and cfg.training:
+        raise ValueError("covariance_parts belongs to inference and statistics handles: training cannot be combined with it")
     if dataset_name == 'kitti':
         if orig_size is None:
             raise ValueError("dataset_name='kitti' needs orig_size (sample_dict['im_size'])")
@@ -261,6 +266,10 @@ class Engine(object):
             out = {"num": np.empty(b, np.int32), "scores": np.empty((b, k, c), np.float32),
                    "means": np.empty((b, k, 4), np.float32), "covs": np.empty((b, k, 4, 4), np.float32),
                    "counts": np.empty((b, k, c), np.float32)}
+        if self.cfg.covariance_parts:                 # (before bod_collect: the parts wait for the batch, the records release the slot)
+            if "cov_parts" not in out:
+                out["cov_parts"] = np.empty((b, k, 3, 4, 4), np.float32)
+            self._chk(self.lib.bod_collect_parts(self.h, slot, fptr(out["cov_parts"])))
         self._chk(self.lib.bod_collect(self.h, slot, iptr(out["num"]), fptr(out["scores"]), fptr(out["means"]),
                                        fptr(out["covs"]), fptr(out["counts"])))
         return out
@@ -459,6 +468,38 @@ class Engine(object):
         self._chk(self.lib.bod_set_posterior(self.h, image_index, m, fptr(counts), fptr(means), fptr(covs),
                                              fptr(ranking)))
 
+    # -- covariance parts (handles made with make_config(covariance_parts=True)): [rows, 3, 4, 4] = epistemic, aleatoric, prior
+    def get_posterior_parts(self, image_index=0):
+        """The three terms every row of ``get_posterior(image_index)["covs"]`` is the sum of (``bod_get_posterior_parts``)."""
+        m = int(self.num_kept()[image_index])
+        parts = np.empty((m, 3, 4, 4), np.float32)
+        self._chk(self.lib.bod_get_posterior_parts(self.h, image_index, fptr(parts)))
+        return parts
+
+    def set_posterior_parts(self, image_index, parts):
+        """The injection that goes with ``set_posterior``: ``parts`` [M,3,4,4] (``bod_set_posterior_parts``)."""
+        parts = as_f32(parts).reshape(-1, 3, 4, 4)
+        self._chk(self.lib.bod_set_posterior_parts(self.h, image_index, parts.shape[0], fptr(parts)))
+
+    def get_detection_parts(self, image_index=0):
+        """[K,3,4,4]: the three terms of every covariance of ``get_detections(image_index)`` (``bod_get_detection_parts``)."""
+        parts = np.empty((self.K, 3, 4, 4), np.float32)
+        n = C.c_int32(0)
+        self._chk(self.lib.bod_get_detection_parts(self.h, image_index, fptr(parts)))
+        self._chk(self.lib.bod_get_detections(self.h, image_index, C.byref(n), None, None, None, None))
+        return parts[:n.value].copy()
+
+    def get_detection_parts_batch(self):
+        """[B,K,3,4,4], padded like ``get_detections_batch`` (``bod_get_detection_parts_batch``)."""
+        parts = np.empty((self.B, self.K, 3, 4, 4), np.float32)
+        self._chk(self.lib.bod_get_detection_parts_batch(self.h, fptr(parts)))
+        return parts
+
+    def device_detection_parts_pointer(self, slot=0):
+        p = C.c_void_p(0)
+        self._chk(self.lib.bod_device_detection_parts(self.h, slot, C.byref(p)))
+        return int(p.value or 0), (self.B, self.K, 3, 16)
+
     def nms(self):
         self._chk(self.lib.bod_nms(self.h))
 
@@ -621,7 +662,8 @@ class Engine(object):
         """The path's one multi-GPU exchange through the C ABI (``bod_gather_detections``): packs this batch's detection
         records on the device and gathers every rank's block on ``root`` with ONE RCCL gather.  ``comm``: an ``ncclComm_t``
         as an integer / ``c_void_p`` (None: single process).  ``slot``: ticket of ``infer_async`` (-1 after ``infer``).
-        Returns [world, B, K, 1+4+16+2C] float32 on the root (None elsewhere); unpack with distributed.unpack_records.
+        Returns [world, B, K, 1+4+16+2C] float32 on the root (None elsewhere; covariance_parts handles: 48 floats wider); unpack
+        with distributed.unpack_records.
         ``want_host=False`` (root only): nothing is copied or waited for; returns ``(device pointer, shape)`` of the gathered
         block, complete after ``collect(slot)`` (a ticket) or ``synchronize()`` (slot -1) -- see include/bayesod.h."""
         w = int(self.lib.bod_record_width(self.h))

@@ -21,7 +21,7 @@ def _bayes_testing_kwargs(bayes_od_config, nms_config, use_full_covar, dataset_n
 
 def bayes_od_inference(model, sample_dict, bayes_od_config, nms_config, use_full_covar=False,
                        dataset_name='bdd', seed=None, image_id=None, nms_variant='A',
-                       return_iou=True, return_engine=False):
+                       return_iou=True, return_engine=False, covariance_parts=False):
     """Same 5 return values as the reference (:217) for a batch-of-1 ``sample_dict``:
 
         dirichlet_posterior_count [M,C], gaussian_posterior_means [M,4,1],
@@ -33,6 +33,8 @@ def bayes_od_inference(model, sample_dict, bayes_od_config, nms_config, use_full
     ``return_engine=True`` appends the handle that produced the results as a sixth value: passing it to
     ``bayes_od_clustering(..., engine=)`` re-uses its device buffers.  Without it the two calls are as independent as
     the reference's (run_inference.py:138-149): nothing is remembered between them.
+    ``covariance_parts=True`` appends (in front of the engine) gaussian_posterior_cov_parts [M,3,4,4]: the epistemic, aleatoric
+    and prior terms every posterior covariance is the sum of.
     """
     image = np.asarray(sample_dict[constants.IMAGE_NORMALIZED_KEY], dtype=np.float32)
     if image.ndim == 3:
@@ -47,6 +49,8 @@ def bayes_od_inference(model, sample_dict, bayes_od_config, nms_config, use_full
                          "(inference_utils.py:241-242)")
     kw = _bayes_testing_kwargs(bayes_od_config, nms_config, use_full_covar, dataset_name, sample_dict,
                                nms_variant)
+    if covariance_parts:
+        kw['covariance_parts'] = True
     eng = model.engine_for(image.shape[1:3], batch=1, mc_samples=model.mc_dropout_samples, **kw)
     eng.set_anchors(anchors)
     seed = model.seed if seed is None else seed
@@ -60,6 +64,8 @@ def bayes_od_inference(model, sample_dict, bayes_od_config, nms_config, use_full
     nms_indices = eng.get_nms(0)
     iou = eng.get_iou_matrix(0) if return_iou else np.zeros((0, 0), np.float32)
     out = (post["counts"], post["means"][:, :, None], post["covs"], nms_indices, iou)
+    if covariance_parts:
+        out += (eng.get_posterior_parts(0),)
     return out + (eng,) if return_engine else out
 
 
@@ -142,15 +148,25 @@ def map_dataset_classes(input_dataset, target_dataset, output_classes):
     return mapped
 
 
+def _detections(engine):
+    """Per image the four detection arrays, and the covariance parts behind them on a covariance_parts handle."""
+    dets = [engine.get_detections(b) for b in range(engine.B)]
+    if engine.cfg.covariance_parts:
+        dets = [d + (engine.get_detection_parts(b),) for b, d in enumerate(dets)]
+    return dets
+
+
 class BayesOdPipeline(object):
     """Batched, fully device-resident form of the reference's per-image loop body
     (src/retina_net/experiments/run_inference.py:137-161): forward -> posterior -> soft-NMS ->
     cluster-and-fuse for ``batch`` images per call, no host round trip in between."""
 
     def __init__(self, model, image_hw, batch, bayes_od_config, nms_config, use_full_covar=True,
-                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None):
+                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, covariance_parts=False):
         self._kw = dict(bayes_od_config=bayes_od_config, nms_config=nms_config, use_full_covar=use_full_covar,
                         dataset_name=dataset_name, nms_variant=nms_variant, orig_size=orig_size)
+        if covariance_parts:
+            self._kw['covariance_parts'] = True
         self.model, self._hw, self._batch = model, tuple(image_hw), batch
         self.engine = self.bind()
         if anchors is not None:
@@ -174,10 +190,11 @@ class BayesOdPipeline(object):
 
     def __call__(self, images=None, seed=0, first_image_id=0):
         """images [B,H,W,3] (or None to reuse the uploaded device batch).  Returns, per image,
-        (output_classes [K,C], output_boxes_vuhw [K,4], output_covs [K,4,4], output_counts [K,C])."""
+        (output_classes [K,C], output_boxes_vuhw [K,4], output_covs [K,4,4], output_counts [K,C]); a pipeline made with
+        ``covariance_parts=True`` adds output_cov_parts [K,3,4,4] (epistemic, aleatoric, prior)."""
         self.bind()
         self.engine.infer(images, seed=seed, first_image_id=first_image_id)
-        return [self.engine.get_detections(b) for b in range(self.engine.B)]
+        return _detections(self.engine)
 
 
 class EnsemblePipeline(object):
@@ -193,7 +210,7 @@ class EnsemblePipeline(object):
     with V views member m, pass p, view index v draws the samples ``((m * passes + p) * V + v) * n ..``."""
 
     def __init__(self, models, image_hw, batch, bayes_od_config, nms_config, samples_per_member, passes=1, use_full_covar=True,
-                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, views=('identity',)):
+                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, views=('identity',), covariance_parts=False):
         from .engine import Engine, make_config
         models = list(models)
         if not models:
@@ -219,21 +236,22 @@ class EnsemblePipeline(object):
         self._hw, self._batch = tuple(image_hw), int(batch)
         self._kw = dict(bayes_od_config=bayes_od_config, nms_config=nms_config, use_full_covar=use_full_covar,
                         dataset_name=dataset_name, nms_variant=nms_variant, orig_size=orig_size)
+        self._parts = bool(covariance_parts)          # on member 0's handle, where the merged posterior and the fusion run
         self.engines = []
         for m in models:
-            eng = Engine(self._config(m))
+            eng = Engine(self._config(m, first=not self.engines))
             eng.load_weights(m._weights)
             self.engines.append(eng)
         self.engine = self.engines[0]             # uploads, the merged accumulator and the Bayesian stages live here
         if anchors is not None:
             self.set_anchors(anchors)
 
-    def _config(self, m):
+    def _config(self, m, first=False):
         from .engine import make_config
         return make_config(self._hw, batch=self._batch, mc_samples=self.n, num_classes=m.num_classes + 1,
                            anchors_per_location=m.anchors_per_location, device=m.device, dropout_rate=m.dropout_rate,
                            has_covar_head=m.compute_covar, precision=m.precision, backbone_depth=m.backbone_depth,
-                           mc_ensemble_size=self.total, mc_statistics=True, **self._kw)
+                           mc_ensemble_size=self.total, mc_statistics=True, covariance_parts=self._parts and first, **self._kw)
 
     def set_anchors(self, anchors):
         for eng in self.engines:
@@ -243,8 +261,8 @@ class EnsemblePipeline(object):
         """Re-apply the testing configuration (a new ``orig_size``: KITTI's per-size rescale) to every member's handle."""
         if orig_size is not None:
             self._kw['orig_size'] = tuple(orig_size)
-            for m, eng in zip(self.models, self.engines):
-                eng.update_config(self._config(m))
+            for i, (m, eng) in enumerate(zip(self.models, self.engines)):
+                eng.update_config(self._config(m, first=i == 0))
         return self.engine
 
     def upload_mixed(self, frames, means, aspect_resize=True):
@@ -270,7 +288,7 @@ class EnsemblePipeline(object):
         self.engine.stat_posterior(seed=seed, first_image_id=first_image_id)
         self.engine.nms()
         self.engine.cluster_fuse()
-        return [self.engine.get_detections(b) for b in range(self.engine.B)]
+        return _detections(self.engine)
 
 
 def post_process_predictions(sample_dict, prediction_dict, dataset_name='bdd', engine=None, nms_config=None):

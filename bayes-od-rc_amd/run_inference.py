@@ -63,19 +63,19 @@ def test_model(config, args):
     predictions_dir = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'], 'predictions')
     writer = writers.PredictionWriter(predictions_dir, test_dataset, test_config['ckpt_idx'],
                                       test_config['uncertainty_method'],
-                                      test_config['bayes_od_config']['fusion_method'])
+                                      test_config['bayes_od_config']['fusion_method'], cov_parts=_want_parts(args))
     categories = dataset_config[training_dataset]['training_data_config']['categories']
     start = time.time()
     n_done = 0
     for lo in range(0, len(frames), batch):              # every frame, like the reference's loop (run_inference.py:137)
         chunk = frames[lo:lo + batch]
         dets = pipe_for(len(chunk))(chunk, seed=args.seed, first_image_id=lo)
-        for b, (classes, boxes_vuhw, covs, counts) in enumerate(dets):
+        for b, (classes, boxes_vuhw, covs, counts, *parts) in enumerate(dets):
             boxes = box_utils.vuhw_to_vuvu_np(boxes_vuhw) if boxes_vuhw.size else boxes_vuhw
             mapped = classes
             if training_dataset != test_dataset and boxes.size > 0:
                 mapped = inference_utils.map_dataset_classes(training_dataset, test_dataset, classes)
-            writer.write('%06d' % (lo + b), boxes, mapped, boxes_vuhw, covs, classes, counts, categories)
+            writer.write('%06d' % (lo + b), boxes, mapped, boxes_vuhw, covs, classes, counts, categories, *parts)
             n_done += 1
         sys.stdout.write('\r{}'.format(n_done) + ' /' + str(len(frames)))
     writer.close()
@@ -96,11 +96,17 @@ def _ensemble_members(config, args):
     return members
 
 
+def _want_parts(args):
+    return bool(getattr(args, 'covariance_parts', False))
+
+
 def _make_pipeline(model, args, hw, batch, bayes_od_config, nms_config, **kw):
     """BayesOdPipeline of the one model, or -- ``model`` a list (--ensemble) -- EnsemblePipeline with the yaml's
     mc_dropout_samples per member and --mc_passes passes each.  --tta_flip: every pass runs the frames as given and mirrored
     left-right; without --ensemble that is a one-member EnsemblePipeline of the one model."""
     tta = bool(getattr(args, 'tta_flip', False))
+    if _want_parts(args):                 # --covariance_parts: every detection's epistemic / aleatoric / prior covariance
+        kw = dict(kw, covariance_parts=True)
     if isinstance(model, list) or tta:
         members = model if isinstance(model, list) else [model]
         return inference_utils.EnsemblePipeline(members, hw, batch, bayes_od_config, nms_config, members[0].mc_dropout_samples,
@@ -120,7 +126,8 @@ def _test_model_on_dataset(config, args, model):
     kitti = test_dataset == 'kitti'
     predictions_dir = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'], 'predictions')
     writer = writers.PredictionWriter(predictions_dir, test_dataset, test_config['ckpt_idx'],
-                                      test_config['uncertainty_method'], test_config['bayes_od_config']['fusion_method'])
+                                      test_config['uncertainty_method'], test_config['bayes_od_config']['fusion_method'],
+                                      cov_parts=_want_parts(args))
     categories = dataset_config[training_dataset]['training_data_config']['categories']
     gen = FpnAnchorGenerator(dataset_config['anchor_generator'])
     pipes = {}
@@ -128,12 +135,12 @@ def _test_model_on_dataset(config, args, model):
     mixed = bool(getattr(args, 'mixed_sizes', False))
 
     def emit(dets):
-        for (name, _, _), (classes, boxes_vuhw, covs, counts) in zip(pending, dets):
+        for (name, _, _), (classes, boxes_vuhw, covs, counts, *parts) in zip(pending, dets):
             boxes = box_utils.vuhw_to_vuvu_np(boxes_vuhw) if boxes_vuhw.size else boxes_vuhw
             mapped = classes
             if training_dataset != test_dataset and boxes.size > 0:
                 mapped = inference_utils.map_dataset_classes(training_dataset, test_dataset, classes)
-            writer.write(name, boxes, mapped, boxes_vuhw, covs, classes, counts, categories)
+            writer.write(name, boxes, mapped, boxes_vuhw, covs, classes, counts, categories, *parts)
         del pending[:]
 
     def flush_mixed():
@@ -207,6 +214,9 @@ def main(argv=None):
                     'samples = k * n samples per member; one weight file with --mc_passes k is N = k * n on one handle)')
     ap.add_argument('--tta_flip', action='store_true', help='test-time augmentation: every pass also runs the frames mirrored '
                     'left-right and its samples enter the same posterior (the network width must be a multiple of 2^max_level)')
+    ap.add_argument('--covariance_parts', action='store_true', help='also write every detection\'s epistemic, aleatoric and prior '
+                    'covariance (cov_epistemic/, cov_aleatoric/, cov_prior/ beside cov/: they sum to it); works with --ensemble, '
+                    '--mc_passes and --tta_flip')
     args = ap.parse_args(argv)
     config = config_utils.load_yaml(args.yaml_path)
     config = config_utils.setup(config, args)

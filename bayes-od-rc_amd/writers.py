@@ -42,21 +42,25 @@ def predictions_to_kitti_format(output_boxes, output_classes):
 
 class PredictionWriter(object):
     """Directory layout predictions/testing/<dataset>/<ckpt_id>/<method>_<fusion>/{data,mean,cov,
-    cat_param,cat_count} and per-frame files (run_inference.py:90-115,174-236)."""
+    cat_param,cat_count} and per-frame files (run_inference.py:90-115,174-236).  ``cov_parts=True`` adds three directories beside
+    them, cov_epistemic / cov_aleatoric / cov_prior, with one [K,4,4] .npy per frame each: the terms ``cov`` is the sum of."""
+    PART_DIRS = ('cov_epistemic', 'cov_aleatoric', 'cov_prior')
 
-    def __init__(self, predictions_dir, dataset, ckpt_id, uncertainty_method='bayes_od', fusion_method='none'):
+    def __init__(self, predictions_dir, dataset, ckpt_id, uncertainty_method='bayes_od', fusion_method='none', cov_parts=False):
         self.dataset = dataset
         root = os.path.join(predictions_dir, 'testing', dataset, str(ckpt_id), uncertainty_method)
         if uncertainty_method == 'bayes_od':
             root += '_' + fusion_method
         self.root = root
         self.dirs = {k: os.path.join(root, k) for k in ('data', 'mean', 'cov', 'cat_param', 'cat_count')}
+        if cov_parts:
+            self.dirs.update({k: os.path.join(root, k) for k in self.PART_DIRS})
         for d in self.dirs.values():
             os.makedirs(d, exist_ok=True)
         self.results = []
 
     def write(self, sample_id, output_boxes_vuvu, output_classes_mapped, output_boxes_vuhw, output_covs,
-              output_classes, output_counts, category_list=None):
+              output_classes, output_counts, category_list=None, output_cov_parts=None):
         if self.dataset == 'kitti':
             rows = predictions_to_kitti_format(output_boxes_vuvu, output_classes_mapped)
             path = os.path.join(self.dirs['data'], sample_id + '.txt')
@@ -71,6 +75,12 @@ class PredictionWriter(object):
         np.save(os.path.join(self.dirs['cov'], sample_id + '.npy'), output_covs)
         np.save(os.path.join(self.dirs['cat_param'], sample_id + '.npy'), output_classes)
         np.save(os.path.join(self.dirs['cat_count'], sample_id + '.npy'), output_counts)
+        if self.PART_DIRS[0] in self.dirs:
+            if output_cov_parts is None:
+                raise ValueError("this writer was made with cov_parts=True: write() needs output_cov_parts [K,3,4,4]")
+            parts = np.asarray(output_cov_parts).reshape(-1, 3, 4, 4)
+            for i, k in enumerate(self.PART_DIRS):
+                np.save(os.path.join(self.dirs[k], sample_id + '.npy'), parts[:, i])
 
     def close(self):
         if self.dataset != 'kitti':

@@ -114,7 +114,16 @@ typedef struct {
                                     sparse tail or halo, because the kept set depends on the merged class statistics and every
                                     anchor's box / covariance statistics must exist before the merge.  0 (default): plans, kernels,
                                     buffers and results exactly as without the field.                                    */
-    int32_t reserved[1];
+    union {                      /* the last reserved int under both names: the size and every offset are unchanged, and a caller
+                                    that zeroes reserved[0] asks for the default                                        */
+        int32_t covariance_parts; /* 1: the handle also reports, for every posterior row and every detection, the three terms
+                                    its covariance is the sum of -- epistemic, aleatoric, prior (the bod_*_parts entry points
+                                    below).  Inference and statistics handles; refused with training = 1.  Two
+                                    more launches per pass, 30 floats per anchor + 48 per detection slot of HBM; record rows
+                                    widen by 48 floats.  0 (default): plans, kernels, buffers and results exactly as without
+                                    the field.                                                                          */
+        int32_t reserved[1];
+    };
 } bod_config;
 
 /* Sizes the caller needs to allocate host buffers. */
@@ -503,7 +512,7 @@ bod_status bod_profile_end(bod_handle h, double* head_conv_ms, int64_t* head_con
 /* ---- the path's ONE multi-GPU exchange for callers of the C ABI (no PyTorch in the loop) ----
  * Images shard across processes (one per GPU); per step every rank contributes the detection records of its batch and `root`
  * receives all of them.  A record row is W = bod_record_width() = 1 + 4 + 16 + 2C floats: [valid, mean (v,u,h,w), covariance
- * row-major, score[C], counts[C]]; a rank's block is [batch][max_detections][W], rows beyond an image's detection count are zero.
+ * row-major, score[C], counts[C]] (covariance_parts handles: + 48, the three parts behind the counts); a rank's block is [batch][max_detections][W], rows beyond an image's detection count are zero.
  *
  * bod_gather_detections packs the records of `slot` (the ticket of bod_infer_async; pass -1 after a synchronous bod_infer) on the
  * device and issues ONE RCCL gather -- ncclGather(send, recv, batch*K*W, ncclFloat32, root, comm, stream).  For a ticket
@@ -526,6 +535,31 @@ bod_status bod_profile_end(bod_handle h, double* head_conv_ms, int64_t* head_con
 int32_t bod_record_width(bod_handle h);
 bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, int32_t world, int32_t rank, int32_t root,
                                  float* gathered_host, float** gathered_device);
+
+/* ---- covariance parts (handles created with bod_config.covariance_parts = 1; every call below returns BOD_ERR_INVALID_ARG on
+ * any other handle) ----
+ * Both fusion steps are linear in the member means, so every covariance they store is exactly the sum of three terms: what the
+ * fused mean inherits from the epistemic noise (the sample covariance over the MC samples), from the aleatoric noise (the
+ * covariance head) and from the Gaussian prior.  Per kept anchor, with lik = (10 A + E) / 11, P = (lik^-1 + I / iso_var)^-1 and
+ * the gain G = P lik^-1 = (I + lik / iso_var)^-1:  epi = G (E / 11) G^T,  ale = G (10 A / 11) G^T,  pri = P P / iso_var  (no Gaussian prior: G = I, pri = 0; no
+ * covariance head: ale = 0; KITTI: each term rescaled like the covariance).  Per cluster, with P_i the inverse of member i's
+ * covariance and F = (sum P_i)^-1:  X_out = 70 F (sum P_i X_i P_i) F.
+ * `parts` is always [rows][3][16]: epistemic, aleatoric, prior, each a row-major 4x4 like `covs`.
+ * bod_get_posterior_parts: the M rows of image_index, in bod_get_posterior's order (all zero after bod_validation_post).
+ * bod_set_posterior_parts: the injection that goes with bod_set_posterior (m = the image's row count).  After bod_set_posterior on
+ * an image WITHOUT it, bod_cluster_fuse still runs, and the detection-parts getters of that image return BOD_ERR_NOT_READY.
+ * bod_get_detection_parts / _batch: [K][3][16] of one image / [batch][max_detections][3][16], rows as bod_get_detections[_batch].
+ * bod_collect_parts: the parts of a bod_infer_async ticket (they are double-buffered with the records and travel to pinned memory
+ * with them); it waits for the batch like bod_collect, does not release the slot, and may be called before bod_collect or after it,
+ * until the next bod_infer_async that reuses the slot.
+ * bod_device_detection_parts: device address of a slot's [batch][max_detections][3][16] array (see bod_device_detections).
+ * On these handles bod_record_width() is 1 + 4 + 16 + 2C + 48: bod_gather_detections appends the parts behind the counts. */
+bod_status bod_get_posterior_parts(bod_handle h, int32_t image_index, float* parts);
+bod_status bod_set_posterior_parts(bod_handle h, int32_t image_index, int32_t m, const float* parts);
+bod_status bod_get_detection_parts(bod_handle h, int32_t image_index, float* parts);
+bod_status bod_get_detection_parts_batch(bod_handle h, float* parts);
+bod_status bod_collect_parts(bod_handle h, int32_t slot, float* parts);
+bod_status bod_device_detection_parts(bod_handle h, int32_t slot, void** ptr);
 
 /* What the handle's plan looks like (tests / bench report it; nothing on the hot path reads it).  info8[0] = 1 when the MC
  * statistics are reduced inside the last tower layers' tiles (no [B,N,A,.] tensors on the bod_infer path), [1] = 1 when the 1x1

@@ -41,7 +41,10 @@ typedef struct {
     int32_t backbone_depth;
     int32_t pipeline_overlap;
     int32_t mc_statistics;
-    int32_t reserved[1];
+    union {
+        int32_t covariance_parts;
+        int32_t reserved[1];
+    };
 } bod_config;
 typedef struct {
     int32_t num_pixels;
@@ -180,6 +183,12 @@ bod_status bod_profile_end(bod_handle h, double* head_conv_ms, int64_t* head_con
 int32_t bod_record_width(bod_handle h);
 bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, int32_t world, int32_t rank, int32_t root,
                                  float* gathered_host, float** gathered_device);
+bod_status bod_get_posterior_parts(bod_handle h, int32_t image_index, float* parts);
+bod_status bod_set_posterior_parts(bod_handle h, int32_t image_index, int32_t m, const float* parts);
+bod_status bod_get_detection_parts(bod_handle h, int32_t image_index, float* parts);
+bod_status bod_get_detection_parts_batch(bod_handle h, float* parts);
+bod_status bod_collect_parts(bod_handle h, int32_t slot, float* parts);
+bod_status bod_device_detection_parts(bod_handle h, int32_t slot, void** ptr);
 bod_status bod_plan_info(bod_handle h, int32_t* info8);
 bod_status bod_plan_info_n(bod_handle h, int32_t* info, int32_t n);
 bod_status bod_stat_reset(bod_handle h);
