@@ -17,6 +17,7 @@ if os.environ.get("BOD_LIB_OVERRIDE"):
     LIB_PATH = os.path.abspath(os.environ["BOD_LIB_OVERRIDE"])
 
 BOD_OK, BOD_ERR_INVALID_ARG, BOD_ERR_HIP, BOD_ERR_OOM, BOD_ERR_NOT_READY, BOD_ERR_NO_DEVICE = range(6)
+BOD_PARTS_COVARIANCE, BOD_PARTS_CLASS = 1, 2      # bits of bod_config.covariance_parts
 BOD_VIEW_IDENTITY, BOD_VIEW_HFLIP = 0, 1          # views of a statistics handle (bod_stat_forward_view / bod_stat_merge_view)
 
 
@@ -156,6 +157,17 @@ SIGNATURES = {
     "bod_get_detection_parts_batch": (C.c_int, [_H, _F]),
     "bod_collect_parts": (C.c_int, [_H, C.c_int32, _F]),
     "bod_device_detection_parts": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
+    "bod_get_posterior_class_parts": (C.c_int, [_H, C.c_int32, _F]),
+    "bod_get_posterior_mean_probs": (C.c_int, [_H, C.c_int32, _F]),
+    "bod_set_posterior_class_parts": (C.c_int, [_H, C.c_int32, C.c_int32, _F, _F]),
+    "bod_get_detection_class_parts": (C.c_int, [_H, C.c_int32, _F]),
+    "bod_get_detection_class_parts_batch": (C.c_int, [_H, _F]),
+    "bod_collect_class_parts": (C.c_int, [_H, C.c_int32, _F]),
+    "bod_device_detection_class_parts": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
+    "bod_stat_get_entropy": (C.c_int, [_H, _F]),
+    "bod_stat_set_entropy": (C.c_int, [_H, _F]),
+    "bod_stat_device_entropy": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
+    "bod_stat_merge_entropy": (C.c_int, [_H, C.c_void_p, C.c_int32]),
     "bod_gather_detections": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
     "bod_profile_end": (C.c_int, [_H, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

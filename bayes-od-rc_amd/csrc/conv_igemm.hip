@@ -502,7 +502,7 @@ struct KTilePipe {
 // (inference_utils.py:220-244 computes the same two-pass).
 // ------------------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
-template <int C>
+template <int C, bool ENT = false>          // ENT (AGG_CLS_ENT): also sum_n H(softmax(logits_n)) -> G.out2 [B,A]
 __device__ __forceinline__ void agg_reduce_cls(const ConvGroup& G, const float* ytile, int ystride, const int* s_off, const int* s_off2,
                                                int tid, int nthreads, int rows) {
     const int N = G.agg_n, AN = G.cout2 / C, Q = rows / N;
@@ -512,6 +512,7 @@ __device__ __forceinline__ void agg_reduce_cls(const ConvGroup& G, const float* 
         const int o0 = s_off2[r0];                       // (image * N + 0) * P + pixel
         const int b = o0 / (N * G.agg_P), p = o0 - b * N * G.agg_P;
         float mp[C];
+        float ent = 0.f;
 #pragma unroll
         for (int j = 0; j < C; ++j) mp[j] = 0.f;
         for (int n = 0; n < N; ++n) {
@@ -526,14 +527,22 @@ __device__ __forceinline__ void agg_reduce_cls(const ConvGroup& G, const float* 
 #pragma unroll
             for (int j = 1; j < C; ++j) mx = fmaxf(mx, v[j]);
             float sden = 0.f;
+            if constexpr (ENT) {             // H_n = log(sden) - (sum_j v_j (l_j - mx)) / sden: post_class_parts_kernel / stat_from_raw_kernel, fused
+                float dot = 0.f;
 #pragma unroll
-            for (int j = 0; j < C; ++j) { v[j] = expf(v[j] - mx); sden += v[j]; }
+                for (int j = 0; j < C; ++j) { const float d = v[j] - mx; v[j] = expf(d); sden += v[j]; dot += v[j] * d; }
+                ent += BOD_LOG_SDEN(sden) - dot / sden;
+            } else {
+#pragma unroll
+                for (int j = 0; j < C; ++j) { v[j] = expf(v[j] - mx); sden += v[j]; }
+            }
 #pragma unroll
             for (int j = 0; j < C; ++j) mp[j] += v[j] / sden;
         }
         float* o = G.agg_out + (((size_t)b * G.agg_P + p) * AN + an) * C;
 #pragma unroll
         for (int k = 0; k < C / 4; ++k) reinterpret_cast<float4*>(o)[k] = make_float4(mp[4 * k], mp[4 * k + 1], mp[4 * k + 2], mp[4 * k + 3]);
+        if constexpr (ENT) G.out2[((size_t)b * G.agg_P + p) * AN + an] = ent;
     }
 }
 
@@ -1975,6 +1984,9 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
                     if (G.agg_kind == AGG_CLS) {
                         if (G.agg_C == 8) agg_reduce_cls<8>(G, ytile, ystride, s_off, s_off2, tid, THREADS, BP);
                         else agg_reduce_cls<4>(G, ytile, ystride, s_off, s_off2, tid, THREADS, BP);
+                    } else if (G.agg_kind == AGG_CLS_ENT) {
+                        if (G.agg_C == 8) agg_reduce_cls<8, true>(G, ytile, ystride, s_off, s_off2, tid, THREADS, BP);
+                        else agg_reduce_cls<4, true>(G, ytile, ystride, s_off, s_off2, tid, THREADS, BP);
                     } else if (G.agg_kind == AGG_BOX) {
                         agg_reduce_box(G, ytile, ystride, s_off, s_off2, tid, THREADS, BP);
                     } else {
@@ -2530,6 +2542,9 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
             if (G.agg_kind == AGG_CLS) {
                 if (G.agg_C == 8) agg_reduce_cls<8>(G, ytile, ystride, s_off, s_off2, tid, THREADS, BP);
                 else agg_reduce_cls<4>(G, ytile, ystride, s_off, s_off2, tid, THREADS, BP);
+            } else if (G.agg_kind == AGG_CLS_ENT) {
+                if (G.agg_C == 8) agg_reduce_cls<8, true>(G, ytile, ystride, s_off, s_off2, tid, THREADS, BP);
+                else agg_reduce_cls<4, true>(G, ytile, ystride, s_off, s_off2, tid, THREADS, BP);
             } else if (G.agg_kind == AGG_BOX) {
                 agg_reduce_box(G, ytile, ystride, s_off, s_off2, tid, THREADS, BP);
             } else {

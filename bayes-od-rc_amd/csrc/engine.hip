@@ -347,6 +347,16 @@ struct bod_context {
     float* out_parts_s[2] = {nullptr, nullptr}; float* out_parts = nullptr;
     std::vector<char> parts_ok, det_parts_ok[2];
     bool parts_staged[2] = {false, false};              // host_stage[slot] holds the parts of a bod_infer_async ticket
+    // Class-entropy parts (bod_config.covariance_parts bit BOD_PARTS_CLASS; nullptr / empty on every other handle).  ent: the fresh
+    // sum_n H(softmax) [B,A] of the last forward (AGG_CLS_ENT epilogue, or stat_from_raw_kernel); stat_ent: its accumulator on a
+    // statistics handle, holding stat_ent_k of the record's stat_k samples; cparts: [B,A,3+C] per kept slot; the detections'
+    // [B,K,4] double-buffered with the records; the *_ok flags as for the covariance parts.
+    bool class_parts = false;
+    float* ent = nullptr; float* stat_ent = nullptr; int stat_ent_k = 0;
+    float* cparts = nullptr;
+    float* out_cparts_s[2] = {nullptr, nullptr}; float* out_cparts = nullptr;
+    std::vector<char> cparts_ok, det_cparts_ok[2];
+    bool cparts_staged[2] = {false, false};
     hipStream_t side = nullptr;
     // ---- CU-partitioned pipeline overlap (bod_config.pipeline_overlap; bod_infer_async only).  The memory-bound front of batch i+1
     // (stem, backbone, FPN) runs on its own stream, masked to the last `ov_front_slots` CU slots of every XCD, while the MFMA-bound
@@ -377,7 +387,7 @@ struct bod_context {
         nms_sel = nms_sel_s[sidx]; nms_nsel = nms_nsel_s[sidx];
         out_scores = out_scores_s[sidx]; out_means = out_means_s[sidx];
         out_covs = out_covs_s[sidx]; out_counts = out_counts_s[sidx];
-        out_parts = out_parts_s[sidx];
+        out_parts = out_parts_s[sidx]; out_cparts = out_cparts_s[sidx];
     }
     float* iou_scratch = nullptr; int64_t iou_cap = 0;
     float* affinity = nullptr; int affinity_img = -1;   // bod_set_affinity: centre columns of a caller-supplied affinity matrix (one-shot)
@@ -727,6 +737,7 @@ bod_status ensure_stat(bod_context* h) {
     BODCHK(h->dalloc(&h->stat_acc[0], BA * c.num_classes));
     BODCHK(h->dalloc(&h->stat_acc[1], BA * 16));
     if (c.has_covar_head) BODCHK(h->dalloc(&h->stat_acc[2], BA * 10));
+    if (c.covariance_parts & BOD_PARTS_CLASS) BODCHK(h->dalloc(&h->stat_ent, BA));
     return BOD_OK;
 }
 
@@ -1067,6 +1078,7 @@ bod_status build_plan(bod_context* h) {
         BODCHK(h->dalloc(&h->agg[0], BA * c.num_classes));
         BODCHK(h->dalloc(&h->agg[1], BA * 16));
         if (c.has_covar_head) BODCHK(h->dalloc(&h->agg[2], BA * 10));
+        if (h->class_parts) BODCHK(h->dalloc(&h->ent, BA));
     } else {
         BODCHK(ensure_raw(h));                 // the ops below reference the raw tensors directly
     }
@@ -1075,6 +1087,7 @@ bod_status build_plan(bod_context* h) {
         const size_t per[3] = {(size_t)c.num_classes, 16, 10};
         for (int k = 0; k < (c.has_covar_head ? 3 : 2); ++k)
             if (!h->agg[k]) BODCHK(h->dalloc(&h->agg[k], BA * per[k]));
+        if (h->class_parts && !h->ent) BODCHK(h->dalloc(&h->ent, BA));
         BODCHK(ensure_stat(h));
     }
     // ---- Sparse tail: only the classification head's statistics decide which anchors are kept (post_sample_kernel), and everything
@@ -1191,6 +1204,7 @@ bod_status build_plan(bod_context* h) {
                     cg.out2 = nullptr;
                     cg.agg_kind = hd == 0 ? AGG_CLS : hd == 1 ? AGG_BOX : AGG_COV;
                     cg.agg_n = N; cg.agg_P = h->P; cg.agg_C = c.num_classes; cg.agg_out = h->agg[hd]; cg.anchors = h->d_anchors;
+                    if (hd == 0 && h->class_parts) { cg.agg_kind = AGG_CLS_ENT; cg.out2 = h->ent; }      // + sum_n H(softmax) [B,A]
                 }
                 fused_flops += 2.0 * ((double)B * N * h->P) * 256.0 * out_ch[hd];      // the 1x1 output conv runs inside this launch
             }
@@ -1370,15 +1384,22 @@ bod_status alloc_post(bod_context* h) {
         BODCHK(h->dalloc(&h->out_means_s[sidx], BK * 4));
         BODCHK(h->dalloc(&h->out_covs_s[sidx], BK * 16));
         BODCHK(h->dalloc(&h->out_counts_s[sidx], BK * c.num_classes));
-        if (c.covariance_parts) BODCHK(h->dalloc(&h->out_parts_s[sidx], BK * 48));
-        const size_t stage_bytes = ((size_t)c.batch + BK * (2 * (size_t)c.num_classes + 20 + (c.covariance_parts ? 48 : 0))) * 4;
+        if (c.covariance_parts & BOD_PARTS_COVARIANCE) BODCHK(h->dalloc(&h->out_parts_s[sidx], BK * 48));
+        if (h->class_parts) BODCHK(h->dalloc(&h->out_cparts_s[sidx], BK * 4));
+        const size_t stage_bytes = ((size_t)c.batch + BK * (2 * (size_t)c.num_classes + 20 + ((c.covariance_parts & BOD_PARTS_COVARIANCE) ? 48 : 0) +
+                                                            (h->class_parts ? 4 : 0))) * 4;
         if (hipHostMalloc(reinterpret_cast<void**>(&h->host_stage[sidx]), stage_bytes, hipHostMallocDefault) != hipSuccess)
             return h->fail(BOD_ERR_OOM, "pinned host staging buffer (%zu bytes)", stage_bytes);
     }
-    if (c.covariance_parts) {
+    if (c.covariance_parts & BOD_PARTS_COVARIANCE) {
         BODCHK(h->dalloc(&h->parts, BA * BOD_PARTS_TRI));
         h->parts_ok.assign((size_t)c.batch, 0);
         for (int sidx = 0; sidx < 2; ++sidx) h->det_parts_ok[sidx].assign((size_t)c.batch, 0);
+    }
+    if (h->class_parts) {
+        BODCHK(h->dalloc(&h->cparts, BA * (3 + (size_t)c.num_classes)));
+        h->cparts_ok.assign((size_t)c.batch, 0);
+        for (int sidx = 0; sidx < 2; ++sidx) h->det_cparts_ok[sidx].assign((size_t)c.batch, 0);
     }
     h->select_slot(0);
     BODCHK(h->dalloc(&h->d_images, (size_t)c.batch * c.image_h * c.image_w * 3));
@@ -1660,6 +1681,7 @@ bod_status run_posterior(bod_context* h, uint64_t seed, uint32_t first_image) {
     }
     HIPCHK(h, keep_done ? launch_posterior_fuse(pc, pb, h->stream) : launch_posterior(pc, pb, h->stream));
     if (h->parts) { HIPCHK(h, launch_posterior_parts(pc, pb, h->parts, h->stream)); std::fill(h->parts_ok.begin(), h->parts_ok.end(), 1); }
+    if (h->cparts) { HIPCHK(h, launch_posterior_class_parts(pc, pb, h->ent, h->cparts, h->stream)); std::fill(h->cparts_ok.begin(), h->cparts_ok.end(), 1); }
     if (h->cfg.ranking_method == BOD_RANK_JOINT_ENTROPY && h->cfg.gaussian_isotropic && h->cfg.dirichlet_non_informative)
         HIPCHK(h, launch_joint_entropy_rank(pc, pb, h->stream));
     if (h->profiling) { HIPCHK(h, hipEventRecord(e1, h->stream)); h->ev_post.emplace_back(e0, e1); }
@@ -1679,6 +1701,10 @@ bod_status run_validation_post(bod_context* h) {
     if (h->parts) {                                   // covs = 0: so are the three terms
         HIPCHK(h, hipMemsetAsync(h->parts, 0, (size_t)h->cfg.batch * h->A * BOD_PARTS_TRI * sizeof(float), h->stream));
         std::fill(h->parts_ok.begin(), h->parts_ok.end(), 1);
+    }
+    if (h->cparts) {                                  // one sample, no MC distribution: zero rows
+        HIPCHK(h, hipMemsetAsync(h->cparts, 0, (size_t)h->cfg.batch * h->A * (3 + h->cfg.num_classes) * sizeof(float), h->stream));
+        std::fill(h->cparts_ok.begin(), h->cparts_ok.end(), 1);
     }
     h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;
     return BOD_OK;
@@ -1709,6 +1735,7 @@ bod_status run_cluster(bod_context* h, hipStream_t st) {
     a.out_scores = h->out_scores; a.out_means = h->out_means; a.out_covs = h->out_covs; a.out_counts = h->out_counts;
     HIPCHK(h, launch_cluster_fuse(a, st));
     if (h->parts) { HIPCHK(h, launch_cluster_parts(a, h->parts, h->out_parts, st)); h->det_parts_ok[h->slot] = h->parts_ok; }
+    if (h->cparts) { HIPCHK(h, launch_cluster_class_parts(a, h->cparts, h->out_cparts, st)); h->det_cparts_ok[h->slot] = h->cparts_ok; }
     h->cluster_done = true;
     return BOD_OK;
 }
@@ -1805,9 +1832,11 @@ bod_status bod_create(const bod_config* cfg, bod_handle* out) {
     if (c.mc_statistics && (c.training || c.pipeline_overlap))
         return bail(h->fail(BOD_ERR_INVALID_ARG, "mc_statistics: statistics handles are inference handles on one stream (%s = 1 refused)",
                             c.training ? "training" : "pipeline_overlap"));
-    if (c.covariance_parts != 0 && c.covariance_parts != 1) return bail(h->fail(BOD_ERR_INVALID_ARG, "covariance_parts must be 0 or 1, got %d", c.covariance_parts));
+    if (c.covariance_parts < 0 || c.covariance_parts > (BOD_PARTS_COVARIANCE | BOD_PARTS_CLASS))
+        return bail(h->fail(BOD_ERR_INVALID_ARG, "covariance_parts must be a set of BOD_PARTS_COVARIANCE (1) and BOD_PARTS_CLASS (2), got %d", c.covariance_parts));
     if (c.covariance_parts && c.training)
         return bail(h->fail(BOD_ERR_INVALID_ARG, "covariance_parts: the parts belong to inference and statistics handles (training = 1 refused)"));
+    h->class_parts = (c.covariance_parts & BOD_PARTS_CLASS) != 0;
     h->es = c.precision == BOD_PRECISION_BF16 ? 2 : 4;
     h->split = c.precision == BOD_PRECISION_BF16X3 || c.precision == BOD_PRECISION_F16MX || c.precision == BOD_PRECISION_F16MX4;
     h->mx = c.precision == BOD_PRECISION_F16MX ? 1 : c.precision == BOD_PRECISION_F16MX4 ? 2 : 0;
@@ -2576,6 +2605,7 @@ bod_status bod_set_posterior(bod_handle h, int32_t img, int32_t m, const float* 
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;
     if (h->parts) h->parts_ok[img] = 0;               // the rows' parts are the previous posterior's until bod_set_posterior_parts
+    if (h->cparts) h->cparts_ok[img] = 0;             // ... until bod_set_posterior_class_parts
     return BOD_OK;
 }
 
@@ -2778,6 +2808,104 @@ bod_status bod_device_detection_parts(bod_handle h, int32_t sidx, void** p) {
     return BOD_OK;
 }
 
+static bod_status class_parts_handle(bod_handle h, const char* who) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    if (!h->class_parts) return h->fail(BOD_ERR_INVALID_ARG, "%s: the handle was created without BOD_PARTS_CLASS in bod_config.covariance_parts", who);
+    return BOD_OK;
+}
+
+bod_status bod_get_posterior_class_parts(bod_handle h, int32_t img, float* rows) {
+    BODCHK(class_parts_handle(h, "bod_get_posterior_class_parts"));
+    BODCHK(join_overlap(h));
+    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
+    int32_t m = 0;
+    BODCHK(image_m(h, img, &m));
+    if (!h->cparts_ok[img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_posterior_class_parts: image %d was injected with bod_set_posterior; bod_set_posterior_class_parts has not followed", img);
+    if (!rows || m == 0) return BOD_OK;
+    const size_t Q = 3 + (size_t)h->cfg.num_classes;
+    std::vector<float> tmp((size_t)m * Q);
+    BODCHK(d2h(h, tmp.data(), h->cparts + (size_t)img * h->A * Q, tmp.size()));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < (size_t)m; ++i)
+        for (int q = 0; q < 3; ++q) rows[i * 3 + q] = tmp[i * Q + q];
+    return BOD_OK;
+}
+
+bod_status bod_get_posterior_mean_probs(bod_handle h, int32_t img, float* mean_probs) {
+    BODCHK(class_parts_handle(h, "bod_get_posterior_mean_probs"));
+    BODCHK(join_overlap(h));
+    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
+    int32_t m = 0;
+    BODCHK(image_m(h, img, &m));
+    if (!h->cparts_ok[img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_posterior_mean_probs: image %d was injected with bod_set_posterior; bod_set_posterior_class_parts has not followed", img);
+    if (!mean_probs || m == 0) return BOD_OK;
+    const size_t C = (size_t)h->cfg.num_classes, Q = 3 + C;
+    std::vector<float> tmp((size_t)m * Q);
+    BODCHK(d2h(h, tmp.data(), h->cparts + (size_t)img * h->A * Q, tmp.size()));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < (size_t)m; ++i)
+        for (size_t j = 0; j < C; ++j) mean_probs[i * C + j] = tmp[i * Q + 3 + j];
+    return BOD_OK;
+}
+
+bod_status bod_set_posterior_class_parts(bod_handle h, int32_t img, int32_t m, const float* mean_probs, const float* rows) {
+    BODCHK(class_parts_handle(h, "bod_set_posterior_class_parts"));
+    BODCHK(join_overlap(h));
+    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior / bod_set_posterior has not run");
+    int32_t mm = 0;
+    BODCHK(image_m(h, img, &mm));
+    if (m != mm || (m > 0 && (!mean_probs || !rows))) return h->fail(BOD_ERR_INVALID_ARG, "bod_set_posterior_class_parts: got %d rows, image %d has %d", m, img, mm);
+    const size_t C = (size_t)h->cfg.num_classes, Q = 3 + C;
+    std::vector<float> tmp((size_t)m * Q);
+    for (size_t i = 0; i < (size_t)m; ++i) {
+        for (int q = 0; q < 3; ++q) tmp[i * Q + q] = rows[i * 3 + q];
+        for (size_t j = 0; j < C; ++j) tmp[i * Q + 3 + j] = mean_probs[i * C + j];
+    }
+    if (m > 0) HIPCHK(h, hipMemcpyAsync(h->cparts + (size_t)img * h->A * Q, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->cparts_ok[img] = 1; h->cluster_done = false;
+    return BOD_OK;
+}
+
+bod_status bod_get_detection_class_parts(bod_handle h, int32_t img, float* rows) {
+    BODCHK(class_parts_handle(h, "bod_get_detection_class_parts"));
+    BODCHK(join_overlap(h));
+    if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+    if (img < 0 || img >= h->cfg.batch) return h->fail(BOD_ERR_INVALID_ARG, "image index out of range");
+    if (!h->det_cparts_ok[h->slot][img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_class_parts: image %d was fused without its posterior's class parts (bod_set_posterior_class_parts)", img);
+    int32_t num = 0;
+    HIPCHK(h, hipMemcpyAsync(&num, h->nms_nsel + img, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    BODCHK(d2h(h, rows, h->out_cparts + (size_t)img * h->cfg.nms_max_output_size * 4, (size_t)num * 4));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BOD_OK;
+}
+
+bod_status bod_get_detection_class_parts_batch(bod_handle h, float* rows) {
+    BODCHK(class_parts_handle(h, "bod_get_detection_class_parts_batch"));
+    BODCHK(join_overlap(h));
+    if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+    for (int img = 0; img < h->cfg.batch; ++img)
+        if (!h->det_cparts_ok[h->slot][img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_class_parts_batch: image %d was fused without its posterior's class parts (bod_set_posterior_class_parts)", img);
+    // rows beyond an image's count are whatever an earlier batch left: zero them on the way out, like the record rows
+    const size_t B = (size_t)h->cfg.batch, K = (size_t)h->cfg.nms_max_output_size;
+    std::vector<int32_t> num(B);
+    HIPCHK(h, hipMemcpyAsync(num.data(), h->nms_nsel, B * 4, hipMemcpyDeviceToHost, h->stream));
+    BODCHK(d2h(h, rows, h->out_cparts, B * K * 4));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t b = 0; rows && b < B; ++b)
+        for (size_t k = (size_t)std::max(num[b], 0); k < K; ++k)
+            for (int q = 0; q < 4; ++q) rows[(b * K + k) * 4 + q] = 0.f;
+    return BOD_OK;
+}
+
+bod_status bod_device_detection_class_parts(bod_handle h, int32_t sidx, void** p) {
+    BODCHK(class_parts_handle(h, "bod_device_detection_class_parts"));
+    if (!p || sidx < 0 || sidx > 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_device_detection_class_parts: slot %d / NULL", sidx);
+    *p = h->out_cparts_s[sidx];
+    return BOD_OK;
+}
+
 bod_status bod_device_raw(bod_handle h, void** p, int32_t mark_ready) {
     if (!h || !p) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
@@ -2863,7 +2991,8 @@ bod_status bod_infer_async(bod_handle h, const float* images, int32_t on_device,
         HIPCHK(h, hipMemcpyAsync(hs, h->out_means_s[sidx], BK * 16, hipMemcpyDeviceToHost, sd)); hs += BK * 16;
         HIPCHK(h, hipMemcpyAsync(hs, h->out_covs_s[sidx], BK * 64, hipMemcpyDeviceToHost, sd)); hs += BK * 64;
         HIPCHK(h, hipMemcpyAsync(hs, h->out_counts_s[sidx], BK * C * 4, hipMemcpyDeviceToHost, sd)); hs += BK * C * 4;
-        if (h->parts) { HIPCHK(h, hipMemcpyAsync(hs, h->out_parts_s[sidx], BK * 48 * 4, hipMemcpyDeviceToHost, sd)); h->parts_staged[sidx] = true; }
+        if (h->parts) { HIPCHK(h, hipMemcpyAsync(hs, h->out_parts_s[sidx], BK * 48 * 4, hipMemcpyDeviceToHost, sd)); h->parts_staged[sidx] = true; hs += BK * 48 * 4; }
+        if (h->cparts) { HIPCHK(h, hipMemcpyAsync(hs, h->out_cparts_s[sidx], BK * 4 * 4, hipMemcpyDeviceToHost, sd)); h->cparts_staged[sidx] = true; }
     }
     HIPCHK(h, hipEventRecord(h->ev_done[sidx], sd));
     h->done_stream[sidx] = sd;
@@ -2898,6 +3027,20 @@ bod_status bod_collect_parts(bod_handle h, int32_t sidx, float* parts) {
     const size_t B = (size_t)h->cfg.batch, BK = B * h->cfg.nms_max_output_size, C = h->cfg.num_classes;
     HIPCHK(h, hipEventSynchronize(h->ev_done[sidx]));
     if (parts) std::memcpy(parts, h->host_stage[sidx] + (B + BK * (2 * C + 20)) * 4, BK * 48 * 4);
+    return BOD_OK;
+}
+
+bod_status bod_collect_class_parts(bod_handle h, int32_t sidx, float* rows) {
+    BODCHK(class_parts_handle(h, "bod_collect_class_parts"));
+    if (sidx < 0 || sidx > 1 || !h->cparts_staged[sidx]) return h->fail(BOD_ERR_NOT_READY, "bod_collect_class_parts: slot %d holds no batch of bod_infer_async", sidx);
+    const size_t B = (size_t)h->cfg.batch, K = (size_t)h->cfg.nms_max_output_size, BK = B * K, C = h->cfg.num_classes;
+    HIPCHK(h, hipEventSynchronize(h->ev_done[sidx]));
+    if (!rows) return BOD_OK;
+    std::memcpy(rows, h->host_stage[sidx] + (B + BK * (2 * C + 20 + (h->parts ? 48 : 0))) * 4, BK * 4 * 4);
+    const int32_t* num = reinterpret_cast<const int32_t*>(h->host_stage[sidx]);      // rows beyond an image's count: zero
+    for (size_t b = 0; b < B; ++b)
+        for (size_t k = (size_t)std::max(num[b], 0); k < K; ++k)
+            for (int q = 0; q < 4; ++q) rows[(b * K + k) * 4 + q] = 0.f;
     return BOD_OK;
 }
 
@@ -3459,7 +3602,7 @@ Rccl& rccl() { static Rccl r; return r; }
 }  // namespace
 }  // extern "C++"
 
-int32_t bod_record_width(bod_handle h) { return h ? 21 + 2 * h->cfg.num_classes + (h->parts ? 48 : 0) : 0; }
+int32_t bod_record_width(bod_handle h) { return h ? 21 + 2 * h->cfg.num_classes + (h->parts ? 48 : 0) + (h->class_parts ? 4 : 0) : 0; }
 
 bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, int32_t world, int32_t rank, int32_t root,
                                  float* gathered_host, float** gathered_device) {
@@ -3494,6 +3637,8 @@ bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, in
     }
     for (int img = 0; h->parts && img < B; ++img)
         if (!h->det_parts_ok[sidx][img]) return h->fail(BOD_ERR_NOT_READY, "bod_gather_detections: image %d was fused without its posterior's parts (bod_set_posterior_parts)", img);
+    for (int img = 0; h->cparts && img < B; ++img)
+        if (!h->det_cparts_ok[sidx][img]) return h->fail(BOD_ERR_NOT_READY, "bod_gather_detections: image %d was fused without its posterior's class parts (bod_set_posterior_class_parts)", img);
     if (!h->rec_send && hipMalloc(reinterpret_cast<void**>(&h->rec_send), block * 4) != hipSuccess)
         return h->fail(BOD_ERR_OOM, "bod_gather_detections: %zu bytes", block * 4);
     // rec_send / rec_recv are shared by the ticket gathers (side stream) and the synchronous form (main stream): a gather that goes to
@@ -3501,7 +3646,10 @@ bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, in
     if (h->ev_gather && h->gather_stream && h->gather_stream != st) HIPCHK(h, hipStreamWaitEvent(st, h->ev_gather, 0));
     // (on the side stream: behind the slot's event; on the records' own stream the wait is a no-op)
     if (slot >= 0) HIPCHK(h, hipStreamWaitEvent(st, h->ev_done[slot], 0));
-    if (h->parts)
+    if (h->cparts)
+        HIPCHK(h, launch_pack_records_class(h->nms_nsel_s[sidx], h->out_scores_s[sidx], h->out_means_s[sidx], h->out_covs_s[sidx],
+                                            h->out_counts_s[sidx], h->out_parts_s[sidx], h->out_cparts_s[sidx], h->rec_send, B, K, C, st));
+    else if (h->parts)
         HIPCHK(h, launch_pack_records_parts(h->nms_nsel_s[sidx], h->out_scores_s[sidx], h->out_means_s[sidx], h->out_covs_s[sidx],
                                             h->out_counts_s[sidx], h->out_parts_s[sidx], h->rec_send, B, K, C, st));
     else
@@ -3611,6 +3759,8 @@ static bod_status stat_view_ready(bod_handle h, const char* who, int32_t view) {
 static bod_status stat_fold(bod_handle h, const char* who, const float* cls, const float* box, const float* cov, int kb, int32_t view = BOD_VIEW_IDENTITY) {
     if (kb < 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: a record of %d samples", who, kb);
     if (h->stat_k > (1 << 24) - kb) return h->fail(BOD_ERR_INVALID_ARG, "%s: more than 2^24 samples in one accumulator", who);
+    if (h->class_parts && h->stat_ent_k != h->stat_k)
+        return h->fail(BOD_ERR_NOT_READY, "%s: ent_sum holds %d of the record's %d samples (bod_stat_merge_entropy / bod_stat_set_entropy has not followed)", who, h->stat_ent_k, h->stat_k);
     StatMergeArgs m{};
     m.BA = (int64_t)h->cfg.batch * h->A; m.C = h->cfg.num_classes; m.ka = h->stat_k; m.kb = kb;
     m.acc_cls = h->stat_acc[0]; m.acc_box = h->stat_acc[1]; m.acc_cov = h->stat_acc[2];
@@ -3632,10 +3782,32 @@ static bod_status stat_fold(bod_handle h, const char* who, const float* cls, con
     return BOD_OK;
 }
 
+// The record's fourth array on BOD_PARTS_CLASS handles: stat_ent (+)= ent_sum (acc + src whatever the sample counts; a copy into an
+// accumulator that holds none), read through the mirror map for BOD_VIEW_HFLIP.  It follows the stat_fold of the same record and
+// brings stat_ent_k level with stat_k.
+static bod_status stat_fold_entropy(bod_handle h, const char* who, const float* ent, int32_t view = BOD_VIEW_IDENTITY) {
+    if (!ent) return h->fail(BOD_ERR_INVALID_ARG, "%s: ent_sum is NULL", who);
+    if (ent == h->stat_ent) return h->fail(BOD_ERR_INVALID_ARG, "%s: the source is the accumulator itself", who);
+    if ((uintptr_t)ent & 15u) return h->fail(BOD_ERR_INVALID_ARG, "%s: ent_sum must be 16-byte aligned", who);
+    if (h->stat_ent_k >= h->stat_k) return h->fail(BOD_ERR_NOT_READY, "%s: ent_sum already holds the record's %d samples (fold the three arrays first)", who, h->stat_k);
+    const int64_t BA = (int64_t)h->cfg.batch * h->A;
+    if (view == BOD_VIEW_HFLIP) {
+        StatMirrorArgs mm{};
+        mm.A = h->A; mm.K = h->cfg.anchors_per_location; mm.nlev = h->nlev;
+        for (int l = 0; l < h->nlev; ++l) { mm.lvl_off[l] = (int32_t)h->lvl_p0[l] * mm.K; mm.lvl_w[l] = h->lw[l]; }
+        mm.lvl_off[h->nlev] = h->A;
+        HIPCHK(h, launch_stat_merge_entropy(h->stat_ent, ent, BA, h->stat_ent_k == 0, &mm, h->stream));
+    } else {
+        HIPCHK(h, launch_stat_merge_entropy(h->stat_ent, ent, BA, h->stat_ent_k == 0, nullptr, h->stream));
+    }
+    h->stat_ent_k = h->stat_k;
+    return BOD_OK;
+}
+
 bod_status bod_stat_reset(bod_handle h) {
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(stat_handle(h, "bod_stat_reset"));
-    h->stat_k = 0;
+    h->stat_k = 0; h->stat_ent_k = 0;
     return BOD_OK;
 }
 
@@ -3672,9 +3844,12 @@ static bod_status stat_forward_view(bod_handle h, const char* who, const float* 
         r.B = c.batch; r.N = n; r.A = h->A; r.C = c.num_classes;
         r.cls = h->raw[0]; r.box = h->raw[1]; r.cov = c.has_covar_head ? h->raw[2] : nullptr; r.anchors = h->d_anchors;
         r.cls_sum = h->agg[0]; r.box_moments = h->agg[1]; r.cov_sum = c.has_covar_head ? h->agg[2] : nullptr;
+        r.ent_sum = h->ent;                               // nullptr without BOD_PARTS_CLASS
         HIPCHK(h, launch_stat_from_raw(r, h->stream));
     }
-    return stat_fold(h, who, h->agg[0], h->agg[1], h->agg[2], n, view);
+    BODCHK(stat_fold(h, who, h->agg[0], h->agg[1], h->agg[2], n, view));
+    if (h->class_parts) BODCHK(stat_fold_entropy(h, who, h->ent, view));
+    return BOD_OK;
 }
 
 bod_status bod_stat_forward(bod_handle h, const float* images, int32_t on_device, uint64_t seed, uint32_t first_image_id, int32_t sample_base) {
@@ -3695,12 +3870,18 @@ bod_status bod_stat_merge_from(bod_handle dst, bod_handle src) {
     const char* field = a.device != b.device ? "device" : a.batch != b.batch ? "batch" : dst->A != src->A ? "num_anchors" :
                         a.num_classes != b.num_classes ? "num_classes" : a.has_covar_head != b.has_covar_head ? "has_covar_head" : nullptr;
     if (field) return dst->fail(BOD_ERR_INVALID_ARG, "bod_stat_merge_from: the handles differ in %s", field);
+    if (dst->class_parts && !src->class_parts)
+        return dst->fail(BOD_ERR_INVALID_ARG, "bod_stat_merge_from: src carries no ent_sum (it was created without BOD_PARTS_CLASS in covariance_parts, dst with it)");
     BODCHK(stat_handle(dst, "bod_stat_merge_from"));
     if (src->stat_k == 0) return BOD_OK;
     if (stat_handle(src, "bod_stat_merge_from") != BOD_OK) return dst->fail(BOD_ERR_HIP, "bod_stat_merge_from: src: %s", src->err.c_str());
+    if (dst->class_parts && (src->stat_ent_k != src->stat_k || dst->stat_ent_k != dst->stat_k))
+        return dst->fail(BOD_ERR_NOT_READY, "bod_stat_merge_from: ent_sum is behind its record (src %d of %d samples, dst %d of %d)", src->stat_ent_k, src->stat_k,
+                         dst->stat_ent_k, dst->stat_k);
     HIPCHK(dst, hipEventRecord(src->ev_stat, src->stream));              // src's accumulator is complete ...
     HIPCHK(dst, hipStreamWaitEvent(dst->stream, src->ev_stat, 0));
     BODCHK(stat_fold(dst, "bod_stat_merge_from", src->stat_acc[0], src->stat_acc[1], src->stat_acc[2], src->stat_k));
+    if (dst->class_parts) BODCHK(stat_fold_entropy(dst, "bod_stat_merge_from", src->stat_ent));
     HIPCHK(dst, hipEventRecord(dst->ev_stat, dst->stream));              // ... and is not rewritten before the merge has read it
     HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev_stat, 0));
     return BOD_OK;
@@ -3755,6 +3936,42 @@ bod_status bod_stat_set(bod_handle h, const float* cls_sum, const float* box_mom
     if (cov_sum) HIPCHK(h, hipMemcpyAsync(h->stat_acc[2], cov_sum, BA * 40, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->stat_k = samples;
+    h->stat_ent_k = 0;                                    // BOD_PARTS_CLASS handles: bod_stat_set_entropy follows
+    return BOD_OK;
+}
+
+bod_status bod_stat_merge_entropy(bod_handle h, const void* ent_sum, int32_t view) {
+    BODCHK(class_parts_handle(h, "bod_stat_merge_entropy"));
+    BODCHK(stat_handle(h, "bod_stat_merge_entropy"));
+    BODCHK(stat_view_ready(h, "bod_stat_merge_entropy", view));
+    return stat_fold_entropy(h, "bod_stat_merge_entropy", static_cast<const float*>(ent_sum), view);
+}
+
+bod_status bod_stat_device_entropy(bod_handle h, void** ptr) {
+    BODCHK(class_parts_handle(h, "bod_stat_device_entropy"));
+    BODCHK(stat_handle(h, "bod_stat_device_entropy"));
+    if (!ptr) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_device_entropy: ptr is NULL");
+    *ptr = h->stat_ent;
+    return BOD_OK;
+}
+
+bod_status bod_stat_get_entropy(bod_handle h, float* ent_sum) {
+    BODCHK(class_parts_handle(h, "bod_stat_get_entropy"));
+    BODCHK(stat_handle(h, "bod_stat_get_entropy"));
+    if (h->stat_ent_k != h->stat_k)
+        return h->fail(BOD_ERR_NOT_READY, "bod_stat_get_entropy: ent_sum holds %d of the record's %d samples", h->stat_ent_k, h->stat_k);
+    BODCHK(d2h(h, ent_sum, h->stat_ent, (size_t)h->cfg.batch * h->A));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BOD_OK;
+}
+
+bod_status bod_stat_set_entropy(bod_handle h, const float* ent_sum) {
+    BODCHK(class_parts_handle(h, "bod_stat_set_entropy"));
+    BODCHK(stat_handle(h, "bod_stat_set_entropy"));
+    if (!ent_sum) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_set_entropy: ent_sum is NULL");
+    HIPCHK(h, hipMemcpyAsync(h->stat_ent, ent_sum, (size_t)h->cfg.batch * h->A * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->stat_ent_k = h->stat_k;
     return BOD_OK;
 }
 
@@ -3762,6 +3979,8 @@ bod_status bod_stat_posterior(bod_handle h, uint64_t seed, uint32_t first_image_
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(stat_handle(h, "bod_stat_posterior"));
     if (h->stat_k < 2) return h->fail(BOD_ERR_NOT_READY, "bod_stat_posterior: the accumulator holds %d samples; bayes_od needs >= 2 (sample covariance divides by N-1)", h->stat_k);
+    if (h->class_parts && h->stat_ent_k != h->stat_k)
+        return h->fail(BOD_ERR_NOT_READY, "bod_stat_posterior: ent_sum holds %d of the record's %d samples (bod_stat_merge_entropy / bod_stat_set_entropy has not followed)", h->stat_ent_k, h->stat_k);
     if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called");
     for (int sidx = 0; sidx < 2; ++sidx)
         if (h->side_pending[sidx]) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_done[sidx], 0));
@@ -3775,6 +3994,7 @@ bod_status bod_stat_posterior(bod_handle h, uint64_t seed, uint32_t first_image_
     h->keep_ready = false;                               // the keep flags are rewritten
     HIPCHK(h, launch_posterior(pc, pb, h->stream));
     if (h->parts) { HIPCHK(h, launch_posterior_parts(pc, pb, h->parts, h->stream)); std::fill(h->parts_ok.begin(), h->parts_ok.end(), 1); }
+    if (h->cparts) { HIPCHK(h, launch_posterior_class_parts(pc, pb, h->stat_ent, h->cparts, h->stream)); std::fill(h->cparts_ok.begin(), h->cparts_ok.end(), 1); }
     if (h->cfg.ranking_method == BOD_RANK_JOINT_ENTROPY && h->cfg.gaussian_isotropic && h->cfg.dirichlet_non_informative)
         HIPCHK(h, launch_joint_entropy_rank(pc, pb, h->stream));
     h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;

@@ -35,7 +35,8 @@ struct ConvGroup {         // element type of in / w / res / out_relu: bf16 (def
     // a tile never leave the CU -- the tile holds ALL agg_n samples of its pixels (row = pixel_slot * agg_n + sample, see the
     // "aggregated" row tables of engine.hip), the fp32 outputs go through LDS and one thread per (pixel, anchor) reduces over
     // the samples: AGG_CLS sum_n softmax(logits) [B,A,C]; AGG_BOX Welford mean + M2 of the decoded boxes [B,A,16] (mean 4, lower
-    // triangle of M2 10, 2 pad); AGG_COV sum_n of the covariance parameters [B,A,10].  out2 is then unused.
+    // triangle of M2 10, 2 pad); AGG_COV sum_n of the covariance parameters [B,A,10].  out2 is then unused, except by AGG_CLS_ENT
+    // (BOD_PARTS_CLASS handles): AGG_CLS plus sum_n H(softmax(logits_n)), one float per (image, anchor), stored to out2 [B,A].
     int32_t agg_kind;
     int32_t agg_n;         // MC samples per pixel in a tile
     int32_t agg_P;         // pixels per image (RowEnt.pad0 = (image * agg_n + sample) * agg_P + pixel)
@@ -59,7 +60,7 @@ struct ConvGroup {         // element type of in / w / res / out_relu: bf16 (def
     // the fused 1x1 + aggregation and every other consumer read); 2 = "h4" rows (f16mx4: e2m1 cross terms, scale bytes in chunk 6)
     int32_t out_hx;
 };
-enum : int32_t { AGG_NONE = 0, AGG_CLS = 1, AGG_BOX = 2, AGG_COV = 3 };
+enum : int32_t { AGG_NONE = 0, AGG_CLS = 1, AGG_BOX = 2, AGG_COV = 3, AGG_CLS_ENT = 4 };
 
 enum : int32_t { CONV_RELU = 1, CONV_DROPOUT = 2, CONV_OUT_F32 = 4,
                  CONV_ACCUM = 8,       // with CONV_OUT_F32: out += result (input gradients of 1x1 layers accumulate in place)
@@ -289,12 +290,31 @@ hipError_t launch_iou_matrix(const float* corners, int M, float* out, hipStream_
 #define BOD_PARTS_TRI 30
 hipError_t launch_posterior_parts(const PostCfg& c, const PostBuffers& b, float* parts, hipStream_t s);
 hipError_t launch_cluster_parts(const ClusterArgs& a, const float* parts, float* out_parts, hipStream_t s);
+// Class-entropy parts (bod_config.covariance_parts bit BOD_PARTS_CLASS): the entropy of the MC predictive class
+// distribution split into its aleatoric part (mean of the samples' entropies), the mutual information between class and weights
+// (epistemic) and, per detection, the disagreement between the members' mean distributions (spatial).
+//   launch_posterior_class_parts  behind post_fuse_kernel, one thread per kept slot: cparts [B,A,3+C] = total, aleatoric, epistemic,
+//                                 mean_probs[C].  ent_sum [B,A] = sum_n H(softmax(logits_n)) with PostCfg.aggregated (the epilogue's
+//                                 AGG_CLS_ENT / the statistics record); otherwise it is summed here from raw cls, operation for
+//                                 operation as agg_reduce_cls<C, true> does
+//   launch_cluster_class_parts    beside cluster_fuse_kernel (same ClusterArgs, same membership test): out [B,max_out,4] = total,
+//                                 aleatoric, epistemic_mc, epistemic_spatial
+// log(sden) of a sample's entropy, sden = sum_j exp(l_j - max l) in [1, C]: the hardware log2 (v_log_f32, 1 ulp; no denormal
+// input here) times ln 2.  Not logf: the library routine's inlined code differs between translation units built with and without
+// -ffp-contract=off (its ln 2 multiply-add fuses in one and not in the other), and the three places that form ent_sum -- the
+// head epilogue in conv_igemm.hip, post_kernels.hip, stat_kernels.hip -- must agree bit for bit.
+#define BOD_LOG_SDEN(x) (__builtin_amdgcn_logf(x) * 0.693147180559945f)
+hipError_t launch_posterior_class_parts(const PostCfg& c, const PostBuffers& b, const float* ent_sum, float* cparts, hipStream_t s);
+hipError_t launch_cluster_class_parts(const ClusterArgs& a, const float* cparts, float* out_cparts, hipStream_t s);
 // detection records [B][K][1 + 4 + 16 + 2C] of the multi-GPU gather (zero rows beyond num[b])
 hipError_t launch_pack_records(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
                                float* rec, int B, int K, int C, hipStream_t s);
 // the same rows with the three covariance parts appended behind the counts: [B][K][1 + 4 + 16 + 2C + 48]
 hipError_t launch_pack_records_parts(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
                                      const float* parts, float* rec, int B, int K, int C, hipStream_t s);
+// rows of a BOD_PARTS_CLASS handle: [B][K][1 + 4 + 16 + 2C (+ 48 when parts != nullptr) + 4], the class-entropy parts last
+hipError_t launch_pack_records_class(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
+                                     const float* parts, const float* cparts, float* rec, int B, int K, int C, hipStream_t s);
 
 struct PreprocArgs {
     const uint8_t* src;        // [B, sh, sw, 3] uint8 RGB
@@ -393,6 +413,7 @@ struct StatRawArgs {
     const float* cls; const float* box; const float* cov;      // raw [B,N,A,C], [B,N,A,4], [B,N,A,10] (cov: nullptr without the head)
     const float* anchors;                                       // [A,4] (v, u, h, w)
     float* cls_sum; float* box_moments; float* cov_sum;         // [B,A,C], [B,A,16], [B,A,10] (nullptr with cov)
+    float* ent_sum;                                             // [B,A] sum_n H(softmax(logits_n)), or nullptr (records without the entropy)
 };
 hipError_t launch_stat_from_raw(const StatRawArgs& a, hipStream_t s);
 struct StatMergeArgs {
@@ -412,6 +433,10 @@ struct StatMirrorArgs {
     float u_flip;                                               // float(image_w - 1): u' = u_flip - u
 };
 hipError_t launch_stat_merge_mirror(const StatMirrorArgs& a, hipStream_t s);
+// The record's fourth array (BOD_PARTS_CLASS handles): acc = acc + src (copy == 0) or acc = src, float4 accesses; with `mirror` the
+// source is gathered from the partner anchor of mirror->'s level table (the value itself is unchanged under a mirror; mirror->m is
+// not read).  acc and src 16-byte aligned.
+hipError_t launch_stat_merge_entropy(float* acc, const float* src, int64_t BA, int copy, const StatMirrorArgs* mirror, hipStream_t s);
 // out[b,y,x,:] = in[b,y,W-1-x,:], fp32 [B,H,W,3]; in != out
 hipError_t launch_mirror_images(const float* in, float* out, int B, int H, int W, hipStream_t s);
 

@@ -761,6 +761,78 @@ hipError_t launch_posterior_parts(const PostCfg& c, const PostBuffers& b, float*
 }
 
 // ------------------------------------------------------------------------------------------------
+// Class-entropy parts, per kept anchor (bod_config.covariance_parts bit BOD_PARTS_CLASS; kernels.h).  With K samples
+// behind the class statistics and pbar = cls_sum / K (post_sample_kernel's mean):
+//   aleatoric = ent_sum / K        total = -sum_j pbar_j log pbar_j  (0 log 0 = 0)        epistemic = max(total - aleatoric, 0)
+// the mutual information between the class and the weights.  ent_sum = sum_n H(softmax(logits_n)) comes from the head epilogue
+// (conv_igemm.hip agg_reduce_cls<C, true>) or the statistics record when the posterior is aggregated; on the raw route this kernel
+// walks the samples itself with that function's operations in its order, so the two routes agree bit for bit.  One thread per kept
+// slot behind post_fuse_kernel, which -- like post_sample_kernel -- is left as it was.
+// ------------------------------------------------------------------------------------------------
+template <int C>
+__global__ __launch_bounds__(POST_BLOCK) void post_class_parts_kernel(PostCfg c, PostBuffers pb, const float* __restrict__ ent_sum,
+                                                                      float* __restrict__ cparts) {
+    const int b = blockIdx.y;
+    const int m = pb.num_kept[b];
+    for (int slot = blockIdx.x * POST_BLOCK + threadIdx.x; slot < m; slot += gridDim.x * POST_BLOCK) {
+        const size_t o = (size_t)b * c.A + slot;
+        const int a = pb.anchor_index[o];
+        float mp[C];
+        float ent = 0.f;
+#pragma unroll
+        for (int j = 0; j < C; ++j) mp[j] = 0.f;
+        if (c.aggregated) {
+            const float4* l = reinterpret_cast<const float4*>(pb.agg_cls + ((size_t)b * c.A + a) * C);
+#pragma unroll
+            for (int k = 0; k < C / 4; ++k) {
+                const float4 t = l[k];
+                mp[4 * k] = t.x; mp[4 * k + 1] = t.y; mp[4 * k + 2] = t.z; mp[4 * k + 3] = t.w;
+            }
+            ent = ent_sum[(size_t)b * c.A + a];
+        }
+        for (int n = 0; n < (c.aggregated ? 0 : c.N); ++n) {
+            const float* l = pb.cls + (((size_t)b * c.N + n) * c.A + a) * C;
+            float v[C];
+#pragma unroll
+            for (int k = 0; k < C / 4; ++k) {
+                const float4 t = reinterpret_cast<const float4*>(l)[k];
+                v[4 * k] = t.x; v[4 * k + 1] = t.y; v[4 * k + 2] = t.z; v[4 * k + 3] = t.w;
+            }
+            float mx = v[0];
+#pragma unroll
+            for (int j = 1; j < C; ++j) mx = fmaxf(mx, v[j]);
+            float sden = 0.f, dot = 0.f;
+#pragma unroll
+            for (int j = 0; j < C; ++j) { const float d = v[j] - mx; v[j] = expf(d); sden += v[j]; dot += v[j] * d; }
+            ent += BOD_LOG_SDEN(sden) - dot / sden;
+#pragma unroll
+            for (int j = 0; j < C; ++j) mp[j] += v[j] / sden;
+        }
+        const float fk = (float)c.N;
+        float total = 0.f;
+#pragma unroll
+        for (int j = 0; j < C; ++j) {
+            mp[j] = mp[j] / fk;
+            if (mp[j] > 0.f) total -= mp[j] * logf(mp[j]);
+        }
+        const float ale = ent / fk;
+        float* out = cparts + o * (3 + C);
+        out[0] = total; out[1] = ale; out[2] = fmaxf(total - ale, 0.f);
+#pragma unroll
+        for (int j = 0; j < C; ++j) out[3 + j] = mp[j];
+    }
+}
+
+hipError_t launch_posterior_class_parts(const PostCfg& c, const PostBuffers& b, const float* ent_sum, float* cparts, hipStream_t s) {
+    if (!cparts || (c.aggregated && !ent_sum) || (c.C != 4 && c.C != 8)) return hipErrorInvalidValue;
+    const int nblocks = (c.A + POST_BLOCK - 1) / POST_BLOCK;
+    const dim3 grid(std::min(nblocks, POST_FUSE_BLOCKS), c.B);
+    if (c.C == 8) hipLaunchKernelGGL(post_class_parts_kernel<8>, grid, dim3(POST_BLOCK), 0, s, c, b, ent_sum, cparts);
+    else hipLaunchKernelGGL(post_class_parts_kernel<4>, grid, dim3(POST_BLOCK), 0, s, c, b, ent_sum, cparts);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // Sparse tail and halo row tables (kernels.h SparseTailArgs, sparse_tables.h).  One workgroup per image:
 //   1. the pixel flags go to LDS, one phase per flag (kept, tail, 3x3 dilation, halo), all threads;
 //   2. every thread counts the run starts of both tables in its contiguous share of the pixels, a block scan places them, and the
@@ -1550,6 +1622,65 @@ hipError_t launch_cluster_parts(const ClusterArgs& a, const float* parts, float*
     return hipGetLastError();
 }
 
+// Class-entropy parts of the fused detections (kernels.h).  The Dirichlet fusion adds the members' counts with equal
+// weight, so the M members are M * K samples of one object: pbar_c = (sum_i pbar_i) / M, total = H(pbar_c), the aleatoric part and
+// the members' own mutual information are the members' means, and what remains -- the disagreement between the members' mean
+// distributions, >= 0 by Jensen's inequality -- is the spatial part.  Same grid, membership expression and reduction as
+// cluster_fuse_kernel: wave butterflies, one LDS exchange, thread 0 finishes.
+template <int C>
+__global__ __launch_bounds__(CL_BLOCK) void cluster_class_parts_kernel(ClusterArgs a, const float* __restrict__ cparts, float* __restrict__ out_cparts) {
+    constexpr int Q = C + 3;                          // sum pbar_i [C], sum aleatoric_i, sum epistemic_i, members
+    __shared__ float red[4 * Q];
+    const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    if (k >= a.num_selected[b]) return;
+    const int M = a.num_kept[b];
+    const int centre = a.selected[(size_t)b * a.max_out + k];
+    const size_t base = (size_t)b * a.A;
+    const float4* boxes = reinterpret_cast<const float4*>(a.corners) + base;
+    const float4 cbox = boxes[centre];
+    float acc[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) acc[q] = 0.f;
+    const float* aff = (a.affinity && b == a.affinity_img) ? a.affinity + (size_t)k * a.A : nullptr;
+    for (int i = tid; i < M; i += CL_BLOCK) {
+        if (!((aff ? aff[i] : iou_plus1(boxes[i], cbox)) > a.thr)) continue;
+        const float* x = cparts + (base + i) * Q;
+#pragma unroll
+        for (int j = 0; j < C; ++j) acc[j] += x[3 + j];
+        acc[C] += x[1]; acc[C + 1] += x[2]; acc[C + 2] += 1.f;
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        float v = acc[q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) red[wave * Q + q] = v;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) acc[q] = (red[q] + red[Q + q]) + (red[2 * Q + q] + red[3 * Q + q]);
+    const float fm = acc[C + 2];                      // >= 1 with the IoU (the centre is its own member); a caller's affinity may leave none
+    float* out = out_cparts + ((size_t)b * a.max_out + k) * 4;
+    if (!(fm > 0.f)) { out[0] = 0.f; out[1] = 0.f; out[2] = 0.f; out[3] = 0.f; return; }
+    float total = 0.f;
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+        const float pj = acc[j] / fm;
+        if (pj > 0.f) total -= pj * logf(pj);
+    }
+    const float ale = acc[C] / fm, emc = acc[C + 1] / fm;
+    out[0] = total; out[1] = ale; out[2] = emc; out[3] = fmaxf(total - (ale + emc), 0.f);
+}
+
+hipError_t launch_cluster_class_parts(const ClusterArgs& a, const float* cparts, float* out_cparts, hipStream_t s) {
+    if (!cparts || !out_cparts || (a.C != 4 && a.C != 8)) return hipErrorInvalidValue;
+    if (a.C == 8) hipLaunchKernelGGL(cluster_class_parts_kernel<8>, dim3(a.max_out, a.B), dim3(CL_BLOCK), 0, s, a, cparts, out_cparts);
+    else hipLaunchKernelGGL(cluster_class_parts_kernel<4>, dim3(a.max_out, a.B), dim3(CL_BLOCK), 0, s, a, cparts, out_cparts);
+    return hipGetLastError();
+}
+
 __global__ void iou_matrix_kernel(const float4* boxes, int M, float* out) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int i = blockIdx.y;
@@ -1619,6 +1750,41 @@ hipError_t launch_pack_records_parts(const int32_t* num, const float* scores, co
     if (!parts) return hipErrorInvalidValue;
     hipLaunchKernelGGL(pack_records_parts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, num, scores, means, covs, counts, parts,
                        rec, B, K, C);
+    return hipGetLastError();
+}
+
+// The record rows of a BOD_PARTS_CLASS handle: the row (with the 48 covariance-part floats when the handle has them) and the four
+// class-entropy parts last
+__global__ __launch_bounds__(256) void pack_records_class_kernel(const int32_t* __restrict__ num, const float* __restrict__ scores,
+                                                                 const float* __restrict__ means, const float* __restrict__ covs,
+                                                                 const float* __restrict__ counts, const float* __restrict__ parts,
+                                                                 const float* __restrict__ cparts, float* __restrict__ rec, int B, int K, int C) {
+    const int W0 = 21 + 2 * C, W1 = W0 + (parts ? 48 : 0), W = W1 + 4;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * K * W) return;
+    const int w = (int)(i % W);
+    const long row = i / W;                      // b * K + k
+    const int b = (int)(row / K), k = (int)(row % K);
+    float v = 0.f;
+    if (k < num[b]) {
+        if (w == 0) v = 1.f;
+        else if (w < 5) v = means[row * 4 + (w - 1)];
+        else if (w < 21) v = covs[row * 16 + (w - 5)];
+        else if (w < 21 + C) v = scores[row * C + (w - 21)];
+        else if (w < W0) v = counts[row * C + (w - 21 - C)];
+        else if (w < W1) v = parts[row * 48 + (w - W0)];
+        else v = cparts[row * 4 + (w - W1)];
+    }
+    rec[i] = v;
+}
+
+hipError_t launch_pack_records_class(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
+                                     const float* parts, const float* cparts, float* rec, int B, int K, int C, hipStream_t s) {
+    const long n = (long)B * K * (21 + 2 * C + (parts ? 48 : 0) + 4);
+    if (n <= 0) return hipSuccess;
+    if (!cparts) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pack_records_class_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, num, scores, means, covs, counts, parts,
+                       cparts, rec, B, K, C);
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 //   cls_sum     [B,A,C]   sum over samples of softmax(logits)
 //   box_moments [B,A,16]  Welford mean[4] of the decoded boxes, lower triangle of the co-moment sums M2 row-major [10], 0, 0
 //   cov_sum     [B,A,10]  sum over samples of the raw covariance parameters (absent without the covariance head)
+//   ent_sum     [B,A]     sum over samples of H(softmax(logits)) (BOD_PARTS_CLASS handles only; agg_reduce_cls<C, true>)
 //
 // produced from raw [B,n,A,.] head outputs (stat_from_raw_kernel: handles without an aggregating plan) and folded into an
 // accumulator of ka samples (stat_merge_kernel).  The file is built with -ffp-contract=off, the correctly rounded division and the
@@ -14,7 +15,7 @@
 // the mirrored anchors; mapping it back is exact in fp32.  With K anchors per location and level l of W_l columns starting at
 // anchor off_l, anchor a = off_l + (y * W_l + x) * K + k has the partner a' = off_l + (y * W_l + (W_l - 1 - x)) * K + k (a level
 // of one column and the middle column of an odd width are their own partners), and the result at a' from the source record at a is
-//   cls_sum      copied
+//   cls_sum      copied (and so is ent_sum)
 //   mean         (v, u, h, w) -> (v, float(image_w - 1) - u, h, w): the flip of the augmented upload's ground truth, x' = (w-1) - x
 //   M2           the entries with exactly one index equal to 1 -- stored positions 1 (1,0), 4 (2,1), 7 (3,1) -- negated; pads 0
 //   cov_sum      the parameters fill_triangular_4 places at (1,0), (2,1), (3,1) -- indices 8, 6, 2 -- negated (S M S with
@@ -30,7 +31,7 @@
 
 // One thread per (image, anchor); the same operations in the same order as agg_reduce_cls / agg_reduce_box / agg_reduce_cov, whose
 // tile holds the n samples of a pixel as LDS rows -- here they are rows of the raw tensors.
-template <int C>
+template <int C, bool ENT>
 __global__ __launch_bounds__(STAT_BLOCK) void stat_from_raw_kernel(StatRawArgs a) {
     const size_t BA = (size_t)a.B * a.A;
     for (size_t idx = (size_t)blockIdx.x * STAT_BLOCK + threadIdx.x; idx < BA; idx += (size_t)gridDim.x * STAT_BLOCK) {
@@ -38,6 +39,7 @@ __global__ __launch_bounds__(STAT_BLOCK) void stat_from_raw_kernel(StatRawArgs a
         const size_t row0 = b * (size_t)a.N * a.A + an;                  // sample 0; sample n at row0 + n * A
         {   // sum_n softmax(logits)
             float mp[C];
+            float ent = 0.f;
 #pragma unroll
             for (int j = 0; j < C; ++j) mp[j] = 0.f;
             for (int n = 0; n < a.N; ++n) {
@@ -52,14 +54,22 @@ __global__ __launch_bounds__(STAT_BLOCK) void stat_from_raw_kernel(StatRawArgs a
 #pragma unroll
                 for (int j = 1; j < C; ++j) mx = fmaxf(mx, v[j]);
                 float sden = 0.f;
+                if constexpr (ENT) {
+                    float dot = 0.f;
 #pragma unroll
-                for (int j = 0; j < C; ++j) { v[j] = expf(v[j] - mx); sden += v[j]; }
+                    for (int j = 0; j < C; ++j) { const float d = v[j] - mx; v[j] = expf(d); sden += v[j]; dot += v[j] * d; }
+                    ent += BOD_LOG_SDEN(sden) - dot / sden;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < C; ++j) { v[j] = expf(v[j] - mx); sden += v[j]; }
+                }
 #pragma unroll
                 for (int j = 0; j < C; ++j) mp[j] += v[j] / sden;
             }
             float* o = a.cls_sum + idx * C;
 #pragma unroll
             for (int k = 0; k < C / 4; ++k) reinterpret_cast<float4*>(o)[k] = make_float4(mp[4 * k], mp[4 * k + 1], mp[4 * k + 2], mp[4 * k + 3]);
+            if constexpr (ENT) a.ent_sum[idx] = ent;
         }
         {   // Welford mean and co-moment sums of the decoded boxes
             const float4 anc = reinterpret_cast<const float4*>(a.anchors)[an];
@@ -111,8 +121,13 @@ hipError_t launch_stat_from_raw(const StatRawArgs& a, hipStream_t s) {
         return hipErrorInvalidValue;
     const size_t BA = (size_t)a.B * a.A;
     const unsigned grid = (unsigned)std::min<size_t>((BA + STAT_BLOCK - 1) / STAT_BLOCK, STAT_MAX_GRID);
-    if (a.C == 8) hipLaunchKernelGGL(stat_from_raw_kernel<8>, dim3(grid), dim3(STAT_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL(stat_from_raw_kernel<4>, dim3(grid), dim3(STAT_BLOCK), 0, s, a);
+    if (a.ent_sum) {
+        if (a.C == 8) hipLaunchKernelGGL((stat_from_raw_kernel<8, true>), dim3(grid), dim3(STAT_BLOCK), 0, s, a);
+        else hipLaunchKernelGGL((stat_from_raw_kernel<4, true>), dim3(grid), dim3(STAT_BLOCK), 0, s, a);
+    } else {
+        if (a.C == 8) hipLaunchKernelGGL((stat_from_raw_kernel<8, false>), dim3(grid), dim3(STAT_BLOCK), 0, s, a);
+        else hipLaunchKernelGGL((stat_from_raw_kernel<4, false>), dim3(grid), dim3(STAT_BLOCK), 0, s, a);
+    }
     return hipGetLastError();
 }
 
@@ -294,6 +309,57 @@ hipError_t launch_stat_merge_mirror(const StatMirrorArgs& a, hipStream_t s) {
     const unsigned grid = (unsigned)std::min<size_t>((total + STAT_BLOCK - 1) / STAT_BLOCK, STAT_MAX_GRID);
     if (m.C == 8) hipLaunchKernelGGL(stat_merge_mirror_kernel<8>, dim3(grid), dim3(STAT_BLOCK), 0, s, a);
     else hipLaunchKernelGGL(stat_merge_mirror_kernel<4>, dim3(grid), dim3(STAT_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// The record's fourth array, ent_sum [BA]: acc = acc + src (independent of the sample counts), or a copy of the source into an
+// empty accumulator.  One float4 per work item (the last one may be partial), no atomics.  MIRROR: the source is gathered from the
+// partner anchor of stat_merge_mirror_kernel's map; an entropy is unchanged under the mirror.
+template <bool MIRROR>
+__global__ __launch_bounds__(STAT_BLOCK) void stat_merge_entropy_kernel(float* __restrict__ acc, const float* __restrict__ src, size_t BA, int copy,
+                                                                        StatMirrorArgs a) {
+    const size_t total = (BA + 3) / 4;
+    for (size_t it = (size_t)blockIdx.x * STAT_BLOCK + threadIdx.x; it < total; it += (size_t)gridDim.x * STAT_BLOCK) {
+        const size_t e0 = it * 4;
+        if (e0 + 4 <= BA) {
+            float4 sv;
+            if constexpr (MIRROR) {
+                sv = make_float4(src[stat_mirror_partner(a, e0)], src[stat_mirror_partner(a, e0 + 1)], src[stat_mirror_partner(a, e0 + 2)],
+                                 src[stat_mirror_partner(a, e0 + 3)]);
+            } else {
+                sv = reinterpret_cast<const float4*>(src)[it];
+            }
+            float4 r = sv;
+            if (!copy) {
+                const float4 av = reinterpret_cast<const float4*>(acc)[it];
+                r = make_float4(av.x + sv.x, av.y + sv.y, av.z + sv.z, av.w + sv.w);
+            }
+            reinterpret_cast<float4*>(acc)[it] = r;
+        } else {
+            for (size_t e = e0; e < BA; ++e) {
+                const float sv = MIRROR ? src[stat_mirror_partner(a, e)] : src[e];
+                acc[e] = copy ? sv : acc[e] + sv;
+            }
+        }
+    }
+}
+
+hipError_t launch_stat_merge_entropy(float* acc, const float* src, int64_t BA, int copy, const StatMirrorArgs* mirror, hipStream_t s) {
+    if (!acc || !src || acc == src || BA < 1) return hipErrorInvalidValue;
+    if (((reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(src)) & 15u) != 0) return hipErrorInvalidValue;
+    const size_t total = ((size_t)BA + 3) / 4;
+    const unsigned grid = (unsigned)std::min<size_t>((total + STAT_BLOCK - 1) / STAT_BLOCK, STAT_MAX_GRID);
+    if (mirror) {
+        const StatMirrorArgs& a = *mirror;
+        if (a.A < 1 || a.K < 1 || a.nlev < 1 || a.nlev > 8 || BA % a.A != 0 || a.lvl_off[0] != 0 || a.lvl_off[a.nlev] != a.A) return hipErrorInvalidValue;
+        for (int l = 0; l < a.nlev; ++l) {
+            const int span = a.lvl_off[l + 1] - a.lvl_off[l];
+            if (a.lvl_w[l] < 1 || span < 1 || span % (a.lvl_w[l] * a.K) != 0) return hipErrorInvalidValue;
+        }
+        hipLaunchKernelGGL(stat_merge_entropy_kernel<true>, dim3(grid), dim3(STAT_BLOCK), 0, s, acc, src, (size_t)BA, copy, a);
+    } else {
+        hipLaunchKernelGGL(stat_merge_entropy_kernel<false>, dim3(grid), dim3(STAT_BLOCK), 0, s, acc, src, (size_t)BA, copy, StatMirrorArgs{});
+    }
     return hipGetLastError();
 }
 

@@ -18,39 +18,51 @@ def shard_range(num_images, world_size, rank):
 
 RECORD_EXTRA = 1      # per-detection record = [valid, means 4, covs 16, scores C, counts C]
 RECORD_PARTS = 48     # ... + the three covariance parts (epistemic, aleatoric, prior: 3 x 16) on covariance_parts handles
+RECORD_CLASS_PARTS = 4    # ... + total, aleatoric, epistemic_mc, epistemic_spatial class entropy on class_parts handles (last)
 
 
-def record_width(num_classes, cov_parts=False):
-    return RECORD_EXTRA + 4 + 16 + 2 * num_classes + (RECORD_PARTS if cov_parts else 0)
+def record_width(num_classes, cov_parts=False, class_parts=False):
+    return RECORD_EXTRA + 4 + 16 + 2 * num_classes + (RECORD_PARTS if cov_parts else 0) + (RECORD_CLASS_PARTS if class_parts else 0)
 
 
-def pack_records(num, scores, means, covs, counts, cov_parts=None):
+def pack_records(num, scores, means, covs, counts, cov_parts=None, class_parts=None):
     """Padded per-image arrays -> one float32 tensor [B, K, 1+4+16+2C]; slot 0 flags valid rows.
     ``cov_parts`` [B,K,3,4,4] (or [B,K,48]): the wide row of a covariance_parts handle, the parts behind the counts.
+    ``class_parts`` [B,K,4]: the row of a class_parts handle, the four entropies last.
     Works on torch tensors of any device (device-side pack before the RCCL gather)."""
     b, k, _ = scores.shape
     valid = (torch.arange(k, device=scores.device)[None, :] < num.to(scores.device)[:, None]).to(scores.dtype)
     cols = [valid[:, :, None], means.reshape(b, k, 4), covs.reshape(b, k, 16), scores, counts]
     if cov_parts is not None:
         cols.append(cov_parts.reshape(b, k, RECORD_PARTS))
+    if class_parts is not None:
+        cols.append(class_parts.reshape(b, k, RECORD_CLASS_PARTS))
     rec = torch.cat(cols, dim=2)
     return rec * valid[:, :, None]
 
 
 def unpack_records(rec, num_classes):
     """[B,K,W] tensor/array -> list of (scores [k,C], means [k,4], covs [k,4,4], counts [k,C]) per image; rows of the wide
-    form (W = 1+4+16+2C+48) give a fifth element, cov_parts [k,3,4,4]."""
+    form (W = 1+4+16+2C+48) give a further element, cov_parts [k,3,4,4]; rows of a class_parts handle (4 floats wider still) one
+    more, class_parts [k,4] = total, aleatoric, epistemic_mc, epistemic_spatial."""
     rec = rec.detach().cpu().numpy() if isinstance(rec, torch.Tensor) else np.asarray(rec)
     out = []
     c = num_classes
-    if rec.shape[-1] not in (record_width(c), record_width(c, True)):
-        raise ValueError("record rows of %d floats: expected %d or %d for %d classes" % (rec.shape[-1], record_width(c), record_width(c, True), c))
-    wide = rec.shape[-1] == record_width(c, True)
+    widths = {record_width(c, p, q): (p, q) for p in (False, True) for q in (False, True)}
+    if rec.shape[-1] not in widths:
+        raise ValueError("record rows of %d floats: expected one of %s for %d classes" % (rec.shape[-1], sorted(widths), c))
+    wide, cls_parts = widths[rec.shape[-1]]
+    w0 = 21 + 2 * c
+    w1 = w0 + (RECORD_PARTS if wide else 0)
     for r in rec:
         k = int(r[:, 0].sum())
         r = r[:k]
         row = (r[:, 21:21 + c], r[:, 1:5], r[:, 5:21].reshape(k, 4, 4), r[:, 21 + c:21 + 2 * c])
-        out.append(row + (r[:, 21 + 2 * c:].reshape(k, 3, 4, 4),) if wide else row)
+        if wide:
+            row += (r[:, w0:w1].reshape(k, 3, 4, 4),)
+        if cls_parts:
+            row += (r[:, w1:w1 + RECORD_CLASS_PARTS],)
+        out.append(row)
     return out
 
 
@@ -185,17 +197,19 @@ class SampleShardedEngine(object):
 # fp32 round-off, not bit for bit -- SampleShardedEngine stays the bit-identical mode.
 # ---------------------------------------------------------------------------------------------------
 def stat_views(engine):
-    """torch tensors aliasing a statistics handle's accumulator: cls [B,A,C], box [B,A,16], cov [B,A,10] (with the head)."""
-    ptrs = engine.stat_device_pointers()
+    """torch tensors aliasing a statistics handle's accumulator: cls [B,A,C], box [B,A,16], cov [B,A,10] (with the head), ent [B,A]
+    (class_parts handles)."""
+    ptrs = list(engine.stat_device_pointers())
     dev = torch.device("cuda", engine.cfg.device)
     b, a = engine.B, engine.A
-    shapes = {"cls": (b, a, engine.Ccls), "box": (b, a, 16), "cov": (b, a, 10)}
+    shapes = {"cls": (b, a, engine.Ccls), "box": (b, a, 16), "cov": (b, a, 10), "ent": (b, a)}
+    ptrs.append(engine.stat_device_entropy_pointer() if engine.has_class_parts else None)
     return {k: torch.as_tensor(DeviceArray(p, shapes[k], "<f4"), device=dev)
-            for k, p in zip(("cls", "box", "cov"), ptrs) if p}
+            for k, p in zip(("cls", "box", "cov", "ent"), ptrs) if p}
 
 
 def _stat_order(stats):
-    return [k for k in ("cls", "box", "cov") if k in stats]
+    return [k for k in ("cls", "box", "cov", "ent") if k in stats]
 
 
 def all_gather_statistics(local, group=None):
@@ -204,7 +218,16 @@ def all_gather_statistics(local, group=None):
     16-byte boundary of its rank's own buffer, as ``bod_stat_merge`` wants)."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     names = _stat_order(local)
-    flat = torch.cat([local[k].reshape(-1) for k in names])
+    pieces, off, offs = [], 0, {}
+    for k in names:                               # ent starts on a 16-byte boundary: a pad in front of it where cov ends off one
+        v = local[k].reshape(-1)
+        if k == "ent" and off % 4:
+            pieces.append(v.new_zeros(4 - off % 4))
+            off += 4 - off % 4
+        offs[k] = off
+        pieces.append(v)
+        off += v.numel()
+    flat = torch.cat(pieces)
     if world == 1:
         bufs = [flat]
     elif flat.is_cuda and dist.get_backend(group) == "gloo":
@@ -217,11 +240,9 @@ def all_gather_statistics(local, group=None):
         dist.all_gather(bufs, flat, group=group)
     out = []
     for buf in bufs:
-        d, off = {}, 0
+        d = {}
         for k in names:
-            n = local[k].numel()
-            d[k] = buf[off:off + n].view(local[k].shape)
-            off += n
+            d[k] = buf[offs[k]:offs[k] + local[k].numel()].view(local[k].shape)
         out.append(d)
     return out
 
@@ -229,8 +250,14 @@ def all_gather_statistics(local, group=None):
 def merge_statistics_np(a, b, ka, kb, dtype=np.float64):
     """The merge of two statistics records on the host, as include/bayesod.h states it: a, b = (cls_sum [...,C], box_moments
     [...,16], cov_sum [...,10] or None) of ka and kb samples; returns the record of ka + kb samples in ``dtype`` (float64: the
-    statement the tests compare the kernel with; float32: the kernel's own operation order).  Used by nothing in the product path."""
+    statement the tests compare the kernel with; float32: the kernel's own operation order).  Used by nothing in the product path.
+    Records of four arrays (class_parts handles: ent_sum [...] last) give four: ent_sum = a + b whatever ka and kb are."""
     t = np.dtype(dtype).type
+    if len(a) == 4 or len(b) == 4:
+        if len(a) != len(b):
+            raise ValueError("one record carries ent_sum, the other does not")
+        ent = np.array(b[3], dtype=t) if int(ka) == 0 else np.asarray(a[3], dtype=t) + np.asarray(b[3], dtype=t)
+        return merge_statistics_np(a[:3], b[:3], ka, kb, dtype) + (ent,)
     cls_a, box_a, cov_a = a
     cls_b, box_b, cov_b = b
     if int(ka) == 0:
@@ -269,11 +296,12 @@ _M2_FLIP = (5, 8, 11)           # box_moments[4 + k] for the stored M2 positions
 _COV_FLIP = (8, 6, 2)           # the parameters model.fill_triangular_4 places at (1,0), (2,1), (3,1)
 
 
-def mirror_statistics_np(cls_sum, box_moments, cov_sum, level_hw, K, image_w):
+def mirror_statistics_np(cls_sum, box_moments, cov_sum, level_hw, K, image_w, ent_sum=None):
     """The mirror map of a statistics record on the host, as include/bayesod.h states it: the record [..., A, .] of a forward of
     the frames mirrored left-right -> the record of the frames as given.  Anchors move to their partner (``mirror_anchor_index``),
     the ``u`` mean becomes ``(image_w - 1) - u`` (one subtraction in the arrays' dtype), the co-moments with exactly one index
-    equal to 1 and the covariance parameters 8, 6, 2 change sign; everything else is copied.  ``cov_sum`` may be None."""
+    equal to 1 and the covariance parameters 8, 6, 2 change sign; everything else is copied.  ``cov_sum`` may be None.
+    ``ent_sum`` [..., A] (class_parts records): moved to the partner anchor, values unchanged; the result then has four arrays."""
     perm = mirror_anchor_index(level_hw, K)
     if np.shape(box_moments)[-2] != perm.shape[0] or np.shape(cls_sum)[-2] != perm.shape[0]:
         raise ValueError("the level table holds %d anchors, the record %d" % (perm.shape[0], np.shape(box_moments)[-2]))
@@ -287,6 +315,8 @@ def mirror_statistics_np(cls_sum, box_moments, cov_sum, level_hw, K, image_w):
         cov = np.array(np.asarray(cov_sum)[..., perm, :])
         for k in _COV_FLIP:
             cov[..., k] = -cov[..., k]
+    if ent_sum is not None:
+        return cls, box, cov, np.array(np.asarray(ent_sum)[..., perm])
     return cls, box, cov
 
 
@@ -340,11 +370,13 @@ class StatShardedEngine(object):
         torch.cuda.synchronize(self._local["cls"].device)
         eng.stat_reset()
         for rec in self._gathered:                # rank order on every rank
-            eng.stat_merge([rec[k].data_ptr() if k in rec else None for k in ("cls", "box", "cov")], self.n)
+            eng.stat_merge([rec[k].data_ptr() if k in rec else None for k in ("cls", "box", "cov", "ent")], self.n)
         eng.stat_posterior(seed=seed, first_image_id=first_image_id)
         eng.nms()
         eng.cluster_fuse()
         out = [eng.get_detections(i) for i in range(eng.B)]
+        if eng.has_class_parts:                   # a fifth element [K,4]: total, aleatoric, epistemic_mc, epistemic_spatial
+            out = [d + (eng.get_detection_class_parts(i),) for i, d in enumerate(out)]
         return out
 
 

@@ -21,7 +21,7 @@ def make_config(image_hw, batch=1, mc_samples=10, num_classes=8, anchors_per_loc
                 has_covar_head=True, dataset_name='bdd', orig_size=None, nms_variant='A',
                 num_categorical_draws=30, layers=(3, 4, 5, 6, 7), precision='bf16', mc_sample_base=0,
                 mc_ensemble_size=0, training=False, backbone_depth=50, pipeline_overlap=False, mc_statistics=False,
-                covariance_parts=False):
+                covariance_parts=False, class_parts=False):
     """Translates the reference's yaml dictionaries (configs/retinanet_bdd_covar.yaml:61-143)
     into a ``bod_config``."""
     bo = bayes_od_config or {'ranking_method': 'score', 'dirichlet_prior': {'type': 'non_informative'},
@@ -63,9 +63,10 @@ def make_config(image_hw, batch=1, mc_samples=10, num_classes=8, anchors_per_loc
     if cfg.mc_statistics and (cfg.training or cfg.pipeline_overlap):
         raise ValueError("mc_statistics handles are inference handles on one stream: training / pipeline_overlap cannot be combined with it")
     # every posterior row and detection also reports the epistemic / aleatoric / prior terms of its covariance (include/bayesod.h)
-    cfg.covariance_parts = int(bool(covariance_parts))
+    # ... (bit BOD_PARTS_COVARIANCE) and / or the aleatoric / epistemic / spatial parts of its class entropy (bit BOD_PARTS_CLASS)
+    cfg.covariance_parts = (_lib.BOD_PARTS_COVARIANCE if covariance_parts else 0) | (_lib.BOD_PARTS_CLASS if class_parts else 0)
     if cfg.covariance_parts and cfg.training:
-        raise ValueError("covariance_parts belongs to inference and statistics handles: training cannot be combined with it")
+        raise ValueError("covariance_parts / class_parts belong to inference and statistics handles: training cannot be combined with them")
     if dataset_name == 'kitti':
         if orig_size is None:
             raise ValueError("dataset_name='kitti' needs orig_size (sample_dict['im_size'])")
@@ -266,7 +267,11 @@ class Engine(object):
             out = {"num": np.empty(b, np.int32), "scores": np.empty((b, k, c), np.float32),
                    "means": np.empty((b, k, 4), np.float32), "covs": np.empty((b, k, 4, 4), np.float32),
                    "counts": np.empty((b, k, c), np.float32)}
-        if self.cfg.covariance_parts:                 # (before bod_collect: the parts wait for the batch, the records release the slot)
+        if self.cfg.covariance_parts & _lib.BOD_PARTS_CLASS:
+            if "class_parts" not in out:
+                out["class_parts"] = np.empty((b, k, 4), np.float32)
+            self._chk(self.lib.bod_collect_class_parts(self.h, slot, fptr(out["class_parts"])))
+        if self.cfg.covariance_parts & _lib.BOD_PARTS_COVARIANCE:      # (before bod_collect: the parts wait for the batch, the records release the slot)
             if "cov_parts" not in out:
                 out["cov_parts"] = np.empty((b, k, 3, 4, 4), np.float32)
             self._chk(self.lib.bod_collect_parts(self.h, slot, fptr(out["cov_parts"])))
@@ -500,6 +505,59 @@ class Engine(object):
         self._chk(self.lib.bod_device_detection_parts(self.h, slot, C.byref(p)))
         return int(p.value or 0), (self.B, self.K, 3, 16)
 
+    # -- class-entropy parts (handles made with make_config(class_parts=True); include/bayesod.h, DESIGN.md 9.8)
+    @property
+    def has_cov_parts(self):
+        return bool(self.cfg.covariance_parts & _lib.BOD_PARTS_COVARIANCE)
+
+    @property
+    def has_class_parts(self):
+        return bool(self.cfg.covariance_parts & _lib.BOD_PARTS_CLASS)
+
+    def get_posterior_class_parts(self, image_index=0):
+        """[M,3] = total, aleatoric, epistemic entropy of the MC class distribution of every row of ``get_posterior(image_index)``
+        (``bod_get_posterior_class_parts``)."""
+        m = int(self.num_kept()[image_index])
+        rows = np.empty((m, 3), np.float32)
+        self._chk(self.lib.bod_get_posterior_class_parts(self.h, image_index, fptr(rows)))
+        return rows
+
+    def get_posterior_mean_probs(self, image_index=0):
+        """[M,C]: the mean over the MC samples of softmax(class logits) of every row of ``get_posterior(image_index)`` -- the
+        distribution the class parts decompose (``bod_get_posterior_mean_probs``)."""
+        m = int(self.num_kept()[image_index])
+        p = np.empty((m, self.Ccls), np.float32)
+        self._chk(self.lib.bod_get_posterior_mean_probs(self.h, image_index, fptr(p)))
+        return p
+
+    def set_posterior_class_parts(self, image_index, mean_probs, rows):
+        """The injection that goes with ``set_posterior``: ``mean_probs`` [M,C] and ``rows`` [M,3] (``bod_set_posterior_class_parts``)."""
+        mean_probs = as_f32(mean_probs).reshape(-1, self.Ccls)
+        rows = as_f32(rows).reshape(-1, 3)
+        if rows.shape[0] != mean_probs.shape[0]:
+            raise ValueError("mean_probs has %d rows, rows has %d" % (mean_probs.shape[0], rows.shape[0]))
+        self._chk(self.lib.bod_set_posterior_class_parts(self.h, image_index, rows.shape[0], fptr(mean_probs), fptr(rows)))
+
+    def get_detection_class_parts(self, image_index=0):
+        """[K,4] = total, aleatoric, epistemic_mc, epistemic_spatial of every detection of ``get_detections(image_index)``
+        (``bod_get_detection_class_parts``); the last three sum to the first."""
+        rows = np.empty((self.K, 4), np.float32)
+        n = C.c_int32(0)
+        self._chk(self.lib.bod_get_detection_class_parts(self.h, image_index, fptr(rows)))
+        self._chk(self.lib.bod_get_detections(self.h, image_index, C.byref(n), None, None, None, None))
+        return rows[:n.value].copy()
+
+    def get_detection_class_parts_batch(self):
+        """[B,K,4], padded with zero rows like ``get_detections_batch`` (``bod_get_detection_class_parts_batch``)."""
+        rows = np.empty((self.B, self.K, 4), np.float32)
+        self._chk(self.lib.bod_get_detection_class_parts_batch(self.h, fptr(rows)))
+        return rows
+
+    def device_detection_class_parts_pointer(self, slot=0):
+        p = C.c_void_p(0)
+        self._chk(self.lib.bod_device_detection_class_parts(self.h, slot, C.byref(p)))
+        return int(p.value or 0), (self.B, self.K, 4)
+
     def nms(self):
         self._chk(self.lib.bod_nms(self.h))
 
@@ -607,12 +665,38 @@ class Engine(object):
     def stat_merge(self, ptrs, samples, view=0):
         """Fold a record of ``samples`` samples given as device addresses (cls_sum, box_moments, cov_sum or None); ``view='hflip'``:
         the record is that of a mirrored forward and is mapped back while it is folded (``bod_stat_merge_view``)."""
-        p = (C.c_void_p * 3)(*[int(x) if x else None for x in (list(ptrs) + [None])[:3]])
+        ptrs = list(ptrs)
+        p = (C.c_void_p * 3)(*[int(x) if x else None for x in (ptrs + [None])[:3]])
         v = self._view(view)
         if v == _lib.BOD_VIEW_IDENTITY:
             self._chk(self.lib.bod_stat_merge(self.h, p, int(samples)))
         else:
             self._chk(self.lib.bod_stat_merge_view(self.h, p, int(samples), v))
+        if len(ptrs) > 3 and ptrs[3]:                     # a class_parts record: ent_sum follows (bod_stat_merge_entropy)
+            self.stat_merge_entropy(ptrs[3], view=v)
+
+    def stat_merge_entropy(self, ptr, view=0):
+        """Fold the ``ent_sum`` [B,A] (device address) of the record the last ``stat_merge`` folded (``bod_stat_merge_entropy``)."""
+        self._chk(self.lib.bod_stat_merge_entropy(self.h, C.c_void_p(int(ptr)), self._view(view)))
+
+    def stat_device_entropy_pointer(self):
+        """Device address of the accumulator's ``ent_sum`` [B,A] (``bod_stat_device_entropy``)."""
+        p = C.c_void_p(0)
+        self._chk(self.lib.bod_stat_device_entropy(self.h, C.byref(p)))
+        return int(p.value or 0)
+
+    def get_entropy(self):
+        """``ent_sum`` [B,A] of the accumulator: the sum over its samples of the entropy of softmax(class logits)."""
+        ent = np.empty((self.B, self.A), np.float32)
+        self._chk(self.lib.bod_stat_get_entropy(self.h, fptr(ent)))
+        return ent
+
+    def set_entropy(self, ent_sum):
+        """Replace the accumulator's ``ent_sum`` (``bod_stat_set_entropy``); follows ``set_statistics`` on a class_parts handle."""
+        ent = as_f32(ent_sum)
+        if ent.shape != (self.B, self.A):
+            raise ValueError("ent_sum of shape %s, expected %s" % (ent.shape, (self.B, self.A)))
+        self._chk(self.lib.bod_stat_set_entropy(self.h, fptr(ent)))
 
     def stat_device_pointers(self):
         """Device addresses [cls_sum [B,A,C], box_moments [B,A,16], cov_sum [B,A,10] or None] of the accumulator."""
@@ -662,7 +746,7 @@ class Engine(object):
         """The path's one multi-GPU exchange through the C ABI (``bod_gather_detections``): packs this batch's detection
         records on the device and gathers every rank's block on ``root`` with ONE RCCL gather.  ``comm``: an ``ncclComm_t``
         as an integer / ``c_void_p`` (None: single process).  ``slot``: ticket of ``infer_async`` (-1 after ``infer``).
-        Returns [world, B, K, 1+4+16+2C] float32 on the root (None elsewhere; covariance_parts handles: 48 floats wider); unpack
+        Returns [world, B, K, 1+4+16+2C] float32 on the root (None elsewhere; covariance_parts handles: 48 floats wider, class_parts handles: 4); unpack
         with distributed.unpack_records.
         ``want_host=False`` (root only): nothing is copied or waited for; returns ``(device pointer, shape)`` of the gathered
         block, complete after ``collect(slot)`` (a ticket) or ``synchronize()`` (slot -1) -- see include/bayesod.h."""

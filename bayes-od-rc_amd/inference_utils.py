@@ -21,7 +21,7 @@ def _bayes_testing_kwargs(bayes_od_config, nms_config, use_full_covar, dataset_n
 
 def bayes_od_inference(model, sample_dict, bayes_od_config, nms_config, use_full_covar=False,
                        dataset_name='bdd', seed=None, image_id=None, nms_variant='A',
-                       return_iou=True, return_engine=False, covariance_parts=False):
+                       return_iou=True, return_engine=False, covariance_parts=False, class_parts=False):
     """Same 5 return values as the reference (:217) for a batch-of-1 ``sample_dict``:
 
         dirichlet_posterior_count [M,C], gaussian_posterior_means [M,4,1],
@@ -34,7 +34,9 @@ def bayes_od_inference(model, sample_dict, bayes_od_config, nms_config, use_full
     ``bayes_od_clustering(..., engine=)`` re-uses its device buffers.  Without it the two calls are as independent as
     the reference's (run_inference.py:138-149): nothing is remembered between them.
     ``covariance_parts=True`` appends (in front of the engine) gaussian_posterior_cov_parts [M,3,4,4]: the epistemic, aleatoric
-    and prior terms every posterior covariance is the sum of.
+    and prior terms every posterior covariance is the sum of.  ``class_parts=True`` appends (behind it, in front of the engine)
+    class_entropy_parts [M,3+C]: total, aleatoric and epistemic entropy of every row's MC class distribution, then that
+    distribution itself (mean_probs) -- the array ``bayes_od_clustering(..., class_parts=)`` takes.
     """
     image = np.asarray(sample_dict[constants.IMAGE_NORMALIZED_KEY], dtype=np.float32)
     if image.ndim == 3:
@@ -51,6 +53,8 @@ def bayes_od_inference(model, sample_dict, bayes_od_config, nms_config, use_full
                                nms_variant)
     if covariance_parts:
         kw['covariance_parts'] = True
+    if class_parts:
+        kw['class_parts'] = True
     eng = model.engine_for(image.shape[1:3], batch=1, mc_samples=model.mc_dropout_samples, **kw)
     eng.set_anchors(anchors)
     seed = model.seed if seed is None else seed
@@ -66,11 +70,13 @@ def bayes_od_inference(model, sample_dict, bayes_od_config, nms_config, use_full
     out = (post["counts"], post["means"][:, :, None], post["covs"], nms_indices, iou)
     if covariance_parts:
         out += (eng.get_posterior_parts(0),)
+    if class_parts:
+        out += (np.concatenate([eng.get_posterior_class_parts(0), eng.get_posterior_mean_probs(0)], axis=1),)
     return out + (eng,) if return_engine else out
 
 
 def bayes_od_clustering(predicted_boxes_class_counts, predicted_boxes_means, predicted_boxes_covs,
-                        cluster_centers, affinity_matrix=None, affinity_threshold=0.7, engine=None):
+                        cluster_centers, affinity_matrix=None, affinity_threshold=0.7, engine=None, class_parts=None):
     """Bayesian cluster-and-fuse on the device (reference :285-364).
 
     Returns (final_scores [K,C], final_means [K,4,1], final_covs [K,4,4] (x70), final_counts [K,C]).
@@ -81,6 +87,9 @@ def bayes_od_clustering(predicted_boxes_class_counts, predicted_boxes_means, pre
     on the device without ever building the M x M matrix.
     ``engine``: optional handle to run on (``bayes_od_inference(..., return_engine=True)``); by default the call runs on a
     small post-processing handle of its own, sized for M boxes -- it depends on nothing but its arguments, like the reference's.
+    ``class_parts``: the rows' class_entropy_parts [M,3+C] as ``bayes_od_inference(..., class_parts=True)`` returns them (total,
+    aleatoric, epistemic, mean_probs[C]); a fifth value follows, final_class_parts [K,4] = total, aleatoric, epistemic_mc,
+    epistemic_spatial entropy of every detection's MC class distribution.  An ``engine`` must then have been made with the option.
     """
     from .engine import Engine, make_config
     counts = np.ascontiguousarray(predicted_boxes_class_counts, dtype=np.float32)
@@ -89,14 +98,23 @@ def bayes_od_clustering(predicted_boxes_class_counts, predicted_boxes_means, pre
     centres = np.ascontiguousarray(cluster_centers, dtype=np.int32).reshape(-1)
     m, c = counts.shape
     k = centres.shape[0]
+    if class_parts is not None:
+        class_parts = np.ascontiguousarray(class_parts, dtype=np.float32)
+        if class_parts.shape != (m, 3 + c):
+            raise ValueError("class_parts must be [M,3+C] = [%d,%d], got %s" % (m, 3 + c, class_parts.shape))
+        if engine is not None and not engine.has_class_parts:
+            raise ValueError("class_parts needs an engine made with class_parts=True")
     if k == 0 or m == 0:
-        return (np.zeros((0, c), np.float32), np.zeros((0, 4, 1), np.float32),
-                np.zeros((0, 4, 4), np.float32), np.zeros((0, c), np.float32))
-    eng = engine if engine is not None else _standalone_engine(m, c, k)
+        out = (np.zeros((0, c), np.float32), np.zeros((0, 4, 1), np.float32),
+               np.zeros((0, 4, 4), np.float32), np.zeros((0, c), np.float32))
+        return out + (np.zeros((0, 4), np.float32),) if class_parts is not None else out
+    eng = engine if engine is not None else _standalone_engine(m, c, k, class_parts is not None)
     cfg = eng.cfg
     cfg.nms_iou_threshold = float(affinity_threshold)
     eng.update_config(cfg)
     eng.set_posterior(0, counts, means, covs, np.zeros(m, np.float32))
+    if class_parts is not None:
+        eng.set_posterior_class_parts(0, class_parts[:, 3:], class_parts[:, :3])
     eng._set_centres(0, centres)
     if affinity_matrix is not None:
         aff = np.asarray(affinity_matrix)
@@ -107,13 +125,14 @@ def bayes_od_clustering(predicted_boxes_class_counts, predicted_boxes_means, pre
         eng.set_affinity(0, np.ascontiguousarray(aff[:, centres].T, dtype=np.float32))
     eng.cluster_fuse()
     scores, fmeans, fcovs, fcounts = eng.get_detections(0)
-    return scores, fmeans[:, :, None], fcovs, fcounts
+    out = (scores, fmeans[:, :, None], fcovs, fcounts)
+    return out + (eng.get_detection_class_parts(0),) if class_parts is not None else out
 
 
 _standalone = {}
 
 
-def _standalone_engine(m, c, k):
+def _standalone_engine(m, c, k, class_parts=False):
     """Small handle used when bayes_od_clustering is called without a model (pure post-processing):
     geometry only sizes the buffers (A >= M)."""
     from .engine import Engine, make_config
@@ -123,10 +142,11 @@ def _standalone_engine(m, c, k):
         if a >= m:
             break
         side *= 2
-    key = (side, c, max(k, 100))
+    key = (side, c, max(k, 100), bool(class_parts))
     if key not in _standalone:
         nms = {'max_output_size': min(max(k, 100), 512), 'iou_threshold': 0.5, 'soft_nms_sigma': 0.5}
-        _standalone[key] = Engine(make_config((side, side), batch=1, mc_samples=2, num_classes=c, nms_config=nms))
+        _standalone[key] = Engine(make_config((side, side), batch=1, mc_samples=2, num_classes=c, nms_config=nms,
+                                                  class_parts=bool(class_parts)))
     return _standalone[key]
 
 
@@ -149,10 +169,13 @@ def map_dataset_classes(input_dataset, target_dataset, output_classes):
 
 
 def _detections(engine):
-    """Per image the four detection arrays, and the covariance parts behind them on a covariance_parts handle."""
+    """Per image the four detection arrays, the covariance parts behind them on a covariance_parts handle, and the class-entropy
+    parts [K,4] last on a class_parts handle."""
     dets = [engine.get_detections(b) for b in range(engine.B)]
-    if engine.cfg.covariance_parts:
+    if engine.has_cov_parts:
         dets = [d + (engine.get_detection_parts(b),) for b, d in enumerate(dets)]
+    if engine.has_class_parts:
+        dets = [d + (engine.get_detection_class_parts(b),) for b, d in enumerate(dets)]
     return dets
 
 
@@ -162,11 +185,13 @@ class BayesOdPipeline(object):
     cluster-and-fuse for ``batch`` images per call, no host round trip in between."""
 
     def __init__(self, model, image_hw, batch, bayes_od_config, nms_config, use_full_covar=True,
-                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, covariance_parts=False):
+                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, covariance_parts=False, class_parts=False):
         self._kw = dict(bayes_od_config=bayes_od_config, nms_config=nms_config, use_full_covar=use_full_covar,
                         dataset_name=dataset_name, nms_variant=nms_variant, orig_size=orig_size)
         if covariance_parts:
             self._kw['covariance_parts'] = True
+        if class_parts:
+            self._kw['class_parts'] = True
         self.model, self._hw, self._batch = model, tuple(image_hw), batch
         self.engine = self.bind()
         if anchors is not None:
@@ -191,7 +216,8 @@ class BayesOdPipeline(object):
     def __call__(self, images=None, seed=0, first_image_id=0):
         """images [B,H,W,3] (or None to reuse the uploaded device batch).  Returns, per image,
         (output_classes [K,C], output_boxes_vuhw [K,4], output_covs [K,4,4], output_counts [K,C]); a pipeline made with
-        ``covariance_parts=True`` adds output_cov_parts [K,3,4,4] (epistemic, aleatoric, prior)."""
+        ``covariance_parts=True`` adds output_cov_parts [K,3,4,4] (epistemic, aleatoric, prior), one made with ``class_parts=True``
+        output_class_parts [K,4] (total, aleatoric, epistemic_mc, epistemic_spatial) last."""
         self.bind()
         self.engine.infer(images, seed=seed, first_image_id=first_image_id)
         return _detections(self.engine)
@@ -210,7 +236,8 @@ class EnsemblePipeline(object):
     with V views member m, pass p, view index v draws the samples ``((m * passes + p) * V + v) * n ..``."""
 
     def __init__(self, models, image_hw, batch, bayes_od_config, nms_config, samples_per_member, passes=1, use_full_covar=True,
-                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, views=('identity',), covariance_parts=False):
+                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, views=('identity',), covariance_parts=False,
+                 class_parts=False):
         from .engine import Engine, make_config
         models = list(models)
         if not models:
@@ -237,6 +264,7 @@ class EnsemblePipeline(object):
         self._kw = dict(bayes_od_config=bayes_od_config, nms_config=nms_config, use_full_covar=use_full_covar,
                         dataset_name=dataset_name, nms_variant=nms_variant, orig_size=orig_size)
         self._parts = bool(covariance_parts)          # on member 0's handle, where the merged posterior and the fusion run
+        self._class_parts = bool(class_parts)         # on every member's handle: each record carries ent_sum into the merge
         self.engines = []
         for m in models:
             eng = Engine(self._config(m, first=not self.engines))
@@ -251,7 +279,8 @@ class EnsemblePipeline(object):
         return make_config(self._hw, batch=self._batch, mc_samples=self.n, num_classes=m.num_classes + 1,
                            anchors_per_location=m.anchors_per_location, device=m.device, dropout_rate=m.dropout_rate,
                            has_covar_head=m.compute_covar, precision=m.precision, backbone_depth=m.backbone_depth,
-                           mc_ensemble_size=self.total, mc_statistics=True, covariance_parts=self._parts and first, **self._kw)
+                           mc_ensemble_size=self.total, mc_statistics=True, covariance_parts=self._parts and first,
+                           class_parts=self._class_parts, **self._kw)
 
     def set_anchors(self, anchors):
         for eng in self.engines:

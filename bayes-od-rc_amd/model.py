@@ -89,7 +89,7 @@ class RetinaNetModel(object):
         n = mc_samples or self.mc_dropout_samples
         precision = 'bf16' if training else self.precision          # training handles are bf16 (include/bayesod.h)
         key = (int(image_hw[0]), int(image_hw[1]), batch, n, precision, self.backbone_depth, bool(training),
-               bool(testing.get('covariance_parts', False)))
+               bool(testing.get('covariance_parts', False)), bool(testing.get('class_parts', False)))
         cfg = make_config(image_hw, batch=batch, mc_samples=n, num_classes=self.num_classes + 1,
                           anchors_per_location=self.anchors_per_location, device=self.device,
                           dropout_rate=self.dropout_rate, has_covar_head=self.compute_covar,

@@ -25,6 +25,7 @@ from .model import RetinaNetModel
 
 def test_model(config, args):
     test_config = config['testing_config']
+    want_class = _want_class_parts(config, args)          # decided once: the writer and every pipeline get the same answer
     if test_config['uncertainty_method'] != 'bayes_od':
         raise ValueError("only uncertainty_method 'bayes_od' is supported (as in the reference release)")
     dataset_config = config['dataset_config']
@@ -58,12 +59,13 @@ def test_model(config, args):
         if b not in pipes:
             pipes[b] = _make_pipeline(model, args, hw, b, test_config['bayes_od_config'], nms_config,
                                       use_full_covar=test_config['use_full_covar'],
-                                      dataset_name=test_dataset, orig_size=orig, anchors=anchors)
+                                      dataset_name=test_dataset, orig_size=orig, anchors=anchors, class_parts=want_class)
         return pipes[b]
     predictions_dir = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'], 'predictions')
     writer = writers.PredictionWriter(predictions_dir, test_dataset, test_config['ckpt_idx'],
                                       test_config['uncertainty_method'],
-                                      test_config['bayes_od_config']['fusion_method'], cov_parts=_want_parts(args))
+                                      test_config['bayes_od_config']['fusion_method'], cov_parts=_want_parts(args),
+                                      class_parts=want_class)
     categories = dataset_config[training_dataset]['training_data_config']['categories']
     start = time.time()
     n_done = 0
@@ -71,11 +73,12 @@ def test_model(config, args):
         chunk = frames[lo:lo + batch]
         dets = pipe_for(len(chunk))(chunk, seed=args.seed, first_image_id=lo)
         for b, (classes, boxes_vuhw, covs, counts, *parts) in enumerate(dets):
+            parts = _part_kwargs(_want_parts(args), want_class, parts)
             boxes = box_utils.vuhw_to_vuvu_np(boxes_vuhw) if boxes_vuhw.size else boxes_vuhw
             mapped = classes
             if training_dataset != test_dataset and boxes.size > 0:
                 mapped = inference_utils.map_dataset_classes(training_dataset, test_dataset, classes)
-            writer.write('%06d' % (lo + b), boxes, mapped, boxes_vuhw, covs, classes, counts, categories, *parts)
+            writer.write('%06d' % (lo + b), boxes, mapped, boxes_vuhw, covs, classes, counts, categories, **parts)
             n_done += 1
         sys.stdout.write('\r{}'.format(n_done) + ' /' + str(len(frames)))
     writer.close()
@@ -100,13 +103,27 @@ def _want_parts(args):
     return bool(getattr(args, 'covariance_parts', False))
 
 
+def _want_class_parts(config, args):
+    """--class_uncertainty, or the yaml's testing_config.class_uncertainty."""
+    return bool(getattr(args, 'class_uncertainty', False) or config.get('testing_config', {}).get('class_uncertainty', False))
+
+
+def _part_kwargs(want_cov, want_class, parts):
+    """The arrays a pipeline appends to a detection tuple (covariance parts, then class parts) as PredictionWriter.write keywords."""
+    names = (['output_cov_parts'] if want_cov else []) + (['output_class_parts'] if want_class else [])
+    return dict(zip(names, parts))
+
+
 def _make_pipeline(model, args, hw, batch, bayes_od_config, nms_config, **kw):
-    """BayesOdPipeline of the one model, or -- ``model`` a list (--ensemble) -- EnsemblePipeline with the yaml's
+    """``class_parts=``: the caller's ``_want_class_parts(config, args)`` -- the same value its writer was made with.
+    BayesOdPipeline of the one model, or -- ``model`` a list (--ensemble) -- EnsemblePipeline with the yaml's
     mc_dropout_samples per member and --mc_passes passes each.  --tta_flip: every pass runs the frames as given and mirrored
     left-right; without --ensemble that is a one-member EnsemblePipeline of the one model."""
     tta = bool(getattr(args, 'tta_flip', False))
     if _want_parts(args):                 # --covariance_parts: every detection's epistemic / aleatoric / prior covariance
         kw = dict(kw, covariance_parts=True)
+    if kw.pop('class_parts', False):      # --class_uncertainty / testing_config.class_uncertainty, decided once by the caller
+        kw = dict(kw, class_parts=True)
     if isinstance(model, list) or tta:
         members = model if isinstance(model, list) else [model]
         return inference_utils.EnsemblePipeline(members, hw, batch, bayes_od_config, nms_config, members[0].mc_dropout_samples,
@@ -120,6 +137,7 @@ def _test_model_on_dataset(config, args, model):
     of equally sized frames here; preprocessing on the device."""
     from . import constants, datasets
     test_config = config['testing_config']
+    want_class = _want_class_parts(config, args)
     dataset_config = config['dataset_config']
     training_dataset, test_dataset = dataset_config['dataset'], test_config['test_dataset']
     handler = datasets.build_dataset(dict(dataset_config, dataset=test_dataset), 'test')
@@ -127,7 +145,7 @@ def _test_model_on_dataset(config, args, model):
     predictions_dir = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'], 'predictions')
     writer = writers.PredictionWriter(predictions_dir, test_dataset, test_config['ckpt_idx'],
                                       test_config['uncertainty_method'], test_config['bayes_od_config']['fusion_method'],
-                                      cov_parts=_want_parts(args))
+                                      cov_parts=_want_parts(args), class_parts=want_class)
     categories = dataset_config[training_dataset]['training_data_config']['categories']
     gen = FpnAnchorGenerator(dataset_config['anchor_generator'])
     pipes = {}
@@ -136,11 +154,12 @@ def _test_model_on_dataset(config, args, model):
 
     def emit(dets):
         for (name, _, _), (classes, boxes_vuhw, covs, counts, *parts) in zip(pending, dets):
+            parts = _part_kwargs(_want_parts(args), want_class, parts)
             boxes = box_utils.vuhw_to_vuvu_np(boxes_vuhw) if boxes_vuhw.size else boxes_vuhw
             mapped = classes
             if training_dataset != test_dataset and boxes.size > 0:
                 mapped = inference_utils.map_dataset_classes(training_dataset, test_dataset, classes)
-            writer.write(name, boxes, mapped, boxes_vuhw, covs, classes, counts, categories, *parts)
+            writer.write(name, boxes, mapped, boxes_vuhw, covs, classes, counts, categories, **parts)
         del pending[:]
 
     def flush_mixed():
@@ -154,7 +173,7 @@ def _test_model_on_dataset(config, args, model):
             pipes[key] = _make_pipeline(
                 model, args, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
                 use_full_covar=test_config['use_full_covar'], dataset_name=test_dataset, orig_size=hw,
-                anchors=gen.generate_all((hw[0], hw[1], 3)))
+                anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class)
         pipe = pipes[key]
         pipe.upload_mixed([p[1] for p in pending], constants.MEANS_DICT[handler.im_normalization], aspect_resize=kitti)
         emit(pipe(None, seed=args.seed, first_image_id=pending[0][2]))
@@ -172,7 +191,7 @@ def _test_model_on_dataset(config, args, model):
             pipes[key] = _make_pipeline(
                 model, args, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
                 use_full_covar=test_config['use_full_covar'], dataset_name=test_dataset, orig_size=src_hw,
-                anchors=gen.generate_all((hw[0], hw[1], 3)))
+                anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class)
         pipe = pipes[key]
         pipe.bind(orig_size=src_hw)      # the handle may be shared with a pipe of another source size: re-apply the KITTI scale
         pipe.engine.upload_frames_u8(frames, constants.MEANS_DICT[handler.im_normalization], aspect_resize=kitti)
@@ -217,6 +236,10 @@ def main(argv=None):
     ap.add_argument('--covariance_parts', action='store_true', help='also write every detection\'s epistemic, aleatoric and prior '
                     'covariance (cov_epistemic/, cov_aleatoric/, cov_prior/ beside cov/: they sum to it); works with --ensemble, '
                     '--mc_passes and --tta_flip')
+    ap.add_argument('--class_uncertainty', action='store_true', help='also write every detection\'s class entropy and its parts '
+                    '(class_entropy/<frame>.npy [K,4]: total, aleatoric, epistemic_mc, epistemic_spatial; the last three sum to the '
+                    'first) beside cov/; works with --ensemble, --mc_passes, --tta_flip and --covariance_parts; yaml key: '
+                    'testing_config.class_uncertainty')
     args = ap.parse_args(argv)
     config = config_utils.load_yaml(args.yaml_path)
     config = config_utils.setup(config, args)

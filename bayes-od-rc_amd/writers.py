@@ -43,10 +43,13 @@ def predictions_to_kitti_format(output_boxes, output_classes):
 class PredictionWriter(object):
     """Directory layout predictions/testing/<dataset>/<ckpt_id>/<method>_<fusion>/{data,mean,cov,
     cat_param,cat_count} and per-frame files (run_inference.py:90-115,174-236).  ``cov_parts=True`` adds three directories beside
-    them, cov_epistemic / cov_aleatoric / cov_prior, with one [K,4,4] .npy per frame each: the terms ``cov`` is the sum of."""
+    them, cov_epistemic / cov_aleatoric / cov_prior, with one [K,4,4] .npy per frame each: the terms ``cov`` is the sum of.
+    ``class_parts=True`` adds class_entropy with one [K,4] .npy per frame: total, aleatoric, epistemic_mc, epistemic_spatial."""
     PART_DIRS = ('cov_epistemic', 'cov_aleatoric', 'cov_prior')
+    CLASS_DIR = 'class_entropy'
 
-    def __init__(self, predictions_dir, dataset, ckpt_id, uncertainty_method='bayes_od', fusion_method='none', cov_parts=False):
+    def __init__(self, predictions_dir, dataset, ckpt_id, uncertainty_method='bayes_od', fusion_method='none', cov_parts=False,
+                 class_parts=False):
         self.dataset = dataset
         root = os.path.join(predictions_dir, 'testing', dataset, str(ckpt_id), uncertainty_method)
         if uncertainty_method == 'bayes_od':
@@ -55,12 +58,14 @@ class PredictionWriter(object):
         self.dirs = {k: os.path.join(root, k) for k in ('data', 'mean', 'cov', 'cat_param', 'cat_count')}
         if cov_parts:
             self.dirs.update({k: os.path.join(root, k) for k in self.PART_DIRS})
+        if class_parts:
+            self.dirs[self.CLASS_DIR] = os.path.join(root, self.CLASS_DIR)
         for d in self.dirs.values():
             os.makedirs(d, exist_ok=True)
         self.results = []
 
     def write(self, sample_id, output_boxes_vuvu, output_classes_mapped, output_boxes_vuhw, output_covs,
-              output_classes, output_counts, category_list=None, output_cov_parts=None):
+              output_classes, output_counts, category_list=None, output_cov_parts=None, output_class_parts=None):
         if self.dataset == 'kitti':
             rows = predictions_to_kitti_format(output_boxes_vuvu, output_classes_mapped)
             path = os.path.join(self.dirs['data'], sample_id + '.txt')
@@ -81,6 +86,10 @@ class PredictionWriter(object):
             parts = np.asarray(output_cov_parts).reshape(-1, 3, 4, 4)
             for i, k in enumerate(self.PART_DIRS):
                 np.save(os.path.join(self.dirs[k], sample_id + '.npy'), parts[:, i])
+        if self.CLASS_DIR in self.dirs:
+            if output_class_parts is None:
+                raise ValueError("this writer was made with class_parts=True: write() needs output_class_parts [K,4]")
+            np.save(os.path.join(self.dirs[self.CLASS_DIR], sample_id + '.npy'), np.asarray(output_class_parts).reshape(-1, 4))
 
     def close(self):
         if self.dataset != 'kitti':

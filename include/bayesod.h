@@ -116,15 +116,21 @@ typedef struct {
                                     buffers and results exactly as without the field.                                    */
     union {                      /* the last reserved int under both names: the size and every offset are unchanged, and a caller
                                     that zeroes reserved[0] asks for the default                                        */
-        int32_t covariance_parts; /* 1: the handle also reports, for every posterior row and every detection, the three terms
+        int32_t covariance_parts; /* A bit set (BOD_PARTS_* below).  BOD_PARTS_COVARIANCE = 1: the handle also reports, for every
+                                    posterior row and every detection, the three terms
                                     its covariance is the sum of -- epistemic, aleatoric, prior (the bod_*_parts entry points
                                     below).  Inference and statistics handles; refused with training = 1.  Two
                                     more launches per pass, 30 floats per anchor + 48 per detection slot of HBM; record rows
-                                    widen by 48 floats.  0 (default): plans, kernels, buffers and results exactly as without
-                                    the field.                                                                          */
+                                    widen by 48 floats.  BOD_PARTS_CLASS = 2: ... and the entropy of the MC class distribution
+                                    split into aleatoric, epistemic (mutual information) and spatial parts (the
+                                    bod_*_class_parts / bod_stat_*entropy entry points below): one more float
+                                    per anchor from the classification head's epilogue, two more launches per pass, 4 + C
+                                    floats per anchor + 4 per detection slot of HBM; record rows widen by 4 floats.  3: both.
+                                    0 (default): plans, kernels, buffers and results exactly as without the field.          */
         int32_t reserved[1];
     };
 } bod_config;
+enum { BOD_PARTS_COVARIANCE = 1, BOD_PARTS_CLASS = 2 };      /* bits of bod_config.covariance_parts */
 
 /* Sizes the caller needs to allocate host buffers. */
 typedef struct {
@@ -512,7 +518,7 @@ bod_status bod_profile_end(bod_handle h, double* head_conv_ms, int64_t* head_con
 /* ---- the path's ONE multi-GPU exchange for callers of the C ABI (no PyTorch in the loop) ----
  * Images shard across processes (one per GPU); per step every rank contributes the detection records of its batch and `root`
  * receives all of them.  A record row is W = bod_record_width() = 1 + 4 + 16 + 2C floats: [valid, mean (v,u,h,w), covariance
- * row-major, score[C], counts[C]] (covariance_parts handles: + 48, the three parts behind the counts); a rank's block is [batch][max_detections][W], rows beyond an image's detection count are zero.
+ * row-major, score[C], counts[C]] (BOD_PARTS_COVARIANCE handles: + 48, the three parts behind the counts; BOD_PARTS_CLASS handles: + 4, the class-entropy parts last); a rank's block is [batch][max_detections][W], rows beyond an image's detection count are zero.
  *
  * bod_gather_detections packs the records of `slot` (the ticket of bod_infer_async; pass -1 after a synchronous bod_infer) on the
  * device and issues ONE RCCL gather -- ncclGather(send, recv, batch*K*W, ncclFloat32, root, comm, stream).  For a ticket
@@ -536,7 +542,7 @@ int32_t bod_record_width(bod_handle h);
 bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, int32_t world, int32_t rank, int32_t root,
                                  float* gathered_host, float** gathered_device);
 
-/* ---- covariance parts (handles created with bod_config.covariance_parts = 1; every call below returns BOD_ERR_INVALID_ARG on
+/* ---- covariance parts (handles created with BOD_PARTS_COVARIANCE in bod_config.covariance_parts; every call below returns BOD_ERR_INVALID_ARG on
  * any other handle) ----
  * Both fusion steps are linear in the member means, so every covariance they store is exactly the sum of three terms: what the
  * fused mean inherits from the epistemic noise (the sample covariance over the MC samples), from the aleatoric noise (the
@@ -560,6 +566,38 @@ bod_status bod_get_detection_parts(bod_handle h, int32_t image_index, float* par
 bod_status bod_get_detection_parts_batch(bod_handle h, float* parts);
 bod_status bod_collect_parts(bod_handle h, int32_t slot, float* parts);
 bod_status bod_device_detection_parts(bod_handle h, int32_t slot, void** ptr);
+
+/* ---- class-entropy parts (handles created with BOD_PARTS_CLASS in bod_config.covariance_parts; every call below returns
+ * BOD_ERR_INVALID_ARG on any other handle) ----
+ * The MC predictive class distribution of an anchor is the mean pbar of its K samples' softmax rows p_n (the distribution the 30
+ * Dirichlet counts are drawn from; NOT the reported `score`).  Its entropy splits into
+ *   aleatoric = (1/K) sum_n H(p_n)      epistemic = H(pbar) - aleatoric, clamped at 0 (the mutual information of class and weights)
+ * with H(p) = -sum_j p_j log p_j (natural log, 0 log 0 = 0).  sum_n H(p_n) is the statistic ent_sum [B,A] the classification head's
+ * epilogue writes beside cls_sum: H_n = log(sden) - (sum_j v_j (l_j - mx)) / sden with mx = max_j l_j, v_j = exp(l_j - mx),
+ * sden = sum_j v_j; fp32, j and n ascending, no fused multiply-add, log(sden) as the hardware log2 times ln 2; the raw route
+ * computes the same bits.
+ * Per detection the M cluster members count as M * K samples of one object: pbar_c = (sum_i pbar_i) / M, total = H(pbar_c),
+ * aleatoric and epistemic_mc the members' means, epistemic_spatial = max(total - (aleatoric + epistemic_mc), 0) -- the disagreement
+ * between the members' mean distributions.
+ * bod_get_posterior_class_parts: rows [M][3] = total, aleatoric, epistemic of image_index, in bod_get_posterior's order (all
+ * zero after bod_validation_post).
+ * bod_get_posterior_mean_probs: the same rows' pbar [M][C], the other half of what bod_set_posterior_class_parts takes (a caller that
+ * keeps a posterior on the host and injects it again, as inference_utils.bayes_od_clustering does, reads both).
+ * bod_set_posterior_class_parts: the injection that goes with bod_set_posterior (m = the image's row count): mean_probs [m][C]
+ * and rows [m][3].  After bod_set_posterior on an image WITHOUT it, bod_cluster_fuse still runs, and the detection getters of that
+ * image return BOD_ERR_NOT_READY.
+ * bod_get_detection_class_parts / _batch: [K][4] of one image / [batch][max_detections][4] (rows beyond an image's count zero) =
+ * total, aleatoric, epistemic_mc, epistemic_spatial; the last three sum to the first.
+ * bod_collect_class_parts: the rows of a bod_infer_async ticket, as bod_collect_parts.
+ * bod_device_detection_class_parts: device address of a slot's [batch][max_detections][4] array (see bod_device_detections).
+ * On these handles bod_record_width() grows by 4: bod_gather_detections appends the four values last. */
+bod_status bod_get_posterior_class_parts(bod_handle h, int32_t image_index, float* rows);
+bod_status bod_get_posterior_mean_probs(bod_handle h, int32_t image_index, float* mean_probs);
+bod_status bod_set_posterior_class_parts(bod_handle h, int32_t image_index, int32_t m, const float* mean_probs, const float* rows);
+bod_status bod_get_detection_class_parts(bod_handle h, int32_t image_index, float* rows);
+bod_status bod_get_detection_class_parts_batch(bod_handle h, float* rows);
+bod_status bod_collect_class_parts(bod_handle h, int32_t slot, float* rows);
+bod_status bod_device_detection_class_parts(bod_handle h, int32_t slot, void** ptr);
 
 /* What the handle's plan looks like (tests / bench report it; nothing on the hot path reads it).  info8[0] = 1 when the MC
  * statistics are reduced inside the last tower layers' tiles (no [B,N,A,.] tensors on the bod_infer path), [1] = 1 when the 1x1
@@ -640,6 +678,20 @@ bod_status bod_stat_forward_view(bod_handle h, const float* images, int32_t imag
  * fold them).  BOD_VIEW_HFLIP needs the anchors (BOD_ERR_NOT_READY).  bod_stat_merge_from has no view: un-mirror where the
  * forward ran. */
 bod_status bod_stat_merge_view(bod_handle h, const void* const* ptrs3, int32_t samples, int32_t view);
+
+/* ---- the record's fourth array on BOD_PARTS_CLASS statistics handles: ent_sum [B,A], the sum over the samples of the entropy of
+ * softmax(class logits).  Two records merge as ent_sum = a + b whatever their sample counts; the mirror map copies the value
+ * from the partner anchor.  bod_stat_forward[_view] and bod_stat_merge_from fold it with the other three (bod_stat_merge_from
+ * refuses a src without ent_sum when dst carries it: BOD_ERR_INVALID_ARG names the field).  The three-array entry points keep
+ * their signatures; on these handles each of them is FOLLOWED by its entropy call, which brings ent_sum level with K:
+ *   bod_stat_merge[_view]  then  bod_stat_merge_entropy(h, device pointer (16-byte aligned), view)
+ *   bod_stat_set           then  bod_stat_set_entropy(h, host array)
+ * Until then ent_sum is behind the record and bod_stat_posterior, a further fold and bod_stat_get_entropy return
+ * BOD_ERR_NOT_READY.  bod_stat_device_entropy: device address of the accumulator's ent_sum, valid until bod_destroy. */
+bod_status bod_stat_get_entropy(bod_handle h, float* ent_sum);
+bod_status bod_stat_set_entropy(bod_handle h, const float* ent_sum);
+bod_status bod_stat_device_entropy(bod_handle h, void** ptr);
+bod_status bod_stat_merge_entropy(bod_handle h, const void* ent_sum, int32_t view);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,7 @@ typedef struct {
         int32_t reserved[1];
     };
 } bod_config;
+enum { BOD_PARTS_COVARIANCE = 1, BOD_PARTS_CLASS = 2 };
 typedef struct {
     int32_t num_pixels;
     int32_t num_anchors;
@@ -189,6 +190,13 @@ bod_status bod_get_detection_parts(bod_handle h, int32_t image_index, float* par
 bod_status bod_get_detection_parts_batch(bod_handle h, float* parts);
 bod_status bod_collect_parts(bod_handle h, int32_t slot, float* parts);
 bod_status bod_device_detection_parts(bod_handle h, int32_t slot, void** ptr);
+bod_status bod_get_posterior_class_parts(bod_handle h, int32_t image_index, float* rows);
+bod_status bod_get_posterior_mean_probs(bod_handle h, int32_t image_index, float* mean_probs);
+bod_status bod_set_posterior_class_parts(bod_handle h, int32_t image_index, int32_t m, const float* mean_probs, const float* rows);
+bod_status bod_get_detection_class_parts(bod_handle h, int32_t image_index, float* rows);
+bod_status bod_get_detection_class_parts_batch(bod_handle h, float* rows);
+bod_status bod_collect_class_parts(bod_handle h, int32_t slot, float* rows);
+bod_status bod_device_detection_class_parts(bod_handle h, int32_t slot, void** ptr);
 bod_status bod_plan_info(bod_handle h, int32_t* info8);
 bod_status bod_plan_info_n(bod_handle h, int32_t* info, int32_t n);
 bod_status bod_stat_reset(bod_handle h);
@@ -204,3 +212,7 @@ enum { BOD_VIEW_IDENTITY = 0, BOD_VIEW_HFLIP = 1 };
 bod_status bod_stat_forward_view(bod_handle h, const float* images, int32_t images_on_device, uint64_t seed, uint32_t first_image_id,
                                  int32_t sample_base, int32_t view);
 bod_status bod_stat_merge_view(bod_handle h, const void* const* ptrs3, int32_t samples, int32_t view);
+bod_status bod_stat_get_entropy(bod_handle h, float* ent_sum);
+bod_status bod_stat_set_entropy(bod_handle h, const float* ent_sum);
+bod_status bod_stat_device_entropy(bod_handle h, void** ptr);
+bod_status bod_stat_merge_entropy(bod_handle h, const void* ent_sum, int32_t view);
