@@ -135,6 +135,7 @@ SIGNATURES = {
                                      _I, _F, _F]),
     "bod_pdq_corner_heatmaps": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _D, _I, _F]),
     "bod_pdq_frames": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, _I, _I, _I, _D, _D, _D, _D, _F]),
+    "bod_score_pairs": (C.c_int, [C.c_int32, C.c_int64, _D, _D, _D, C.c_int32, C.c_uint64, C.c_uint64, _D, _I]),
     "bod_bench_head_conv": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bod_profile_begin": (C.c_int, [_H]),
     "bod_profile_select": (C.c_int, [_H, C.c_int32]),

@@ -18,6 +18,7 @@ SOURCES = [
     ("post_kernels.hip", ["-ffp-contract=off"]),
     ("loss_kernels.hip", ["-ffp-contract=off"]),
     ("pdq_kernels.hip", ["-ffp-contract=off"]),
+    ("score_kernels.hip", ["-ffp-contract=off"]),
     ("target_kernels.hip", ["-ffp-contract=off"]),
     # the merge of MC statistics is compared with a float64 statement of its formula, the reduction from raw outputs with the
     # fused epilogues' (which are bracketed by `#pragma clang fp contract(off)`) for equality

@@ -3518,6 +3518,13 @@ bod_status bod_pdq_frames(int32_t device, int32_t img_h, int32_t img_w, int32_t 
     });
 }
 
+bod_status bod_score_pairs(int32_t device, int64_t n, const double* means, const double* covs, const double* targets,
+                           int32_t num_samples, uint64_t seed, uint64_t first_row_id, double* out, int32_t* status) {
+    return pdq_call(device, [&](hipStream_t s, char* err, size_t cap) {
+        return score_pairs_run(n, means, covs, targets, num_samples, seed, first_row_id, out, status, s, err, cap);
+    });
+}
+
 bod_status bod_bench_head_conv(bod_handle h, int32_t layer, int32_t variant, int32_t iters, double* mean_ms, double* flops) {
     if (!h || !mean_ms || iters < 1 || layer < 0 || layer > 7) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));

@@ -518,3 +518,6 @@ int pdq_corner_heatmaps_run(int H, int W, int n, const double* means_yx, const d
 int pdq_frames_run(int H, int W, int F, const int32_t* num_gt, const int32_t* gt_boxes, const int32_t* num_det, const int32_t* det_boxes,
                    const double* det_corner_covs, double* fg_loss, double* bg_loss, double* det_bg_loss, float* heatmaps, hipStream_t s,
                    char* errbuf, size_t errcap);
+// Scoring rules (score_kernels.hip): host driver of bod_score_pairs, same conventions; rows are staged in internal batches.
+int score_pairs_run(long long n, const double* means, const double* covs, const double* targets, int num_samples, unsigned long long seed,
+                    unsigned long long first_row_id, double* out, int32_t* status, hipStream_t s, char* errbuf, size_t errcap);

@@ -21,6 +21,7 @@
 // rows in order.  Nothing depends on which other frames share a launch, so one call of N frames and N calls of one frame
 // give the same bits.  The only atomics are integer min / max of the region bounds.
 #include "../../include/bayesod.h"
+#include "host_call.h"
 #include "kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -346,27 +347,6 @@ __global__ __launch_bounds__(PDQ_BLOCK) void pdq_reduce_kernel(const PdqFrame* _
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
-struct Err {
-    char* buf; size_t cap;
-    int fail(int status, const char* fmt, ...) {
-        va_list ap; va_start(ap, fmt); vsnprintf(buf, cap, fmt, ap); va_end(ap);
-        return status;
-    }
-};
-
-struct DevArena {           // device allocations of one call, freed on every exit path
-    std::vector<void*> ptrs;
-    ~DevArena() { for (void* p : ptrs) hipFree(p); }
-    template <typename T> hipError_t alloc(T** p, size_t n) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(n * sizeof(T), 256));
-        if (e == hipSuccess) ptrs.push_back(q);
-        *p = reinterpret_cast<T*>(q);
-        return e;
-    }
-    void release() { for (void* p : ptrs) hipFree(p); ptrs.clear(); }
-};
-
 #define PDQ_HIP(expr)                                                                                       \
     do {                                                                                                    \
         hipError_t _e = (expr);                                                                             \

@@ -72,3 +72,5 @@ BOD_HD DropPair dropout_run_windows(const Philox4& r, int u) {
 }
 
 #define BOD_CAT_TAG 0x00CA7E60u
+// energy-score normals (score_kernels.hip, scoring_rules.py): counter = (sample, row id low, BOD_SCORE_TAG, row id high)
+#define BOD_SCORE_TAG 0x005C04E5u

@@ -1054,3 +1054,23 @@ def pdq_frames(img_hw, num_gt, gt_boxes, num_det, det_boxes, det_corner_covs, de
         p += g_n * d_n
         d += d_n
     return fgs, bgs, dbgs, heat
+
+
+def score_pairs(means, covs, targets, num_samples=1000, seed=0, first_row_id=0, device=0):
+    """Scoring rules of n paired box Gaussians on the device (``bod_score_pairs``, score_kernels.hip): means [n,4], covs
+    [n,4,4] (lower triangle read), targets [n,4].  Returns (out [n,8] float64 = nll, squared Mahalanobis distance, energy
+    score, four PITs, ln det; status [n] int32: 0 ok, 1 not positive definite, 2 non-finite input -- such rows are NaN).
+    Row i draws its normals from the id ``first_row_id + i`` alone (scoring_rules.score_pairs_np is the host twin)."""
+    lib = _lib.load()
+    means = np.ascontiguousarray(means, dtype=np.float64).reshape(-1, 4)
+    covs = np.ascontiguousarray(covs, dtype=np.float64).reshape(-1, 4, 4)
+    targets = np.ascontiguousarray(targets, dtype=np.float64).reshape(-1, 4)
+    n = means.shape[0]
+    if covs.shape[0] != n or targets.shape[0] != n:
+        raise ValueError("means, covs and targets must have one row per pair")
+    out = np.empty((n, 8), np.float64)
+    status = np.zeros(n, np.int32)
+    st = lib.bod_score_pairs(device, n, _lib.dptr(means), _lib.dptr(covs), _lib.dptr(targets), int(num_samples),
+                             int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_row_id) & 0xFFFFFFFFFFFFFFFF, _lib.dptr(out), iptr(status))
+    _lib.check(lib, None, st)
+    return out, status

@@ -13,6 +13,11 @@ The reference scripts hard-code their paths and print a table; here the same com
 
 ``pdq --gpu-device N`` computes the per-pair losses on GPU N (bod_pdq_frames, pdq_kernels.hip); the rest is the same code.
 
+    python -m bayes_od_rc_amd.offline_eval scores --labels val.json --predictions <..>/bayes_od_none [--gpu-device N] [--parts]
+
+``scores`` reports proper scoring rules and calibration of the predictive distributions (scoring_rules.py: NLL, energy
+score, PIT calibration error, the covariance scale that minimises the NLL, classification NLL / Brier / ECE).
+
 ``--predictions`` is the directory holding ``data/ mean/ cov/ cat_param/`` (run_inference.py:90-115); labels are
 BDD-format records ``{name, category, bbox: [x1, y1, x2, y2]}`` or, for KITTI, the label_2 text files (converted to the
 same records by ``kitti_records``).  Host NumPy like the reference.
@@ -223,7 +228,7 @@ def pdq_report(gt_records, tree, frames, img_shape, categories=BDD_CATEGORIES, c
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('metric', choices=('ap', 'mue', 'pdq'))
+    ap.add_argument('metric', choices=('ap', 'mue', 'pdq', 'scores'))
     ap.add_argument('--labels', required=True, help='BDD-format ground-truth json, or (with --dataset kitti) the label_2 directory')
     ap.add_argument('--dataset', default='bdd', choices=('bdd', 'kitti'))
     ap.add_argument('--difficulty', default='all', choices=('easy', 'moderate', 'hard', 'all'))
@@ -231,13 +236,21 @@ def main(argv=None):
     ap.add_argument('--entropy', default='gaussian', choices=('gaussian', 'categorical'))
     ap.add_argument('--compute-method', default='Categorical', choices=('Categorical', 'All'))
     ap.add_argument('--image-size', type=int, nargs=2, default=(720, 1280), metavar=('H', 'W'))
-    ap.add_argument('--gpu-device', type=int, default=None, metavar='N', help='pdq: compute the losses on GPU N (pdq_kernels.hip)')
+    ap.add_argument('--gpu-device', type=int, default=None, metavar='N',
+                    help='pdq: compute the losses on GPU N (pdq_kernels.hip); scores: score the pairs on GPU N (score_kernels.hip)')
+    ap.add_argument('--samples', type=int, default=1000, metavar='M', help='scores: Gaussian samples per pair of the energy score')
+    ap.add_argument('--seed', type=int, default=0, help='scores: seed of the energy score\'s samples')
+    ap.add_argument('--cov-scale', type=float, default=1.0, metavar='X', help='scores: factor on every covariance before scoring')
+    ap.add_argument('--score-threshold', type=float, default=0.5445, metavar='T', help='scores: lowest best-class score of a detection')
+    ap.add_argument('--parts', action='store_true', help='scores: also score the epistemic / aleatoric covariance parts')
     args = ap.parse_args(argv)
     if args.dataset == 'kitti':
         if args.metric == 'ap':
             out = ap_report(*kitti_records(args.labels, args.predictions, args.difficulty))
         elif args.metric == 'pdq':
             out = kitti_pdq_report(args.labels, args.predictions, args.difficulty, device=args.gpu_device)
+        elif args.metric == 'scores':
+            raise SystemExit('scores --dataset kitti: convert the labels to records with kitti_records() and call scoring_rules.scores_report()')
         else:
             raise SystemExit('mue --dataset kitti: convert the labels to records with kitti_records() and call uncertainty_error_report()')
         print(json.dumps(out, indent=1))
@@ -251,6 +264,10 @@ def main(argv=None):
         frames = sorted(f[:-4] for f in os.listdir(os.path.join(args.predictions, 'mean')) if f.endswith('.npy'))
         if args.metric == 'mue':
             out = uncertainty_error_report(gt, args.predictions, frames, entropy_method=args.entropy, compute_method=args.compute_method)
+        elif args.metric == 'scores':
+            from . import scoring_rules                   # (imports this module)
+            out = scoring_rules.scores_report(gt, args.predictions, frames, score_threshold=args.score_threshold, cov_scale=args.cov_scale,
+                                              num_samples=args.samples, seed=args.seed, device=args.gpu_device, parts=args.parts)
         else:
             out = pdq_report(gt, args.predictions, frames, args.image_size, device=args.gpu_device)
     print(json.dumps(out, indent=1))

@@ -497,6 +497,22 @@ bod_status bod_pdq_frames(int32_t device, int32_t img_h, int32_t img_w, int32_t 
                           const double* det_corner_covs, double* fg_loss, double* bg_loss, double* det_bg_loss,
                           float* heatmaps);
 
+/* Scoring rules of the box Gaussian on the device (score_kernels.hip, scoring_rules.py); stateless, fp64.
+ * Row i pairs a 4-dimensional Gaussian (means [n,4], covs [n,4,4]) with a target (targets [n,4]).  L = lower Cholesky
+ * factor of the covariance (Cholesky-Banachiewicz on the LOWER triangle; the upper one is not read).  out [n,8]:
+ *   [0] nll = 0.5 (4 ln 2pi + ln det + m2)          [1] m2 = |L^-1 (g - mu)|^2 (squared Mahalanobis distance)
+ *   [2] energy score (1/M) sum_{i<M} |z_i - g| - 1/(2(M-1)) sum_{i<M-1} |z_i - z_{i+1}|,  z_i = mu + L n_i,  M = num_samples
+ *   [3..6] PIT_k = 0.5 erfc(-(g_k - mu_k) / sqrt(2 cov_kk))                              [7] ln det = 2 sum ln L_kk
+ * status [n]: 2 = a non-finite input, 1 = a pivot <= 0 or non-finite, 0 otherwise; a row with status != 0 gets NaN in its
+ * eight outputs, disturbs no other row and is no error of the call.
+ * Normals: sample i of the row with id r = first_row_id + i_row is ONE call philox4x32_10(i, r & 0xffffffff, 0x005C04E5,
+ * r >> 32, seed & 0xffffffff, seed >> 32) -> (x, y, z, w); u(t) = (t + 0.5) 2^-32; n0, n1 = sqrt(-2 ln u(x)) (cos, sin)
+ * (2 pi u(y)), n2, n3 likewise from (z, w).  A row's result depends on its id alone: not on n, on its position, or on how
+ * rows are split over calls (bitwise).  n = 0 is BOD_OK; n < 0, num_samples outside [2, 65536] or a NULL array with n > 0
+ * fail with BOD_ERR_INVALID_ARG.  Errors via bod_last_error(NULL). */
+bod_status bod_score_pairs(int32_t device, int64_t n, const double* means, const double* covs, const double* targets,
+                           int32_t num_samples, uint64_t seed, uint64_t first_row_id, double* out, int32_t* status);
+
 /* Kernel micro-benchmark (tests/tools): re-launches the `layer`-th head-tower launch of a bod_infer step
  * (0 = de-duplicated fan-out layer, 1 = tower layer 1; on plans with the fused MC aggregation 2 = layer 2 of the
  * heads that continue, 3 = layer 2 of the head that ends there (aggregating), 4 = layer 3; otherwise 2, 3 = layers

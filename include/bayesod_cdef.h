@@ -175,6 +175,8 @@ bod_status bod_pdq_frames(int32_t device, int32_t img_h, int32_t img_w, int32_t 
                           const int32_t* gt_boxes, const int32_t* num_det, const int32_t* det_boxes,
                           const double* det_corner_covs, double* fg_loss, double* bg_loss, double* det_bg_loss,
                           float* heatmaps);
+bod_status bod_score_pairs(int32_t device, int64_t n, const double* means, const double* covs, const double* targets,
+                           int32_t num_samples, uint64_t seed, uint64_t first_row_id, double* out, int32_t* status);
 bod_status bod_bench_head_conv(bod_handle h, int32_t layer, int32_t variant, int32_t iters,
                                double* mean_ms, double* flops_per_launch);
 bod_status bod_profile_begin(bod_handle h);
