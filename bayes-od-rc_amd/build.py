@@ -123,6 +123,7 @@ def build(force=False, verbose=True):
             regs = kernel_guard.verify(os.path.join(obj_dir, "conv_igemm.o"))
             regs.update(kernel_guard.verify_aux(os.path.join(obj_dir, "aux_kernels.o")))
             regs.update(kernel_guard.verify_pointwise(os.path.join(obj_dir, "conv_pointwise.o")))
+            regs.update(kernel_guard.verify_pointwise_stage3(os.path.join(obj_dir, "conv_pointwise.o")))
             n_checked = sum(kernel_guard.check_no_packed_fp32(o) for o in objs)          # (-fno-slp-vectorize took effect everywhere)
             if verbose:
                 print("no packed fp32 instruction in %d kernels" % n_checked, flush=True)

@@ -2657,7 +2657,12 @@ __global__ __launch_bounds__(64 * WC * WP, (ABL == 10 ? (BC == 64 ? 3 : 2) : 1))
         // order -- the valid tiles are dispatched first and spread over all XCDs; the rest of the worst-case grid retires at once.
         // (The persistent form, which would not dispatch them, spills 54 VGPRs: the tile loop keeps the loop's descriptors live.)
         if (a.tile_count) {
-            if (bx >= *a.tile_count) return;
+            // (the valid workgroups take the dense branch's XCD-contiguous tile order over the DEVICE count: a bijection on [0, nb), so
+            //  neighbouring tiles share their halo rows through one L2 here too)
+            const int nb = *a.tile_count;
+            if (bx >= nb) return;
+            const int q = nb >> 3, r = nb & 7, xcd = bx & 7, idx = bx >> 3;
+            bx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
             conv_tile<BC, BP, WC, WP, ABL, XR, SPLIT>(a, gz, bx, by, smem);
             return;
         }

@@ -23,6 +23,12 @@
 
 typedef __attribute__((ext_vector_type(8))) short pw_bf16x8;
 typedef __attribute__((ext_vector_type(16))) float pw_f32x16;
+// (LDS accesses of pw_conv512_next_kernel use these, not float4 / uint4 / int4: the compiler waits vmcnt(0) in front of every LDS read
+//  it cannot type while an LDS-DMA is pending -- the structs' reads are such -- which would drain the next tile's pieces in mid-tile)
+typedef __attribute__((ext_vector_type(4))) float pw_f32x4;
+typedef __attribute__((ext_vector_type(2))) uint32_t pw_u32x2;
+typedef __attribute__((ext_vector_type(4))) uint32_t pw_u32x4;
+typedef __attribute__((ext_vector_type(4))) int pw_i32x4;
 
 #define PW_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define PW_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
@@ -52,12 +58,21 @@ __device__ __forceinline__ float pw_bf2f(uint32_t v) { return __uint_as_float(v 
 template <int CPR> __device__ __forceinline__ int pw_swz(int px) { return CPR >= 16 ? (px & 15) : ((px >> 1) & 7); }
 
 template <int N> __device__ __forceinline__ void pw_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// Workgroup barrier that orders LDS accesses ONLY (this wave's ds_reads / ds_writes retired, then s_barrier).  __syncthreads() carries a
+// fence for which the compiler waits vmcnt(0) whenever an LDS-DMA may be pending -- it drains the next tile's pieces and the last
+// tile's stores at every barrier; with this one they stay in flight, and the DMA pieces are ordered by pw_wait_vm alone.
+__device__ __forceinline__ void pw_lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
 
 // BC = 128 (four waves) is the kernel described above.  BC = 256 with NEXT (eight waves, one workgroup per CU) is the fused form of
 // ResNet stage 2: the cout tile spans ALL 256 channels of a pixel, so the NEXT block's 1x1 reduction `2a` (256 -> 64, + bias + ReLU,
 // ConvGroup.ch_w3 / ch_b3 / ch_out3) is computed from the finished tile while it is still in LDS -- the 2.1 GB block output is
 // written once and read once (by the next shortcut) instead of twice, and the next block's `2a` launch disappears.  The `2a` MFMAs
 // read the stored bf16 values of the tile in ascending k order like the generic kernel would from memory: bit-identical.
+// (Stage 3's form of the same dataflow -- 128 -> 512 with the next 512 -> 128 -- is a kernel of its own, pw_conv512_next_kernel below.)
 // NEXT = 2 ("dual", round 4): the second 64-cout convolution reads the INPUT tile instead of the finished one -- a ConvBlock's first
 // two launches, `branch1` (64 -> 256, the projection shortcut) and `2a` (64 -> 64 + ReLU), both 1x1 over the same pooled plane
 // (feature_extractor.py:283-309), become one: the plane is read once, and the 2a launch -- a one-K-tile layer that ran 4.16 M
@@ -273,6 +288,229 @@ static hipError_t pw_launch_cfg(const ConvArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// ResNet stage 3's fused form: the 1x1 expansion `2c` (128 -> 512, + shortcut + ReLU) carries the NEXT block's 1x1 reduction `2a`
+// (512 -> 128, + bias + ReLU -> ConvGroup.ch_out3) -- stage 2's NEXT = 1 dataflow one size up.  The cout tile spans all 512
+// channels of a 32-pixel tile (64-pixel tiles would need 160 KB of LDS); one workgroup of EIGHT waves per compute unit:
+//   * 2c: a wave owns two 32-cout blocks (64 weight registers) and reads each input fragment once for both;
+//   * 2a: 128 couts x 512 k are 4 cout blocks x 32 k-steps; a wave cannot hold a block's 128 weight registers beside its 2c weights,
+//     so wave w holds cout block w & 3 for the K HALF w >> 2 (64 registers).  Waves 0-3 run k-steps 0-15 and hand their accumulator
+//     over through LDS (fp32, exact); waves 4-7 load it as the C operand and CONTINUE the chain with k-steps 16-31 -- one fp32
+//     accumulator chain per fragment in ascending k order, never a sum of partials: bit-identical to the separate launch.
+// Same MFMA, same epilogue arithmetic and the same vmcnt model as pw_conv_kernel (every thread issues the same vector-memory
+// instructions per tile: 1 + 4 DMA pieces, the row-table load, 4 + 1 stores).  The biases live in LDS.
+// With ONE workgroup per CU nothing else hides the DMA latency, so the next tile's pieces must really stay in flight under this
+// tile's MFMAs.  In pw_conv_kernel they do not: each __syncthreads() carries a fence for which the compiler waits vmcnt(0) while an
+// LDS-DMA is pending (its two or three workgroups per CU cover for one another).  Here every barrier of the loop is pw_lds_barrier()
+// (lgkmcnt(0) + s_barrier), and every LDS access is an ext_vector_type or plain int access: in front of an LDS read it cannot type
+// (float4 / uint4 / int4 are such) the compiler waits vmcnt(0) too.  What orders the DMA pieces is pw_wait_vm followed by a barrier
+// alone; the one vmcnt(0) left in the loop (the row-table entry, written to LDS behind the last barrier of a tile) falls a whole
+// tile's work behind the pieces it drains.  Measured per launch at 512 frames: 1.27-1.32 ms with __syncthreads(), 1.18-1.22 with
+// the barrier alone, 1.18-1.20 on a slower box with the typed accesses as well (profiles/pw_stage3_ab.txt).
+// LDS: 2 x 8 KB input + 2 x 32 KB shortcut/output + 1.5 KB row tables + 8 KB 2a tile + 16 KB accumulator relay + 2.5 KB biases = 108 KB.
+// ------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(512, 1) void pw_conv512_next_kernel(const ConvArgs a, int ptiles, int pstride) {
+    constexpr int K = 128, BP = 32, BC = 512, C2 = 128, THREADS = 512;
+    constexpr int CPX = K / 8, RCH = BC / 8, TCH = C2 / 8;      // 16-byte chunks per row of the input / output / 2a tile
+    constexpr int XB = BP * K * 2, RB = BP * BC * 2, TB = BP * C2 * 2;
+    constexpr int NXP = BP * CPX / THREADS, NRP = BP * RCH / THREADS, NTP = BP * TCH / THREADS;
+    constexpr int KS = K / 16, KSH = BC / 32;     // k-steps of the 2c; k-steps of one K half of the 2a
+    static_assert(NXP == 1 && NRP == 4 && NTP == 1, "tile shape");
+    extern __shared__ __attribute__((aligned(16))) char pw_smem[];
+    char* const xbuf = pw_smem;                   // [2][BP][K] bf16, chunk-swizzled
+    char* const rbuf = pw_smem + 2 * XB;          // [2][BP][BC] bf16, chunk-swizzled
+    pw_i32x4* const meta = reinterpret_cast<pw_i32x4*>(pw_smem + 2 * XB + 2 * RB);                              // [3][BP] {in_off, out_off, res_off, valid}
+    char* const tbuf = pw_smem + 2 * XB + 2 * RB + 3 * BP * 16;                                         // [BP][C2] bf16 tile of the fused 2a
+    pw_f32x4* const relay = reinterpret_cast<pw_f32x4*>(pw_smem + 2 * XB + 2 * RB + 3 * BP * 16 + TB);      // [4 cout blocks][4 groups][64 lanes]: the 2a accumulators after K half 0
+    float* const sbias = reinterpret_cast<float*>(pw_smem + 2 * XB + 2 * RB + 3 * BP * 16 + TB + 16384);// [BC] of the 2c, [C2] of the 2a
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int frow = lane & 31, fhalf = lane >> 5;
+    const int cb = wave & 3, kh = wave >> 2;      // 2a: cout block, K half
+    const ConvGroup& G = a.g[0];
+    const int p0 = blockIdx.x;
+    const int nt = p0 < ptiles ? (ptiles - p0 + pstride - 1) / pstride : 0;
+    if (nt == 0) return;
+
+    auto load_ent = [&](int t) {                  // row-table entry of this thread's pixel (tid % BP) of the workgroup's tile t
+        const int tt = t < nt ? t : nt - 1;
+        int m = (p0 + tt * pstride) * BP + (tid % BP);
+        const int valid = m < a.M;
+        m = valid ? m : a.M - 1;
+        const int4 e = *reinterpret_cast<const int4*>(&a.rows[m]);
+        return pw_i32x4{e.x, e.z, e.w, valid};    // in_off, out_off, res_off
+    };
+    auto issue = [&](int t) {                     // LDS-DMA of tile t's input rows and shortcut rows into buffer t & 1
+        // (the row offsets as plain int reads, all in front of the first piece: see the note at pw_f32x4)
+        const int* mt = reinterpret_cast<const int*>(meta + (t % 3) * BP);
+        const int in_off = mt[(tid / CPX) * 4];
+        int res_off[NRP];
+#pragma unroll
+        for (int i = 0; i < NRP; ++i) res_off[i] = mt[((i * THREADS + tid) / RCH) * 4 + 2];
+        {
+            const int row = tid / CPX, cp = tid % CPX;
+            const int c = cp ^ pw_swz<CPX>(row);
+            const char* src = reinterpret_cast<const char*>(G.in) + ((size_t)in_off * a.in_cstride + G.in_coff + c * 8) * 2;
+            __builtin_amdgcn_global_load_lds(PW_GLOBAL_PTR(src), PW_LDS_PTR(xbuf + (t & 1) * XB + (wave * 64) * 16), 16, 0, 0);
+        }
+        char* rb = rbuf + (t & 1) * RB;
+#pragma unroll
+        for (int i = 0; i < NRP; ++i) {
+            const int q = i * THREADS + tid, row = q / RCH, cp = q % RCH;
+            const int c = cp ^ pw_swz<RCH>(row);
+            const char* src = reinterpret_cast<const char*>(G.res) + ((size_t)res_off[i] * a.res_cstride + c * 8) * 2;
+            __builtin_amdgcn_global_load_lds(PW_GLOBAL_PTR(src), PW_LDS_PTR(rb + (i * THREADS + wave * 64) * 16), 16, 0, 0);
+        }
+    };
+
+    // ---- prologue: row tables of tiles 0 and 1, the biases into LDS, tile 0's DMA, the weights into registers
+    {
+        const pw_i32x4 e0 = load_ent(0), e1 = load_ent(1);
+        if (tid < BP) { meta[tid] = e0; meta[BP + tid] = e1; }
+        sbias[tid] = G.bias[tid];
+        if (tid < C2) sbias[BC + tid] = G.ch_b3[tid];
+    }
+    __syncthreads();
+    issue(0);
+    asm volatile("" ::: "memory");
+    pw_bf16x8 wf[2][KS], wf2[KSH];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const char* wrow = reinterpret_cast<const char*>(G.w) + ((size_t)(wave * 64 + b * 32 + frow) * K + fhalf * 8) * 2;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) wf[b][ks] = *reinterpret_cast<const pw_bf16x8*>(wrow + ks * 32);
+    }
+    {
+        const char* wrow = reinterpret_cast<const char*>(G.ch_w3) + ((size_t)(cb * 32 + frow) * BC + kh * (BC / 2) + fhalf * 8) * 2;
+#pragma unroll
+        for (int ks = 0; ks < KSH; ++ks) wf2[ks] = *reinterpret_cast<const pw_bf16x8*>(wrow + ks * 32);
+    }
+    const bool relu = a.flags & CONV_RELU;
+    const int px = frow;                          // the lane's pixel of the tile
+
+    for (int t = 0; t < nt; ++t) {
+        pw_lds_barrier();                          // meta of tile t+1 visible; the buffers of tile t+1 (= of tile t-1) are free
+        const bool more = t + 1 < nt;
+        if (more) issue(t + 1);
+        asm volatile("" ::: "memory");
+        const pw_i32x4 ent = load_ent(t + 2);
+        asm volatile("" ::: "memory");
+        // (the count of pw_conv_kernel: this iteration's pieces + row-table load and, from the second tile on, the previous iteration's
+        //  row-table load and output stores stay in flight)
+        if (more) { if (t > 0) pw_wait_vm<1 + NRP + NTP + NXP + NRP + 1>(); else pw_wait_vm<NXP + NRP + 1>(); }
+        else pw_wait_vm<1>();
+        pw_lds_barrier();
+
+        const char* xb = xbuf + (t & 1) * XB;
+        char* rb = rbuf + (t & 1) * RB;
+        // the pixel's chunk swizzle (the same for all three tiles), opaque per tile: hoisted out of the loop, the ~50 swizzled fragment
+        // addresses it feeds would cost more registers than the kernel has left (the weights hold 128)
+        int sw = pw_swz<RCH>(px);
+        asm volatile("" : "+v"(sw));
+        pw_f32x16 acc[2];
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const pw_bf16x8 bf = *reinterpret_cast<const pw_bf16x8*>(xb + px * (K * 2) + (((ks * 2 + fhalf) ^ sw) << 4));
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[0][ks], bf, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[1][ks], bf, acc[1], 0, 0, 0);
+        }
+        // ---- finish in LDS: the lane's four consecutive channels of a pixel are 8 bytes of the shortcut tile, overwritten in place
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                char* p = rb + px * (BC * 2) + ((((wave * 2 + b) * 4 + g) ^ sw) << 4) + fhalf * 8;
+                const pw_f32x4 bv = *reinterpret_cast<const pw_f32x4*>(sbias + (wave * 2 + b) * 32 + g * 8 + fhalf * 4);
+                float v0 = __builtin_fmaf(acc[b][g * 4 + 0], 1.0f, bv.x), v1 = __builtin_fmaf(acc[b][g * 4 + 1], 1.0f, bv.y);
+                float v2 = __builtin_fmaf(acc[b][g * 4 + 2], 1.0f, bv.z), v3 = __builtin_fmaf(acc[b][g * 4 + 3], 1.0f, bv.w);
+                const pw_u32x2 r = *reinterpret_cast<const pw_u32x2*>(p);
+                v0 += pw_bf2f(r.x & 0xFFFFu) * 1.0f; v1 += pw_bf2f(r.x >> 16) * 1.0f;
+                v2 += pw_bf2f(r.y & 0xFFFFu) * 1.0f; v3 += pw_bf2f(r.y >> 16) * 1.0f;
+                pw_u32x2 o;
+                o.x = pw_pack(v0, v1); o.y = pw_pack(v2, v3);
+                if (relu) { o.x = pw_relu(o.x); o.y = pw_relu(o.y); }
+                *reinterpret_cast<pw_u32x2*>(p) = o;
+            }
+        pw_lds_barrier();
+        const pw_i32x4* mt = meta + (t % 3) * BP;
+#pragma unroll
+        for (int i = 0; i < NRP; ++i) {
+            const int q = i * THREADS + tid, row = q / RCH, cp = q % RCH;
+            const int c = cp ^ pw_swz<RCH>(row);
+            const pw_u32x4 v = *reinterpret_cast<const pw_u32x4*>(rb + q * 16);
+            const pw_i32x4 e = mt[row];
+            pw_u32x4* dst = e.w ? reinterpret_cast<pw_u32x4*>(reinterpret_cast<uint16_t*>(G.out) + (size_t)e.y * a.out_cstride + c * 8) : reinterpret_cast<pw_u32x4*>(&pw_sink[lane]);
+            *dst = v;
+        }
+        // ---- the next block's 2a on the finished tile (its stored bf16 values): D[128 couts][BP pixels] over k = 0 .. 511
+        pw_f32x16 acc2;
+        if (kh == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < KSH; ++ks) {
+                const pw_bf16x8 bf = *reinterpret_cast<const pw_bf16x8*>(rb + px * (BC * 2) + (((ks * 2 + fhalf) ^ sw) << 4));
+                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf2[ks], bf, acc2, 0, 0, 0);
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) relay[(cb * 4 + g) * 64 + lane] = pw_f32x4{acc2[g * 4 + 0], acc2[g * 4 + 1], acc2[g * 4 + 2], acc2[g * 4 + 3]};
+        }
+        pw_lds_barrier();
+        if (kh == 1) {                            // continue K half 0's accumulator chain with k-steps 16 .. 31
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const pw_f32x4 v = relay[(cb * 4 + g) * 64 + lane];
+                acc2[g * 4 + 0] = v.x; acc2[g * 4 + 1] = v.y; acc2[g * 4 + 2] = v.z; acc2[g * 4 + 3] = v.w;
+            }
+#pragma unroll
+            for (int ks = 0; ks < KSH; ++ks) {
+                const pw_bf16x8 bf = *reinterpret_cast<const pw_bf16x8*>(rb + px * (BC * 2) + (((KSH * 2 + ks * 2 + fhalf) ^ sw) << 4));
+                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf2[ks], bf, acc2, 0, 0, 0);
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const pw_f32x4 bv = *reinterpret_cast<const pw_f32x4*>(sbias + BC + cb * 32 + g * 8 + fhalf * 4);
+                pw_u32x2 o;
+                o.x = pw_relu(pw_pack(__builtin_fmaf(acc2[g * 4 + 0], 1.0f, bv.x), __builtin_fmaf(acc2[g * 4 + 1], 1.0f, bv.y)));
+                o.y = pw_relu(pw_pack(__builtin_fmaf(acc2[g * 4 + 2], 1.0f, bv.z), __builtin_fmaf(acc2[g * 4 + 3], 1.0f, bv.w)));
+                *reinterpret_cast<pw_u32x2*>(tbuf + px * (C2 * 2) + (((cb * 4 + g) ^ sw) << 4) + fhalf * 8) = o;
+            }
+        }
+        pw_lds_barrier();
+        if (tid < BP) meta[((t + 2) % 3) * BP + tid] = ent;     // (the compiler waits for the load; visible after the next barrier)
+        {
+            const int row = tid / TCH, cp = tid % TCH;                 // BP * 16 = THREADS pieces: one per thread
+            const int c = cp ^ pw_swz<TCH>(row);
+            const pw_u32x4 v = *reinterpret_cast<const pw_u32x4*>(tbuf + tid * 16);
+            const pw_i32x4 e = mt[row];
+            pw_u32x4* dst = e.w ? reinterpret_cast<pw_u32x4*>(reinterpret_cast<uint16_t*>(G.ch_out3) + (size_t)e.y * C2 + c * 8) : reinterpret_cast<pw_u32x4*>(&pw_sink[lane]);
+            *dst = v;
+        }
+    }
+}
+
+static hipError_t pw_launch_next512(const ConvArgs& a, hipStream_t s) {
+    constexpr int BP = 32;
+    constexpr int LDS = 2 * BP * 128 * 2 + 2 * BP * 512 * 2 + 3 * BP * 16 + BP * 128 * 2 + 16384 + (512 + 128) * 4;
+    static PerDeviceOnce once;
+    bool& attr_set = *once.slot();
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pw_conv512_next_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    const int ptiles = (a.M + BP - 1) / BP;
+    int pstride = std::min(launch_cus(a), ptiles) / 8 * 8;  // persistent workgroups, one per compute unit: a multiple of the 8 XCDs
+    if (pstride < 8) pstride = 8;
+    hipLaunchKernelGGL(pw_conv512_next_kernel, dim3(pstride), dim3(512), LDS, s, a, ptiles, pstride);
+    return hipGetLastError();
+}
+
 // true when the launch was taken by the pointwise kernel
 bool conv_pointwise_eligible(const ConvArgs& a) {
     static const bool on = [] { const char* e = getenv("BOD_POINTWISE"); return !e || atoi(e) != 0; }();
@@ -281,7 +519,9 @@ bool conv_pointwise_eligible(const ConvArgs& a) {
     if (a.variant != 0 || a.split || a.xreuse || a.ksplit > 1 || a.groups != 1 || a.taps != 1 || a.fan_count > 1) return false;
     if (a.flags & (CONV_DROPOUT | CONV_OUT_F32 | CONV_ACCUM)) return false;
     if (g.w2 || g.ch_w2 || g.out_relu || g.agg_kind) return false;
-    if (g.ch_w3 && !(a.cin == 64 && a.cout_pad == 256 && (g.res != nullptr) != (g.ch_dual != 0) && g.ch_b3 && g.ch_out3)) return false;   // fused 2a: stage 2's shapes only
+    // fused 2a: stage 2's shapes (64 -> 256, next or dual form) and stage 3's (128 -> 512 with shortcut, next form) only
+    if (g.ch_w3 && !(g.ch_b3 && g.ch_out3 && ((a.cin == 64 && a.cout_pad == 256 && (g.res != nullptr) != (g.ch_dual != 0)) ||
+                                              (a.cin == 128 && a.cout_pad == 512 && g.res && !g.ch_dual)))) return false;
     // (512-channel reductions WITH shortcut need two output buffers and fit one workgroup per CU only: +0.55 ms per 256-frame step
     //  against the generic kernel, not kept)
     // 512-channel reductions WITHOUT shortcut (stage 3's `2a`, stage 4's first block, the C3 lateral of the FPN): 128 weight registers,
@@ -302,6 +542,7 @@ bool conv_pointwise_eligible(const ConvArgs& a) {
 hipError_t launch_conv_pointwise(const ConvArgs& a, hipStream_t s) {
     const bool res = a.g[0].res != nullptr;
     if (a.g[0].ch_w3 && a.g[0].ch_dual) return pw_launch_cfg<64, 64, false, 1, 256, 2>(a, s);   // branch1 + the same block's 2a on one input tile (stage 2's ConvBlock)
+    if (a.g[0].ch_w3 && a.cin == 128) return pw_launch_next512(a, s);              // 2c + the next block's 2a (stage 3)
     if (a.g[0].ch_w3) return pw_launch_cfg<64, 64, true, 1, 256, 1>(a, s);         // 2c + the next block's 2a (stage 2)
     // (32-pixel tiles with 5 / 4 workgroups per CU for the 64- / 128-channel reductions measured: +0.3 ms per 256-frame step)
     if (a.cin == 64) return res ? pw_launch_cfg<64, 64, true, 3>(a, s) : pw_launch_cfg<64, 64, false, 3>(a, s);
@@ -634,6 +875,16 @@ bool conv_pointwise_can_fuse_next(const ConvArgs& a) {
     static const bool forced = [] { const char* e = getenv("BOD_FORCE_CONV_TILE"); return e && atoi(e) != 0; }();
     if (!on || forced) return false;
     return a.cin == 64 && a.cout_pad == 256 && a.g[0].res && conv_pointwise_eligible(a);
+}
+
+// Stage 3's twin: may a 128 -> 512 expansion with shortcut carry the next block's 2a (512 -> 128) on pw_conv512_next_kernel?  A switch of
+// its own (BOD_PW_FUSE_NEXT3=0 plans the separate launches), independent of stage 2's.  conv_pointwise_eligible holds the persistent-
+// workgroup floor (BOD_POINTWISE_MIN_M).
+bool conv_pointwise_can_fuse_next3(const ConvArgs& a) {
+    static const bool on = [] { const char* e = getenv("BOD_PW_FUSE_NEXT3"); return !e || atoi(e) != 0; }();
+    static const bool forced = [] { const char* e = getenv("BOD_FORCE_CONV_TILE"); return e && atoi(e) != 0; }();
+    if (!on || forced) return false;
+    return a.cin == 128 && a.cout_pad == 512 && a.g[0].res && conv_pointwise_eligible(a);
 }
 
 // ... and may a 64 -> 256 projection shortcut (no residual of its own) carry its block's 2a on the same input tile (dual form)?

@@ -864,16 +864,18 @@ bod_status build_plan(bod_context* h) {
             // Stage 2 on the streaming pointwise kernel (conv_pointwise.hip, BC = 256): the 1x1 expansion just added carries the NEXT
             // block's 1x1 reduction -- computed from the finished tile in LDS, written to the t1 plane this block's 3x3 has already
             // consumed -- when the launch is certain to run on that kernel (conv_pointwise_can_fuse_next).  BOD_PW_FUSE_NEXT=0: off.
+            // Stage 3 (128 -> 512, the next 2a 512 -> 128) does the same on pw_conv512_next_kernel's 512-channel tile of 32 pixels
+            // (conv_pointwise_can_fuse_next3; its own switch, BOD_PW_FUSE_NEXT3=0: off).
             auto fuse_next_2a = [&](const char* blk) -> bod_status {
-                if (st != 2 || blk[1] == 0 || train_mode || h->es != 2 || h->split) return BOD_OK;
+                if ((st != 2 && st != 3) || blk[1] == 0 || train_mode || h->es != 2 || h->split) return BOD_OK;
                 Op& op2c = h->ops.back();
-                if (!conv_pointwise_can_fuse_next(op2c.conv) || op2c.conv.ksplit > 1) return BOD_OK;
+                if (!(st == 2 ? conv_pointwise_can_fuse_next(op2c.conv) : conv_pointwise_can_fuse_next3(op2c.conv)) || op2c.conv.ksplit > 1) return BOD_OK;
                 char nb[64], nbb[64];
                 snprintf(nb, sizeof nb, "res%d%c_branch2a", st, blk[1]);
                 snprintf(nbb, sizeof nbb, "bn%d%c_branch2a", st, blk[1]);
                 PackedConv p2a;
                 BODCHK(pack_conv(h, nb, nbb, 64, &p2a));
-                if (p2a.cin != f3 || p2a.cout != f1 || p2a.taps != 1 || p2a.cout_pad != 64) return BOD_OK;
+                if (p2a.cin != f3 || p2a.cout != f1 || p2a.taps != 1 || p2a.cout_pad != (st == 2 ? 64 : 128)) return BOD_OK;
                 ConvGroup& G = op2c.conv.g[0];
                 G.ch_w3 = p2a.w; G.ch_b3 = p2a.bias; G.ch_out3 = t1.d;
                 op2c.flops += 2.0 * op2c.conv.M * (double)f1 * f3;
@@ -1344,7 +1346,7 @@ bod_status build_plan(bod_context* h) {
                     bytes += (double)a.M * a.cin * h->es;                                                    // input pixels (stride-2 3x3: ~4x that)
                     bytes += (double)a.M * std::max(1, a.fan_count) * a.cout_valid * es;                     // output(s)
                     if (a.g[g].res) bytes += (double)a.M * a.cout_valid * h->es;
-                    if (a.g[g].ch_w3) bytes += (double)a.M * 64 * h->es;
+                    if (a.g[g].ch_w3) bytes += (double)a.M * (a.cin == 128 ? 128 : 64) * h->es;      // the fused 2a's plane (stage 3: 128 channels)
                     bytes += (double)a.taps * a.cin * a.cout_pad * h->es;
                 }
             }

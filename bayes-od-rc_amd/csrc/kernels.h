@@ -50,6 +50,8 @@ struct ConvGroup {         // element type of in / w / res / out_relu: bf16 (def
     // geometry (pixel index = RowEnt.out_off); the 2b output itself is not stored.  feature_extractor.py:195-213,283-309.
     const void* ch_w2; const float* ch_b2; const void* ch_res; void* ch_out; int32_t ch_c2;
     const void* ch_w3; const float* ch_b3; void* ch_out3;
+    // Pointwise kernel, next form (conv_pointwise.hip; ch_w3 without ch_w2): this group's conv is a block's `2c` itself (64 -> 256 of
+    // stage 2, 128 -> 512 of stage 3) and ch_w3 / ch_b3 / ch_out3 the next block's `2a` (256 -> 64, 512 -> 128) on its finished tile.
     // Pointwise kernel, dual form (conv_pointwise.hip, NEXT = 2): ch_w3 / ch_b3 / ch_out3 describe a second 1x1 convolution (64 couts,
     // + bias + ReLU) of the SAME input tile -- a ConvBlock's `2a` riding on its projection shortcut `branch1` -- instead of one of
     // the finished output tile.
@@ -445,7 +447,8 @@ hipError_t launch_mirror_images(const float* in, float* out, int B, int H, int W
 // launches there (BOD_POINTWISE=0: off)
 bool conv_pointwise_eligible(const ConvArgs& a);
 bool conv_pointwise_can_fuse_next(const ConvArgs& a);      // plan time: may a 64 -> 256 expansion carry the next block's 2a (ch_w3)?
-bool conv_pointwise_can_fuse_dual(const ConvArgs& a);      // plan time: may a 64 -> 256 projection shortcut carry its own block's 2a (ch_w3 + ch_dual)?
+bool conv_pointwise_can_fuse_next3(const ConvArgs& a);     // plan time: may a 128 -> 512 expansion (stage 3) carry the next block's 2a (512 -> 128)?  BOD_PW_FUSE_NEXT3=0: never
+bool conv_pointwise_can_fuse_dual(const ConvArgs& a);     // plan time: may a 64 -> 256 projection shortcut carry its own block's 2a (ch_w3 + ch_dual)?
 hipError_t launch_conv_pointwise(const ConvArgs& a, hipStream_t s);
 // Sliding-window 3x3 stride-1 SAME convolution, 64 -> 64 channels (ResNet stage 2's `2b`; conv_pointwise.hip, BOD_SLIDE3X3=0: off)
 bool conv_slide3x3_eligible(const ConvArgs& a);

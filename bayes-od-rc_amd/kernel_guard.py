@@ -328,6 +328,8 @@ def verify_aux(host_obj, wanted=AUX_PRODUCTION):
 # register budget without spilling
 POINTWISE_PRODUCTION = ["pw_conv_kernelILi64ELi64E", "pw_conv_kernelILi128ELi64E", "pw_conv_kernelILi256ELi32E", "pw_conv_kernelILi512ELi32E",
                         "slide3x3_c64_kernel", "slide3x3_c128_kernel"]
+# stage 3's fused expansion + next reduction: one workgroup of eight waves per CU, 128 weight registers per lane
+POINTWISE_STAGE3 = ["pw_conv512_next_kernel"]
 
 
 def verify_pointwise(host_obj):
@@ -345,7 +347,17 @@ def verify_pointwise(host_obj):
     return regs
 
 
-PACKED_FP32_RE = r"v_pk_(?:mul|add|fma)_f32\b"
+def verify_pointwise_stage3(host_obj):
+    """pw_conv512_next_kernel: no scratch (a scratch access is a vector-memory instruction its hand-counted vmcnt waits do not know)
+    and at most the 256 registers of two waves per SIMD.  Raises GuardError; returns {kernel: registers}."""
+    regs = verify_aux(host_obj, POINTWISE_STAGE3)
+    for n, v in regs.items():
+        if v > 256:
+            raise GuardError("%s uses %d registers: more than the 256 of two waves per SIMD" % (n, v))
+    return regs
+
+
+PACKED_FP32_RE =r"v_pk_(?:mul|add|fma)_f32\b"
 
 
 def check_no_packed_fp32(host_obj):
