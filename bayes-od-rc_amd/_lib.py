@@ -48,6 +48,19 @@ class BodAugment(C.Structure):
                 ("gain", C.c_float), ("bias", C.c_float)]
 
 
+class BodLossOptions(C.Structure):
+    """bod_loss_options: the energy score's sample count and the key of its normals."""
+    _fields_ = [("energy_samples", C.c_int32), ("seed", C.c_uint64), ("first_image_id", C.c_uint32), ("reserved", C.c_int32 * 4)]
+
+
+BOD_LOSS_ONE_IMAGE_ID = 1                          # flag in bod_loss_options.reserved[0]
+
+
+def loss_options(energy_samples=64, seed=0, first_image_id=0, one_image_id=False):
+    flags = (C.c_int32 * 4)(BOD_LOSS_ONE_IMAGE_ID if one_image_id else 0, 0, 0, 0)
+    return BodLossOptions(int(energy_samples), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_image_id) & 0xFFFFFFFF, flags)
+
+
 class BodSizes(C.Structure):
     _fields_ = [
         ("num_pixels", C.c_int32), ("num_anchors", C.c_int32), ("level_h", C.c_int32 * 8),
@@ -114,6 +127,10 @@ SIGNATURES = {
     "bod_loss_forward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F, _F, _F, _F, _F,
                                    C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_float,
                                    C.POINTER(C.c_double)]),
+    "bod_loss_forward_ex": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F, _F, _F, _F, _F,
+                                      C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_float,
+                                      C.POINTER(C.c_double), C.POINTER(BodLossOptions)]),
+    "bod_set_loss_options": (C.c_int, [_H, C.POINTER(BodLossOptions)]),
     "bod_train_step": (C.c_int, [_H, C.c_void_p, C.c_int32, _F, _F, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_uint64, C.c_uint32,
                                  C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_double)]),
     "bod_train_step_boxes": (C.c_int, [_H, C.c_void_p, C.c_int32, _I, _F, _F, C.c_float, C.c_float, C.c_uint64, C.c_uint32,
@@ -127,6 +144,9 @@ SIGNATURES = {
     "bod_loss_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F, _F, _F, _F, _F,
                                     C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_float,
                                     C.c_float, C.c_float, C.POINTER(C.c_double), _F, _F, _F]),
+    "bod_loss_backward_ex": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F, _F, _F, _F, _F,
+                                       C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_float,
+                                       C.c_float, C.c_float, C.POINTER(C.c_double), _F, _F, _F, C.POINTER(BodLossOptions)]),
     "bod_anchor_targets": (C.c_int, [C.c_int32, C.c_int32, _F, C.c_int32, _I, _F, _F, C.c_int32, C.c_float, C.c_float, _F, _F,
                                      C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _I, _F]),
     "bod_validation_losses_boxes": (C.c_int, [_H, _I, _F, _F, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, _D]),

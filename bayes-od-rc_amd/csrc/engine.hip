@@ -244,6 +244,11 @@ struct bod_context {
     int64_t device_bytes = 0;
     struct TrainState* train = nullptr;                 // training mode (train_impl.inc)
     struct ValState* val = nullptr;                     // validation from boxes (validate_impl.inc): allocated by its first call
+    // reg_kind 5 (bod_set_loss_options): samples per row; seed / first image id of the validation entries (the
+    // training step takes its own from the step's arguments).  The two buffers are allocated by the first kind-5 call.
+    int32_t energy_samples = BOD_ENERGY_DEFAULT_SAMPLES;
+    uint64_t loss_seed = 0; uint32_t loss_first_image_id = 0; int32_t loss_id_stride = 1;
+    int32_t* energy_list = nullptr; float* energy_term = nullptr;    // [batch * A + 1] positive indices, [batch * A] row terms
 
     // geometry
     int sh = 0, sw = 0, ph = 0, pw = 0;                 // stem / pool output
@@ -3325,10 +3330,25 @@ bod_status bod_stage_conv_wgrad(int32_t device, const float* x, int32_t B, int32
     return done(run());
 }
 
+// the handle's buffers of reg_kind 5 (kernels.h: launch_loss_compact), allocated on first use -- never inside a capture: the
+// training step runs every configuration eagerly once before it records it
+static bod_status energy_buffers(bod_context* h) {
+    const size_t n = (size_t)h->cfg.batch * h->A;
+    if (!h->energy_list) BODCHK(h->dalloc(&h->energy_list, n + 1));
+    if (!h->energy_term) BODCHK(h->dalloc(&h->energy_term, n));
+    return BOD_OK;
+}
+
+// what bod_loss_options may hold: NULL = the defaults
+static bool loss_options_ok(const bod_loss_options* o) {
+    return !o || (o->energy_samples >= BOD_ENERGY_MIN_SAMPLES && o->energy_samples <= BOD_ENERGY_MAX_SAMPLES);
+}
+
 static bod_status loss_impl(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls, const float* cls_t,
                             const float* box, const float* box_t, const float* cov, const float* anchors,
                             const uint8_t* pos, const uint8_t* neg, int32_t do_cls, int32_t reg_kind,
-                            float label_smoothing, double* out4, float w_cls, float w_reg, float* dcls, float* dbox, float* dcov) {
+                            float label_smoothing, double* out4, float w_cls, float w_reg, float* dcls, float* dbox, float* dcov,
+                            const bod_loss_options* opt) {
     bod_context ctx;
     bod_context* h = &ctx;
     auto done = [&](bod_status s) {
@@ -3339,8 +3359,13 @@ static bod_status loss_impl(int32_t device, int32_t B, int32_t A, int32_t C, con
         h->allocs.clear(); h->stream = nullptr;
         return s;
     };
-    if (B < 1 || A < 1 || (C != 4 && C != 8) || !pos || !neg || !out4 || reg_kind < 0 || reg_kind > 3)
+    if (B < 1 || A < 1 || (C != 4 && C != 8) || !pos || !neg || !out4 || reg_kind < 0 || reg_kind > 5)
         return done(h->fail(BOD_ERR_INVALID_ARG, "bod_loss_forward: bad argument (C must be 4 or 8)"));
+    if (!loss_options_ok(opt))
+        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_loss_forward: energy_samples %d outside [%d, %d]", opt->energy_samples,
+                            BOD_ENERGY_MIN_SAMPLES, BOD_ENERGY_MAX_SAMPLES));
+    if (reg_kind == 5 && (long long)B * A >= 0x7fffffffLL)
+        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_loss_forward: reg_kind 5 takes fewer than 2^31 - 1 anchors in a call"));
     if ((do_cls && (!cls || !cls_t)) || (reg_kind && (!box || !box_t)) || (reg_kind >= 2 && (!cov || !anchors)))
         return done(h->fail(BOD_ERR_INVALID_ARG, "bod_loss_forward: a tensor required by the selected losses is NULL"));
     int ndev = 0;
@@ -3367,6 +3392,19 @@ static bod_status loss_impl(int32_t device, int32_t B, int32_t A, int32_t C, con
         const int nblocks = (int)((n + 255) / 256);
         float* partial = nullptr;
         BODCHK(h->dalloc(&partial, (size_t)nblocks * 4));
+        EnergyArgs ea{};
+        if (reg_kind == 5) {                                              // the positives' energy terms first: launch_loss sums them
+            int32_t* list = nullptr; float* term = nullptr;
+            BODCHK(h->dalloc(&list, n + 1)); BODCHK(h->dalloc(&term, n));
+            ea.B = B; ea.A = A; ea.M = opt ? opt->energy_samples : BOD_ENERGY_DEFAULT_SAMPLES;
+            ea.box = a.box; ea.box_t = a.box_t; ea.cov = a.cov; ea.anchors = a.anchors;
+            ea.seed_lo = opt ? (uint32_t)opt->seed : 0u; ea.seed_hi = opt ? (uint32_t)(opt->seed >> 32) : 0u;
+            ea.first_image_id = opt ? opt->first_image_id : 0u;
+            ea.id_stride = (opt && (opt->reserved[0] & BOD_LOSS_ONE_IMAGE_ID)) ? 0 : 1;
+            ea.list = list; ea.row_term = term; a.row_term = term;
+            HIPCHK(h, launch_loss_compact(a.pos, (long long)n, list, h->stream));
+            HIPCHK(h, launch_energy_forward(ea, h->stream));
+        }
         HIPCHK(h, launch_loss(a, partial, nblocks, h->stream));
         std::vector<float> hp((size_t)nblocks * 4);
         HIPCHK(h, hipMemcpyAsync(hp.data(), partial, hp.size() * 4, hipMemcpyDeviceToHost, h->stream));
@@ -3382,6 +3420,7 @@ static bod_status loss_impl(int32_t device, int32_t B, int32_t A, int32_t C, con
             if (dcov) BODCHK(h->dalloc(&g_cov, n * 10));
             HIPCHK(h, launch_loss_reduce(partial, nblocks, sums, h->stream));
             HIPCHK(h, launch_loss_backward(a, sums, w_cls, w_reg, g_cls, g_box, g_cov, h->stream));
+            if (reg_kind == 5 && (g_box || g_cov)) HIPCHK(h, launch_energy_backward(ea, sums, w_reg, g_box, g_cov, h->stream));
             if (dcls) HIPCHK(h, hipMemcpyAsync(dcls, g_cls, n * C * 4, hipMemcpyDeviceToHost, h->stream));
             if (dbox) HIPCHK(h, hipMemcpyAsync(dbox, g_box, n * 16, hipMemcpyDeviceToHost, h->stream));
             if (dcov) HIPCHK(h, hipMemcpyAsync(dcov, g_cov, n * 40, hipMemcpyDeviceToHost, h->stream));
@@ -3392,21 +3431,50 @@ static bod_status loss_impl(int32_t device, int32_t B, int32_t A, int32_t C, con
     return done(run());
 }
 
+bod_status bod_loss_forward_ex(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls, const float* cls_t,
+                               const float* box, const float* box_t, const float* cov, const float* anchors,
+                               const uint8_t* pos, const uint8_t* neg, int32_t do_cls, int32_t reg_kind,
+                               float label_smoothing, double* out4, const bod_loss_options* options) {
+    return loss_impl(device, B, A, C, cls, cls_t, box, box_t, cov, anchors, pos, neg, do_cls, reg_kind, label_smoothing, out4,
+                     0.f, 0.f, nullptr, nullptr, nullptr, options);
+}
+
 bod_status bod_loss_forward(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls, const float* cls_t,
                             const float* box, const float* box_t, const float* cov, const float* anchors,
                             const uint8_t* pos, const uint8_t* neg, int32_t do_cls, int32_t reg_kind,
                             float label_smoothing, double* out4) {
+    return bod_loss_forward_ex(device, B, A, C, cls, cls_t, box, box_t, cov, anchors, pos, neg, do_cls, reg_kind, label_smoothing, out4,
+                               nullptr);
+}
+
+bod_status bod_loss_backward_ex(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls, const float* cls_t,
+                                const float* box, const float* box_t, const float* cov, const float* anchors,
+                                const uint8_t* pos, const uint8_t* neg, int32_t do_cls, int32_t reg_kind,
+                                float label_smoothing, float w_cls, float w_reg, double* out4, float* dcls, float* dbox, float* dcov,
+                                const bod_loss_options* options) {
+    if (!dcls && !dbox && !dcov) return BOD_ERR_INVALID_ARG;
     return loss_impl(device, B, A, C, cls, cls_t, box, box_t, cov, anchors, pos, neg, do_cls, reg_kind, label_smoothing, out4,
-                     0.f, 0.f, nullptr, nullptr, nullptr);
+                     w_cls, w_reg, dcls, dbox, dcov, options);
 }
 
 bod_status bod_loss_backward(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls, const float* cls_t,
                              const float* box, const float* box_t, const float* cov, const float* anchors,
                              const uint8_t* pos, const uint8_t* neg, int32_t do_cls, int32_t reg_kind,
                              float label_smoothing, float w_cls, float w_reg, double* out4, float* dcls, float* dbox, float* dcov) {
-    if (!dcls && !dbox && !dcov) return BOD_ERR_INVALID_ARG;
-    return loss_impl(device, B, A, C, cls, cls_t, box, box_t, cov, anchors, pos, neg, do_cls, reg_kind, label_smoothing, out4,
-                     w_cls, w_reg, dcls, dbox, dcov);
+    return bod_loss_backward_ex(device, B, A, C, cls, cls_t, box, box_t, cov, anchors, pos, neg, do_cls, reg_kind, label_smoothing, w_cls,
+                                w_reg, out4, dcls, dbox, dcov, nullptr);
+}
+
+bod_status bod_set_loss_options(bod_handle h, const bod_loss_options* options) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    if (!loss_options_ok(options))
+        return h->fail(BOD_ERR_INVALID_ARG, "bod_set_loss_options: energy_samples %d outside [%d, %d]", options->energy_samples,
+                       BOD_ENERGY_MIN_SAMPLES, BOD_ENERGY_MAX_SAMPLES);
+    h->energy_samples = options ? options->energy_samples : BOD_ENERGY_DEFAULT_SAMPLES;
+    h->loss_seed = options ? options->seed : 0;
+    h->loss_first_image_id = options ? options->first_image_id : 0;
+    h->loss_id_stride = (options && (options->reserved[0] & BOD_LOSS_ONE_IMAGE_ID)) ? 0 : 1;
+    return BOD_OK;
 }
 
 // Packs a minibatch's ground truth for launch_anchor_targets: [B+1] row offsets, then the [sum G,4] corners, then the [sum G,C]

@@ -374,13 +374,14 @@ hipError_t launch_preprocess_augment(const PreprocAugArgs& a, hipStream_t s);
 struct LossArgs {
     int32_t B, A, C;
     int32_t do_cls;          // focal classification term
-    int32_t reg_kind;        // 0 none, 1 'regression', 2 'regression_var', 3 'regression_covar'
+    int32_t reg_kind;        // 0 none, 1 'regression', 2 'regression_var', 3 'regression_covar', 4 'regression_nll', 5 'regression_energy'
     float label_smoothing;
     const float* cls; const float* cls_t;       // [B,A,C]
     const float* box; const float* box_t;       // [B,A,4]
     const float* cov;                           // [B,A,10] fill_triangular parameters
     const float* anchors;                       // [A,4]
     const uint8_t* pos; const uint8_t* neg;     // [B,A]
+    const float* row_term;                      // [B,A] reg_kind 5: a positive row's energy-score term (launch_energy_forward), read as s_cmp
 };
 hipError_t launch_loss(const LossArgs& a, float* partial, int nblocks, hipStream_t s);
 hipError_t launch_loss_reduce(const float* partial, int nblocks, float* sums4, hipStream_t s);
@@ -390,6 +391,29 @@ hipError_t launch_loss_frames(const LossArgs& a, float* partial, hipStream_t s);
 hipError_t launch_loss_frames_reduce(const float* partial, int frames, int nblocks, double* sums, hipStream_t s);
 hipError_t launch_loss_backward(const LossArgs& a, const float* sums4, float w_cls, float w_reg, float* dcls, float* dbox, float* dcov,
                                 hipStream_t s);
+// reg_kind 5, the sample-based energy score: one wave64 per positive row over a fixed grid that strides over the
+// list launch_loss_compact writes (list[0] = number of positives, list[1..] = their flat indices b * A + a, ascending), so the
+// launches can sit in a captured graph.  The forward writes row_term[idx] of every positive row -- launch_loss / launch_loss_frames
+// then sum it as s_cmp -- and the backward overwrites the positive rows of dbox / dcov that launch_loss_backward has zeroed.
+#define BOD_ENERGY_MIN_SAMPLES 2
+#define BOD_ENERGY_MAX_SAMPLES 1024
+#define BOD_ENERGY_DEFAULT_SAMPLES 64
+struct EnergyArgs {
+    int32_t B, A, M;                            // M samples per row
+    const float* box; const float* box_t;       // [B,A,4]
+    const float* cov;                           // [B,A,10]
+    const float* anchors;                       // [A,4]
+    const uint32_t* dyn;                        // device {seed low, seed high, first image id} (a replayed graph), or nullptr: the three below
+    uint32_t seed_lo, seed_hi, first_image_id;
+    int32_t id_stride;                          // image id of frame b = first image id + b * id_stride: 1, or 0 (BOD_LOSS_ONE_IMAGE_ID)
+    const int32_t* list;                        // [B*A + 1]
+    float* row_term;                            // [B,A]
+};
+hipError_t launch_loss_compact(const uint8_t* pos, long long n, int32_t* list, hipStream_t s);
+hipError_t launch_energy_forward(const EnergyArgs& a, hipStream_t s);
+hipError_t launch_energy_backward(const EnergyArgs& a, const float* sums4, float w_reg, float* dbox, float* dcov, hipStream_t s);
+// out[c] = sum_r g[r * nch + c]: the output-bias gradient of a head from dbox / dcov [rows = B * positions][nch = anchors per location * width]
+hipError_t launch_head_bias_grad(const float* g, long long rows, int nch, float* out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // Anchor-target assignment (target_kernels.hip): IoU of every anchor with its frame's GT rows, positive / negative masks, the best

@@ -74,3 +74,5 @@ BOD_HD DropPair dropout_run_windows(const Philox4& r, int u) {
 #define BOD_CAT_TAG 0x00CA7E60u
 // energy-score normals (score_kernels.hip, scoring_rules.py): counter = (sample, row id low, BOD_SCORE_TAG, row id high)
 #define BOD_SCORE_TAG 0x005C04E5u
+// energy-score TRAINING normals (loss_kernels.hip, proper_losses.py): counter = (sample, anchor, BOD_LOSS_TAG, image id)
+#define BOD_LOSS_TAG 0x0010555Eu

@@ -601,6 +601,19 @@ bod_status train_enqueue(bod_context* h, const float* dev, uint64_t seed, uint32
     la.B = c.batch; la.A = h->A; la.C = c.num_classes; la.do_cls = 1; la.reg_kind = reg_kind; la.label_smoothing = label_smoothing;
     la.cls = h->raw[0]; la.cls_t = t->cls_t; la.box = h->raw[1]; la.box_t = t->box_t; la.cov = h->raw[2]; la.anchors = h->d_anchors;
     la.pos = t->pos; la.neg = t->neg;
+    EnergyArgs ea{};
+    if (reg_kind == 5) {
+        // the energy score's normals are keyed like the dropout masks: a recorded step reads this step's seed and image base
+        // from t->dyn, the fp32 verification handle (never recorded) takes them by argument like its convolutions
+        ea.B = c.batch; ea.A = h->A; ea.M = h->energy_samples;
+        ea.box = la.box; ea.box_t = la.box_t; ea.cov = la.cov; ea.anchors = la.anchors;
+        ea.dyn = t->f32 ? nullptr : t->dyn;
+        ea.seed_lo = (uint32_t)seed; ea.seed_hi = (uint32_t)(seed >> 32); ea.first_image_id = first_image_id;
+        ea.id_stride = 1;                                           // (a step's frames are consecutive images, as for dropout)
+        ea.list = h->energy_list; ea.row_term = h->energy_term; la.row_term = h->energy_term;
+        HIPCHK(h, launch_loss_compact(t->pos, (long long)c.batch * h->A, h->energy_list, h->stream));
+        HIPCHK(h, launch_energy_forward(ea, h->stream));
+    }
     HIPCHK(h, launch_loss(la, t->loss_partial, t->loss_blocks, h->stream));
     HIPCHK(h, launch_loss_reduce(t->loss_partial, t->loss_blocks, t->loss_sums, h->stream));
     HIPCHK(h, hipMemsetAsync(t->act_grad_arena, 0, t->act_grad_n * 4, h->stream));
@@ -614,6 +627,7 @@ bod_status train_enqueue(bod_context* h, const float* dev, uint64_t seed, uint32
     float* dcov = c.has_covar_head ? grad_buffer(h, h->raw[2], act_elems_of(h, h->raw[2], 4)) : nullptr;
     if (!dcls || !dbox) return h->fail(BOD_ERR_OOM, "training: gradient buffer");
     HIPCHK(h, launch_loss_backward(la, t->loss_sums, w_cls, w_reg, dcls, dbox, reg_kind >= 2 ? dcov : nullptr, h->stream));
+    if (reg_kind == 5) HIPCHK(h, launch_energy_backward(ea, t->loss_sums, w_reg, dbox, dcov, h->stream));
     // ---- backward through the plan
     t->cur_images = dev;
     if (!t->f32) {
@@ -621,6 +635,21 @@ bod_status train_enqueue(bod_context* h, const float* dev, uint64_t seed, uint32
         HIPCHK(h, launch_f32_to_bf16(dev, t->img_bf16, (long)npx, h->stream));
     }
     BODCHK(train_backward(h));
+    if (reg_kind >= 4 && !t->f32) {
+        // The proper scoring rules' gradients reach the heads' output biases in fp32: the weight-gradient GEMM above read dZ from bf16
+        // storage (2^-9 per element), so for these two kinds the bias rows it wrote are replaced by the column sums of dbox / dcov
+        // (train_backward has joined the weight-gradient streams).  Kinds 1-3 keep the gradients they had.
+        const long long rows = (long long)c.batch * h->A / c.anchors_per_location;
+        const struct { const char* layer; const float* g; int width; } heads[2] = {{"pyramid_regression", dbox, 4}, {"pyramid_cov", dcov, 10}};
+        for (const auto& hd : heads) {
+            auto it = t->index.find(hd.layer);
+            if (it == t->index.end() || !hd.g) return h->fail(BOD_ERR_INVALID_ARG, "training: reg_kind %d needs the output convolution '%s'", reg_kind, hd.layer);
+            const TrainConv& tc = t->convs[it->second];
+            if (!tc.bias.present || tc.cout != c.anchors_per_location * hd.width)
+                return h->fail(BOD_ERR_INVALID_ARG, "training: '%s' has no bias of %d channels", hd.layer, c.anchors_per_location * hd.width);
+            HIPCHK(h, launch_head_bias_grad(hd.g, rows, tc.cout, t->grad + tc.bias.off, h->stream));
+        }
+    }
     // ---- global-norm clip, Adam (the L2 terms were added by the weight-gradient pass)
     HIPCHK(h, launch_sumsq(t->grad, (long)t->arena_n, t->scalars + 1, t->sumsq_partial, h->stream));
     if (apply_update) BODCHK(train_apply(h));
@@ -683,8 +712,10 @@ bod_status train_run_step(bod_context* h, const float* images, int32_t on_device
     }
     if (apply_update) BODCHK(train_set_rate(h, learning_rate));
     // ---- the device work of the step: replayed from a hipGraph once the same configuration has run eagerly
-    char key[160];
-    snprintf(key, sizeof key, "%p|%d|%a|%a|%a|%a|%d", (const void*)dev, reg_kind, label_smoothing, w_cls, w_reg, l2_rate, apply_update);
+    if (reg_kind == 5) BODCHK(energy_buffers(h));                 // (before any capture: allocates on the first kind-5 step)
+    char key[176];
+    snprintf(key, sizeof key, "%p|%d|%a|%a|%a|%a|%d|%d", (const void*)dev, reg_kind, label_smoothing, w_cls, w_reg, l2_rate, apply_update,
+             reg_kind == 5 ? h->energy_samples : 0);                // the sample count is baked into a recorded step
     // opt-in (BOD_TRAIN_GRAPH=1): measured on MI355X the replay frees the host (11 ms of enqueue per step at a minibatch of
     // three) but is not faster than the eager two-stream step -- the step is bound by its ~1 000 dependent small kernels
     const char* genv = getenv("BOD_TRAIN_GRAPH");
@@ -743,7 +774,7 @@ bod_status train_run_step(bod_context* h, const float* images, int32_t on_device
 bod_status train_step_check(bod_context* h, const char* who, int32_t reg_kind) {
     if (!h->train || !h->weights_ready) return h->fail(BOD_ERR_NOT_READY, "%s needs a handle created with training = 1 and finalized weights", who);
     if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called");
-    if (reg_kind < 1 || reg_kind > 3 || (reg_kind >= 2 && !h->cfg.has_covar_head)) return h->fail(BOD_ERR_INVALID_ARG, "%s: reg_kind %d", who, reg_kind);
+    if (reg_kind < 1 || reg_kind > 5 || (reg_kind >= 2 && !h->cfg.has_covar_head)) return h->fail(BOD_ERR_INVALID_ARG, "%s: reg_kind %d", who, reg_kind);
     return BOD_OK;
 }
 }  // namespace

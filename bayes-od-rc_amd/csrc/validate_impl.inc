@@ -59,7 +59,7 @@ bod_status val_check(bod_context* h, const char* who, const int32_t* num_gt, int
     const bod_config& c = h->cfg;
     if (c.training) return h->fail(BOD_ERR_INVALID_ARG, "%s: a training handle runs its forward with dropout on; validate on an inference handle", who);
     if (c.mc_samples != 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: validation is one deterministic sample, this handle has mc_samples = %d", who, c.mc_samples);
-    if (reg_kind < 0 || reg_kind > 3) return h->fail(BOD_ERR_INVALID_ARG, "%s: reg_kind %d", who, reg_kind);
+    if (reg_kind < 0 || reg_kind > 5) return h->fail(BOD_ERR_INVALID_ARG, "%s: reg_kind %d", who, reg_kind);
     if (reg_kind >= 2 && !c.has_covar_head) return h->fail(BOD_ERR_INVALID_ARG, "%s: reg_kind %d needs the covariance head, this handle has none", who, reg_kind);
     if (c.num_classes != 4 && c.num_classes != 8)
         return h->fail(BOD_ERR_INVALID_ARG, "%s: the loss kernels support 4 or 8 classes (background included), this handle has %d", who, c.num_classes);
@@ -98,6 +98,17 @@ bod_status val_losses_enqueue(bod_context* h, const int32_t* num_gt, const float
     la.B = c.batch; la.A = h->A; la.C = c.num_classes; la.do_cls = do_cls ? 1 : 0; la.reg_kind = reg_kind; la.label_smoothing = label_smoothing;
     la.cls = h->raw[0]; la.box = h->raw[1]; la.cov = h->raw[2];                      // [B,1,A,.]: MC sample 0 is the only one
     la.cls_t = v->cls_t; la.box_t = v->box_t; la.anchors = h->d_anchors; la.pos = v->pos; la.neg = v->neg;
+    if (reg_kind == 5) {                                                             // per-row energy terms first (bod_set_loss_options keys them)
+        BODCHK(energy_buffers(h));
+        EnergyArgs ea{};
+        ea.B = c.batch; ea.A = h->A; ea.M = h->energy_samples;
+        ea.box = la.box; ea.box_t = la.box_t; ea.cov = la.cov; ea.anchors = la.anchors;
+        ea.seed_lo = (uint32_t)h->loss_seed; ea.seed_hi = (uint32_t)(h->loss_seed >> 32); ea.first_image_id = h->loss_first_image_id;
+        ea.id_stride = h->loss_id_stride;
+        ea.list = h->energy_list; ea.row_term = h->energy_term; la.row_term = h->energy_term;
+        HIPCHK(h, launch_loss_compact(v->pos, (long long)c.batch * h->A, h->energy_list, h->stream));
+        HIPCHK(h, launch_energy_forward(ea, h->stream));
+    }
     HIPCHK(h, launch_loss_frames(la, v->partial, h->stream));
     HIPCHK(h, launch_loss_frames_reduce(v->partial, c.batch, (h->A + 255) / 256, v->sums, h->stream));
     return BOD_OK;

@@ -307,12 +307,29 @@ class Engine(object):
     def posterior(self, seed=0, first_image_id=0):
         self._chk(self.lib.bod_posterior(self.h, seed, first_image_id))
 
+    # -- options of the proper-scoring-rule losses -------------------------------
+    def set_loss_options(self, energy_samples=None, seed=None, first_image_id=None, one_image_id=None):
+        """``bod_set_loss_options``: M of 'regression_energy' (reg_kind 5) for every entry of this handle; ``seed``,
+        ``first_image_id`` and ``one_image_id`` (every frame of a call is image ``first_image_id`` itself, so a frame's loss
+        is the one it has alone) key its normals in validation_losses_boxes / validate_boxes (a training step takes its own).
+        An argument left at None keeps the handle's value (initially 64, 0, 0, False).  A sample count outside [2, 1024] is a
+        ValueError and changes nothing."""
+        cur = dict(getattr(self, "_loss_options", {"energy_samples": 64, "seed": 0, "first_image_id": 0, "one_image_id": False}))
+        for k, v in (("energy_samples", energy_samples), ("seed", seed), ("first_image_id", first_image_id), ("one_image_id", one_image_id)):
+            if v is not None:
+                cur[k] = v
+        self._chk(self.lib.bod_set_loss_options(self.h, C.byref(_lib.loss_options(**cur))))
+        self._loss_options = cur
+
     # -- training (SURVEY.md section 8 f1) ------------------------------------------------------
     def train_step(self, images, cls_targets, box_targets, positive_mask, negative_mask, seed=0, first_image_id=0,
                    reg_kind=3, label_smoothing=0.001, w_cls=5.0, w_reg=1.0, l2_rate=1e-6, learning_rate=1e-3,
-                   apply_update=True):
+                   apply_update=True, energy_samples=None):
         """run_training.train_single_step on a handle made with make_config(training=True): returns a dict with
-        total_loss, cls_loss, reg_loss, covariance_loss, regularization_loss and the global gradient norm."""
+        total_loss, cls_loss, reg_loss, covariance_loss, regularization_loss and the global gradient norm.
+        ``energy_samples``: set_loss_options(energy_samples) first (reg_kind 5; None keeps the handle's)."""
+        if energy_samples is not None:
+            self.set_loss_options(energy_samples)
         b, a = self.B, self.A
         ct = as_f32(cls_targets).reshape(b, a, self.Ccls)
         bt = as_f32(box_targets).reshape(b, a, 4)
@@ -333,9 +350,11 @@ class Engine(object):
 
     def train_step_boxes(self, images, gt_boxes, gt_classes, min_positive_iou=0.5, max_negative_iou=0.4, seed=0, first_image_id=0,
                          reg_kind=3, label_smoothing=0.001, w_cls=5.0, w_reg=1.0, l2_rate=1e-6, learning_rate=1e-3,
-                         apply_update=True):
+                         apply_update=True, energy_samples=None):
         """train_step from ground-truth boxes (``bod_train_step_boxes``): per-frame lists of [G_b,4] corners (y1,x1,y2,x2)
         and [G_b,C] class rows; the dense targets are assigned on the device against the handle's anchors."""
+        if energy_samples is not None:
+            self.set_loss_options(energy_samples)
         ng, boxes, classes = _pack_gt(gt_boxes, gt_classes, self.B, self.Ccls)
         out = (C.c_double * 6)()
         if images is None:
@@ -409,10 +428,13 @@ class Engine(object):
         self._chk(st)
 
     def validation_losses_boxes(self, gt_boxes, gt_classes, min_positive_iou=0.5, max_negative_iou=0.4, do_classification=True,
-                                reg_kind=3, label_smoothing=0.001):
+                                reg_kind=3, label_smoothing=0.001, loss_options=None):
         """Per-frame loss sums of the handle's current raw outputs (``bod_validation_losses_boxes``): [B,4] float64 rows
         (sum of masked focal terms, sum of positive regression terms, sum of positive 0.5 sum(log D) terms, positives).
-        Ground truth as in train_step_boxes; the dense targets are assigned on the device."""
+        Ground truth as in train_step_boxes; the dense targets are assigned on the device.  ``loss_options``: keyword
+        arguments of set_loss_options, applied first (reg_kind 5)."""
+        if loss_options is not None:
+            self.set_loss_options(**loss_options)
         ng, boxes, classes = _pack_gt(gt_boxes, gt_classes, self.B, self.Ccls)
         sums = np.empty((self.B, 4), np.float64)
         self._chk_val(self.lib.bod_validation_losses_boxes(self.h, iptr(ng), fptr(boxes), fptr(classes), float(min_positive_iou),
@@ -432,10 +454,12 @@ class Engine(object):
         return self._val_records(num, scores, corners)
 
     def validate_boxes(self, images, gt_boxes, gt_classes, min_positive_iou=0.5, max_negative_iou=0.4, do_classification=True,
-                       reg_kind=3, label_smoothing=0.001):
+                       reg_kind=3, label_smoothing=0.001, loss_options=None):
         """The validation loop body for a batch (``bod_validate_boxes``): forward, per-frame loss sums, validation post,
         soft-NMS, record gather.  images=None uses the frames uploaded with upload_frames_u8 / upload_images.  Returns
-        (sums [B,4] float64, [(class rows [K,C], corners [K,4])] per image)."""
+        (sums [B,4] float64, [(class rows [K,C], corners [K,4])] per image).  ``loss_options`` as in validation_losses_boxes."""
+        if loss_options is not None:
+            self.set_loss_options(**loss_options)
         ng, boxes, classes = _pack_gt(gt_boxes, gt_classes, self.B, self.Ccls)
         if images is None:
             ptr, on_dev = self.lib.bod_device_images(self.h), 1

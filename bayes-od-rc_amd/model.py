@@ -136,12 +136,13 @@ class RetinaNetModel(object):
 
     call = __call__
 
-    _REG_KIND = {'regression': 1, 'regression_var': 2, 'regression_covar': 3}
+    _REG_KIND = {'regression': 1, 'regression_var': 2, 'regression_covar': 3, 'regression_nll': 4, 'regression_energy': 5}
 
-    def get_loss(self, sample_dict, prediction_dict):
+    def get_loss(self, sample_dict, prediction_dict, seed=None, image_id=0):
         """Loss FORWARD with the reference's signature and return value ``(total_loss, loss_dict)``
         (retinanet_model.py:151-328; keys src/core/constants.py:66-71), evaluated on the device.
-        The backward pass / optimizer belong to the training step."""
+        The backward pass / optimizer belong to the training step.  ``seed`` (default: the model's)
+        and ``image_id`` of the first frame key the normals of 'regression_energy' (DESIGN.md 9.10); no other loss reads them."""
         import ctypes as C
         from . import _lib
         losses = self.model_config['losses']
@@ -173,10 +174,12 @@ class RetinaNetModel(object):
         out = (C.c_double * 4)()
         lib = _lib.load()
         u8 = C.POINTER(C.c_uint8)
-        st = lib.bod_loss_forward(self.device, b, a, c, _lib.fptr(cls), _lib.fptr(cls_t), _lib.fptr(box), _lib.fptr(box_t),
-                                  _lib.fptr(cov), _lib.fptr(anchors), pos.ctypes.data_as(u8), neg.ctypes.data_as(u8),
-                                  int('classification' in names), kind,
-                                  float(losses.get('label_smoothing_epsilon', 0.001)), out)
+        # 'regression_energy' draws its normals per (seed, image id, anchor): the images of this call count on from image_id
+        opts = _lib.loss_options(losses.get('energy_samples', 64), self.seed if seed is None else seed, image_id)
+        st = lib.bod_loss_forward_ex(self.device, b, a, c, _lib.fptr(cls), _lib.fptr(cls_t), _lib.fptr(box), _lib.fptr(box_t),
+                                     _lib.fptr(cov), _lib.fptr(anchors), pos.ctypes.data_as(u8), neg.ctypes.data_as(u8),
+                                     int('classification' in names), kind,
+                                     float(losses.get('label_smoothing_epsilon', 0.001)), out, C.byref(opts))
         _lib.check(lib, None, st)
         return loss_from_sums(names, weights, out)
 

@@ -27,7 +27,7 @@ from .anchor_generator import FpnAnchorGenerator
 from .engine import Engine, augment_boxes, augment_config, draw_augmentation, make_config
 from .sample_builder import create_sample_dict
 
-_REG_KIND = {'regression': 1, 'regression_var': 2, 'regression_covar': 3}
+_REG_KIND = {'regression': 1, 'regression_var': 2, 'regression_covar': 3, 'regression_nll': 4, 'regression_energy': 5}
 
 
 def piecewise_learning_rate(training_config, epoch_size):
@@ -72,6 +72,10 @@ class Trainer(object):
                                          dropout_rate=float(header['dropout_rate']),
                                          has_covar_head='regression_covar' in model_config['output_names'], training=True,
                                          backbone_depth=101 if '101' in str(model_config.get('feature_extractor', {}).get('name', '')) else 50))
+        # 'regression_energy': samples per positive anchor (losses.energy_samples, default 64); the step keys them by its seed / image ids
+        self.energy_samples = int(losses.get('energy_samples', 64))
+        if self.reg_kind == 5:
+            self.engine.set_loss_options(energy_samples=self.energy_samples)
         self.engine.load_weights(weights)
         self._init = weights
         self.anchor_config = config['dataset_config']['anchor_generator']

@@ -108,6 +108,10 @@ def validate_batch(model, config, batch, mixed_sizes=False):
     anchor_config = dataset_config['anchor_generator']
     losses = config['model_config']['losses']
     do_cls, reg_kind = model.loss_kinds()
+    if reg_kind == 5:
+        # 'regression_energy' is a sample estimate: every frame draws the normals of image 0 under the model's seed, as
+        # val_single_step's get_loss does for a frame alone -- its loss depends neither on its batch nor on its place there
+        eng.set_loss_options(energy_samples=int(losses.get('energy_samples', 64)), seed=model.seed, first_image_id=0, one_image_id=True)
     sums, detections = eng.validate_boxes(
         images, [s[constants.BOXES_2D_GT_KEY] for s in batch], [s[constants.BOXES_CLASS_GT_KEY] for s in batch],
         float(anchor_config['min_positive_iou']), float(anchor_config['max_negative_iou']), do_classification=do_cls,

@@ -416,7 +416,8 @@ bod_status bod_train_step_count(bod_handle h, int64_t* get, int64_t set);
  * BASELINE config 5's loss, forward only).  Host arrays: cls/cls_targets [B,A,C], box/box_targets [B,A,4],
  * covar_params [B,A,10] (pre fill_triangular; may be NULL unless reg_kind >= 2), anchors [A,4],
  * positive/negative masks [B,A] (bytes).  reg_kind: 0 none, 1 'regression', 2 'regression_var',
- * 3 'regression_covar'.  out4 = {sum of masked focal terms, sum of positive regression terms,
+ * 3 'regression_covar', 4 'regression_nll', 5 'regression_energy' (the last two: below).
+ * out4 = {sum of masked focal terms, sum of positive regression terms,
  * sum of positive 0.5*sum(log D) terms, number of positives}; the caller applies the
  * /max(num_pos,1) normalisation and the yaml loss weights. Errors via bod_last_error(NULL). */
 bod_status bod_loss_forward(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls,
@@ -424,6 +425,42 @@ bod_status bod_loss_forward(int32_t device, int32_t B, int32_t A, int32_t C, con
                             const float* covar_params, const float* anchors, const uint8_t* positive_mask,
                             const uint8_t* negative_mask, int32_t do_classification, int32_t reg_kind,
                             float label_smoothing, double* out4);
+
+/* Proper scoring rules as training losses.  Per positive anchor, with pb / tb the decoded prediction and
+ * target in vuhw pixels (the decode of reg_kind 2 / 3, clips and their zero gradient included), e = pb - tb, c[0..9] the raw
+ * covariance parameters, ld = (c4, c9, c5, c0), A1 the unit-lower matrix with rows (1), (c8, 1), (c7, c6, 1), (c3, c2, c1, 1) and
+ * Sigma = A1^-1 diag(exp ld) A1^-T -- the full covariance inference builds from the same ten numbers:
+ *   reg_kind 4 'regression_nll':    regression term 0.5 sum_k exp(-ld_k) r_k^2 with r = A1 e, covariance term 0.5 sum_k ld_k
+ *                                   (their sum + 2 ln 2pi is the Gaussian negative log-likelihood of tb);
+ *   reg_kind 5 'regression_energy': regression term (1/M) sum_{i<M} |z_i - g| - 1/(2(M-1)) sum_{i<M-1} |z_i - z_{i+1}| with
+ *                                   A1 y_i = exp(ld/2) o n_i, z_i = T (pb + y_i), g = T tb, T: vuhw -> (x1, y1, x2, y2);
+ *                                   covariance term 0.
+ * Normals of reg_kind 5: sample i of (image id, anchor a) is ONE call philox4x32_10(i, a, 0x0010555E, image id, seed &
+ * 0xffffffff, seed >> 32) -> (x, y, z, w), u(t) = (t + 0.5) 2^-32, n0, n1 = sqrt(-2 ln u(x)) (cos, sin)(2 pi u(y)), n2, n3
+ * likewise from (z, w); image id = first_image_id + frame.  A row's term and gradient depend on (seed, image id, anchor, M)
+ * and the row's own tensors alone (bitwise), not on the batch around it.
+ * energy_samples = M in [2, 1024]; anything else is BOD_ERR_INVALID_ARG.  reserved[0] holds flags: BOD_LOSS_ONE_IMAGE_ID = every
+ * frame of the call is image `first_image_id` itself (validation: a frame's loss is then the one it has alone, whatever batch it
+ * sits in and wherever; the training step ignores the flag).  reserved[1..3]: set to 0. */
+#define BOD_LOSS_ONE_IMAGE_ID 1
+typedef struct {
+    int32_t energy_samples;
+    uint64_t seed;
+    uint32_t first_image_id;
+    int32_t reserved[4];
+} bod_loss_options;
+/* bod_loss_forward / bod_loss_backward with the options of reg_kind 5; NULL = the defaults {64, 0, 0}, which is what the two
+ * plain entries use.  reg_kind 0..4 ignore everything but the range check of energy_samples. */
+bod_status bod_loss_forward_ex(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls,
+                               const float* cls_targets, const float* box, const float* box_targets,
+                               const float* covar_params, const float* anchors, const uint8_t* positive_mask,
+                               const uint8_t* negative_mask, int32_t do_classification, int32_t reg_kind,
+                               float label_smoothing, double* out4, const bod_loss_options* options);
+/* The options of a handle's entries (NULL = defaults).  bod_train_step / bod_train_step_boxes take energy_samples from here and
+ * the seed and the first image id from their own arguments (a recorded step reads them from the device scalars its dropout
+ * reads, so every replay draws new normals; another energy_samples re-records).  bod_validation_losses_boxes and
+ * bod_validate_boxes take all three from here. */
+bod_status bod_set_loss_options(bod_handle h, const bod_loss_options* options);
 
 /* Anchor-target assignment (bbox_iou_vuvu + positive_negative_batching + generate_anchor_targets of the dataset handlers;
  * stateless, host arrays in and out): anchors_vuhw [A,4], per frame num_gt[b] >= 1 rows of gt_boxes_vuvu [sum G,4] and
@@ -477,6 +514,13 @@ bod_status bod_loss_backward(int32_t device, int32_t B, int32_t A, int32_t C, co
                              const float* covar_params, const float* anchors, const uint8_t* positive_mask,
                              const uint8_t* negative_mask, int32_t do_cls, int32_t reg_kind, float label_smoothing,
                              float w_cls, float w_reg, double* out4, float* dcls, float* dbox, float* dcov);
+/* The same with the options of reg_kind 5 (bod_loss_forward_ex); NULL = defaults. */
+bod_status bod_loss_backward_ex(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls,
+                                const float* cls_targets, const float* box, const float* box_targets,
+                                const float* covar_params, const float* anchors, const uint8_t* positive_mask,
+                                const uint8_t* negative_mask, int32_t do_cls, int32_t reg_kind, float label_smoothing,
+                                float w_cls, float w_reg, double* out4, float* dcls, float* dbox, float* dcov,
+                                const bod_loss_options* options);
 
 /* PDQ (Probability-based Detection Quality, prob_detection_quality.py) on the device; stateless, like bod_loss_forward.
  * Results match the CPU path's rules: corner regions, fp64 bivariate-normal CDFs stored as float32 heatmaps, NumPy slice

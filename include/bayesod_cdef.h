@@ -152,6 +152,18 @@ bod_status bod_loss_forward(int32_t device, int32_t B, int32_t A, int32_t C, con
                             const float* covar_params, const float* anchors, const uint8_t* positive_mask,
                             const uint8_t* negative_mask, int32_t do_classification, int32_t reg_kind,
                             float label_smoothing, double* out4);
+typedef struct {
+    int32_t energy_samples;
+    uint64_t seed;
+    uint32_t first_image_id;
+    int32_t reserved[4];
+} bod_loss_options;
+bod_status bod_loss_forward_ex(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls,
+                               const float* cls_targets, const float* box, const float* box_targets,
+                               const float* covar_params, const float* anchors, const uint8_t* positive_mask,
+                               const uint8_t* negative_mask, int32_t do_classification, int32_t reg_kind,
+                               float label_smoothing, double* out4, const bod_loss_options* options);
+bod_status bod_set_loss_options(bod_handle h, const bod_loss_options* options);
 bod_status bod_anchor_targets(int32_t device, int32_t A, const float* anchors_vuhw, int32_t B, const int32_t* num_gt,
                               const float* gt_boxes_vuvu, const float* gt_classes, int32_t C, float min_positive_iou,
                               float max_negative_iou, float* cls_targets, float* box_targets, uint8_t* positive_mask,
@@ -169,6 +181,12 @@ bod_status bod_loss_backward(int32_t device, int32_t B, int32_t A, int32_t C, co
                              const float* covar_params, const float* anchors, const uint8_t* positive_mask,
                              const uint8_t* negative_mask, int32_t do_cls, int32_t reg_kind, float label_smoothing,
                              float w_cls, float w_reg, double* out4, float* dcls, float* dbox, float* dcov);
+bod_status bod_loss_backward_ex(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls,
+                                const float* cls_targets, const float* box, const float* box_targets,
+                                const float* covar_params, const float* anchors, const uint8_t* positive_mask,
+                                const uint8_t* negative_mask, int32_t do_cls, int32_t reg_kind, float label_smoothing,
+                                float w_cls, float w_reg, double* out4, float* dcls, float* dbox, float* dcov,
+                                const bod_loss_options* options);
 bod_status bod_pdq_corner_heatmaps(int32_t device, int32_t img_h, int32_t img_w, int32_t n, const double* means_yx,
                                    const double* covs_yx, int32_t* rois, float* heatmaps);
 bod_status bod_pdq_frames(int32_t device, int32_t img_h, int32_t img_w, int32_t num_frames, const int32_t* num_gt,
