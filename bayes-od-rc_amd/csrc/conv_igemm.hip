@@ -728,8 +728,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
     // library's GEMMs level off.  Same LDS image, same swizzle (conflict-free for the 16-row fragments too), same bytes per
     // FLOP (wave tile 128 x 64 = 8 x 4 fragments of 16 x 16): a lane then holds, per fragment, 4 consecutive couts
     // (fc*16 + (lane>>4)*4 + r) of pixel fp*16 + (lane & 15).
-    constexpr bool M16 = XR && !SPLIT && ABL != 81 && BC == 256 && BP == 256 && WC == 2 && WP == 4;
-    constexpr int FC16 = M16 ? 8 : 1, FP16 = M16 ? 4 : 1;
+    // BP = 192 (the sparse tail's tiles, which close on their extended rows at about 15 of 25 pixel slots): the same loop with THREE
+    // 16-row pixel fragments per wave -- three MFMAs per step instead of four, three B fragments per set; every `FP16` below.
+    constexpr bool M16 = XR && !SPLIT && ABL != 81 && BC == 256 && (BP == 256 || BP == 192) && WC == 2 && WP == 4;
+    constexpr int FC16 = M16 ? 8 : 1, FP16 = M16 ? WTP / 16 : 1;
     f32x4 acc4[FC16][FP16];
 #pragma unroll
     for (int i = 0; i < FC16; ++i)
@@ -743,7 +745,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
 #pragma unroll
         for (int i = 0; i < FC16; ++i) {
 #if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("" : "+v"(acc4[i][0]), "+v"(acc4[i][1]), "+v"(acc4[i][2]), "+v"(acc4[i][3]));
+            if constexpr (FP16 == 4) asm volatile("" : "+v"(acc4[i][0]), "+v"(acc4[i][1]), "+v"(acc4[i][2]), "+v"(acc4[i][3]));
+            else asm volatile("" : "+v"(acc4[i][0]), "+v"(acc4[i][1]), "+v"(acc4[i][2]));
 #endif
         }
     }
@@ -770,7 +773,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
         // k-step the A fragments are double-buffered in pairs (i = 0,1 | 2,3) and the B fragments across
         // k-steps, every ds_read_b128 is issued >= 4 MFMAs before its first use, and the only exposed LDS
         // wait is the first fragment set after each block barrier (covered by issuing the LDS-DMA there).
-        static_assert(BC == 256 && BP == 256 && WC == 2 && WP == 4, "written for the 256x256 8-wave tile");
+        static_assert(BC == 256 && (BP == 256 || (M16 && BP == 192 && ABL == 0)) && WC == 2 && WP == 4, "written for the 256x256 8-wave tile (256x192: production build)");
         static_assert(M16 || !(!SPLIT && FP == 2 && ABL != 81), "decisions are drawn in the loop by the 16x16x32 builds only");
         constexpr int WST = BC * ROWB, XBUF = XR_EXT_ROWS * ROWB, NXE = XR_EXT_ROWS * 8 / THREADS;   // 5 pieces / thread
         // 32-bit offsets are taken against the tile's FIRST extended row (the smallest pixel index of the tile: the
@@ -829,7 +832,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
         const int a_c0 = (fhalf ^ fswz) << 4;                                // chunk byte offset of k-step 0 (k-step ks: ^ (ks << 5))
         const int a_row = (wc * WTC + frow) * ROWB + a_c0;
         const int NG = KT / 3;
-        constexpr bool PH_BUILD = !SPLIT && FP == 2 && (ABL == 0 || ABL == 9 || ABL == 90 || ABL == 30 || ABL == 31 || ABL == 1 || ABL == 2);
+        constexpr bool PH_BUILD = !SPLIT && (FP == 2 || BP == 192) && (ABL == 0 || ABL == 9 || ABL == 90 || ABL == 30 || ABL == 31 || ABL == 1 || ABL == 2);
         const bool ph_on = PH_BUILD && (a.flags & CONV_DROPOUT) && !(a.flags & CONV_OUT_F32) && a.fan_count <= 1 && NG >= 8 && bc0 == 0 &&
                            a.drop_threshold >= 1 && a.variant != 83;            // (variant 83: decisions drawn in the epilogue, A/B)
         ph_inloop = ph_on;
@@ -908,7 +911,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
             // the fragments of k-step ks; the set not in use is refilled half a K-tile ahead: k-step 1's fragments behind steps 2..5,
             // the next K-tile's k-step-0 fragments behind steps 9..12 (same staged rows, one further: resident since the group's
             // first barrier) or, at a group's last K-tile, behind the barrier (steps 14, 15: the next group's rows)
-            bf16x8 Ar[4], Bc[2][4];
+            bf16x8 Ar[4], Bc[2][FP16];
             // uniform inputs of the in-loop Philox set-up, pinned in scalar registers: a kernel-argument load inside the loop makes the
             // compiler wait lgkmcnt(0) behind it, which also drains the fragment reads in flight
             uint32_t ph_lid16 = (uint32_t)G.layer_id << 16, ph_sbase = a.sample_base;
@@ -941,14 +944,14 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
             rdA(Ar[0], a_cur, 0);
             if constexpr (AHEAD == 3) rdA(Ar[1], a_cur, 1);
             rdB(Bc[0][0], b_addr(0, 0, 0)); rdB(Bc[0][1], b_addr(0, 1, 0));
-            rdA(Ar[AHEAD - 1], a_cur, AHEAD - 1); rdB(Bc[0][2], b_addr(0, 2, 0)); rdB(Bc[0][3], b_addr(0, 3, 0));
+            rdA(Ar[AHEAD - 1], a_cur, AHEAD - 1); rdB(Bc[0][2], b_addr(0, 2, 0)); if constexpr (FP16 == 4) rdB(Bc[0][3], b_addr(0, 3, 0));
             __builtin_amdgcn_sched_barrier(0);
             for (int g = 0; g < NG; ++g) {
                 const bool xnext = g + 1 < NG;
                 const bool next_row = ky + 1 < 3;
                 const int xdst = 2 * WST + ((g + 1) & 1) * XBUF;
-                const bool ph_act = ph_on && g < 8;
-                // group g < 8 draws ONE call in slots 0..9 (contract v3: 16 decisions per call): pixel fragment fp = g >> 1, cout fragment
+                const bool ph_act = ph_on && g < 2 * FP16;
+                // group g < 8 (g < 6 on the 192-row tile: three pixel fragments) draws ONE call in slots 0..9 (contract v3: 16 decisions per call): pixel fragment fp = g >> 1, cout fragment
                 // pair tt = (g & 1) * 2 + (q4 >> 1) -- the lane pair (l, l ^ 32) shares the calls of a fragment pair's two halves: the lower
                 // lane half draws the even pairs, the upper half the odd ones, and they swap their 128 keep bits after the loop
                 auto ph_slot = [&](int sidx) {
@@ -980,9 +983,9 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
                     const int kt = g * 3 + kxc;
                     const bool w1 = kt + 1 < KT, w2 = kt + 2 < KT;
                     // B fragments: k-step 1 of this K-tile; k-step 0 of the next (same rows one further, or the next group's rows)
-                    uint32_t xb1[4], xbn[4];
+                    uint32_t xb1[FP16], xbn[FP16];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
+                    for (int j = 0; j < FP16; ++j) {
                         xb1[j] = b_addr(g & 1, j, kxc) ^ 64u;
                         xbn[j] = kxc < 2 ? b_addr(g & 1, j, kxc + 1) : b_addr((g + 1) & 1, j, 0);
                     }
@@ -1006,9 +1009,13 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
                         if (st + AHEAD <= 15) rdA(Ar[(st + AHEAD) & 3], (st + AHEAD) < 8 ? a_cur : a_k1, (st + AHEAD) & 7);
                         else if (st == 14) { rdA(Ar[0], a_nxt, 0); if constexpr (AHEAD == 3) rdA(Ar[1], a_nxt, 1); }
                         else if (st == 15) rdA(Ar[AHEAD - 1], a_nxt, AHEAD - 1);
-                        if (st >= 2 && st <= 5) rdB(Bc[1][st - 2], xb1[st - 2]);
-                        if (kxc < 2 && st >= 9 && st <= 12) rdB(Bc[0][st - 9], xbn[st - 9]);
-                        if (kxc == 2 && st >= 14) { rdB(Bc[0][2 * (st - 14)], xbn[2 * (st - 14)]); rdB(Bc[0][2 * (st - 14) + 1], xbn[2 * (st - 14) + 1]); }
+                        if (st >= 2 && st < 2 + FP16) rdB(Bc[1][st - 2], xb1[st - 2]);
+                        if (kxc < 2 && st >= 9 && st < 9 + FP16) rdB(Bc[0][st - 9], xbn[st - 9]);
+                        if (kxc == 2 && st >= 14) {
+                            rdB(Bc[0][2 * (st - 14)], xbn[2 * (st - 14)]);
+                            if constexpr (FP16 == 4) rdB(Bc[0][2 * (st - 14) + 1], xbn[2 * (st - 14) + 1]);
+                            else if (st == 14) rdB(Bc[0][1], xbn[1]);
+                        }
                         // ---- reads younger than the operands of this step's MFMAs (LDS returns in order).  Step 0: A(0) and the B set were
                         // issued by the previous K-tile -- behind its barrier if that was a group's last one (kxc == 0 here): then only
                         // A(AHEAD) is younger than the last B fragment.
@@ -1018,12 +1025,17 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
                             constexpr int W_LAST3[16] = {3, 3, 4, 5, 6, 7, 6, 5, 3, 3, 3, 3, 3, 2, -1, -1};     // kxc == 2: next B set read behind the barrier
                             constexpr int W_SAME2[16] = {2, 2, 3, 4, 5, 5, 4, 3, 2, 3, 4, 5, 5, 4, -1, -1};
                             constexpr int W_LAST2[16] = {2, 2, 3, 4, 5, 5, 4, 3, 2, 2, 2, 2, 2, 2, -1, -1};
+                            // (three B fragments per set, AHEAD 2: `tests/tools/lds_wait_tables_frags.py 2 3`)
+                            constexpr int W_SAME2F3[16] = {2, 2, 3, 4, 5, 4, 3, 2, 2, 3, 4, 5, 4, 3, -1, -1};
+                            constexpr int W_LAST2F3[16] = {2, 2, 3, 4, 5, 4, 3, 2, 2, 2, 2, 2, 2, 2, -1, -1};
+                            static_assert(FP16 == 4 || AHEAD == 2, "the three-fragment tables exist for AHEAD 2");
                             int n = AHEAD == 3 ? (kxc < 2 ? W_SAME3[st] : W_LAST3[st]) : (kxc < 2 ? W_SAME2[st] : W_LAST2[st]);
+                            if constexpr (FP16 == 3) n = kxc < 2 ? W_SAME2F3[st] : W_LAST2F3[st];
                             if (st == 0 && kxc == 0) n = 1;
                             if (n >= 0) lgkm(n);
                         }
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) mfma16_inplace(acc4[fc][j], Ar[st & 3], Bc[ks][j]);
+                        for (int j = 0; j < FP16; ++j) mfma16_inplace(acc4[fc][j], Ar[st & 3], Bc[ks][j]);
                         if (st & 1) {                        // 8 slots per K-tile, behind steps 1, 3, .. 15
                             const int slot = st >> 1;
                             __builtin_amdgcn_sched_barrier(0);
@@ -1048,8 +1060,12 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
                 if (++ky == 3) { ky = 0; ++cc; }
             }
             // the reads issued for a K-tile that does not exist: their registers stay allocated until they have landed
+            if constexpr (FP16 == 4)
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Ar[0]), "+v"(Ar[1]), "+v"(Ar[2]), "+v"(Ar[3]), "+v"(Bc[0][0]), "+v"(Bc[0][1]), "+v"(Bc[0][2]), "+v"(Bc[0][3]),
                          "+v"(Bc[1][0]), "+v"(Bc[1][1]), "+v"(Bc[1][2]), "+v"(Bc[1][3]) :: "memory");
+            else
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Ar[0]), "+v"(Ar[1]), "+v"(Ar[2]), "+v"(Ar[3]), "+v"(Bc[0][0]), "+v"(Bc[0][1]), "+v"(Bc[0][2]),
+                         "+v"(Bc[1][0]), "+v"(Bc[1][1]), "+v"(Bc[1][2]) :: "memory");
 #endif
         } else if constexpr (MXL) {
             // ---- f16mx: the K-tile flavour is fixed per loop -- chunk cc = 2p is the H chunk of 64-channel group p (f16 hi: four f16
@@ -2283,7 +2299,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
             for (int k = 0; k < 4; ++k) ph_oth[k] = (uint32_t)__shfl_xor((int)ph_bits[k], 32, 64);
         }
     }
-    // M16, decisions drawn in the loop: group g = fp*2 + (fc>>2) left the 16 keep bits of a call at bit (7 - g)*16 of the 128 -- drawn by
+    // M16, decisions drawn in the loop: group g = fp*2 + (fc>>2) left the 16 keep bits of a call at bit (7 - g)*16 of the 128 (192-row tile: six calls, bit (5 - g)*16 of 96) -- drawn by
     // the lower lane half for the even fragment pairs (fc>>1 even), by the upper half for the odd ones (T0 / T1 below) -- and of that
     // call the lane's run is u = (fc&1)*2 + (q4>>1): bits 4u .. 4u+3.  Source and the (q4>>1) part of the shift are selected ONCE per
     // word here, so that the per-fragment expansion below is four constant-position bit extracts.
@@ -2316,7 +2332,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
                     if (drop && ph_inloop) {
                         // the call of fragment pair fc>>1 left its 16 bits at a fixed position; the lane's nibble (run (fc&1)*2 + (q4>>1)) sits
                         // at bit (fc&1)*8 of that field in ph_En (even pairs) / ph_On (odd pairs).  Bit r -> 16-bit lane r of the 4 packed channels.
-                        const int bitpos = (7 - (fp * 2 + (fc >> 2))) * 16 + (fc & 1) * 8;
+                        const int bitpos = (2 * FP16 - 1 - (fp * 2 + (fc >> 2))) * 16 + (fc & 1) * 8;
                         const int P = bitpos & 31;
                         const uint32_t srcw = ((fc >> 1) & 1) ? ph_On[bitpos >> 5] : ph_En[bitpos >> 5];
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -2602,15 +2618,16 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gz, const
                 obase = reinterpret_cast<char*>((uintptr_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uint64_t)(uintptr_t)obase >> 32)) << 32) |
                                                              (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)obase)));
                 const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, 0x7FFFFFFF, 0x00020000);      // raw, 2 GiB window
-                int offs[16];
+                constexpr int NPC = BP / 16;                  // 16-byte pieces per thread: 16 rows of 32 pieces per pass
+                int offs[NPC];
 #pragma unroll
-                for (int k = 0; k < 16; ++k) offs[k] = s_off[prow0 + 16 * k];
-                u32x4 v[16];
+                for (int k = 0; k < NPC; ++k) offs[k] = s_off[prow0 + 16 * k];
+                u32x4 v[NPC];
 #pragma unroll
-                for (int k = 0; k < 16; ++k) v[k] = *reinterpret_cast<const u32x4*>(smem + (prow0 + 16 * k) * (BC * 2) + cp * 16);
+                for (int k = 0; k < NPC; ++k) v[k] = *reinterpret_cast<const u32x4*>(smem + (prow0 + 16 * k) * (BC * 2) + cp * 16);
                 const int rowb = a.out_cstride * 2;
 #pragma unroll
-                for (int k = 0; k < 16; ++k) {
+                for (int k = 0; k < NPC; ++k) {
                     const int c16 = (cp ^ (prow0 + 16 * k)) & (CPR - 1);
                     const uint32_t vo = offs[k] < 0 ? 0xFFFFFFF0u : (uint32_t)(offs[k] - first) * (uint32_t)rowb + (uint32_t)(c16 * 16);
                     __builtin_amdgcn_raw_buffer_store_b128(v[k], orsrc, (int)vo, 0, 0);
@@ -2884,6 +2901,7 @@ static hipError_t launch_xr_persistent(const ConvArgs& a, hipStream_t s) {
 template <int BC, int BP, int WC, int WP, int ABL, bool XR = false, bool SPLIT = false>
 static hipError_t launch_cfg(const ConvArgs& a, hipStream_t s) {
     using Cfg = ConvCfg<BC, BP, WC, WP, XR>;
+    static_assert(Cfg::LDS <= 160 * 1024, "LDS of a compute unit");
     static PerDeviceOnce once;
     bool& attr_set = *once.slot();
     const int nx = (a.M + BP - 1) / BP, ny = a.cout_pad / BC;
@@ -3035,6 +3053,7 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     const ConvArgs& a = a_local;
     if (a.M <= 0) return hipSuccess;
     if (a.tile_count && (a.mx || a.split || !a.xreuse || a.ksplit > 1)) return hipErrorInvalidValue;       // (the bf16 row-reuse loop only)
+    if (a.tile_rows != 0 && a.tile_rows != 256 && !(a.tile_rows == 192 && a.tile_count)) return hipErrorInvalidValue;
     if (a.cin % 64 != 0 || a.cout_pad % 64 != 0) return hipErrorInvalidValue;
     if (a.mx) {                                      // f16mx precision: head-tower launches on the row-reuse loop, whatever the tile heuristics say
         if ((a.mx < 1 || a.mx > 3) || !a.split || a.xreuse != 2 || a.cout_pad != 256 || a.cin != 512 || a.taps != 9 || a.KW != 3 || !a.ext || a.M % 256 != 0 ||
@@ -3105,10 +3124,13 @@ hipError_t launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     }
     const int variant = a.variant;
     if (a.xreuse) {
-        if (!(big && a.cout_pad == 256 && a.taps == 9 && a.KW == 3 && a.ext && a.M % 256 == 0)) return hipErrorInvalidValue;
+        const int tile_rows = a.tile_rows == 192 ? 192 : 256;
+        if (!(big && a.cout_pad == 256 && a.taps == 9 && a.KW == 3 && a.ext && a.M % tile_rows == 0)) return hipErrorInvalidValue;
         for (int g = 0; g < a.groups; ++g) if (a.g[g].res || a.g[g].out_relu) return hipErrorInvalidValue;   // compiled out of the row-reuse kernel
         if (a.flags & CONV_OUT_F32) return hipErrorInvalidValue;                                              // likewise
         // device-side tile count (the sparse tail): the production loop (conv_igemm_kernel, above)
+        // (192-row tiles -- three pixel fragments per wave -- are their own symbol: the sparse tail, ConvArgs.tile_rows)
+        if (a.tile_count && tile_rows == 192) return (a.xreuse == 2 && a.variant == 0 && a.fan_count <= 1) ? launch_cfg<256, 192, 2, 4, 0, true>(a, s) : hipErrorInvalidValue;
         if (a.tile_count) return (a.xreuse == 2 && a.variant == 0 && a.fan_count <= 1) ? launch_cfg<256, 256, 2, 4, 0, true>(a, s) : hipErrorInvalidValue;
         // xreuse == 2: compact-state, software-pipelined loop (32-bit byte offsets against the tile's first extended row);
         // otherwise (or variant 81, for A/B timing) the first-generation loop with 64-bit pointers

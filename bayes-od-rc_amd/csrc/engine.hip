@@ -311,6 +311,7 @@ struct bod_context {
     bool plan_sparse = false;
     bool plan_halo = false;                              // ... and box layer 1 / covariance layer 2 over the tail's 3x3 halo
     SparseTailArgs sparse{};
+    int plan_tail_rows = 0;                              // rows per tile of the sparse tail launch (bod_plan_info_n slot 9; 0: no sparse tail)
     bool agg_sparse = false;                             // the last forward's agg[1] / agg[2] are sparse
     // Statistics handles (bod_config.mc_statistics): the accumulator of the bod_stat_* entry points -- a second set of the three
     // agg[] arrays holding the merged statistics of stat_k samples.  agg[] itself receives every bod_stat_forward's fresh record (from
@@ -1121,6 +1122,21 @@ bod_status build_plan(bod_context* h) {
         // both tables: B * (P / st_min_pixels + 1) tiles of 256 rows (8 KiB) + XR_EXT_ROWS extended rows (2.5 KiB) each; 512 frames
         // of 512x512 at N = 10: 279 552 tiles, 3.0 GB per table
         sa.cap_tiles = B * (h->P / st_min_pixels(N) + 1);
+        // The tail's tiles have 192 rows -- three 16-row pixel fragments per wave instead of four: its tiles close on their extended
+        // rows at 15 of 25 slots (N = 10), so the fourth fragment multiplied padding (conv_igemm.hip, BP = 192).  Same pixels in as
+        // many tiles (+0.1 %), each with three quarters of the MFMAs.  BOD_SPARSE_TAIL_ROWS=256: the 256-row tiles, A/B twin.
+        sa.tail_rows = 192;
+        if (const char* e = getenv("BOD_SPARSE_TAIL_ROWS")) { if (atoi(e) == 256) sa.tail_rows = 256; }
+        {
+            // the launch needs the 256-cout tile for its M = cap_tiles * rows (launch_conv_igemm refuses it otherwise): cap_tiles is at
+            // least 2.4 times the dense tile count, so 0.75 of it passes wherever the dense launch did -- checked, not assumed
+            ConvArgs probe{};
+            probe.M = sa.cap_tiles * sa.tail_rows; probe.cout_pad = 256; probe.fan_count = 1; probe.flags = CONV_RELU;
+            if (!conv_igemm_uses_full_cout_tile(probe)) sa.tail_rows = 256;
+        }
+        // (the fewest pixels of a closed tile are set by the extended rows, about 106 / N < 192 / N: cap_tiles holds for either height)
+        if (st_min_pixels(N, sa.tail_rows) != st_min_pixels(N))
+            return h->fail(BOD_ERR_INVALID_ARG, "sparse tail: %d-row tiles change the tile bound at N = %d", sa.tail_rows, N);
         sa.lv.n = 5;
         {
             const PyramidGeometry pg = pyramid_geometry(h->lh, h->lw);
@@ -1131,7 +1147,7 @@ bod_status build_plan(bod_context* h) {
         HIPCHK(h, hipMemcpyAsync(pix, t2.data(), (size_t)h->P * sizeof(RowEnt), hipMemcpyHostToDevice, h->stream));     // image 0, sample 0
         HIPCHK(h, hipStreamSynchronize(h->stream));
         sa.pix = pix;
-        BODCHK(h->dalloc(&sa.rows, (size_t)sa.cap_tiles * 256, false));
+        BODCHK(h->dalloc(&sa.rows, (size_t)sa.cap_tiles * sa.tail_rows, false));
         BODCHK(h->dalloc(&sa.ext, (size_t)sa.cap_tiles * XR_EXT_ROWS, false));
         if (halo) {
             BODCHK(h->dalloc(&sa.halo_rows, (size_t)sa.cap_tiles * 256, false));
@@ -1144,6 +1160,7 @@ bod_status build_plan(bod_context* h) {
     }
     h->plan_sparse = sparse;
     h->plan_halo = halo;
+    h->plan_tail_rows = sparse ? h->sparse.tail_rows : 0;
     Op sparse_op; sparse_op.kind = Op::CONV; sparse_op.is_head3x3 = true; sparse_op.flavour = FLAVOUR_AGG;
     int sparse_groups = 0; PackedConv sparse_pc{};
     Op halo_op = sparse_op;
@@ -1302,7 +1319,8 @@ bod_status build_plan(bod_context* h) {
             halo_op.name = "head_tower_layer_2(halo)";
             h->ops.push_back(halo_op);
         }
-        ConvArgs a = base_args(sparse_pc, sa.rows, sa.cap_tiles * 256, 256, 256);
+        ConvArgs a = base_args(sparse_pc, sa.rows, sa.cap_tiles * sa.tail_rows, 256, 256);
+        a.tile_rows = sa.tail_rows;
         for (int q = 0; q < sparse_groups; ++q) a.g[q] = sparse_op.conv.g[q];
         a.groups = sparse_groups;
         a.flags = CONV_RELU | (mc ? CONV_DROPOUT : 0);
@@ -1578,6 +1596,30 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
                 SparseTailArgs sa = h->sparse;
                 sa.keep = h->pb.keep;
                 HIPCHK(h, launch_sparse_tail_rows(sa, st));
+                // BOD_SPARSE_STATS=1 (diagnostic; it waits for the stream and reads the tail table back): how many tiles the tables got
+                // and how full the tail's are
+                static const bool sparse_stats = [] { const char* e = getenv("BOD_SPARSE_STATS"); return e && atoi(e) != 0; }();
+                if (sparse_stats) {
+                    HIPCHK(h, hipStreamSynchronize(st));
+                    int32_t cnt[2] = {0, 0};
+                    HIPCHK(h, hipMemcpy(cnt, sa.tile_count, sizeof cnt, hipMemcpyDeviceToHost));
+                    const int R = sa.tail_rows;
+                    long valid = 0, full = 0;
+                    if (cnt[0] > 0 && cnt[0] <= sa.cap_tiles) {
+                        std::vector<int32_t> off((size_t)cnt[0] * R);
+                        HIPCHK(h, hipMemcpy2D(off.data(), sizeof(int32_t), &sa.rows[0].out_off, sizeof(RowEnt), sizeof(int32_t), off.size(), hipMemcpyDeviceToHost));
+                        for (int t = 0; t < cnt[0]; ++t) {
+                            int v = 0;
+                            for (int r = 0; r < R; ++r) v += off[(size_t)t * R + r] >= 0 ? 1 : 0;
+                            valid += v;
+                            full += v == R ? 1 : 0;       // no padding row: the tile closed on its slots and R is a multiple of N
+                        }
+                    }
+                    const long dense = ((long)sa.B * sa.N * sa.P + 255) / 256;
+                    std::fprintf(stderr, "BOD_SPARSE_STATS: tail %d tiles of %d rows, %.1f valid rows per tile (%ld rows = %.3f of the dense launch's), %ld tiles with all %d rows valid; "
+                                 "halo %d tiles of 256 rows; dense plain tiles %ld; capacity %d tiles\n", (int)cnt[0], R,
+                                 cnt[0] > 0 ? (double)valid / cnt[0] : 0.0, valid, (double)valid / ((double)sa.B * sa.N * sa.P), full, R, (int)cnt[1], dense, (int)sa.cap_tiles);
+                }
                 h->keep_ready = true; h->keep_seed = seed; h->keep_first = first_image;
                 break;
             }
@@ -3781,10 +3823,11 @@ bod_status bod_plan_info(bod_handle h, int32_t* info8) {
 
 bod_status bod_plan_info_n(bod_handle h, int32_t* info, int32_t n) {
     if (!h || !info || n < 0) return BOD_ERR_INVALID_ARG;
-    int32_t all[9];
+    int32_t all[10];
     BODCHK(bod_plan_info(h, all));
     all[8] = h->plan_halo;
-    for (int i = 0; i < n && i < 9; ++i) info[i] = all[i];
+    all[9] = h->plan_tail_rows;
+    for (int i = 0; i < n && i < 10; ++i) info[i] = all[i];
     return BOD_OK;
 }
 

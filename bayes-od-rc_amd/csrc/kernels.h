@@ -130,8 +130,12 @@ struct ConvArgs {
     // the 256 rows).  0 = off.
     int32_t mx;
     int32_t mx_loader;     // f16mx loop: which waves issue the weight pieces (conv_igemm.hip; 0 all, 1 lower four, 2 upper four)
+    // Rows per pixel tile of a launch with `tile_count`: 0 or 256 = the 256x256 tile; 192 = the 256-cout x 192-row build (three 16-row
+    // pixel fragments per wave: the sparse tail, whose tiles close on their extended rows long before 256 rows are full).  `rows`
+    // then holds M / 192 tiles of 192 rows; `ext` is XR_EXT_ROWS per tile either way.
+    int32_t tile_rows;          // (in the padding in front of the pointer: the argument block keeps its size)
     // Row-reuse launch whose tile count is only known on the device (the sparse tail, launch_sparse_tail_rows): `rows` / `ext` hold
-    // capacity for M / 256 tiles, the first *tile_count of them are valid (conv_igemm_kernel).  nullptr = M / 256 tiles.
+    // capacity for M / 256 tiles (M / tile_rows with `tile_rows`), the first *tile_count of them are valid (conv_igemm_kernel).  nullptr = M / 256 tiles.
     const int32_t* tile_count;
 };
 
@@ -221,7 +225,7 @@ hipError_t launch_posterior_fuse(const PostCfg& c, const PostBuffers& b, hipStre
 struct SparseTailArgs {
     const uint8_t* keep;        // [B, A] (post_sample_kernel)
     const RowEnt* pix;          // [P]
-    RowEnt* rows;               // tail: [cap_tiles * 256]
+    RowEnt* rows;               // tail: [cap_tiles * tail_rows]
     int2* ext;                  // tail: [cap_tiles * XR_EXT_ROWS]
     RowEnt* halo_rows;          // halo: [cap_tiles * 256], or nullptr (tail only)
     int2* halo_ext;             // halo: [cap_tiles * XR_EXT_ROWS]
@@ -230,6 +234,7 @@ struct SparseTailArgs {
     StQuad* chunks;             // scratch [tables * B * P]: pieces (sparse_tables.h StPack)
     StQuad* tiles;              // scratch [tables * B * P]: tiles
     int32_t B, N, P, apl, cap_tiles;
+    int32_t tail_rows;          // rows per tail tile: 192 or 256 (the halo table's tiles always have 256)
     int64_t Ppad;
     SparseLevels lv;
 };

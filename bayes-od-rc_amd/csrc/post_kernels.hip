@@ -901,13 +901,14 @@ __global__ __launch_bounds__(256) void sparse_tail_rows_kernel(SparseTailArgs a)
         StQuad* chunks = a.chunks + ((size_t)t * B + b) * P;
         StQuad* tiles = a.tiles + ((size_t)t * B + b) * P;
         const int nrun = s_nrun[t];
+        const int R = t == 0 ? a.tail_rows : 256;       // rows per tile of this table
         StPack st{0, 0, 0, 0, 0, 0};
         for (int r0 = 0; r0 < nrun; r0 += 64) {
             const int2 mine = r0 + lane < nrun ? runs[r0 + lane] : make_int2(0, 0);
             const int n = min(64, nrun - r0);
             for (int j = 0; j < n; ++j) {
                 const int p = __shfl(mine.x, j), q = __shfl(mine.y, j);
-                st_pack_run(st, p, q - p + 1, N, chunks, tiles, lane == 0);
+                st_pack_run(st, p, q - p + 1, N, chunks, tiles, lane == 0, R);
             }
         }
         st_pack_close(st, tiles, lane == 0);
@@ -921,6 +922,7 @@ __global__ __launch_bounds__(256) void sparse_tail_rows_kernel(SparseTailArgs a)
     const RowEnt invalid = st_invalid_row(a.pix[0]);
     for (int t = 0; t < T; ++t) {
         const int nchunk = s_nchunk[t], ntile = s_ntile[t], base = s_base[t];
+        const int R = t == 0 ? a.tail_rows : 256;
         if (base + ntile > a.cap_tiles) continue;       // (cannot happen: cap_tiles is sized by st_min_pixels)
         RowEnt* rows = t == 0 ? a.rows : a.halo_rows;
         ExtRow* ext = reinterpret_cast<ExtRow*>(t == 0 ? a.ext : a.halo_ext);
@@ -929,11 +931,11 @@ __global__ __launch_bounds__(256) void sparse_tail_rows_kernel(SparseTailArgs a)
         for (int i = tid; i < nchunk * N; i += blockDim.x) {
             const int ci = i / N, n = i - ci * N;
             const StQuad c = chunks[ci];
-            st_write_piece(c, n, b, base + c.y, a.pix, N, P, a.Ppad, rows, ext);
+            st_write_piece(c, n, b, base + c.y, a.pix, N, P, a.Ppad, rows, ext, R);
         }
-        for (int i = tid; i < ntile * 256; i += blockDim.x) {
-            const int tt = i >> 8, r = i & 255;
-            if (st_pad_row(tiles[tt], r, N)) rows[(size_t)(base + tt) * 256 + r] = invalid;
+        for (int i = tid; i < ntile * R; i += blockDim.x) {
+            const int tt = i / R, r = i - tt * R;
+            if (st_pad_row(tiles[tt], r, N)) rows[(size_t)(base + tt) * R + r] = invalid;
         }
         for (int i = tid; i < ntile * XR_EXT_ROWS; i += blockDim.x) {
             const int tt = i / XR_EXT_ROWS, r = i - tt * XR_EXT_ROWS;
@@ -946,6 +948,7 @@ __global__ __launch_bounds__(256) void sparse_tail_rows_kernel(SparseTailArgs a)
 hipError_t launch_sparse_tail_rows(const SparseTailArgs& a, hipStream_t s) {
     if (a.B <= 0 || a.P <= 0 || a.N < 1 || 256 / a.N < 1 || XR_EXT_ROWS / a.N - 2 < 1 || a.P > 65536 || a.lv.n < 1 || a.lv.n > 5)
         return hipErrorInvalidValue;
+    if ((a.tail_rows != 192 && a.tail_rows != 256) || a.tail_rows / a.N < 1) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(a.tile_count, 0, 2 * sizeof(int32_t), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(sparse_tail_rows_kernel, dim3(a.B), dim3(256), (size_t)a.P, s, a);

@@ -10,7 +10,9 @@
 //   ST_HALO  the halo launch computes it: ST_DIL, or a single pixel between two ST_DIL ones in a row (taken along as above)
 // Each flag depends only on the flags before it, so a phase may set its bit while other threads read the older bits.
 // A table is the list of maximal runs of x-adjacent member pixels, cut into pieces and packed, in pixel order, into sample-complete
-// tiles of at most 256 / N pixel slots and XR_EXT_ROWS extended rows (the rules of xr_tile_rows_aggregated, plan_tables.h).
+// tiles of at most R / N pixel slots and XR_EXT_ROWS extended rows (the rules of xr_tile_rows_aggregated, plan_tables.h).  R is the
+// tile height in rows: 256 (the halo table, and every call that does not name it) or 192 (the tail table: its tiles close on their
+// extended rows at about 15 of 25 slots, so three 16-row pixel fragments per wave hold them as well as four).
 #pragma once
 #include "plan_tables.h"
 
@@ -74,8 +76,8 @@ ST_HD inline int st_run_edge(const uint8_t* f, const SparseLevels& g, int p, uin
 }
 
 // the packing of one run [p, p + L): identical to the serial walk it replaced (pieces cut by free slots and free extended rows)
-ST_HD inline void st_pack_run(StPack& s, int p, int L, int N, StQuad* chunks, StQuad* tiles, bool write) {
-    const int Qmax = 256 / N;
+ST_HD inline void st_pack_run(StPack& s, int p, int L, int N, StQuad* chunks, StQuad* tiles, bool write, int R = 256) {
+    const int Qmax = R / N;
     while (L > 0) {
         if (!s.open) { s.first = p; s.Q = 0; s.X = 0; s.open = 1; }
         int take = L < Qmax - s.Q ? L : Qmax - s.Q;
@@ -113,15 +115,15 @@ ST_HD inline RowEnt st_row(const RowEnt& pix_p, int b, int n, int p, int N, int 
     return e;
 }
 
-// sample n of piece c: take + 2 extended rows and take rows of tile `tile` (global index)
+// sample n of piece c: take + 2 extended rows and take rows of tile `tile` (global index; R rows per tile)
 ST_HD inline void st_write_piece(const StQuad& c, int n, int b, int tile, const RowEnt* pix, int N, int P, int64_t Ppad,
-                                 RowEnt* rows, ExtRow* ext) {
+                                 RowEnt* rows, ExtRow* ext, int R = 256) {
     const int p0 = c.x, Q0 = c.z, X0 = c.w & 0xFFFF, take = c.w >> 16;
     const int x0 = X0 + n * (take + 2);
     const RowEnt first = st_row(pix[p0], b, n, p0, N, P, Ppad);
     ExtRow* e = ext + (size_t)tile * XR_EXT_ROWS + x0;
     for (int k = 0; k < take + 2; ++k) e[k] = ExtRow{first.in_off + k, first.in_pitch};
-    RowEnt* r = rows + (size_t)tile * 256;
+    RowEnt* r = rows + (size_t)tile * R;
     for (int k = 0; k < take; ++k) {
         RowEnt q = st_row(pix[p0 + k], b, n, p0 + k, N, P, Ppad);
         q.pad1 = x0 + k;
@@ -144,7 +146,8 @@ ST_HD inline ExtRow st_pad_ext(const StQuad& ti, int b, const RowEnt* pix, int N
 
 // fewest pixels a tile closed before the image's end holds: closed when its slots are full or when a piece of one pixel (3N extended
 // rows) no longer fits; a piece of k pixels costs N * (k + 2) <= 3N * k extended rows.  Bounds the tiles of both tables.
-inline int st_min_pixels(int N) {
-    const int Qmax = 256 / N;
+// (The extended-row term, about 106 / N, is below 192 / N for every N: 192-row tiles have the same bound -- the planner checks.)
+inline int st_min_pixels(int N, int R = 256) {
+    const int Qmax = R / N;
     return std::max(1, std::min(Qmax, (XR_EXT_ROWS - 3 * N) / (3 * N) + 1));
 }

@@ -55,6 +55,7 @@ PRODUCTION = [     # <BC, BP, WC, WP, ABL, XR, SPLIT>
     "conv_igemm_mx_kernelILi1EE",                              # f16mx precision: head towers, hx rows in (f16 + block-scaled e2m3 products, tied inline asm)
     "conv_igemm_mx_kernelILi2EE",                              # f16mx precision: first tower layer ((hi, lo) pairs in, hx rows out)
     "conv_igemm_mx_kernelILi3EE",                              # f16mx4 precision: head towers, h4 rows in (f16 + block-scaled e2m1 products)
+    "conv_igemm_kernelILi256ELi192ELi2ELi4ELi0ELb1ELb0EE",     # the sparse tail on 192-row tiles: the tower loop with three pixel fragments per wave
 ]
 MX_ASM_MFMA = ["conv_igemm_mx_kernelILi1EE", "conv_igemm_mx_kernelILi3EE"]                   # ... whose two MFMA flavours are tied inline asm on the 32x32 accumulators
 MX_MFMA_RE = r"(?:v_mfma_scale_f32_32x32x64_f8f6f4|v_mfma_f32_32x32x16_f16)"
@@ -66,9 +67,12 @@ def _select(*markers):
 
 
 # the kernels on the 16x16x32 inline-asm loop: row reuse (XR = true, SPLIT = false) with ABL 0 / 5 / 6, and the round-2 twin ABL 9
-INLINE_ASM_MFMA = _select("ELi0ELb1ELb0E", "ELi5ELb1ELb0E", "ELi6ELb1ELb0E", "ELi9ELb1ELb0E")
+# (markers carry the tile height where two heights share an ABL: <256, 256, ..., 0> and <256, 192, ..., 0>)
+INLINE_ASM_MFMA = _select("ELi256ELi2ELi4ELi0ELb1ELb0E", "ELi5ELb1ELb0E", "ELi6ELb1ELb0E", "ELi9ELb1ELb0E", "ELi192ELi2ELi4ELi0ELb1ELb0E")
 # ... whose fragment reads and lgkmcnt waits are hand-written too (mid-tile barrier)
-INLINE_ASM_LDS = _select("ELi0ELb1ELb0E", "ELi5ELb1ELb0E", "ELi6ELb1ELb0E")
+INLINE_ASM_LDS = _select("ELi256ELi2ELi4ELi0ELb1ELb0E", "ELi5ELb1ELb0E", "ELi6ELb1ELb0E", "ELi192ELi2ELi4ELi0ELb1ELb0E")
+# MFMAs of three unrolled K-tiles: 64 each with four pixel fragments per wave, 48 with three (the 192-row tile)
+MIN_LOOP_MFMA = {k: (144 if "ILi256ELi192E" in k else 192) for k in INLINE_ASM_MFMA}
 # scratch bytes per lane a kernel may park ACROSS its main loop (checked on the disassembly: none inside it); growth fails the guard.
 # Empty since the end of round 6: the f16mx kernels <1> and <3> parked 16 bytes until their epilogue's ReLU + clamp became one v_med3_f32.
 TOLERATED_SCRATCH = {}
@@ -177,9 +181,12 @@ def _regs(tok):
 MFMA = "v_mfma_f32_16x16x32_bf16"
 
 
-def check_inline_asm_mfma(body, want, window=16, min_mfma=192, mfma_re=None):
+def check_inline_asm_mfma(body, want, window=16, min_mfma=None, mfma_re=None):
     """`body`: instruction list of one kernel.  Returns the number of MFMAs checked.  mfma_re: regex of the tied inline-asm MFMA
-    mnemonics (default: the 16x16x32 bf16 form of the tower loop)."""
+    mnemonics (default: the 16x16x32 bf16 form of the tower loop).  min_mfma: fewest MFMAs the loop must show (default: the
+    kernel's entry in MIN_LOOP_MFMA, else 192)."""
+    if min_mfma is None:
+        min_mfma = MIN_LOOP_MFMA.get(want, 192)
     MFMA = mfma_re or globals()["MFMA"]
     is_mfma = (lambda l: re.match(MFMA, l) is not None) if mfma_re else (lambda l: l.startswith(MFMA))
     mf = [i for i, l in enumerate(body) if is_mfma(l)]
