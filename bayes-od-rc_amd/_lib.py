@@ -53,6 +53,12 @@ class BodLossOptions(C.Structure):
     _fields_ = [("energy_samples", C.c_int32), ("seed", C.c_uint64), ("first_image_id", C.c_uint32), ("reserved", C.c_int32 * 4)]
 
 
+class BodJpegInfo(C.Structure):
+    """struct bod_jpeg_info: what a JPEG file's header says."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("h_samp", C.c_int32), ("v_samp", C.c_int32),
+                ("restart_interval", C.c_int32), ("supported", C.c_int32), ("coef_count", C.c_int64)]
+
+
 BOD_LOSS_ONE_IMAGE_ID = 1                          # flag in bod_loss_options.reserved[0]
 
 
@@ -116,6 +122,14 @@ SIGNATURES = {
     "bod_upload_frames_u8_augmented_async": (C.c_int, [_H, C.POINTER(C.c_uint8), _I, _F, C.c_int32, C.POINTER(BodAugment), C.c_int32]),
     "bod_augment_boxes": (C.c_int, [C.c_int32, _I, C.c_int32, C.c_int32, C.c_int32, C.POINTER(BodAugment), _I, _F, _F, C.c_int32,
                                     C.c_float, _I, _F, _F]),
+    "bod_jpeg_info": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(BodJpegInfo)]),
+    "bod_jpeg_entropy_decode": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int16), C.c_int64, C.POINTER(C.c_uint16)]),
+    "bod_jpeg_decode_rgb": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int32,
+                                      C.POINTER(C.c_uint8), C.c_int64, _I]),
+    "bod_upload_frames_jpeg": (C.c_int, [_H, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), _F, C.c_int32, C.POINTER(BodAugment),
+                                         C.c_int32, _I]),
+    "bod_upload_frames_jpeg_async": (C.c_int, [_H, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), _F, C.c_int32, C.POINTER(BodAugment),
+                                               C.c_int32, _I, C.c_int32]),
     "bod_device_images_buffer": (C.c_void_p, [_H, C.c_int32]),
     "bod_device_images": (C.c_void_p, [_H]),
     "bod_synchronize": (C.c_int, [_H]),

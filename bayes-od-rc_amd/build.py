@@ -24,6 +24,8 @@ SOURCES = [
     # fused epilogues' (which are bracketed by `#pragma clang fp contract(off)`) for equality
     ("stat_kernels.hip", ["-ffp-contract=off"]),
     ("train_kernels.hip", []),
+    # integer code only (the JPEG inverse DCT, upsampling and colour conversion: DESIGN.md 9.11)
+    ("jpeg_kernels.hip", []),
     ("engine.hip", []),
 ]
 # -fno-slp-vectorize (round 6): NO packed fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) in any kernel of

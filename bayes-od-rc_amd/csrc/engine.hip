@@ -4,8 +4,10 @@
 // -> RetinaNetModel.call.
 #include "../../include/bayesod.h"
 #include "kernels.h"
+#include "jpeg_entropy.h"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
@@ -21,6 +23,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <system_error>
 #include <vector>
 #include <dlfcn.h>
 
@@ -235,6 +238,28 @@ void unpack_h4_row(const uint8_t* src, int C, float* v) {
 
 }  // namespace
 
+// One JPEG batch in flight (bod_upload_frames_jpeg[_async], bod_jpeg_decode_rgb).  `pinned` holds the [n] JpegFrame
+// records and, 128-byte aligned behind them, the coefficients the host threads decode; one copy takes both to `dev`.  `copied`: that
+// copy has left `pinned` -- the next batch's host decode into it waits for the event.
+struct JpegSlot {
+    char* pinned = nullptr; size_t pinned_cap = 0;
+    char* dev = nullptr; size_t dev_cap = 0;
+    uint8_t* planes = nullptr; size_t planes_cap = 0;     // the components' MCU-padded uint8 planes (device scratch)
+    hipEvent_t copied = nullptr;
+    // of the batch decoded last
+    int32_t n = 0;
+    size_t stage_bytes = 0, coef_base = 0, plane_bytes = 0;
+    int64_t rgb_bytes = 0;
+    int32_t idct_wgs_per_frame = 0, color_wgs_per_frame = 0;
+    void release() {
+        if (pinned) hipHostFree(pinned);
+        if (dev) hipFree(dev);
+        if (planes) hipFree(planes);
+        if (copied) hipEventDestroy(copied);
+        *this = JpegSlot();
+    }
+};
+
 struct bod_context {
     bod_config cfg{};
     std::string err;
@@ -286,6 +311,7 @@ struct bod_context {
     struct RaggedTable { std::vector<char> host; char* dev = nullptr; };
     RaggedTable rag_sync, rag_b[2];
     RaggedTable aug_sync, aug_b[2];       // the augmented uploads' own (their records are PreprocAugFrame, without factors)
+    JpegSlot jpeg_slot[3];                              // JPEG uploads: one per image buffer, [2] the synchronous route's
     hipEvent_t ev_tab[2] = {nullptr, nullptr};          // the copy of rag_b[k].host has left the host (its next rewrite waits for it)
     const float* kscale_src[2] = {nullptr, nullptr};
     float* kscale_cur[2] = {nullptr, nullptr}; int kscale_i = 0;
@@ -1991,6 +2017,7 @@ bod_status bod_destroy(bod_handle h) {
     for (int k = 0; k < 2; ++k) if (h->aug_b[k].dev) hipFree(h->aug_b[k].dev);
     for (int k = 0; k < 2; ++k) { if (h->rag_b[k].dev) hipFree(h->rag_b[k].dev); if (h->ev_tab[k]) hipEventDestroy(h->ev_tab[k]); if (h->kscale_cur[k]) hipFree(h->kscale_cur[k]); }
     if (h->copy) { hipStreamSynchronize(h->copy); hipStreamDestroy(h->copy); }
+    for (JpegSlot& js : h->jpeg_slot) js.release();
     for (int k = 0; k < 2; ++k) {
         if (h->d_u8_b[k]) hipFree(h->d_u8_b[k]);
         if (h->ev_img_ready[k]) hipEventDestroy(h->ev_img_ready[k]);
@@ -2267,10 +2294,122 @@ bod_status bod_upload_frames_u8(bod_handle h, const uint8_t* rgb, int32_t src_h,
     return BOD_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// JPEG frames: Huffman decoding on host threads (jpeg_entropy.h), the rest on the device (jpeg_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+#define JPEG_FAIL(st, ...) do { char _b[512]; snprintf(_b, sizeof _b, __VA_ARGS__); *err = _b; return (st); } while (0)
+
+// Host half of a batch: parse every header, lay the batch out, wait until the previous copy has left the slot's pinned staging, then
+// decode the scans into it on `threads` threads (at most 16, at most one per frame; the calling thread alone when that is 1).
+// Nothing is enqueued and nothing of a handle changes here; `data` is no longer needed afterwards.  src_hw: [n][2].
+static bod_status jpeg_host_decode(JpegSlot& s, const char* who, int32_t n, const uint8_t* const* data, const int64_t* len, int32_t threads,
+                                   int32_t* src_hw, std::string* err) try {
+    std::vector<JpegHeader> hd((size_t)n);
+    std::vector<JpegFrame> fr((size_t)n);
+    int64_t coefs = 0, planes = 0, rgb = 0, max_blocks = 0, max_groups = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!data[i] || len[i] < 0) JPEG_FAIL(BOD_ERR_INVALID_ARG, "%s: frame %d has no data", who, i);
+        JpegHeader& h = hd[(size_t)i];
+        if (jpeg_parse(data[i], len[i], &h) != JPEG_OK) JPEG_FAIL(BOD_ERR_INVALID_ARG, "%s: frame %d is corrupt: %s", who, i, h.msg);
+        if (!h.supported) JPEG_FAIL(BOD_ERR_INVALID_ARG, "%s: frame %d is not a supported JPEG: %s", who, i, h.msg);
+        JpegFrame& f = fr[(size_t)i];
+        f = JpegFrame{};
+        for (int c = 0; c < h.components; ++c) {
+            f.coef_off[c] = coefs + h.coef_off[c];
+            f.plane_off[c] = planes;
+            f.bw[c] = h.bw[c]; f.bh[c] = h.bh[c];
+            planes += (int64_t)h.bw[c] * h.bh[c] * 64;             // (multiples of 64: every offset stays 16-byte aligned)
+        }
+        f.rgb_off = rgb;
+        f.components = h.components; f.h_samp = h.h_samp; f.v_samp = h.v_samp; f.width = h.width; f.height = h.height;
+        coefs += h.coef_count;
+        max_blocks = std::max(max_blocks, h.coef_count / 64);
+        max_groups = std::max(max_groups, (int64_t)h.height * ((h.width + 3) / 4));
+        rgb += (int64_t)3 * h.height * h.width;
+        src_hw[2 * i] = h.height; src_hw[2 * i + 1] = h.width;
+    }
+    // every frame gets the workgroups of the largest (kernels.h, JpegArgs): both grids must fit a launch
+    const int64_t idct_wgs = (max_blocks + 31) / 32, color_wgs = (max_groups + 255) / 256;
+    if (n * idct_wgs > 0x7FFFFFFF || n * color_wgs > 0x7FFFFFFF)
+        JPEG_FAIL(BOD_ERR_INVALID_ARG, "%s: %d frames of up to %lld blocks are more than one launch covers", who, n, (long long)max_blocks);
+    const size_t coef_base = ((size_t)n * sizeof(JpegFrame) + 127) & ~(size_t)127;
+    const size_t stage_bytes = coef_base + (size_t)coefs * sizeof(int16_t);
+    if (s.copied && hipEventSynchronize(s.copied) != hipSuccess) JPEG_FAIL(BOD_ERR_HIP, "%s: waiting for the previous coefficient copy failed", who);
+    if (stage_bytes > s.pinned_cap) {
+        if (s.pinned) hipHostFree(s.pinned);
+        s.pinned = nullptr; s.pinned_cap = 0;
+        if (hipHostMalloc(reinterpret_cast<void**>(&s.pinned), stage_bytes, hipHostMallocDefault) != hipSuccess) {
+            s.pinned = nullptr;
+            JPEG_FAIL(BOD_ERR_OOM, "%s: %zu bytes of pinned coefficient staging", who, stage_bytes);
+        }
+        s.pinned_cap = stage_bytes;
+    }
+    int16_t* coef_host = reinterpret_cast<int16_t*>(s.pinned + coef_base);
+    std::vector<int> status((size_t)n, JPEG_OK);
+    std::vector<std::array<char, 192>> msgs((size_t)n);
+    std::atomic<int> next{0};
+    auto work = [&]() {
+        for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
+            JpegFrame& f = fr[(size_t)i];
+            msgs[(size_t)i][0] = 0;
+            status[(size_t)i] = jpeg_decode(data[i], len[i], hd[(size_t)i], coef_host + (f.coef_off[0] - hd[(size_t)i].coef_off[0]), &f.quant[0][0],
+                                            msgs[(size_t)i].data(), msgs[(size_t)i].size());
+        }
+    };
+    const int workers = std::max(1, std::min(std::min(threads, 16), n));
+    {
+        // the calling thread is one of the workers: whatever could not be started is decoded here
+        std::vector<std::thread> pool;
+        pool.reserve((size_t)workers);
+        try { for (int k = 1; k < workers; ++k) pool.emplace_back(work); } catch (const std::system_error&) {}
+        work();
+        for (std::thread& t : pool) t.join();
+    }
+    for (int i = 0; i < n; ++i)
+        if (status[(size_t)i] != JPEG_OK) JPEG_FAIL(BOD_ERR_INVALID_ARG, "%s: frame %d is corrupt: %s", who, i, msgs[(size_t)i].data());
+    std::memcpy(s.pinned, fr.data(), (size_t)n * sizeof(JpegFrame));
+    s.n = n; s.stage_bytes = stage_bytes; s.coef_base = coef_base; s.plane_bytes = (size_t)planes;
+    s.rgb_bytes = rgb; s.idct_wgs_per_frame = (int32_t)idct_wgs; s.color_wgs_per_frame = (int32_t)color_wgs;
+    return BOD_OK;
+} catch (const std::bad_alloc&) {
+    JPEG_FAIL(BOD_ERR_OOM, "%s: out of host memory for %d frame headers", who, n);
+}
+
+// Device half: one copy of the records + coefficients, then the two kernels, which leave the packed RGB frames at rgb_dst (room for
+// s.rgb_bytes).  The slot's device buffers grow here; `stream` is the only stream that ever touches them.
+static bod_status jpeg_enqueue(JpegSlot& s, const char* who, uint8_t* rgb_dst, hipStream_t stream, std::string* err) {
+    if (s.stage_bytes > s.dev_cap || s.plane_bytes > s.planes_cap) {
+        if (hipStreamSynchronize(stream) != hipSuccess) JPEG_FAIL(BOD_ERR_HIP, "%s: hipStreamSynchronize failed", who);
+        if (s.stage_bytes > s.dev_cap) {
+            if (s.dev) hipFree(s.dev);
+            s.dev = nullptr; s.dev_cap = 0;
+            if (hipMalloc(reinterpret_cast<void**>(&s.dev), s.stage_bytes) != hipSuccess) { s.dev = nullptr; JPEG_FAIL(BOD_ERR_OOM, "%s: %zu bytes of coefficients", who, s.stage_bytes); }
+            s.dev_cap = s.stage_bytes;
+        }
+        if (s.plane_bytes > s.planes_cap) {
+            if (s.planes) hipFree(s.planes);
+            s.planes = nullptr; s.planes_cap = 0;
+            if (hipMalloc(reinterpret_cast<void**>(&s.planes), s.plane_bytes) != hipSuccess) { s.planes = nullptr; JPEG_FAIL(BOD_ERR_OOM, "%s: %zu bytes of component planes", who, s.plane_bytes); }
+            s.planes_cap = s.plane_bytes;
+        }
+    }
+    if (!s.copied && hipEventCreateWithFlags(&s.copied, hipEventDisableTiming) != hipSuccess) { s.copied = nullptr; JPEG_FAIL(BOD_ERR_HIP, "%s: hipEventCreate failed", who); }
+    JpegArgs a{};
+    a.frames = reinterpret_cast<const JpegFrame*>(s.dev);
+    a.coefs = reinterpret_cast<const int16_t*>(s.dev + s.coef_base);
+    a.planes = s.planes; a.rgb = rgb_dst; a.n = s.n; a.idct_wgs_per_frame = s.idct_wgs_per_frame; a.color_wgs_per_frame = s.color_wgs_per_frame;
+    hipError_t e = hipMemcpyAsync(s.dev, s.pinned, s.stage_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipEventRecord(s.copied, stream);
+    if (e == hipSuccess) e = launch_jpeg_idct(a, stream);
+    if (e == hipSuccess) e = launch_jpeg_color(a, stream);
+    if (e != hipSuccess) JPEG_FAIL(BOD_ERR_HIP, "%s: JPEG device stage failed: %s", who, hipGetErrorString(e));
+    return BOD_OK;
+}
+
 // The synchronous upload of a packed batch: the ragged route (aug == nullptr) or the augmented one, which differ in their table and
-// their kernel only.
+// their kernel only.  js != nullptr: the packed frames come from a decoded JPEG batch (jpeg_host_decode) instead of rgb_packed.
 static bod_status upload_packed(bod_handle h, const char* who, const uint8_t* rgb_packed, const int32_t* src_hw, const float* rgb_means,
-                                int32_t aspect_resize, const bod_augment* aug) {
+                                int32_t aspect_resize, const bod_augment* aug, JpegSlot* js = nullptr) {
     MarkerRange mr_api("bod:upload");
     BODCHK(join_overlap(h));
     const bod_config& c = h->cfg;
@@ -2288,7 +2427,13 @@ static bod_status upload_packed(bod_handle h, const char* who, const uint8_t* rg
         h->frames_u8_cap = bytes;
     }
     HIPCHK(h, hipMemcpyAsync(t.dev, t.host.data(), t.host.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_frames_u8, rgb_packed, bytes, hipMemcpyHostToDevice, h->stream));
+    if (js) {
+        std::string err;
+        const bod_status st = jpeg_enqueue(*js, who, h->d_frames_u8, h->stream, &err);
+        if (st != BOD_OK) return h->fail(st, "%s", err.c_str());
+    } else {
+        HIPCHK(h, hipMemcpyAsync(h->d_frames_u8, rgb_packed, bytes, hipMemcpyHostToDevice, h->stream));
+    }
     if (aug) {
         PreprocAugArgs a = augment_args(h, t, rgb_means);
         a.src = h->d_frames_u8; a.dst = h->d_images;
@@ -2360,7 +2505,8 @@ bod_status bod_upload_frames_u8_async(bod_handle h, const uint8_t* rgb, int32_t 
 
 // The pipelined upload of a packed batch, ragged (aug == nullptr) or augmented.
 static bod_status upload_packed_async(bod_handle h, const char* who, const uint8_t* rgb_packed, const int32_t* src_hw,
-                                      const float* rgb_means, int32_t aspect_resize, const bod_augment* aug, int32_t buffer) {
+                                      const float* rgb_means, int32_t aspect_resize, const bod_augment* aug, int32_t buffer,
+                                      JpegSlot* js = nullptr) {
     MarkerRange mr_api("bod:upload");
     if (buffer < 0 || buffer > 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: buffer must be 0 or 1", who);
     const bod_config& c = h->cfg;
@@ -2400,7 +2546,13 @@ static bod_status upload_packed_async(bod_handle h, const char* who, const uint8
     HIPCHK(h, hipMemcpyAsync(t.dev, t.host.data(), t.host.size(), hipMemcpyHostToDevice, h->copy));
     if (!h->ev_tab[buffer]) HIPCHK(h, hipEventCreateWithFlags(&h->ev_tab[buffer], hipEventDisableTiming));
     HIPCHK(h, hipEventRecord(h->ev_tab[buffer], h->copy));
-    HIPCHK(h, hipMemcpyAsync(h->d_u8_b[buffer], rgb_packed, bytes, hipMemcpyHostToDevice, h->copy));
+    if (js) {
+        std::string err;
+        const bod_status st = jpeg_enqueue(*js, who, h->d_u8_b[buffer], h->copy, &err);
+        if (st != BOD_OK) return h->fail(st, "%s", err.c_str());
+    } else {
+        HIPCHK(h, hipMemcpyAsync(h->d_u8_b[buffer], rgb_packed, bytes, hipMemcpyHostToDevice, h->copy));
+    }
     if (aug) {
         PreprocAugArgs a = augment_args(h, t, rgb_means);
         a.src = h->d_u8_b[buffer]; a.dst = h->d_images_b[buffer];
@@ -2426,6 +2578,62 @@ bod_status bod_upload_frames_u8_augmented_async(bod_handle h, const uint8_t* rgb
                                                 int32_t aspect_resize, const bod_augment* aug, int32_t buffer) {
     if (!h || !rgb_packed || !src_hw || !rgb_means || !aug) return BOD_ERR_INVALID_ARG;
     return upload_packed_async(h, "bod_upload_frames_u8_augmented_async", rgb_packed, src_hw, rgb_means, aspect_resize, aug, buffer);
+}
+
+// The JPEG upload routes: the host decode first (nothing of the handle has changed when it fails, and `data` is free once it is done),
+// then the ragged or augmented upload with the decoded batch in the place of the packed host frames.
+static bod_status upload_jpeg(bod_handle h, const char* who, const uint8_t* const* data, const int64_t* len, const float* rgb_means,
+                              int32_t aspect_resize, const bod_augment* aug, int32_t threads, int32_t* src_hw_out, int32_t buffer) {
+    if (!h || !data || !len || !rgb_means) return BOD_ERR_INVALID_ARG;
+    if (buffer < -1 || buffer > 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: buffer must be 0 or 1", who);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    JpegSlot& js = h->jpeg_slot[buffer < 0 ? 2 : buffer];
+    std::vector<int32_t> hw((size_t)h->cfg.batch * 2);
+    std::string err;
+    const bod_status st = jpeg_host_decode(js, who, h->cfg.batch, data, len, threads, hw.data(), &err);
+    if (st != BOD_OK) return h->fail(st, "%s", err.c_str());
+    if (src_hw_out) std::memcpy(src_hw_out, hw.data(), hw.size() * sizeof(int32_t));
+    if (buffer < 0) return upload_packed(h, who, nullptr, hw.data(), rgb_means, aspect_resize, aug, &js);
+    return upload_packed_async(h, who, nullptr, hw.data(), rgb_means, aspect_resize, aug, buffer, &js);
+}
+
+bod_status bod_upload_frames_jpeg(bod_handle h, const uint8_t* const* data, const int64_t* len, const float* rgb_means,
+                                  int32_t aspect_resize, const bod_augment* aug, int32_t threads, int32_t* src_hw_out) {
+    return upload_jpeg(h, "bod_upload_frames_jpeg", data, len, rgb_means, aspect_resize, aug, threads, src_hw_out, -1);
+}
+
+bod_status bod_upload_frames_jpeg_async(bod_handle h, const uint8_t* const* data, const int64_t* len, const float* rgb_means,
+                                        int32_t aspect_resize, const bod_augment* aug, int32_t threads, int32_t* src_hw_out, int32_t buffer) {
+    if (h && (buffer < 0 || buffer > 1)) return h->fail(BOD_ERR_INVALID_ARG, "bod_upload_frames_jpeg_async: buffer must be 0 or 1");
+    return upload_jpeg(h, "bod_upload_frames_jpeg_async", data, len, rgb_means, aspect_resize, aug, threads, src_hw_out, buffer);
+}
+
+// Header and entropy stage alone (bayesod.h): host only, no handle, no device.
+bod_status bod_jpeg_info(const uint8_t* data, int64_t len, struct bod_jpeg_info* out) {
+    if (!data || !out || len < 0) { g_create_error = "bod_jpeg_info: NULL argument"; return BOD_ERR_INVALID_ARG; }
+    std::memset(out, 0, sizeof *out);
+    std::unique_ptr<JpegHeader> h(new JpegHeader);
+    if (jpeg_parse(data, len, h.get()) != JPEG_OK) { g_create_error = std::string("bod_jpeg_info: ") + h->msg; return BOD_ERR_INVALID_ARG; }
+    out->width = h->width; out->height = h->height; out->components = h->components;
+    out->h_samp = h->h_samp; out->v_samp = h->v_samp; out->restart_interval = h->restart_interval;
+    out->supported = h->supported; out->coef_count = h->coef_count;
+    g_create_error = h->supported ? "" : std::string("bod_jpeg_info: ") + h->msg;
+    return BOD_OK;
+}
+
+bod_status bod_jpeg_entropy_decode(const uint8_t* data, int64_t len, int16_t* coefs, int64_t coef_capacity, uint16_t* quant3x64) {
+    static const char* who = "bod_jpeg_entropy_decode";
+    if (!data || !coefs || !quant3x64 || len < 0) { g_create_error = std::string(who) + ": NULL argument"; return BOD_ERR_INVALID_ARG; }
+    std::unique_ptr<JpegHeader> h(new JpegHeader);
+    if (jpeg_parse(data, len, h.get()) != JPEG_OK) { g_create_error = std::string(who) + ": " + h->msg; return BOD_ERR_INVALID_ARG; }
+    if (!h->supported) { g_create_error = std::string(who) + ": not a supported JPEG: " + h->msg; return BOD_ERR_INVALID_ARG; }
+    if (h->coef_count > coef_capacity) {
+        g_create_error = std::string(who) + ": the stream has " + std::to_string(h->coef_count) + " coefficients, the buffer holds " + std::to_string(coef_capacity);
+        return BOD_ERR_INVALID_ARG;
+    }
+    char msg[192] = {0};
+    if (jpeg_decode(data, len, *h, coefs, quant3x64, msg, sizeof msg) != JPEG_OK) { g_create_error = std::string(who) + ": " + msg; return BOD_ERR_INVALID_ARG; }
+    return BOD_OK;
 }
 
 // Ground truth through an augmented frame's geometry (bayesod.h): host arithmetic only, in fp32, no device call.
@@ -3634,6 +3842,36 @@ bod_status bod_score_pairs(int32_t device, int64_t n, const double* means, const
                            int32_t num_samples, uint64_t seed, uint64_t first_row_id, double* out, int32_t* status) {
     return pdq_call(device, [&](hipStream_t s, char* err, size_t cap) {
         return score_pairs_run(n, means, covs, targets, num_samples, seed, first_row_id, out, status, s, err, cap);
+    });
+}
+
+// The decoder alone (bayesod.h): n files -> packed RGB on the host.  Stateless; its buffers live for the call.
+bod_status bod_jpeg_decode_rgb(int32_t device, int32_t n, const uint8_t* const* data, const int64_t* len, int32_t threads,
+                               uint8_t* rgb_packed, int64_t rgb_capacity, int32_t* src_hw) {
+    static const char* who = "bod_jpeg_decode_rgb";
+    if (n < 1 || !data || !len || !rgb_packed || !src_hw) { g_create_error = std::string(who) + ": NULL argument or no frame"; return BOD_ERR_INVALID_ARG; }
+    return pdq_call(device, [&](hipStream_t s, char* err, size_t cap) -> int {
+        JpegSlot js;
+        std::string e;
+        uint8_t* d_rgb = nullptr;
+        bod_status st = jpeg_host_decode(js, who, n, data, len, threads, src_hw, &e);
+        if (st == BOD_OK && js.rgb_bytes > rgb_capacity) {
+            e = std::string(who) + ": the frames take " + std::to_string(js.rgb_bytes) + " bytes, the buffer holds " + std::to_string(rgb_capacity);
+            st = BOD_ERR_INVALID_ARG;
+        }
+        if (st == BOD_OK && hipMalloc(reinterpret_cast<void**>(&d_rgb), (size_t)js.rgb_bytes) != hipSuccess) {
+            d_rgb = nullptr; e = std::string(who) + ": out of device memory for the frames"; st = BOD_ERR_OOM;
+        }
+        if (st == BOD_OK) st = jpeg_enqueue(js, who, d_rgb, s, &e);
+        if (st == BOD_OK && (hipMemcpyAsync(rgb_packed, d_rgb, (size_t)js.rgb_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                             hipStreamSynchronize(s) != hipSuccess)) {
+            e = std::string(who) + ": copying the frames back failed: " + hipGetErrorString(hipGetLastError()); st = BOD_ERR_HIP;
+        }
+        hipStreamSynchronize(s);
+        if (d_rgb) hipFree(d_rgb);
+        js.release();
+        if (st != BOD_OK) snprintf(err, cap, "%s", e.c_str());
+        return st;
     });
 }
 

@@ -373,6 +373,34 @@ struct PreprocAugArgs {
 };
 hipError_t launch_preprocess_augment(const PreprocAugArgs& a, hipStream_t s);
 
+// JPEG frames (jpeg_kernels.hip): the host's entropy decoder (jpeg_entropy.h) leaves each component's coefficient
+// blocks, the two kernels turn them into the packed uint8 RGB frames the ragged / augmented preprocess kernels read.  One record per
+// frame, written and validated on the host; every device address comes from it.
+struct JpegFrame {             // 512 B
+    int64_t coef_off[3];       // first int16 of each component in the batch's coefficient buffer (multiples of 64)
+    int64_t plane_off[3];      // first byte of each component's MCU-padded uint8 plane in the scratch (multiples of 16)
+    int64_t rgb_off;           // first byte of the frame in the packed RGB buffer (PreprocFrame::offset)
+    int32_t bw[3], bh[3];      // blocks per row / column of each component's plane
+    int32_t components;        // 1 (grayscale) or 3 (YCbCr)
+    int32_t h_samp, v_samp;    // luma sampling: 1x1, 2x1 or 2x2; chroma is 1x1
+    int32_t width, height;
+    int32_t pad[7];
+    uint16_t quant[3][64];     // natural order
+};
+static_assert(sizeof(JpegFrame) == 512 && offsetof(JpegFrame, quant) == 128, "JpegFrame layout (16-byte loads of the quantisation rows)");
+struct JpegArgs {
+    const JpegFrame* frames;   // [n], device memory
+    const int16_t* coefs;      // 64 per block, natural order
+    uint8_t* planes;           // scratch: the components' planes
+    uint8_t* rgb;              // packed uint8 RGB frames
+    int32_t n;
+    // every frame gets the same number of workgroups, enough for the largest: the frame of a workgroup is wave-uniform
+    int32_t idct_wgs_per_frame;    // ceil(max over the frames of their 8x8 blocks / 32)
+    int32_t color_wgs_per_frame;   // ceil(max over the frames of their 4-pixel groups / 256)
+};
+hipError_t launch_jpeg_idct(const JpegArgs& a, hipStream_t s);
+hipError_t launch_jpeg_color(const JpegArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------------
 // Loss forward (loss_kernels.hip)
 // ------------------------------------------------------------------------------------------------

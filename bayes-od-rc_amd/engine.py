@@ -216,6 +216,36 @@ class Engine(object):
             self._ragged_keep = {}
         self._ragged_keep[int(buffer)] = buf
 
+    def _jpeg_upload(self, files, means, aspect_resize, aug, threads, buffer):
+        from . import constants
+        ptrs, lens = _jpeg_files(files, self.B)
+        m = np.ascontiguousarray(constants.MEANS_DICT['ImageNet'] if means is None else means, dtype=np.float32)
+        rec = None if aug is None else augment_records(aug, self.B)
+        recp = None if rec is None else rec.ctypes.data_as(C.POINTER(_lib.BodAugment))
+        src_hw = np.zeros((self.B, 2), np.int32)
+        threads = min(16, self.B) if threads is None else int(threads)
+        if buffer is None:
+            st = self.lib.bod_upload_frames_jpeg(self.h, ptrs, lens, fptr(m), int(bool(aspect_resize)), recp, threads, iptr(src_hw))
+        else:
+            st = self.lib.bod_upload_frames_jpeg_async(self.h, ptrs, lens, fptr(m), int(bool(aspect_resize)), recp, threads,
+                                                       iptr(src_hw), int(buffer))
+        self._chk(st)
+        return src_hw
+
+    def upload_frames_jpeg(self, files, means=None, aspect_resize=True, aug=None, threads=None):
+        """``upload_frames_u8_ragged`` (``aug=None``) or ``upload_frames_u8_augmented`` of JPEG files decoded inside the library
+        (``bod_upload_frames_jpeg``): ``files`` is a list of ``batch`` ``bytes`` objects, each a baseline JPEG file.
+        The Huffman decoding runs on ``threads`` host threads outside the GIL (default ``min(16, batch)``), the rest on the device;
+        the image buffer ends up bit for bit as after the upload of PIL's ``convert('RGB')`` decode of the files.  Returns the
+        frames' sizes, int32 [batch, 2] (h, w).  ``ValueError`` naming the frame for a corrupt or unsupported file
+        (``jpeg_info`` tells in advance); the handle and the frames it held stay as they were."""
+        return self._jpeg_upload(files, means, aspect_resize, aug, threads, None)
+
+    def upload_frames_jpeg_async(self, files, buffer, means=None, aspect_resize=True, aug=None, threads=None):
+        """Pipelined form (``bod_upload_frames_jpeg_async``), used like ``upload_frames_u8_ragged_async``.  The host decode is
+        done when this returns: ``files`` need not be kept."""
+        return self._jpeg_upload(files, means, aspect_resize, aug, threads, int(buffer))
+
     def _device_images(self, image_buffer):
         ptr = self.lib.bod_device_images(self.h) if image_buffer is None else self.lib.bod_device_images_buffer(self.h, int(image_buffer))
         if not ptr:
@@ -1078,6 +1108,77 @@ def pdq_frames(img_hw, num_gt, gt_boxes, num_det, det_boxes, det_corner_covs, de
         p += g_n * d_n
         d += d_n
     return fgs, bgs, dbgs, heat
+
+
+def _jpeg_files(files, batch=None):
+    """A list of bytes objects as the (const uint8_t* const*, const int64_t*) pair of the JPEG entry points."""
+    files = list(files)
+    if batch is not None and len(files) != batch:
+        raise ValueError("expected %d JPEG files, got %d" % (batch, len(files)))
+    for i, f in enumerate(files):
+        if not isinstance(f, bytes):
+            raise ValueError("JPEG file %d must be a bytes object, got %s" % (i, type(f).__name__))
+    ptrs = (C.c_char_p * len(files))(*files)
+    lens = (C.c_int64 * len(files))(*[len(f) for f in files])
+    return ptrs, lens
+
+
+def jpeg_info(data):
+    """What a JPEG file's header says (``bod_jpeg_info``; host only): a dict of width, height, components, h_samp, v_samp (luma
+    sampling), restart_interval, coef_count, supported, and ``reason`` -- why not, for a well-formed file outside the subset the
+    library decodes (progressive, CMYK, ...; a file without SOI marker, such as a PNG, is reported the same way).  ``ValueError``
+    for a corrupt header."""
+    lib = _lib.load()
+    if not isinstance(data, bytes):
+        raise ValueError("a JPEG file must be a bytes object, got %s" % type(data).__name__)
+    info = _lib.BodJpegInfo()
+    _lib.check(lib, None, lib.bod_jpeg_info(data, len(data), C.byref(info)))
+    out = {name: int(getattr(info, name)) for name, _ in _lib.BodJpegInfo._fields_}
+    out["supported"] = bool(info.supported)
+    reason = lib.bod_last_error(None)
+    out["reason"] = "" if info.supported else (reason.decode() if reason else "")
+    return out
+
+
+def jpeg_entropy_decode(data):
+    """The host half of the decoder alone (``bod_jpeg_entropy_decode``): (coefs int16 [coef_count] -- per component the blocks of
+    its MCU-padded plane in raster block order, 64 per block in natural order --, quant uint16 [3, 64] in natural order)."""
+    lib = _lib.load()
+    info = jpeg_info(data)
+    if not info["supported"]:
+        raise ValueError(info["reason"])
+    coefs = np.empty(info["coef_count"], np.int16)
+    quant = np.zeros((3, 64), np.uint16)
+    st = lib.bod_jpeg_entropy_decode(data, len(data), coefs.ctypes.data_as(C.POINTER(C.c_int16)), coefs.size,
+                                     quant.ctypes.data_as(C.POINTER(C.c_uint16)))
+    _lib.check(lib, None, st)
+    return coefs, quant
+
+
+def decode_jpeg_rgb(files, device=0, threads=None):
+    """JPEG files -> a list of uint8 [h, w, 3] RGB frames, decoded by the library (``bod_jpeg_decode_rgb``: Huffman decoding on
+    ``threads`` host threads, default ``min(16, len(files))``, everything else on the device).  Equal to PIL's ``convert('RGB')``."""
+    lib = _lib.load()
+    ptrs, lens = _jpeg_files(files)
+    n = len(lens)
+    if n == 0:
+        return []
+    total = 0
+    for i in range(n):
+        info = jpeg_info(files[i])
+        if not info["supported"]:
+            raise ValueError("bod_jpeg_decode_rgb: frame %d is not a supported JPEG: %s" % (i, info["reason"]))
+        total += 3 * info["width"] * info["height"]
+    rgb = np.empty(total, np.uint8)
+    src_hw = np.zeros((n, 2), np.int32)
+    st = lib.bod_jpeg_decode_rgb(int(device), n, ptrs, lens, min(16, n) if threads is None else int(threads),
+                                 rgb.ctypes.data_as(C.POINTER(C.c_uint8)), rgb.size, iptr(src_hw))
+    _lib.check(lib, None, st)
+    out, off = [], 0
+    for h, w in src_hw:
+        out.append(rgb[off:off + 3 * h * w].reshape(h, w, 3))
+        off += 3 * h * w
+    return out
 
 
 def score_pairs(means, covs, targets, num_samples=1000, seed=0, first_row_id=0, device=0):

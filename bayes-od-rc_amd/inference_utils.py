@@ -211,7 +211,8 @@ class BayesOdPipeline(object):
         """``batch`` uint8 frames of mixed source sizes into the engine, for ``__call__(None, ...)``: every frame is rescaled by
         its own S = orig / net (inference_utils.py:147-167 takes it per sample), so no ``bind(orig_size=...)`` per size."""
         self.bind()
-        self.engine.upload_frames_u8_ragged(frames, means, aspect_resize=aspect_resize)
+        from . import datasets
+        datasets.upload_frames(self.engine, frames, means, aspect_resize=aspect_resize)     # (--device_jpeg: frames may be JPEG files)
 
     def __call__(self, images=None, seed=0, first_image_id=0):
         """images [B,H,W,3] (or None to reuse the uploaded device batch).  Returns, per image,
@@ -295,7 +296,8 @@ class EnsemblePipeline(object):
         return self.engine
 
     def upload_mixed(self, frames, means, aspect_resize=True):
-        self.engine.upload_frames_u8_ragged(frames, means, aspect_resize=aspect_resize)
+        from . import datasets
+        datasets.upload_frames(self.engine, frames, means, aspect_resize=aspect_resize)
 
     def __call__(self, images=None, seed=0, first_image_id=0):
         """images [B,H,W,3], or None to run every member on the batch uploaded into member 0's handle."""

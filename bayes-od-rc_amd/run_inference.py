@@ -150,7 +150,9 @@ def _test_model_on_dataset(config, args, model):
     gen = FpnAnchorGenerator(dataset_config['anchor_generator'])
     pipes = {}
     pending = []
-    mixed = bool(getattr(args, 'mixed_sizes', False))
+    device_jpeg = bool(getattr(args, 'device_jpeg', False))
+    mixed = bool(getattr(args, 'mixed_sizes', False)) or device_jpeg          # --device_jpeg forms its batches as --mixed_sizes does
+    handler.defer_decode = device_jpeg       # JPEG files travel as bytes and are decoded on the device at upload
 
     def emit(dets):
         for (name, _, _), (classes, boxes_vuhw, covs, counts, *parts) in zip(pending, dets):
@@ -199,7 +201,7 @@ def _test_model_on_dataset(config, args, model):
 
     start, n_done = time.time(), 0
     for idx, sample in enumerate(handler.create_dataset()):
-        rgb = sample[datasets.IMAGE_UINT8_KEY]
+        rgb = datasets.sample_frame(sample)
         name = os.path.splitext(os.path.basename(handler.im_paths[idx]))[0]
         if pending and ((not mixed and pending[0][1].shape != rgb.shape) or len(pending) == args.batch):
             flush()
@@ -227,6 +229,9 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--mixed_sizes', action='store_true', help='with --dataset: batches in dataset order whatever the frame sizes '
                     '(default: a batch ends where the source size changes)')
+    ap.add_argument('--device_jpeg', action='store_true', help='with --dataset: baseline JPEG files are decoded inside the library '
+                    '(Huffman decoding on host threads, the rest on the GPU) instead of by PIL; batches as under --mixed_sizes; a batch '
+                    'with any other file in it takes the PIL route; the outputs are identical either way')
     ap.add_argument('--ensemble', type=str, nargs='+', default=None, help='weight files of an ensemble: every member runs the '
                     'yaml\'s mc_dropout_samples samples and ONE posterior is formed from all of them (overrides --weights)')
     ap.add_argument('--mc_passes', type=int, default=1, help='with --ensemble or --tta_flip: forwards per member (k passes of n '
@@ -243,6 +248,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     config = config_utils.load_yaml(args.yaml_path)
     config = config_utils.setup(config, args)
+    if args.device_jpeg and not args.dataset:
+        ap.error('--device_jpeg requires --dataset')
     try:
         return test_model(config, args)
     except ValueError as e:

@@ -86,7 +86,12 @@ class Trainer(object):
         samples have no host image (IMAGE_NORMALIZED_KEY is None): their uint8 frames are resized and normalised on the device."""
         if self.augmentation is not None:
             return self._train_step_augmented(sample_dicts, learning_rate)
-        if sample_dicts[0][constants.IMAGE_NORMALIZED_KEY] is None:
+        if any(s.get('image_jpeg') is not None for s in sample_dicts):     # --device_jpeg: JPEG files decoded at upload (DESIGN.md 9.11)
+            from . import datasets
+            datasets.upload_frames(self.engine, [datasets.sample_frame(s) for s in sample_dicts], constants.MEANS_DICT[self.im_normalization],
+                                   aspect_resize='boxes_2d_gt_source' in sample_dicts[0])
+            imgs = None
+        elif sample_dicts[0][constants.IMAGE_NORMALIZED_KEY] is None:
             frames = [s['image_uint8'] for s in sample_dicts]
             if len(set(f.shape for f in frames)) > 1:                  # --mixed_sizes: a minibatch in the handler's order
                 self.engine.upload_frames_u8_ragged(frames, constants.MEANS_DICT[self.im_normalization], aspect_resize=True)
@@ -106,11 +111,12 @@ class Trainer(object):
         streams are keyed by), so a resumed run draws what an uninterrupted one would.  The uint8 frames -- KITTI's of equal or
         mixed sizes, BDD's at the network size -- go up through the augmented entry point and the ground truth, kept in source
         pixels, is mapped by the same geometry on the host."""
-        kitti = sample_dicts[0][constants.IMAGE_NORMALIZED_KEY] is None
-        frames = [s['image_uint8'] for s in sample_dicts]
+        from . import datasets
+        kitti = 'boxes_2d_gt_source' in sample_dicts[0]          # the KITTI handler's key (a deferred BDD JPEG has no host image either)
+        frames = [datasets.sample_frame(s) for s in sample_dicts]                    # uint8 arrays, or JPEG files under --device_jpeg
         first = self.step * self.batch
         aug = draw_augmentation(self.augmentation, self.seed, [first + i for i in range(len(frames))])
-        self.engine.upload_frames_u8_augmented(frames, aug, constants.MEANS_DICT[self.im_normalization], aspect_resize=kitti)
+        datasets.upload_frames(self.engine, frames, constants.MEANS_DICT[self.im_normalization], aspect_resize=kitti, aug=aug)
         boxes, classes = augment_boxes(
             [f.shape[:2] for f in frames], self.image_hw, aug,
             [s['boxes_2d_gt_source'] if kitti else s[constants.BOXES_2D_GT_KEY] for s in sample_dicts],
@@ -265,11 +271,16 @@ def train(config, args):
         # one minibatch at a time
         handler = datasets.build_dataset(dataset_config, 'train')
         handler.dense_targets = False
-        # (the augmented upload takes equal and mixed sizes alike: no buckets needed)
-        stream = stream_minibatches(handler, mb, mixed_sizes=bool(getattr(args, 'mixed_sizes', False)) or augmentation is not None)
+        device_jpeg = bool(getattr(args, 'device_jpeg', False))
+        handler.defer_decode = device_jpeg       # JPEG files travel as bytes and are decoded on the device at upload
+        # (the augmented upload takes equal and mixed sizes alike: no buckets needed; --device_jpeg forms its minibatches the same way)
+        stream = stream_minibatches(handler, mb, mixed_sizes=bool(getattr(args, 'mixed_sizes', False)) or augmentation is not None or device_jpeg)
         pending = next(stream)                                        # the first minibatch also tells the frame size
         first = pending[0][constants.IMAGE_NORMALIZED_KEY]
-        hw = tuple(handler.resize_shape) if first is None else first.shape[:2]
+        if hasattr(handler, 'resize_shape'):
+            hw = tuple(handler.resize_shape)
+        else:
+            hw = tuple(int(v) for v in pending[0][constants.ORIGINAL_IM_SIZE_KEY][:2]) if first is None else first.shape[:2]
         samples = None
         epoch_size = max(handler.epoch_size // mb, 1)
     else:
@@ -412,7 +423,12 @@ def main(argv=None):
                     'per frame, on the device (training_config[\'augmentation\'] of the yaml, else mild defaults)')
     ap.add_argument('--no_resume', action='store_true', help='start from scratch: existing checkpoints of this run are not restored; they are moved to '
                     'checkpoints/superseded-<time>/ (never deleted) once the trainer has been built')
+    ap.add_argument('--device_jpeg', action='store_true', help='with --dataset: baseline JPEG files are decoded inside the library '
+                    '(Huffman decoding on host threads, the rest on the GPU) instead of by PIL; minibatches as under --mixed_sizes; '
+                    '--augment passes its records through; a minibatch with any other file in it takes the PIL route')
     args = ap.parse_args(argv)
+    if args.device_jpeg and not args.dataset:
+        ap.error('--device_jpeg requires --dataset')
     config = config_utils.setup(config_utils.load_yaml(args.yaml_path), args)
     return train(config, args)
 

@@ -91,12 +91,22 @@ def validate_batch(model, config, batch, mixed_sizes=False):
     ``post_process_predictions`` give for the frame alone, plus the regularisation term (run_validation.py:252-258)."""
     dataset_config = config['dataset_config']
     first = batch[0][constants.IMAGE_NORMALIZED_KEY]
-    on_device_resize = first is None                       # KITTI: the pixels are produced on the device
-    hw = tuple(int(v) for v in dataset_config['kitti']['resize_shape']) if on_device_resize else tuple(first.shape[:2])
+    deferred = any(s.get('image_jpeg') is not None for s in batch)      # --device_jpeg: JPEG files decoded at upload (DESIGN.md 9.11)
+    # KITTI: the pixels are produced on the device (a deferred BDD JPEG has no host image either: the handler's extra key tells)
+    on_device_resize = first is None and 'boxes_2d_gt_source' in batch[0] if deferred else first is None
+    if on_device_resize:
+        hw = tuple(int(v) for v in dataset_config['kitti']['resize_shape'])
+    else:
+        hw = tuple(int(v) for v in batch[0][constants.ORIGINAL_IM_SIZE_KEY][:2]) if deferred else tuple(first.shape[:2])
     eng = model.engine_for(hw, batch=len(batch), mc_samples=1, nms_config=VALIDATION_NMS)
     if not eng._anchors_set:
         eng.set_anchors(np.asarray(batch[0][constants.ANCHORS_KEY], np.float32))
-    if 'image_uint8' in batch[0]:
+    if deferred:
+        from . import datasets
+        means = constants.MEANS_DICT[dataset_config.get('im_normalization', 'ImageNet')]
+        datasets.upload_frames(eng, [datasets.sample_frame(s) for s in batch], means, aspect_resize=on_device_resize)
+        images = None
+    elif 'image_uint8' in batch[0]:
         means = constants.MEANS_DICT[dataset_config.get('im_normalization', 'ImageNet')]
         if mixed_sizes:
             eng.upload_frames_u8_ragged([s['image_uint8'] for s in batch], means, aspect_resize=on_device_resize)
@@ -298,9 +308,14 @@ def main(argv=None):
     ap.add_argument('--batch', type=int, default=8, help='frames per call on the --dataset route (frames are bucketed by source size)')
     ap.add_argument('--mixed_sizes', action='store_true', help='with --dataset: one pass in dataset order, frames of any source sizes in '
                     'one batch (default: bucketed by source size)')
+    ap.add_argument('--device_jpeg', action='store_true', help='with --dataset: baseline JPEG files are decoded inside the library '
+                    '(Huffman decoding on host threads, the rest on the GPU) instead of by PIL; batches as under --mixed_sizes; a batch '
+                    'with any other file in it takes the PIL route; the results are identical either way')
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error('--batch must be at least 1')
+    if args.device_jpeg and not args.dataset:
+        ap.error('--device_jpeg requires --dataset')
     config = config_utils.setup(config_utils.load_yaml(args.yaml_path), args)
     dataset_config = config['dataset_config']
     categories = None
@@ -309,6 +324,7 @@ def main(argv=None):
         # the split is streamed, once per checkpoint: samples carry the GT boxes only (the targets are assigned on the device)
         handler = datasets.build_dataset(dataset_config, args.data_split)
         handler.dense_targets = False
+        handler.defer_decode = bool(args.device_jpeg)
         samples, sample_ids = handler.create_dataset, list(handler.sample_ids)
         categories = handler.training_data_config['categories'] if dataset_config['dataset'] == 'bdd' else None
     else:
@@ -318,7 +334,7 @@ def main(argv=None):
         sample_ids = ['synthetic_%04d.jpg' % i for i in range(len(samples))]
         categories = ['car', 'truck', 'bus', 'person', 'rider', 'bike', 'motor'][:num_classes]
     return validate(config, samples, sample_ids, categories=categories, poll_seconds=args.poll or None, batch=args.batch,
-                    mixed_sizes=bool(args.mixed_sizes and args.dataset))
+                    mixed_sizes=bool((args.mixed_sizes or args.device_jpeg) and args.dataset))
 
 
 if __name__ == '__main__':

@@ -334,6 +334,48 @@ bod_status bod_augment_boxes(int32_t B, const int32_t* src_hw, int32_t net_h, in
                              const bod_augment* aug, const int32_t* num_gt, const float* gt_boxes_vuvu_src,
                              const float* gt_classes, int32_t C, float min_visible,
                              int32_t* num_out, float* boxes_out, float* classes_out);
+/* Baseline JPEG frames decoded inside the library.  Marker parsing and Huffman decoding run on host threads; the
+ * dequantisation, the 8x8 inverse DCT (libjpeg's "islow"), the "fancy" chroma upsampling and YCbCr -> RGB run on the device and
+ * write the uint8 RGB frames into the staging buffer the ragged / augmented preprocess kernels read: the decoded frame never
+ * exists on the host.  The frames equal PIL's Image.open(..).convert('RGB') (libjpeg-turbo) byte for byte.
+ * Supported: 8-bit baseline (SOF0) streams with one interleaved scan, 1 component (grayscale) or 3 (YCbCr) with luma sampling
+ * 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) and chroma 1x1; restart intervals; any Huffman tables.  Progressive, arithmetic, lossless
+ * and 12-bit streams, several scans, DNL, 16-bit quantisation tables, 4 components, other samplings and Adobe RGB are well-formed
+ * but NOT supported: bod_jpeg_info reports them with supported = 0 and the reason in bod_last_error(NULL) (so does a file without
+ * an SOI marker: a PNG), the other entry points refuse them with BOD_ERR_INVALID_ARG.  A corrupt or truncated stream is
+ * BOD_ERR_INVALID_ARG everywhere.
+ * (The struct has no typedef: in C a typedef would share the function's name space.) */
+struct bod_jpeg_info {
+    int32_t width, height, components;
+    int32_t h_samp, v_samp;          /* luma sampling; chroma is 1x1 */
+    int32_t restart_interval;
+    int32_t supported;               /* 0: well-formed but outside the supported subset (the message says why) */
+    int64_t coef_count;              /* int16 coefficients bod_jpeg_entropy_decode writes */
+};
+/* Header and entropy stage alone: host only, no handle, no device (as bod_augment_boxes); errors through bod_last_error(NULL).
+ * bod_jpeg_entropy_decode writes, per component, the coefficient blocks of the MCU-padded plane in raster block order, 64 int16
+ * per block in natural (row-major) order, and the components' quantisation tables in natural order into quant3x64[3][64]. */
+bod_status bod_jpeg_info(const uint8_t* data, int64_t len, struct bod_jpeg_info* out);
+bod_status bod_jpeg_entropy_decode(const uint8_t* data, int64_t len, int16_t* coefs, int64_t coef_capacity,
+                                   uint16_t* quant3x64);
+/* The decoder alone (stand-alone device entry, as bod_score_pairs): n files -> packed RGB on the host (frame b at byte 3 * sum of
+ * h_i * w_i over i < b) + src_hw[n][2].  `threads` host threads decode the scans (capped at 16 and at n; <= 0 means 1). */
+bod_status bod_jpeg_decode_rgb(int32_t device, int32_t n, const uint8_t* const* data, const int64_t* len,
+                               int32_t threads, uint8_t* rgb_packed, int64_t rgb_capacity, int32_t* src_hw);
+/* The upload routes: data[batch] / len[batch] are the files.  The scans are decoded on `threads` host threads into pinned staging
+ * the handle owns (one per image buffer; the host waits for the previous copy out of it first), then the copy, the two JPEG
+ * kernels and the ragged (aug == NULL) or augmented preprocess kernel run on the upload's stream.  Everything else -- geometry
+ * errors, the per-frame KITTI factors, which image buffer is filled, the ordering against the forward that consumes it -- is
+ * bod_upload_frames_u8_ragged[_async] / bod_upload_frames_u8_augmented[_async] of the decoded frames, bit for bit.  The host
+ * decode finishes before the call returns: `data` is free on return, in the async form as well.  src_hw_out[batch][2] (may be
+ * NULL) receives the frames' sizes.  A corrupt or unsupported frame gives BOD_ERR_INVALID_ARG naming the frame and the reason;
+ * nothing is enqueued, the handle and the frames it held stay as they were. */
+bod_status bod_upload_frames_jpeg(bod_handle h, const uint8_t* const* data, const int64_t* len,
+                                  const float* rgb_means, int32_t aspect_resize, const bod_augment* aug,
+                                  int32_t threads, int32_t* src_hw_out);
+bod_status bod_upload_frames_jpeg_async(bod_handle h, const uint8_t* const* data, const int64_t* len,
+                                        const float* rgb_means, int32_t aspect_resize, const bod_augment* aug,
+                                        int32_t threads, int32_t* src_hw_out, int32_t buffer);
 const float* bod_device_images_buffer(bod_handle h, int32_t buffer);
 const float* bod_device_images(bod_handle h);
 bod_status bod_synchronize(bod_handle h);

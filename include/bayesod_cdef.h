@@ -119,6 +119,24 @@ bod_status bod_augment_boxes(int32_t B, const int32_t* src_hw, int32_t net_h, in
                              const bod_augment* aug, const int32_t* num_gt, const float* gt_boxes_vuvu_src,
                              const float* gt_classes, int32_t C, float min_visible,
                              int32_t* num_out, float* boxes_out, float* classes_out);
+struct bod_jpeg_info {
+    int32_t width, height, components;
+    int32_t h_samp, v_samp;
+    int32_t restart_interval;
+    int32_t supported;
+    int64_t coef_count;
+};
+bod_status bod_jpeg_info(const uint8_t* data, int64_t len, struct bod_jpeg_info* out);
+bod_status bod_jpeg_entropy_decode(const uint8_t* data, int64_t len, int16_t* coefs, int64_t coef_capacity,
+                                   uint16_t* quant3x64);
+bod_status bod_jpeg_decode_rgb(int32_t device, int32_t n, const uint8_t* const* data, const int64_t* len,
+                               int32_t threads, uint8_t* rgb_packed, int64_t rgb_capacity, int32_t* src_hw);
+bod_status bod_upload_frames_jpeg(bod_handle h, const uint8_t* const* data, const int64_t* len,
+                                  const float* rgb_means, int32_t aspect_resize, const bod_augment* aug,
+                                  int32_t threads, int32_t* src_hw_out);
+bod_status bod_upload_frames_jpeg_async(bod_handle h, const uint8_t* const* data, const int64_t* len,
+                                        const float* rgb_means, int32_t aspect_resize, const bod_augment* aug,
+                                        int32_t threads, int32_t* src_hw_out, int32_t buffer);
 const float* bod_device_images_buffer(bod_handle h, int32_t buffer);
 const float* bod_device_images(bod_handle h);
 bod_status bod_synchronize(bod_handle h);
