@@ -923,7 +923,13 @@ __global__ __launch_bounds__(256) void sparse_tail_rows_kernel(SparseTailArgs a)
     for (int t = 0; t < T; ++t) {
         const int nchunk = s_nchunk[t], ntile = s_ntile[t], base = s_base[t];
         const int R = t == 0 ? a.tail_rows : 256;
-        if (base + ntile > a.cap_tiles) continue;       // (cannot happen: cap_tiles is sized by st_min_pixels)
+        // Cannot happen.  A tile that closes before its image's end closes on its slots (R / N pixels) or because fewer than 3N
+        // extended rows are free; k pixels cost at most 3N * k of them, so it holds more than (XR_EXT_ROWS - 3N) / 3N pixels: at
+        // least m = st_min_pixels(N) either way.  An image's table with T tiles has at least (T - 1) * m + 1 member pixels of its P, so
+        // T <= P / m + 1, the images' reservations sum to at most B * (P / m + 1) = cap_tiles, and base + ntile stays within it in
+        // whatever order the images reserve.  (tests/test_sparse_tables_reference_host.py holds the bound on the worst masks,
+        // tests/test_gpu_sparse_masks.py holds the device's counts against the capacity.)
+        if (base + ntile > a.cap_tiles) continue;
         RowEnt* rows = t == 0 ? a.rows : a.halo_rows;
         ExtRow* ext = reinterpret_cast<ExtRow*>(t == 0 ? a.ext : a.halo_ext);
         const StQuad* chunks = a.chunks + ((size_t)t * B + b) * P;

@@ -2,7 +2,8 @@
 the keep flags, over the 3x3 dilation of the sparse tail's pixels only, and keep dense raw-only launches for raw forwards.  Detections,
 posteriors, a posterior under another seed (the raw re-run) and the raw head outputs must equal the tail-only plan's
 (BOD_SPARSE_HALO=0) and the dense plan's (BOD_SPARSE_TAIL=0) bit for bit: square and non-square frames, N = 10 and 30, a frame that
-keeps nothing, a nearly-all-kept batch and two-slot pipelining."""
+keeps nothing, a nearly-all-kept batch and two-slot pipelining.  The keep sets here are whatever the random network fires on;
+test_gpu_sparse_masks.py chooses them through a class layer that ignores its input (a bias f keeps each pixel with one probability)."""
 import os
 import subprocess
 import sys

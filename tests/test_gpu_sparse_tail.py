@@ -4,7 +4,8 @@ posterior reads of those heads belongs to kept anchors, so detections and poster
 (BOD_SPARSE_TAIL=0) bit for bit: square and non-square frames (pyramid widths that are not multiples of 4), N = 10 and 30, a
 frame that keeps nothing, a foreground bias at which nearly every anchor is kept (the row table's worst case), and two-slot pipelining
 (whose later calls find the earlier calls' statistics in the buffers: stale entries of anchors not kept must stay unread).
-pipeline_overlap handles (experimental) keep the dense plan."""
+pipeline_overlap handles (experimental) keep the dense plan.  The keep sets here are whatever the random network fires on;
+test_gpu_sparse_masks.py chooses them through a class layer that ignores its input (a bias f keeps each pixel with one probability)."""
 import os
 import subprocess
 import sys

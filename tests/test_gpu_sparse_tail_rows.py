@@ -10,7 +10,8 @@ a foreground bias that keeps every anchor (long runs, full tiles), one that keep
 exits) and one that keeps a handful.  With little kept, N = 2 tiles close on their extended rows half empty, so N = 2 also runs with
 every anchor kept: whole pyramid rows as runs, tiles that close on their 96 slots with all 192 rows valid and no padding row.  That
 case reads the engine's BOD_SPARSE_STATS line and holds the tile count and the number of full tiles against a replay of the packing
-rule.  plan_info() reports the tile height."""
+rule.  plan_info() reports the tile height.  The keep sets here are whatever the random network fires on; test_gpu_sparse_masks.py
+chooses them through a class layer that ignores its input (a bias f keeps each pixel with one probability)."""
 import os
 import re
 import subprocess
