@@ -59,6 +59,17 @@ class BodJpegInfo(C.Structure):
                 ("restart_interval", C.c_int32), ("supported", C.c_int32), ("coef_count", C.c_int64)]
 
 
+class BodFoldLayer(C.Structure):
+    """bod_fold_layer: one layer of bod_stage_fold_pack (inputs, geometry, host output arrays)."""
+    _fields_ = [("kernel", C.POINTER(C.c_float)), ("bias", C.POINTER(C.c_float)), ("gamma", C.POINTER(C.c_float)),
+                ("beta", C.POINTER(C.c_float)), ("mean", C.POINTER(C.c_float)), ("var", C.POINTER(C.c_float)),
+                ("taps", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("cout_pad", C.c_int32),
+                ("w_fwd", C.POINTER(C.c_uint16)), ("w_bwd", C.POINTER(C.c_uint16)), ("w_flip", C.POINTER(C.c_uint16)),
+                ("w_fwd32", C.POINTER(C.c_float)), ("b_fwd", C.POINTER(C.c_float))]
+
+
+BOD_DGRAD_FLIP, BOD_DGRAD_ROWS, BOD_DGRAD_COL2IM = 0, 1, 2       # routes of bod_stage_conv_dgrad
+
 BOD_LOSS_ONE_IMAGE_ID = 1                          # flag in bod_loss_options.reserved[0]
 
 
@@ -135,6 +146,12 @@ SIGNATURES = {
     "bod_synchronize": (C.c_int, [_H]),
     "bod_stage_conv_wgrad": (C.c_int, [C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F]),
+    "bod_stage_act_backward": (C.c_int, [C.c_int32, C.c_int32, _F, _F, _F, C.c_int64, _I, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_float, C.c_int32, _F, C.c_int64, _F, _F, _F, _I]),
+    "bod_stage_conv_dgrad": (C.c_int, [C.c_int32, C.c_int32, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _I]),
+    "bod_stage_stem_pool_backward": (C.c_int, [C.c_int32, C.c_int32, _F, _F, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _F]),
+    "bod_stage_fold_pack": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(BodFoldLayer)]),
     "bod_stage_conv": (C.c_int, [C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F,
                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F,
                                  C.c_float, C.c_uint64, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, _F]),

@@ -437,6 +437,40 @@ bod_status train_wgrad(bod_context* h, TrainConv& tc, const WgradSlot& slot, con
     return BOD_OK;
 }
 
+// The three input-gradient launches of a convolution whose forward launch is `a` (train_backward; bod_stage_conv_dgrad runs the
+// same three on a layer of its own, so what the tests pin is what the step launches).
+// 1. stride-1 SAME 3x3 with identical plane layouts: dX = conv(dZ plane, flipped / swapped weights) through the FORWARD row table
+//    (window origin and centre pixel coincide in both planes); accumulates in place
+ConvArgs dgrad_flip_args(const ConvArgs& a, const void* dzp, const void* w_flip, const float* zero_bias, float* din) {
+    ConvArgs d{};
+    d.rows = a.rows; d.M = a.M; d.taps = 9; d.KW = 3; d.cin = a.cout_pad; d.in_cstride = a.out_cstride;
+    d.cout_pad = a.cin; d.cout_valid = a.cin; d.out_cstride = a.in_cstride; d.res_cstride = a.in_cstride; d.groups = 1; d.fan_count = 1;
+    d.flags = CONV_OUT_F32 | CONV_ACCUM;
+    d.g[0] = ConvGroup{dzp, w_flip, zero_bias, din, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0};
+    return d;
+}
+// 2. 1x1 (any stride): every output pixel owns one input pixel, so the GEMM accumulates straight into the input's gradient plane
+//    through the row table of launch_make_dgrad_rows -- no dXcol, no atomics
+ConvArgs dgrad_rows_args(const ConvArgs& a, const RowEnt* dgrad_rows, const void* dz, const void* w_bwd, const float* zero_bias, float* din) {
+    const int NK = a.taps * a.cin;
+    ConvArgs d{};
+    d.rows = dgrad_rows; d.M = a.M; d.taps = 1; d.KW = 1; d.cin = a.cout_pad; d.in_cstride = a.cout_pad;
+    d.cout_pad = NK; d.cout_valid = NK; d.out_cstride = a.in_cstride; d.res_cstride = a.in_cstride; d.groups = 1; d.fan_count = 1;
+    d.flags = CONV_OUT_F32 | CONV_ACCUM;
+    d.g[0] = ConvGroup{dz, w_bwd, zero_bias, din, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0};
+    return d;
+}
+// 3. everything else: dXcol[m][(tap, ci)] = dZ[m][:] . Wfolded[(tap, ci)][:] (launch_col2im scatters it into the plane)
+ConvArgs dgrad_xcol_args(const ConvArgs& a, const RowEnt* iota, const void* dz, const void* w_bwd, const float* zero_bias, float* dxcol) {
+    const int NK = a.taps * a.cin;
+    ConvArgs d{};
+    d.rows = iota; d.M = a.M; d.taps = 1; d.KW = 1; d.cin = a.cout_pad; d.in_cstride = a.cout_pad;
+    d.cout_pad = NK; d.cout_valid = NK; d.out_cstride = NK; d.res_cstride = NK; d.groups = 1; d.fan_count = 1;
+    d.flags = CONV_OUT_F32;
+    d.g[0] = ConvGroup{dz, w_bwd, zero_bias, dxcol, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0};
+    return d;
+}
+
 bod_status train_backward(bod_context* h) {
     TrainState* t = h->train;
     const bod_config& c = h->cfg;
@@ -495,15 +529,10 @@ bod_status train_backward(bod_context* h) {
                 // input gradient: dXcol[m][(tap, ci)] = dZ[m][:] . Wfolded[(tap, ci)][:], then col2im into the input's gradient plane
                 float* din = grad_buffer(h, G.in, act_elems_of(h, G.in, es));
                 if (!din) return h->fail(BOD_ERR_OOM, "training: gradient buffer");
-                const int NK = a.taps * a.cin;
                 if (conv_dgrad) {
                     // stride-1 SAME 3x3 with identical plane layouts: dX = conv(dZ plane, flipped / swapped weights) through the
                     // FORWARD row table (window origin and centre pixel coincide in both planes); accumulates in place
-                    ConvArgs d{};
-                    d.rows = a.rows; d.M = a.M; d.taps = 9; d.KW = 3; d.cin = a.cout_pad; d.in_cstride = a.out_cstride;
-                    d.cout_pad = a.cin; d.cout_valid = a.cin; d.out_cstride = a.in_cstride; d.res_cstride = a.in_cstride; d.groups = 1; d.fan_count = 1;
-                    d.flags = CONV_OUT_F32 | CONV_ACCUM;
-                    d.g[0] = ConvGroup{ab.dzp, tc.w_flip, t->zero_bias, din, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0};
+                    ConvArgs d = dgrad_flip_args(a, ab.dzp, tc.w_flip, t->zero_bias, din);
                     if (grouped_dgrad) {
                         if (ndeferred == 0) dgroup = d;
                         dgroup.g[ndeferred++] = d.g[0];
@@ -520,19 +549,11 @@ bod_status train_backward(bod_context* h) {
                         BODCHK(h->dalloc(&dr, (size_t)a.M, false));
                         HIPCHK(h, launch_make_dgrad_rows(a.rows, dr, a.M, h->stream));
                     }
-                    ConvArgs d{};
-                    d.rows = dr; d.M = a.M; d.taps = 1; d.KW = 1; d.cin = a.cout_pad; d.in_cstride = a.cout_pad;
-                    d.cout_pad = NK; d.cout_valid = NK; d.out_cstride = a.in_cstride; d.res_cstride = a.in_cstride; d.groups = 1; d.fan_count = 1;
-                    d.flags = CONV_OUT_F32 | CONV_ACCUM;
-                    d.g[0] = ConvGroup{t->dz, tc.w_bwd, t->zero_bias, din, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0};
+                    ConvArgs d = dgrad_rows_args(a, dr, t->dz, tc.w_bwd, t->zero_bias, din);
                     HIPCHK(h, gemm(d));
                     continue;
                 }
-                ConvArgs d{};
-                d.rows = t->iota; d.M = a.M; d.taps = 1; d.KW = 1; d.cin = a.cout_pad; d.in_cstride = a.cout_pad;
-                d.cout_pad = NK; d.cout_valid = NK; d.out_cstride = NK; d.res_cstride = NK; d.groups = 1; d.fan_count = 1;
-                d.flags = CONV_OUT_F32;
-                d.g[0] = ConvGroup{t->dz, tc.w_bwd, t->zero_bias, t->dxcol, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0};
+                ConvArgs d = dgrad_xcol_args(a, t->iota, t->dz, tc.w_bwd, t->zero_bias, t->dxcol);
                 HIPCHK(h, gemm(d));
                 HIPCHK(h, launch_col2im(t->dxcol, a.rows, din, a.M, a.taps, a.KW, a.cin, a.in_cstride, h->stream));
             }
@@ -896,4 +917,326 @@ bod_status bod_train_step_count(bod_handle h, int64_t* get, int64_t set) {
     if (set >= 0) h->train->step = set;
     if (get) *get = (int64_t)h->train->step;
     return BOD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Stage entry points of the backward kernels that only the bf16 training handle launches (include/bayesod.h): a throw-away
+// context, host arrays in and out, the launchers called as train_backward / train_fold_all call them.  Every argument a kernel
+// turns into an address is checked on the host first; nothing is launched on a bad one.
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct StageScope {
+    bod_context ctx;
+    bod_context* h = &ctx;
+    bod_status done(bod_status s) {
+        if (s != BOD_OK) g_create_error = h->err;
+        if (h->stream) hipStreamSynchronize(h->stream);
+        for (void* p : h->allocs) hipFree(p);
+        if (h->stream) hipStreamDestroy(h->stream);
+        h->allocs.clear(); h->stream = nullptr;
+        return s;
+    }
+    bod_status open(int32_t device) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+            return h->fail(BOD_ERR_NO_DEVICE, "no HIP device %d: libbayesod_hip has no CPU fallback", device);
+        if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
+            return h->fail(BOD_ERR_HIP, "cannot set up device %d", device);
+        return BOD_OK;
+    }
+};
+// host fp32 -> device buffer of the handle's element type (bf16: rounded like a stored activation); synchronises
+bod_status stage_upload(bod_context* h, const float* src, size_t n, bool f32, void** dst) {
+    char* d = nullptr;
+    BODCHK(h->dalloc(&d, n * (f32 ? 4 : 2), false));
+    std::vector<uint16_t> hb(f32 ? 0 : n);
+    for (size_t i = 0; i < hb.size(); ++i) hb[i] = f2bf(src[i]);
+    HIPCHK(h, hipMemcpyAsync(d, f32 ? (const void*)src : (const void*)hb.data(), n * (f32 ? 4 : 2), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *dst = d;
+    return BOD_OK;
+}
+bod_status stage_download(bod_context* h, const void* src, size_t n, bool f32, float* dst) {
+    std::vector<uint16_t> hb(f32 ? 0 : n);
+    HIPCHK(h, hipMemcpyAsync(f32 ? (void*)dst : (void*)hb.data(), src, n * (f32 ? 4 : 2), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < hb.size(); ++i) dst[i] = bf2f(hb[i]);
+    return BOD_OK;
+}
+}  // namespace
+
+bod_status bod_stage_act_backward(int32_t device, int32_t precision, const float* dout, const float* out_act, const float* dout_relu,
+                                  int64_t out_elems, const int32_t* out_off, const int32_t* res_off, int32_t M, int32_t cout,
+                                  int32_t cout_pad, int32_t out_cstride, int32_t res_cstride, float scale, int32_t Kpad, float* dres,
+                                  int64_t dres_elems, float* dz, float* dzp, float* dzt, int32_t* wrote_transpose) {
+    StageScope sc;
+    bod_context* h = sc.h;
+    const bool f32 = precision == BOD_PRECISION_FP32;
+    h->es = f32 ? 4 : 2;
+    auto bad = [&](const char* what) { return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_act_backward: %s", what)); };
+    if (precision != BOD_PRECISION_BF16 && !f32) return bad("precision must be BOD_PRECISION_BF16 or BOD_PRECISION_FP32");
+    if (!dout || !out_off || !dz || !wrote_transpose) return bad("dout, out_off, dz and wrote_transpose must not be NULL");
+    if (M < 1 || M > (1 << 22) || cout < 1 || cout > cout_pad || cout_pad > 4096) return bad("need 1 <= M <= 2^22 and 1 <= cout <= cout_pad <= 4096");
+    if (out_cstride < cout || out_elems < 1 || out_elems > ((int64_t)1 << 28)) return bad("need out_cstride >= cout and 1 <= out_elems <= 2^28");
+    if (Kpad < M || Kpad > (1 << 23)) return bad("Kpad must be at least M");
+    if (dout_relu && !out_act) return bad("dout_relu needs the stored output");
+    if (dres && (!res_off || res_cstride < cout || dres_elems < 1 || dres_elems > ((int64_t)1 << 28))) return bad("dres needs res_off, res_cstride >= cout and 1 <= dres_elems <= 2^28");
+    for (int m = 0; m < M; ++m) {
+        if (out_off[m] < 0 || (int64_t)out_off[m] * out_cstride + cout > out_elems) return bad("out_off outside the output buffer");
+        if (dres && (res_off[m] < 0 || (int64_t)res_off[m] * res_cstride + cout > dres_elems)) return bad("res_off outside the residual gradient buffer");
+    }
+    if (const bod_status s = sc.open(device)) return sc.done(s);
+    auto run = [&]() -> bod_status {
+        const size_t es = h->es, n_out = (size_t)out_elems, n_dz = (size_t)M * cout_pad, n_dzt = (size_t)cout_pad * Kpad;
+        float *d_dout = nullptr, *d_drelu = nullptr, *d_dres = nullptr;
+        void *d_out = nullptr, *d_dzp = nullptr, *d_dzt = nullptr;
+        char* d_dz = nullptr;
+        BODCHK(stage_upload(h, dout, n_out, true, reinterpret_cast<void**>(&d_dout)));
+        if (out_act) BODCHK(stage_upload(h, out_act, n_out, f32, &d_out));
+        if (dout_relu) BODCHK(stage_upload(h, dout_relu, n_out, true, reinterpret_cast<void**>(&d_drelu)));
+        if (dres) BODCHK(stage_upload(h, dres, (size_t)dres_elems, true, reinterpret_cast<void**>(&d_dres)));
+        if (dzp) BODCHK(stage_upload(h, dzp, n_out, f32, &d_dzp));
+        if (dzt) BODCHK(stage_upload(h, dzt, n_dzt, f32, &d_dzt));
+        BODCHK(h->dalloc(&d_dz, n_dz * es, false));
+        HIPCHK(h, hipMemsetAsync(d_dz, 0xFF, n_dz * es, h->stream));             // NaN in either type: an element the launch leaves out shows
+        std::vector<RowEnt> rows((size_t)M);
+        for (int m = 0; m < M; ++m) { RowEnt e{}; e.out_off = out_off[m]; e.res_off = dres ? res_off[m] : 0; rows[m] = e; }
+        RowEnt* d_rows = nullptr;
+        BODCHK(h->dalloc(&d_rows, rows.size(), false));
+        HIPCHK(h, hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(RowEnt), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (dout_relu) HIPCHK(h, launch_relu_merge(d_drelu, d_out, d_dout, (long)n_out, h->stream, f32));
+        ActBwdArgs ab{};
+        ab.dout = d_dout; ab.out_bf16 = reinterpret_cast<const uint16_t*>(d_out);
+        ab.rows = d_rows; ab.dz = reinterpret_cast<uint16_t*>(d_dz); ab.M = M; ab.cout = cout; ab.cout_pad = cout_pad;
+        ab.out_cstride = out_cstride; ab.res_cstride = res_cstride;
+        ab.scale = scale;
+        ab.f32 = f32 ? 1 : 0;
+        ab.dres = d_dres;
+        ab.dzp = reinterpret_cast<uint16_t*>(d_dzp);
+        ab.dzt = reinterpret_cast<uint16_t*>(d_dzt); ab.Kpad = Kpad;
+        bool transposed = false;
+        HIPCHK(h, launch_act_backward_gather(ab, h->stream, &transposed));
+        if (dzt && !transposed) HIPCHK(h, launch_gather_transpose(d_dz, nullptr, d_dzt, M, Kpad, cout_pad, cout_pad, 1, 1, false, h->stream, f32));
+        BODCHK(stage_download(h, d_dz, n_dz, f32, dz));
+        if (dzp) BODCHK(stage_download(h, d_dzp, n_out, f32, dzp));
+        if (dzt) BODCHK(stage_download(h, d_dzt, n_dzt, f32, dzt));
+        if (dres) BODCHK(stage_download(h, d_dres, (size_t)dres_elems, true, dres));
+        *wrote_transpose = transposed ? 1 : 0;
+        return BOD_OK;
+    };
+    return sc.done(run());
+}
+
+bod_status bod_stage_conv_dgrad(int32_t device, int32_t route, const float* dz, const float* w, int32_t B, int32_t H, int32_t W,
+                                int32_t Cin, int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t same_padding,
+                                int32_t ksplit, int32_t groups, float* din, int32_t* info2) {
+    StageScope sc;
+    bod_context* h = sc.h;
+    h->es = 2;
+    auto bad = [&](const char* what) { return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv_dgrad: %s", what)); };
+    if (!dz || !w || !din) return bad("dz, w and din must not be NULL");
+    if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 || KH > 3 || KW > 3 || stride < 1 || stride > 2) return bad("bad geometry");
+    if (Cin % 64 != 0 || Cin > 4096 || Cout > 4096) return bad("Cin must be a multiple of 64 (the input-gradient launches' output tile); at most 4096 channels");
+    if ((int64_t)B * (H + 2) * (W + 2) > (1 << 20)) return bad("at most 2^20 plane pixels");
+    if (route < BOD_DGRAD_FLIP || route > BOD_DGRAD_COL2IM) return bad("route must be BOD_DGRAD_FLIP, BOD_DGRAD_ROWS or BOD_DGRAD_COL2IM");
+    if (route == BOD_DGRAD_FLIP && !(KH == 3 && KW == 3 && stride == 1 && same_padding)) return bad("BOD_DGRAD_FLIP is the route of 3x3, stride 1, SAME layers");
+    if (route == BOD_DGRAD_ROWS && !(KH == 1 && KW == 1)) return bad("BOD_DGRAD_ROWS is the route of 1x1 layers");
+    if (groups < 1 || groups > 3 || (groups > 1 && route != BOD_DGRAD_FLIP)) return bad("groups: 1..3, more than one on BOD_DGRAD_FLIP only");
+    const int cout_pad = (Cout + 63) / 64 * 64, taps = KH * KW;
+    if (ksplit < 0 || ksplit > 64 || (ksplit > 1 && (cout_pad / 64) % ksplit != 0)) return bad("ksplit must divide the reduction's 64-channel chunks (cout_pad / 64)");
+    int OH, OW, oy = 1, ox = 1;
+    if (same_padding) {
+        OH = (H + stride - 1) / stride; OW = (W + stride - 1) / stride;
+        oy = 1 - same_pad_before(H, KH, stride); ox = 1 - same_pad_before(W, KW, stride);
+    } else {
+        OH = (H - KH) / stride + 1; OW = (W - KW) / stride + 1;
+    }
+    if (OH < 1 || OW < 1) return bad("empty output");
+    // forward row table on the zero-bordered input plane (bod_stage_conv_wgrad's); BOD_DGRAD_FLIP: the output plane has the same geometry
+    const int pitch = W + 2;
+    const int64_t bstride = (int64_t)(H + 2) * (W + 2), npix = (int64_t)B * bstride;
+    const int M = B * OH * OW;
+    std::vector<RowEnt> rows((size_t)M);
+    {
+        size_t r = 0;
+        for (int b = 0; b < B; ++b)
+            for (int y = 0; y < OH; ++y)
+                for (int xx = 0; xx < OW; ++xx) {
+                    RowEnt e{};
+                    e.in_off = (int32_t)(b * bstride + (int64_t)(y * stride + oy) * pitch + (xx * stride + ox));
+                    e.in_pitch = pitch;
+                    e.out_off = route == BOD_DGRAD_FLIP ? (int32_t)(b * bstride + (int64_t)(y + 1) * pitch + (xx + 1)) : (int32_t)r;
+                    // every pixel a window touches lies on the plane of its own image
+                    const int y0 = y * stride + oy, x0 = xx * stride + ox;
+                    if (y0 < 0 || x0 < 0 || y0 + KH - 1 > H + 1 || x0 + KW - 1 > W + 1) return bad("a window leaves the bordered plane");
+                    rows[r++] = e;
+                }
+    }
+    if (const bod_status s = sc.open(device)) return sc.done(s);
+    auto run = [&]() -> bod_status {
+        const size_t n_w = (size_t)taps * Cin * Cout, n_wp = (size_t)taps * Cin * cout_pad, n_dz = (size_t)M * Cout, n_din = (size_t)npix * Cin;
+        RowEnt* d_rows = nullptr;
+        BODCHK(h->dalloc(&d_rows, rows.size(), false));
+        HIPCHK(h, hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(RowEnt), hipMemcpyHostToDevice, h->stream));
+        float *d_zero = nullptr, *d_bscratch = nullptr;
+        BODCHK(h->dalloc(&d_zero, (size_t)std::max(cout_pad, taps * Cin)));
+        BODCHK(h->dalloc(&d_bscratch, (size_t)cout_pad));
+        // the forward launch of the layer, as far as the input-gradient launches read it
+        ConvArgs a{};
+        a.rows = d_rows; a.M = M; a.taps = taps; a.KW = KW; a.cin = Cin; a.in_cstride = Cin;
+        a.cout_pad = cout_pad; a.cout_valid = Cout; a.out_cstride = cout_pad; a.res_cstride = cout_pad; a.groups = groups;
+        uint16_t* d_wp[3] = {nullptr, nullptr, nullptr};
+        uint16_t* d_dz[3] = {nullptr, nullptr, nullptr};
+        float* d_din[3] = {nullptr, nullptr, nullptr};
+        for (int g = 0; g < groups; ++g) {
+            void* d_w = nullptr;
+            BODCHK(stage_upload(h, w + (size_t)g * n_w, n_w, true, &d_w));
+            BODCHK(h->dalloc(&d_wp[g], n_wp));
+            FoldArgs f{};
+            f.kernel = reinterpret_cast<const float*>(d_w); f.eps = BN_EPS; f.taps = taps; f.cin = Cin; f.cout = Cout; f.cout_pad = cout_pad;
+            if (route == BOD_DGRAD_FLIP) f.w_flip = d_wp[g]; else f.w_bwd = d_wp[g];
+            f.b_fwd = d_bscratch;
+            HIPCHK(h, launch_fold_pack(f, h->stream));
+            // dZ: on the zero-bordered output plane (BOD_DGRAD_FLIP), else dense [M][cout_pad]
+            const size_t n_dzb = (route == BOD_DGRAD_FLIP ? (size_t)npix : (size_t)M) * cout_pad;
+            std::vector<uint16_t> hz(n_dzb, 0);
+            for (int m = 0; m < M; ++m) {
+                const size_t pix = route == BOD_DGRAD_FLIP ? (size_t)rows[m].out_off : (size_t)m;
+                for (int c = 0; c < Cout; ++c) hz[pix * cout_pad + c] = f2bf(dz[(size_t)g * n_dz + (size_t)m * Cout + c]);
+            }
+            BODCHK(h->dalloc(&d_dz[g], n_dzb, false));
+            HIPCHK(h, hipMemcpyAsync(d_dz[g], hz.data(), n_dzb * 2, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            void* p = nullptr;
+            BODCHK(stage_upload(h, din + (size_t)g * n_din, n_din, true, &p));
+            d_din[g] = reinterpret_cast<float*>(p);
+        }
+        ConvArgs d{};
+        float* d_dxcol = nullptr;
+        if (route == BOD_DGRAD_FLIP) {
+            d = dgrad_flip_args(a, d_dz[0], d_wp[0], d_zero, d_din[0]);
+            for (int g = 1; g < groups; ++g) d.g[g] = dgrad_flip_args(a, d_dz[g], d_wp[g], d_zero, d_din[g]).g[0];
+            d.groups = groups;                       // (train_backward: one grouped launch for groups that read different inputs)
+        } else if (route == BOD_DGRAD_ROWS) {
+            RowEnt* dr = nullptr;
+            BODCHK(h->dalloc(&dr, (size_t)M, false));
+            HIPCHK(h, launch_make_dgrad_rows(d_rows, dr, M, h->stream));
+            d = dgrad_rows_args(a, dr, d_dz[0], d_wp[0], d_zero, d_din[0]);
+        } else {
+            std::vector<RowEnt> io((size_t)M);
+            for (int m = 0; m < M; ++m) { RowEnt e{}; e.in_off = m; e.out_off = m; io[m] = e; }
+            RowEnt* d_iota = nullptr;
+            BODCHK(h->dalloc(&d_iota, io.size(), false));
+            HIPCHK(h, hipMemcpyAsync(d_iota, io.data(), io.size() * sizeof(RowEnt), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            BODCHK(h->dalloc(&d_dxcol, (size_t)M * taps * Cin));
+            d = dgrad_xcol_args(a, d_iota, d_dz[0], d_wp[0], d_zero, d_dxcol);
+        }
+        // split-K as train_backward's `gemm` decides it, or as the caller forces it
+        const int S = ksplit > 0 ? ksplit : dgrad_splits(d.M, d.cin, d.taps, d.cout_pad, d.groups);
+        if (S > 1) {
+            if ((d.cin / 64) % S != 0) return h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv_dgrad: ksplit %d does not divide %d chunks", S, d.cin / 64);
+            d.ksplit = S;
+            BODCHK(h->dalloc(&d.partial, (size_t)S * d.groups * d.M * d.cout_pad, false));
+        }
+        if (info2) { info2[0] = S; info2[1] = (S <= 1 && conv_igemm_uses_big_tile(d)) ? 1 : 0; }
+        HIPCHK(h, launch_conv_igemm(d, h->stream));
+        if (route == BOD_DGRAD_COL2IM) HIPCHK(h, launch_col2im(d_dxcol, a.rows, d_din[0], a.M, a.taps, a.KW, a.cin, a.in_cstride, h->stream));
+        for (int g = 0; g < groups; ++g) BODCHK(stage_download(h, d_din[g], n_din, true, din + (size_t)g * n_din));
+        return BOD_OK;
+    };
+    return sc.done(run());
+}
+
+bod_status bod_stage_stem_pool_backward(int32_t device, int32_t precision, const float* stem_out, const float* dpool, int64_t dpool_elems,
+                                        int32_t B, int32_t ih, int32_t iw, float* dz) {
+    StageScope sc;
+    bod_context* h = sc.h;
+    const bool f32 = precision == BOD_PRECISION_FP32;
+    h->es = f32 ? 4 : 2;
+    auto bad = [&](const char* what) { return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_stem_pool_backward: %s", what)); };
+    if (precision != BOD_PRECISION_BF16 && !f32) return bad("precision must be BOD_PRECISION_BF16 or BOD_PRECISION_FP32");
+    if (!stem_out || !dpool || !dz) return bad("stem_out, dpool and dz must not be NULL");
+    if (B < 1 || ih < 1 || iw < 1 || (int64_t)B * ih * iw > (1 << 22)) return bad("need B, ih, iw >= 1 and at most 2^22 stem pixels");
+    // the pooled plane as bod_create lays it out: ZeroPadding2D((1, 2)) + MaxPool 3x3 s2 VALID, one pixel of border
+    const int oh = (ih + 2 - 3) / 2 + 1, ow = (iw + 4 - 3) / 2 + 1;
+    const int pool_pitch = ow + 2, pool_plane = (oh + 2) * (ow + 2);
+    if (dpool_elems != (int64_t)B * pool_plane * 64) return bad("dpool must hold B * (oh + 2) * (ow + 2) * 64 floats (oh = (ih - 1) / 2 + 1, ow = (iw + 1) / 2 + 1)");
+    if (const bod_status s = sc.open(device)) return sc.done(s);
+    auto run = [&]() -> bod_status {
+        const size_t n = (size_t)B * ih * iw * 64;
+        void *d_stem = nullptr, *d_dpool = nullptr;
+        char* d_dz = nullptr;
+        BODCHK(stage_upload(h, stem_out, n, f32, &d_stem));
+        BODCHK(stage_upload(h, dpool, (size_t)dpool_elems, true, &d_dpool));
+        BODCHK(h->dalloc(&d_dz, n * h->es, false));
+        HIPCHK(h, hipMemsetAsync(d_dz, 0xFF, n * h->es, h->stream));
+        HIPCHK(h, launch_stem_pool_backward(d_stem, reinterpret_cast<const float*>(d_dpool), d_dz, B, ih, iw, oh, ow, pool_pitch, pool_plane, h->stream, f32));
+        return stage_download(h, d_dz, n, f32, dz);
+    };
+    return sc.done(run());
+}
+
+bod_status bod_stage_fold_pack(int32_t device, int32_t count, const bod_fold_layer* layers) {
+    StageScope sc;
+    bod_context* h = sc.h;
+    h->es = 2;
+    auto bad = [&](const char* what) { return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_fold_pack: %s", what)); };
+    if (!layers || count < 1 || count > 64) return bad("1..64 layers");
+    for (int i = 0; i < count; ++i) {
+        const bod_fold_layer& L = layers[i];
+        if (!L.kernel || !L.b_fwd) return bad("kernel and b_fwd must not be NULL");
+        if (L.taps < 1 || L.taps > 49 || L.cin < 1 || L.cin > 4096 || L.cout < 1 || L.cout > L.cout_pad || L.cout_pad > 4096) return bad("need 1 <= taps <= 49, 1 <= cin <= 4096, 1 <= cout <= cout_pad <= 4096");
+        const int nbn = (L.gamma != nullptr) + (L.beta != nullptr) + (L.mean != nullptr) + (L.var != nullptr);
+        if (nbn != 0 && nbn != 4) return bad("gamma, beta, mean and var come together or not at all");
+    }
+    if (const bod_status s = sc.open(device)) return sc.done(s);
+    auto run = [&]() -> bod_status {
+        std::vector<FoldArgs> all((size_t)count);
+        long fold_max = 0;
+        auto up = [&](const float* src, size_t n, const float** dst) -> bod_status {
+            void* p = nullptr;
+            if (src) BODCHK(stage_upload(h, src, n, true, &p));
+            *dst = reinterpret_cast<const float*>(p);
+            return BOD_OK;
+        };
+        for (int i = 0; i < count; ++i) {
+            const bod_fold_layer& L = layers[i];
+            FoldArgs& f = all[i];
+            const size_t n_pack = (size_t)L.cout_pad * L.taps * L.cin;
+            BODCHK(up(L.kernel, (size_t)L.taps * L.cin * L.cout, &f.kernel));
+            BODCHK(up(L.bias, (size_t)L.cout, &f.bias));
+            BODCHK(up(L.gamma, (size_t)L.cout, &f.gamma)); BODCHK(up(L.beta, (size_t)L.cout, &f.beta));
+            BODCHK(up(L.mean, (size_t)L.cout, &f.mean)); BODCHK(up(L.var, (size_t)L.cout, &f.var));
+            f.eps = BN_EPS; f.taps = L.taps; f.cin = L.cin; f.cout = L.cout; f.cout_pad = L.cout_pad; f.f32 = 0;
+            // 0xFF fill (bf16 / fp32 NaN): an element the launch leaves out shows
+            auto out16 = [&](uint16_t** p) -> bod_status { BODCHK(h->dalloc(p, n_pack, false)); HIPCHK(h, hipMemsetAsync(*p, 0xFF, n_pack * 2, h->stream)); return BOD_OK; };
+            if (L.w_fwd) BODCHK(out16(&f.w_fwd));
+            if (L.w_bwd) BODCHK(out16(&f.w_bwd));
+            if (L.w_flip) BODCHK(out16(&f.w_flip));
+            if (L.w_fwd32) { BODCHK(h->dalloc(&f.w_fwd32, (size_t)L.taps * L.cin * L.cout, false)); HIPCHK(h, hipMemsetAsync(f.w_fwd32, 0xFF, (size_t)L.taps * L.cin * L.cout * 4, h->stream)); }
+            BODCHK(h->dalloc(&f.b_fwd, (size_t)L.cout_pad, false));
+            HIPCHK(h, hipMemsetAsync(f.b_fwd, 0xFF, (size_t)L.cout_pad * 4, h->stream));
+            fold_max = std::max(fold_max, (long)n_pack);
+        }
+        FoldArgs* d_desc = nullptr;
+        BODCHK(h->dalloc(&d_desc, all.size(), false));
+        HIPCHK(h, hipMemcpyAsync(d_desc, all.data(), all.size() * sizeof(FoldArgs), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, launch_fold_pack_all(d_desc, count, fold_max, h->stream));
+        for (int i = 0; i < count; ++i) {
+            const bod_fold_layer& L = layers[i];
+            const FoldArgs& f = all[i];
+            const size_t n_pack = (size_t)L.cout_pad * L.taps * L.cin;
+            if (L.w_fwd) HIPCHK(h, hipMemcpyAsync(L.w_fwd, f.w_fwd, n_pack * 2, hipMemcpyDeviceToHost, h->stream));
+            if (L.w_bwd) HIPCHK(h, hipMemcpyAsync(L.w_bwd, f.w_bwd, n_pack * 2, hipMemcpyDeviceToHost, h->stream));
+            if (L.w_flip) HIPCHK(h, hipMemcpyAsync(L.w_flip, f.w_flip, n_pack * 2, hipMemcpyDeviceToHost, h->stream));
+            if (L.w_fwd32) HIPCHK(h, hipMemcpyAsync(L.w_fwd32, f.w_fwd32, (size_t)L.taps * L.cin * L.cout * 4, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(L.b_fwd, f.b_fwd, (size_t)L.cout_pad * 4, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return BOD_OK;
+    };
+    return sc.done(run());
 }

@@ -1060,6 +1060,117 @@ def stage_conv_dgrad(dy, w, padding="same", device=0):
     return stage_conv(dy, wt, None, stride=1, padding="same", device=device)
 
 
+def stage_act_backward(dout, out_off, cout, cout_pad, out_cstride, kpad, out_act=None, dout_relu=None, scale=1.0, res_off=None,
+                       res_cstride=0, dres=None, dzp=None, dzt=None, precision="bf16", device=0):
+    """Activation backward of one layer as the training step launches it (``bod_stage_act_backward``).  dout / out_act /
+    dout_relu: flat arrays in the output buffer's layout; out_off / res_off [M] int32 pixel indices; dres, dzp (like dout) and dzt
+    [cout_pad, kpad] are prefills (None: not wanted).  Returns dict(dz [M, cout_pad], dzp, dzt, dres, wrote_transpose); bf16 values
+    come back widened to float32."""
+    lib = _lib.load()
+    dout = as_f32(dout).reshape(-1)
+    out_off = np.ascontiguousarray(out_off, dtype=np.int32).reshape(-1)
+    m = int(out_off.size)
+    flat = lambda a: None if a is None else as_f32(a).reshape(-1).copy()
+    out_act, dout_relu, dres, dzp, dzt = flat(out_act), flat(dout_relu), flat(dres), flat(dzp), flat(dzt)
+    for name, a in (("out_act", out_act), ("dout_relu", dout_relu), ("dzp", dzp)):
+        if a is not None and a.size != dout.size:
+            raise ValueError("%s must have dout's %d elements" % (name, dout.size))
+    if dzt is not None and dzt.size != int(cout_pad) * int(kpad):
+        raise ValueError("dzt must have cout_pad * kpad elements")
+    if res_off is not None:
+        res_off = np.ascontiguousarray(res_off, dtype=np.int32).reshape(-1)
+        if res_off.size != m:
+            raise ValueError("res_off must have one entry per row")
+    dz = np.empty((m, int(cout_pad)), np.float32)
+    wrote = C.c_int32(-1)
+    st = lib.bod_stage_act_backward(device, PRECISIONS[precision], fptr(dout), fptr(out_act), fptr(dout_relu), dout.size, iptr(out_off),
+                                    iptr(res_off), m, int(cout), int(cout_pad), int(out_cstride), int(res_cstride), float(scale),
+                                    int(kpad), fptr(dres), 0 if dres is None else dres.size, fptr(dz), fptr(dzp), fptr(dzt),
+                                    C.byref(wrote))
+    _lib.check(lib, None, st)
+    return {"dz": dz, "dzp": dzp, "dzt": None if dzt is None else dzt.reshape(int(cout_pad), int(kpad)), "dres": dres,
+            "wrote_transpose": bool(wrote.value)}
+
+
+DGRAD_ROUTES = {"flip": _lib.BOD_DGRAD_FLIP, "rows": _lib.BOD_DGRAD_ROWS, "col2im": _lib.BOD_DGRAD_COL2IM}
+
+
+def stage_conv_dgrad_route(dz, w, in_hw, din, route, stride=1, padding="same", ksplit=0, device=0):
+    """Input gradient of one bf16 Conv2D through one of the training step's three launches (``bod_stage_conv_dgrad``): dz
+    [G,B,OH,OW,Cout] or [B,OH,OW,Cout], w [G,KH,KW,Cin,Cout] or HWIO, din [G,B,H+2,W+2,Cin] or [B,H+2,W+2,Cin]: the prefilled fp32
+    gradient plane of the input with its border.  Returns (din after the launch, same shape; split-K factor used; whether the
+    launch took the 256x256 tile)."""
+    lib = _lib.load()
+    dz, w, din = as_f32(dz), as_f32(w), as_f32(din).copy()
+    grouped = w.ndim == 5
+    g = w.shape[0] if grouped else 1
+    kh, kw, cin, cout = w.shape[-4:]
+    h, wd = int(in_hw[0]), int(in_hw[1])
+    b = dz.shape[-4]
+    if padding == "same":
+        oh, ow = -(-h // stride), -(-wd // stride)
+    else:
+        oh, ow = (h - kh) // stride + 1, (wd - kw) // stride + 1
+    lead = (g,) if grouped else ()
+    if dz.shape != lead + (b, oh, ow, cout) or din.shape != lead + (b, h + 2, wd + 2, cin):
+        raise ValueError("dz %s / din %s do not fit %d group(s) of a %dx%d input" % (dz.shape, din.shape, g, h, wd))
+    info = np.zeros(2, np.int32)
+    st = lib.bod_stage_conv_dgrad(device, DGRAD_ROUTES[route], fptr(dz), fptr(w), b, h, wd, cin, cout, kh, kw, int(stride),
+                                  int(padding == "same"), int(ksplit), g, fptr(din), iptr(info))
+    _lib.check(lib, None, st)
+    return din, int(info[0]), bool(info[1])
+
+
+def stage_stem_pool_backward(stem_out, dpool, precision="bf16", device=0):
+    """Backward of the stem's zero-pad + 3x3 s2 max-pool under its ReLU (``bod_stage_stem_pool_backward``): stem_out [B,ih,iw,64],
+    dpool [B,oh+2,ow+2,64] (the pooled gradient on its bordered plane); returns dz [B,ih,iw,64] float32."""
+    lib = _lib.load()
+    stem_out, dpool = as_f32(stem_out), as_f32(dpool)
+    b, ih, iw, c = stem_out.shape
+    if c != 64:
+        raise ValueError("the stem has 64 channels")
+    dz = np.empty_like(stem_out)
+    st = lib.bod_stage_stem_pool_backward(device, PRECISIONS[precision], fptr(stem_out), fptr(dpool), dpool.size, b, ih, iw, fptr(dz))
+    _lib.check(lib, None, st)
+    return dz
+
+
+def stage_fold_pack(layers, device=0):
+    """Batch-norm folding and the three bf16 weight packings of every layer in ONE launch (``bod_stage_fold_pack``).  layers:
+    dicts with kernel [taps,cin,cout] (or HWIO), cout_pad, optional bias and gamma / beta / mean / var.  Returns one dict per
+    layer: w_fwd [cout_pad,taps,cin], w_bwd [taps*cin,cout_pad], w_flip [cin,taps,cout_pad] (uint16: raw bf16 bits), b_fwd
+    [cout_pad] (float32) and, for a layer with ``fwd32`` set, w_fwd32 [taps*cin,cout] (float32; else None).  As in the training
+    step, a layer that asks for the fp32 packing (the stem) is packed element by element, the others in 64x64 tiles when their
+    cin and cout_pad allow."""
+    lib = _lib.load()
+    n = len(layers)
+    arr = (_lib.BodFoldLayer * max(n, 1))()
+    u16 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint16))
+    keep, outs = [], []
+    for i, layer in enumerate(layers):
+        k = as_f32(layer["kernel"])
+        cin, cout = k.shape[-2:]
+        taps = int(k.size // (cin * cout))
+        cp = int(layer["cout_pad"])
+        ins = {name: (as_f32(layer[name]).reshape(-1) if layer.get(name) is not None else None)
+               for name in ("bias", "gamma", "beta", "mean", "var")}
+        for name, a in ins.items():
+            if a is not None and a.size != cout:
+                raise ValueError("layer %d: %s must have %d elements" % (i, name, cout))
+        o = {"w_fwd": np.zeros((max(cp, 0), taps, cin), np.uint16), "w_bwd": np.zeros((taps * cin, max(cp, 0)), np.uint16),
+             "w_flip": np.zeros((cin, taps, max(cp, 0)), np.uint16),
+             "w_fwd32": np.zeros((taps * cin, cout), np.float32) if layer.get("fwd32") else None,
+             "b_fwd": np.zeros((max(cp, 0),), np.float32)}
+        keep.append((k, ins))
+        outs.append(o)
+        arr[i] = _lib.BodFoldLayer(fptr(k), fptr(ins["bias"]), fptr(ins["gamma"]), fptr(ins["beta"]), fptr(ins["mean"]), fptr(ins["var"]),
+                                   taps, cin, cout, cp, u16(o["w_fwd"]), u16(o["w_bwd"]), u16(o["w_flip"]), fptr(o["w_fwd32"]),
+                                   fptr(o["b_fwd"]))
+    st = lib.bod_stage_fold_pack(device, n, arr)
+    _lib.check(lib, None, st)
+    return outs
+
+
 def pdq_corner_heatmaps(img_hw, means_yx, covs_yx, device=0, heatmaps=True):
     """Gaussian corners on the device (``bod_pdq_corner_heatmaps``), for parity tests of prob_detection_quality.corner_roi /
     corner_heatmap: means_yx [n,2], covs_yx [n,2,2] in (y, x) order; returns (rois [n,4] x0 y0 x1 y1, heatmaps [n,H,W] float32

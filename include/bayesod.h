@@ -406,11 +406,61 @@ bod_status bod_stage_conv(int32_t device, const float* x, int32_t B, int32_t H, 
  * bod_stage_conv; x and dy are rounded to bf16 like stored activations, accumulation is fp32).  Runs as a
  * pixel-reduction GEMM on the forward implicit-GEMM MFMA kernel: im2col^T of x through the forward row table,
  * dy transposed, reduction split over `ksplit` workgroups per tile (0 = chosen automatically).  The input
- * gradient needs no entry point of its own: it is bod_stage_conv on dy with the spatially flipped, cin/cout
- * swapped weights (tests/test_gpu_train_blocks.py).  Errors via bod_last_error(NULL). */
+ * gradient as a forward convolution needs no entry point of its own: it is bod_stage_conv on dy with the spatially
+ * flipped, cin/cout swapped weights (tests/test_gpu_train_blocks.py); the step's own three accumulating launches are
+ * bod_stage_conv_dgrad below.  Errors via bod_last_error(NULL). */
 bod_status bod_stage_conv_wgrad(int32_t device, const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin,
                                 const float* dy, int32_t KH, int32_t KW, int32_t Cout, int32_t stride,
                                 int32_t same_padding, int32_t ksplit, float* dw, float* db);
+
+/* Stage entry points of the backward kernels that only the bf16 training handle launches (DESIGN.md 9.12,
+ * tests/test_gpu_train_backward_kernels.py).  Each one builds a throw-away context, calls the library's own launchers
+ * the way the training step does and copies the results back.  Every offset and size a kernel would turn into an
+ * address is checked on the host first: BOD_ERR_INVALID_ARG, nothing launched.  bf16 tensors cross the boundary as
+ * fp32 host arrays (rounded to nearest even on the way in, widened exactly on the way out) unless stated otherwise.
+ * Errors via bod_last_error(NULL).
+ *
+ * Activation backward of one layer (launch_relu_merge when dout_relu is given, then launch_act_backward_gather, then
+ * launch_gather_transpose when dZ^T is wanted and the launch did not write it).  dout [out_elems] fp32 is the gradient
+ * of the layer's output in the output buffer's own layout, out_act [out_elems] the stored output (NULL: no activation),
+ * dout_relu [out_elems] the gradient of the output's ReLU'd copy (NULL: none).  Row m reads pixel out_off[m] (channel
+ * stride out_cstride) and, with dres, adds into pixel res_off[m] (stride res_cstride) of dres [dres_elems], which is
+ * read and written.  dz [M][cout_pad] is written; dzp [out_elems] and dzt [cout_pad][Kpad] are optional (NULL: not
+ * wanted, the launcher then sees no such buffer), prefilled by the caller and written where the kernels write them.
+ * *wrote_transpose: 1 when the tile kernel wrote dZ^T itself.  precision: BOD_PRECISION_BF16 or BOD_PRECISION_FP32. */
+bod_status bod_stage_act_backward(int32_t device, int32_t precision, const float* dout, const float* out_act, const float* dout_relu,
+                                  int64_t out_elems, const int32_t* out_off, const int32_t* res_off, int32_t M, int32_t cout,
+                                  int32_t cout_pad, int32_t out_cstride, int32_t res_cstride, float scale, int32_t Kpad, float* dres,
+                                  int64_t dres_elems, float* dz, float* dzp, float* dzt, int32_t* wrote_transpose);
+
+/* Input gradient of one bf16 Conv2D through one of the training step's three launches, each with CONV_OUT_F32 and (the
+ * first two) CONV_ACCUM: BOD_DGRAD_FLIP = convolution of the dZ plane with the flipped weights (3x3, stride 1, SAME),
+ * BOD_DGRAD_ROWS = the 1x1 GEMM through the table of launch_make_dgrad_rows, BOD_DGRAD_COL2IM = dXcol + col2im.
+ * dz [groups][B,OH,OW,Cout] and w [groups][KH,KW,Cin,Cout] (master layout, packed by launch_fold_pack without
+ * batch-norm) are rounded to bf16; din [groups][B,H+2,W+2,Cin] is the fp32 gradient plane of the layer's input with
+ * its one-pixel border, read and written.  ksplit 0 = the step's own rule, otherwise forced; groups 1..3 run as one
+ * grouped launch (BOD_DGRAD_FLIP only).  info2 (may be NULL): {split-K factor used, 1 if the launch took the 256x256 tile}. */
+enum { BOD_DGRAD_FLIP = 0, BOD_DGRAD_ROWS = 1, BOD_DGRAD_COL2IM = 2 };
+bod_status bod_stage_conv_dgrad(int32_t device, int32_t route, const float* dz, const float* w, int32_t B, int32_t H, int32_t W,
+                                int32_t Cin, int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t same_padding,
+                                int32_t ksplit, int32_t groups, float* din, int32_t* info2);
+
+/* Backward of ZeroPadding2D((1,2)) + MaxPool 3x3 s2 under the stem's ReLU (launch_stem_pool_backward): stem_out and dz
+ * [B,ih,iw,64]; dpool is the pooled gradient on its bordered plane [B,oh+2,ow+2,64] fp32 with oh = (ih - 1) / 2 + 1 and
+ * ow = (iw + 1) / 2 + 1 as handle creation derives them (dpool_elems must say exactly that). */
+bod_status bod_stage_stem_pool_backward(int32_t device, int32_t precision, const float* stem_out, const float* dpool, int64_t dpool_elems,
+                                        int32_t B, int32_t ih, int32_t iw, float* dz);
+
+/* Fold batch-norm into the master weights and pack them, all `count` layers in ONE launch_fold_pack_all launch, bf16
+ * mode.  Inputs: kernel [taps][cin][cout], bias / gamma / beta / mean / var [cout] or NULL (the four batch-norm arrays
+ * together).  Outputs, each optional except b_fwd: w_fwd [cout_pad][taps][cin], w_bwd [(tap, ci)][cout_pad] and w_flip
+ * [cin][taps, flipped][cout_pad] as raw bf16 bits, w_fwd32 [taps*cin][cout] fp32 (the stem's), b_fwd [cout_pad] fp32. */
+typedef struct bod_fold_layer {
+    const float* kernel; const float* bias; const float* gamma; const float* beta; const float* mean; const float* var;
+    int32_t taps, cin, cout, cout_pad;
+    uint16_t* w_fwd; uint16_t* w_bwd; uint16_t* w_flip; float* w_fwd32; float* b_fwd;
+} bod_fold_layer;
+bod_status bod_stage_fold_pack(int32_t device, int32_t count, const bod_fold_layer* layers);
 
 /* One training step, run_training.train_single_step (:208-247), on a handle created with training = 1:
  * forward in training mode (dropout on, batch-norm frozen), total loss = w_cls * focal + w_reg * regression

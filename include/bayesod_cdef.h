@@ -148,6 +148,22 @@ bod_status bod_stage_conv(int32_t device, const float* x, int32_t B, int32_t H, 
 bod_status bod_stage_conv_wgrad(int32_t device, const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin,
                                 const float* dy, int32_t KH, int32_t KW, int32_t Cout, int32_t stride,
                                 int32_t same_padding, int32_t ksplit, float* dw, float* db);
+bod_status bod_stage_act_backward(int32_t device, int32_t precision, const float* dout, const float* out_act, const float* dout_relu,
+                                  int64_t out_elems, const int32_t* out_off, const int32_t* res_off, int32_t M, int32_t cout,
+                                  int32_t cout_pad, int32_t out_cstride, int32_t res_cstride, float scale, int32_t Kpad, float* dres,
+                                  int64_t dres_elems, float* dz, float* dzp, float* dzt, int32_t* wrote_transpose);
+enum { BOD_DGRAD_FLIP = 0, BOD_DGRAD_ROWS = 1, BOD_DGRAD_COL2IM = 2 };
+bod_status bod_stage_conv_dgrad(int32_t device, int32_t route, const float* dz, const float* w, int32_t B, int32_t H, int32_t W,
+                                int32_t Cin, int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t same_padding,
+                                int32_t ksplit, int32_t groups, float* din, int32_t* info2);
+bod_status bod_stage_stem_pool_backward(int32_t device, int32_t precision, const float* stem_out, const float* dpool, int64_t dpool_elems,
+                                        int32_t B, int32_t ih, int32_t iw, float* dz);
+typedef struct bod_fold_layer {
+    const float* kernel; const float* bias; const float* gamma; const float* beta; const float* mean; const float* var;
+    int32_t taps, cin, cout, cout_pad;
+    uint16_t* w_fwd; uint16_t* w_bwd; uint16_t* w_flip; float* w_fwd32; float* b_fwd;
+} bod_fold_layer;
+bod_status bod_stage_fold_pack(int32_t device, int32_t count, const bod_fold_layer* layers);
 bod_status bod_train_step(bod_handle h, const float* images, int32_t images_on_device, const float* cls_targets,
                           const float* box_targets, const uint8_t* positive_mask, const uint8_t* negative_mask,
                           uint64_t seed, uint32_t first_image_id, int32_t reg_kind, float label_smoothing,

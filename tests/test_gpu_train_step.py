@@ -6,7 +6,8 @@ GEMMs) meets the oracle ELEMENT-WISE on every gradient tensor, the loss terms an
 handle (the product: bf16 activations / weights / dZ, fp32 accumulation through ~60 layers) runs the same op walk and is
 compared per tensor by direction and size (cosine similarity, norm ratio): bf16 storage decorrelates two evaluations of
 this network at the level of its own rounding noise (oracle/torch_train.py's bf16 emulation accumulated in fp32 vs in
-fp64 already differ by ~10 % per tensor), so no element-wise bound exists for it."""
+fp64 already differ by ~10 % per tensor), so no element-wise bound exists for it.
+One layer deep such bounds do exist: tests/test_gpu_train_backward_kernels.py pins the kernels only the bf16 handle launches."""
 import numpy as np
 import pytest
 
