@@ -59,6 +59,12 @@ class BodJpegInfo(C.Structure):
                 ("restart_interval", C.c_int32), ("supported", C.c_int32), ("coef_count", C.c_int64)]
 
 
+class BodCorruptOp(C.Structure):
+    """bod_corrupt_op: one op of a frame's corruption chain (``corruptions.OP_DTYPE`` is the same layout as a NumPy dtype)."""
+    _fields_ = [("kind", C.c_int32), ("f0", C.c_float), ("u0", C.c_uint32), ("tap_offset", C.c_int32), ("ksize", C.c_int32),
+                ("table", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class BodFoldLayer(C.Structure):
     """bod_fold_layer: one layer of bod_stage_fold_pack (inputs, geometry, host output arrays)."""
     _fields_ = [("kernel", C.POINTER(C.c_float)), ("bias", C.POINTER(C.c_float)), ("gamma", C.POINTER(C.c_float)),
@@ -141,6 +147,11 @@ SIGNATURES = {
                                          C.c_int32, _I]),
     "bod_upload_frames_jpeg_async": (C.c_int, [_H, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), _F, C.c_int32, C.POINTER(BodAugment),
                                                C.c_int32, _I, C.c_int32]),
+    "bod_corrupt_frames_u8": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_uint8), _I, C.POINTER(BodCorruptOp), C.c_int32,
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint16), C.c_int32, C.POINTER(C.c_uint8), C.c_int32,
+                                        C.POINTER(C.c_uint16), C.c_int32, C.c_uint64, C.POINTER(C.c_uint8)]),
+    "bod_set_upload_corruption": (C.c_int, [_H, C.POINTER(BodCorruptOp), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint16),
+                                            C.c_int32, C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_uint16), C.c_int32, C.c_uint64]),
     "bod_device_images_buffer": (C.c_void_p, [_H, C.c_int32]),
     "bod_device_images": (C.c_void_p, [_H]),
     "bod_synchronize": (C.c_int, [_H]),

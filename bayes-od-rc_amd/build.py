@@ -26,6 +26,8 @@ SOURCES = [
     ("train_kernels.hip", []),
     # integer code only (the JPEG inverse DCT, upsampling and colour conversion: DESIGN.md 9.11)
     ("jpeg_kernels.hip", []),
+    # frame corruptions: integer code, and fp32 ops whose order a NumPy restatement repeats
+    ("corrupt_kernels.hip", ["-ffp-contract=off"]),
     ("engine.hip", []),
 ]
 # -fno-slp-vectorize (round 6): NO packed fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) in any kernel of

@@ -312,6 +312,10 @@ struct bod_context {
     RaggedTable rag_sync, rag_b[2];
     RaggedTable aug_sync, aug_b[2];       // the augmented uploads' own (their records are PreprocAugFrame, without factors)
     JpegSlot jpeg_slot[3];                              // JPEG uploads: one per image buffer, [2] the synchronous route's
+    // frame corruptions: the one-shot description bod_set_upload_corruption left for the next packed upload, and
+    // each route's tables and scratch (indexed as jpeg_slot)
+    CorruptSpec corrupt_pending;
+    CorruptSlot corrupt_slot[3];
     hipEvent_t ev_tab[2] = {nullptr, nullptr};          // the copy of rag_b[k].host has left the host (its next rewrite waits for it)
     const float* kscale_src[2] = {nullptr, nullptr};
     float* kscale_cur[2] = {nullptr, nullptr}; int kscale_i = 0;
@@ -2018,6 +2022,7 @@ bod_status bod_destroy(bod_handle h) {
     for (int k = 0; k < 2; ++k) { if (h->rag_b[k].dev) hipFree(h->rag_b[k].dev); if (h->ev_tab[k]) hipEventDestroy(h->ev_tab[k]); if (h->kscale_cur[k]) hipFree(h->kscale_cur[k]); }
     if (h->copy) { hipStreamSynchronize(h->copy); hipStreamDestroy(h->copy); }
     for (JpegSlot& js : h->jpeg_slot) js.release();
+    for (CorruptSlot& cs : h->corrupt_slot) cs.release();
     for (int k = 0; k < 2; ++k) {
         if (h->d_u8_b[k]) hipFree(h->d_u8_b[k]);
         if (h->ev_img_ready[k]) hipEventDestroy(h->ev_img_ready[k]);
@@ -2270,10 +2275,15 @@ static const float* ragged_factors(bod_handle h, const bod_context::RaggedTable&
     return reinterpret_cast<const float*>(t.dev + (size_t)h->cfg.batch * sizeof(PreprocFrame));
 }
 
+// (a pending corruption is described per frame of a PACKED batch: the uniform uploads refuse it and leave it pending)
+static const char* const CORRUPT_UNIFORM_MSG =
+    "an upload corruption is pending (bod_set_upload_corruption): it applies to the ragged, augmented and JPEG uploads only";
+
 bod_status bod_upload_frames_u8(bod_handle h, const uint8_t* rgb, int32_t src_h, int32_t src_w, const float* rgb_means,
                                 int32_t aspect_resize) {
     MarkerRange mr_api("bod:upload");
     if (!h || !rgb || !rgb_means || src_h < 1 || src_w < 1) return BOD_ERR_INVALID_ARG;
+    if (h->corrupt_pending.n) return h->fail(BOD_ERR_INVALID_ARG, "bod_upload_frames_u8: %s", CORRUPT_UNIFORM_MSG);
     BODCHK(join_overlap(h));
     const bod_config& c = h->cfg;
     HIPCHK(h, hipSetDevice(c.device));
@@ -2406,6 +2416,24 @@ static bod_status jpeg_enqueue(JpegSlot& s, const char* who, uint8_t* rgb_dst, h
     return BOD_OK;
 }
 
+// Frame corruptions: the pending one-shot description of bod_set_upload_corruption in a packed upload.  The host half
+// runs before anything of the upload is enqueued; the device half runs between the frames' arrival and the preprocess kernel and
+// consumes the description.
+static bod_status corrupt_prepare_pending(bod_handle h, const char* who, const int32_t* src_hw, CorruptSlot* slot, hipStream_t stream) {
+    char err[512] = {0};
+    const int st = corrupt_prepare(*slot, who, h->corrupt_pending, src_hw, stream, err, sizeof err);
+    return st == BOD_OK ? BOD_OK : h->fail((bod_status)st, "%s", err);
+}
+static bod_status corrupt_run_pending(bod_handle h, const char* who, CorruptSlot* slot, uint8_t* buf, hipStream_t stream, const uint8_t** result) {
+    char err[512] = {0};
+    uint8_t* out = buf;
+    const int st = corrupt_enqueue(*slot, who, h->corrupt_pending, buf, stream, &out, err, sizeof err);
+    if (st != BOD_OK) return h->fail((bod_status)st, "%s", err);
+    *result = out;
+    h->corrupt_pending = CorruptSpec{};
+    return BOD_OK;
+}
+
 // The synchronous upload of a packed batch: the ragged route (aug == nullptr) or the augmented one, which differ in their table and
 // their kernel only.  js != nullptr: the packed frames come from a decoded JPEG batch (jpeg_host_decode) instead of rgb_packed.
 static bod_status upload_packed(bod_handle h, const char* who, const uint8_t* rgb_packed, const int32_t* src_hw, const float* rgb_means,
@@ -2420,6 +2448,8 @@ static bod_status upload_packed(bod_handle h, const char* who, const uint8_t* rg
     if (aug) BODCHK(augment_table(h, who, src_hw, aspect_resize, aug, &t, &bytes));
     else BODCHK(ragged_table(h, who, src_hw, aspect_resize, &t, &bytes, &with_factors));
     BODCHK(ragged_alloc(h, who, &t));
+    const bool corrupt = h->corrupt_pending.n != 0;
+    if (corrupt) BODCHK(corrupt_prepare_pending(h, who, src_hw, &h->corrupt_slot[2], h->stream));
     if (bytes > h->frames_u8_cap) {
         if (h->d_frames_u8) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(h->d_frames_u8); h->d_frames_u8 = nullptr; h->frames_u8_cap = 0; }
         if (hipMalloc(reinterpret_cast<void**>(&h->d_frames_u8), bytes) != hipSuccess)
@@ -2434,13 +2464,15 @@ static bod_status upload_packed(bod_handle h, const char* who, const uint8_t* rg
     } else {
         HIPCHK(h, hipMemcpyAsync(h->d_frames_u8, rgb_packed, bytes, hipMemcpyHostToDevice, h->stream));
     }
+    const uint8_t* frames_u8 = h->d_frames_u8;
+    if (corrupt) BODCHK(corrupt_run_pending(h, who, &h->corrupt_slot[2], h->d_frames_u8, h->stream, &frames_u8));
     if (aug) {
         PreprocAugArgs a = augment_args(h, t, rgb_means);
-        a.src = h->d_frames_u8; a.dst = h->d_images;
+        a.src = frames_u8; a.dst = h->d_images;
         HIPCHK(h, launch_preprocess_augment(a, h->stream));
     } else {
         PreprocRaggedArgs a = ragged_args(h, t, rgb_means, aspect_resize);
-        a.src = h->d_frames_u8; a.dst = h->d_images;
+        a.src = frames_u8; a.dst = h->d_images;
         HIPCHK(h, launch_preprocess_ragged(a, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));       // the caller may reuse `rgb_packed` on return
@@ -2467,6 +2499,7 @@ bod_status bod_upload_frames_u8_async(bod_handle h, const uint8_t* rgb, int32_t 
     if (buffer < 0 || buffer > 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_upload_frames_u8_async: buffer must be 0 or 1");
     const bod_config& c = h->cfg;
     HIPCHK(h, hipSetDevice(c.device));
+    if (h->corrupt_pending.n) return h->fail(BOD_ERR_INVALID_ARG, "bod_upload_frames_u8_async: %s", CORRUPT_UNIFORM_MSG);
     PreprocArgs a{};
     BODCHK(preproc_geometry(h, src_h, src_w, rgb_means, aspect_resize, &a));
     if (!h->copy) {
@@ -2536,6 +2569,8 @@ static bod_status upload_packed_async(bod_handle h, const char* who, const uint8
             return h->fail(BOD_ERR_OOM, "%s: %zu bytes of staging", who, bytes);
         h->u8_cap_b[buffer] = bytes;
     }
+    const bool corrupt = h->corrupt_pending.n != 0;
+    if (corrupt) BODCHK(corrupt_prepare_pending(h, who, src_hw, &h->corrupt_slot[buffer], h->copy));
     // the frames AND the table of this buffer stay until the forward that reads them has passed its stem (it snapshots the factors
     // in front of ev_img_free: stage_images)
     if (h->img_free_pending[buffer]) { HIPCHK(h, hipStreamWaitEvent(h->copy, h->ev_img_free[buffer], 0)); h->img_free_pending[buffer] = false; }
@@ -2553,13 +2588,16 @@ static bod_status upload_packed_async(bod_handle h, const char* who, const uint8
     } else {
         HIPCHK(h, hipMemcpyAsync(h->d_u8_b[buffer], rgb_packed, bytes, hipMemcpyHostToDevice, h->copy));
     }
+    // (the corruption's scratch, like the staging, is touched on the copy stream alone: the preprocess kernel behind it is its last reader)
+    const uint8_t* frames_u8 = h->d_u8_b[buffer];
+    if (corrupt) BODCHK(corrupt_run_pending(h, who, &h->corrupt_slot[buffer], h->d_u8_b[buffer], h->copy, &frames_u8));
     if (aug) {
         PreprocAugArgs a = augment_args(h, t, rgb_means);
-        a.src = h->d_u8_b[buffer]; a.dst = h->d_images_b[buffer];
+        a.src = frames_u8; a.dst = h->d_images_b[buffer];
         HIPCHK(h, launch_preprocess_augment(a, h->copy));
     } else {
         PreprocRaggedArgs a = ragged_args(h, t, rgb_means, aspect_resize);
-        a.src = h->d_u8_b[buffer]; a.dst = h->d_images_b[buffer];
+        a.src = frames_u8; a.dst = h->d_images_b[buffer];
         HIPCHK(h, launch_preprocess_ragged(a, h->copy));
     }
     HIPCHK(h, hipEventRecord(h->ev_img_ready[buffer], h->copy));
@@ -3843,6 +3881,55 @@ bod_status bod_score_pairs(int32_t device, int64_t n, const double* means, const
     return pdq_call(device, [&](hipStream_t s, char* err, size_t cap) {
         return score_pairs_run(n, means, covs, targets, num_samples, seed, first_row_id, out, status, s, err, cap);
     });
+}
+
+// The corruption stage alone (bayesod.h): packed frames in, packed frames out.  Stateless; its buffers live for the call.
+bod_status bod_corrupt_frames_u8(int32_t device, int32_t n, const uint8_t* rgb_packed_in, const int32_t* src_hw, const bod_corrupt_op* ops,
+                                 int32_t ops_per_frame, const uint32_t* frame_ids, const uint16_t* taps, int32_t n_taps, const uint8_t* luts,
+                                 int32_t n_luts, const uint16_t* qtables, int32_t n_qtables, uint64_t seed, uint8_t* rgb_packed_out) {
+    static const char* who = "bod_corrupt_frames_u8";
+    if (n < 1 || !rgb_packed_in || !src_hw || !ops || !rgb_packed_out) { g_create_error = std::string(who) + ": NULL argument or no frame"; return BOD_ERR_INVALID_ARG; }
+    CorruptSpec spec;
+    {
+        char err[512] = {0};
+        const int st = corrupt_spec_make(who, n, ops, ops_per_frame, frame_ids, taps, n_taps, luts, n_luts, qtables, n_qtables, seed, &spec, err, sizeof err);
+        if (st != BOD_OK) { g_create_error = err; return (bod_status)st; }
+    }
+    return pdq_call(device, [&](hipStream_t s, char* err, size_t cap) -> int {
+        CorruptSlot slot;
+        uint8_t* d_rgb = nullptr;
+        uint8_t* d_out = nullptr;
+        int st = corrupt_prepare(slot, who, spec, src_hw, s, err, cap);
+        if (st == BOD_OK && hipMalloc(reinterpret_cast<void**>(&d_rgb), slot.frame_bytes) != hipSuccess) {
+            d_rgb = nullptr; snprintf(err, cap, "%s: out of device memory for the frames", who); st = BOD_ERR_OOM;
+        }
+        if (st == BOD_OK && hipMemcpyAsync(d_rgb, rgb_packed_in, slot.frame_bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
+            snprintf(err, cap, "%s: copying the frames in failed", who); st = BOD_ERR_HIP;
+        }
+        if (st == BOD_OK) st = corrupt_enqueue(slot, who, spec, d_rgb, s, &d_out, err, cap);
+        if (st == BOD_OK && (hipMemcpyAsync(rgb_packed_out, d_out, slot.frame_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                             hipStreamSynchronize(s) != hipSuccess)) {
+            snprintf(err, cap, "%s: copying the frames back failed: %s", who, hipGetErrorString(hipGetLastError())); st = BOD_ERR_HIP;
+        }
+        hipStreamSynchronize(s);
+        if (d_rgb) hipFree(d_rgb);
+        slot.release();
+        return st;
+    });
+}
+
+bod_status bod_set_upload_corruption(bod_handle h, const bod_corrupt_op* ops, int32_t ops_per_frame, const uint32_t* frame_ids,
+                                     const uint16_t* taps, int32_t n_taps, const uint8_t* luts, int32_t n_luts, const uint16_t* qtables,
+                                     int32_t n_qtables, uint64_t seed) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    if (!ops) { h->corrupt_pending = CorruptSpec{}; return BOD_OK; }
+    CorruptSpec spec;
+    char err[512] = {0};
+    const int st = corrupt_spec_make("bod_set_upload_corruption", h->cfg.batch, ops, ops_per_frame, frame_ids, taps, n_taps, luts, n_luts, qtables,
+                                     n_qtables, seed, &spec, err, sizeof err);
+    if (st != BOD_OK) return h->fail((bod_status)st, "%s", err);
+    h->corrupt_pending = std::move(spec);
+    return BOD_OK;
 }
 
 // The decoder alone (bayesod.h): n files -> packed RGB on the host.  Stateless; its buffers live for the call.

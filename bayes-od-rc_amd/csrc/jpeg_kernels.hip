@@ -5,6 +5,7 @@
 // Integer arithmetic only; bit-equal to libjpeg(-turbo)'s default decode for encoder-made streams.  All addressing comes from the
 // host-validated JpegFrame table: no address depends on a coefficient or a sample, so a hostile stream cannot move an access.
 // Products and sums are formed in uint32 (two's complement, wrap-around defined) and read back as int32.
+#include "jpeg_dct.h"
 #include "kernels.h"
 
 namespace {
@@ -12,26 +13,6 @@ namespace {
 constexpr int IDCT_THREADS = 256;                 // 8 lanes per block: 32 blocks per workgroup, 8 per wave
 constexpr int IDCT_PITCH = 9;                     // int32 per row of a block's LDS tile (8 + 1: the column reads spread over the banks)
 constexpr int COLOR_THREADS = 256;                // one thread per 4 horizontally adjacent pixels
-
-__device__ __forceinline__ int32_t descale(uint32_t x, int s) { return (int32_t)(x + (1u << (s - 1))) >> s; }
-
-// jidctint.c's 1-D transform (CONST_BITS = 13) on x[0..7] in place, without the descale.
-__device__ __forceinline__ void idct_1d(uint32_t x[8]) {
-    uint32_t z1 = (x[2] + x[6]) * 4433u;
-    const uint32_t t2 = z1 - x[6] * 15137u, t3 = z1 + x[2] * 6270u;
-    const uint32_t t0 = (x[0] + x[4]) << 13, t1 = (x[0] - x[4]) << 13;
-    const uint32_t t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    uint32_t a = x[7], b = x[5], c = x[3], d = x[1];
-    z1 = a + d;
-    uint32_t z2 = b + c, z3 = a + c, z4 = b + d;
-    const uint32_t z5 = (z3 + z4) * 9633u;
-    a *= 2446u; b *= 16819u; c *= 25172u; d *= 12299u;
-    z1 *= (uint32_t)-7373; z2 *= (uint32_t)-20995;
-    z3 = z3 * (uint32_t)-16069 + z5; z4 = z4 * (uint32_t)-3196 + z5;
-    a += z1 + z3; b += z2 + z4; c += z2 + z3; d += z1 + z4;
-    x[0] = t10 + d; x[1] = t11 + c; x[2] = t12 + b; x[3] = t13 + a;
-    x[4] = t13 - a; x[5] = t12 - b; x[6] = t11 - c; x[7] = t10 - d;
-}
 
 __global__ __launch_bounds__(IDCT_THREADS) void jpeg_idct_kernel(JpegArgs a) {
     __shared__ int32_t tile[IDCT_THREADS / 8][8 * IDCT_PITCH];
@@ -67,22 +48,22 @@ __global__ __launch_bounds__(IDCT_THREADS) void jpeg_idct_kernel(JpegArgs a) {
     if (live) {                                   // pass 1: column t
 #pragma unroll
         for (int r = 0; r < 8; ++r) x[r] = (uint32_t)ws[r * IDCT_PITCH + t];
-        idct_1d(x);
+        jpeg_idct_1d(x);
     }
     __syncthreads();
     if (live) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) ws[r * IDCT_PITCH + t] = descale(x[r], 11);
+        for (int r = 0; r < 8; ++r) ws[r * IDCT_PITCH + t] = jpeg_descale(x[r], 11);
     }
     __syncthreads();
     if (live) {                                   // pass 2: row t
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = (uint32_t)ws[t * IDCT_PITCH + j];
-        idct_1d(x);
+        jpeg_idct_1d(x);
         uint32_t w[2] = {0, 0};
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int32_t v = min(max(descale(x[j], 18) + 128, 0), 255);
+            const int32_t v = min(max(jpeg_descale(x[j], 18) + 128, 0), 255);
             w[j >> 2] |= (uint32_t)v << (8 * (j & 3));
         }
         *reinterpret_cast<uint2*>(out) = make_uint2(w[0], w[1]);
@@ -152,11 +133,7 @@ __global__ __launch_bounds__(COLOR_THREADS) void jpeg_color_kernel(JpegArgs a) {
     for (int k = 0; k < 4; ++k) {                 // (pixels past the frame's edge are computed from in-plane samples and not stored)
         const int Y = (int)(y4 >> (8 * k) & 255), cb = cb4[k] - 128, cr = cr4[k] - 128;
         int R = Y, G = Y, B = Y;
-        if (color) {
-            R = min(max(Y + ((91881 * cr + 32768) >> 16), 0), 255);
-            B = min(max(Y + ((116130 * cb + 32768) >> 16), 0), 255);
-            G = min(max(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16), 0), 255);
-        }
+        if (color) jpeg_ycc_to_rgb(Y, cb, cr, R, G, B);
         px[3 * k] = (uint8_t)R; px[3 * k + 1] = (uint8_t)G; px[3 * k + 2] = (uint8_t)B;
     }
     uint8_t* dst = a.rgb + fr.rgb_off + ((int64_t)y * W + x0) * 3;

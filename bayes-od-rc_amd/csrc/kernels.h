@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
+#include "../../include/bayesod.h"
 #include "plan_tables.h"
 #include "sparse_tables.h"
 
@@ -581,3 +583,38 @@ int pdq_frames_run(int H, int W, int F, const int32_t* num_gt, const int32_t* gt
 // Scoring rules (score_kernels.hip): host driver of bod_score_pairs, same conventions; rows are staged in internal batches.
 int score_pairs_run(long long n, const double* means, const double* covs, const double* targets, int num_samples, unsigned long long seed,
                     unsigned long long first_row_id, double* out, int32_t* status, hipStream_t s, char* errbuf, size_t errcap);
+
+// ------------------------------------------------------------------------------------------------
+// Frame corruptions (corrupt_kernels.hip): op chains on the packed uint8 RGB frames, between the copy (or the JPEG
+// colour kernel) and the preprocess kernels.  The functions return a bod_status value; on failure errbuf holds the message.
+// ------------------------------------------------------------------------------------------------
+struct CorruptSpec {                       // a validated description, copied from the caller: n == 0 means none
+    int32_t n = 0, ops_per_frame = 0;
+    std::vector<bod_corrupt_op> ops;       // [n][ops_per_frame]
+    std::vector<uint32_t> frame_ids;       // [n]
+    std::vector<uint16_t> taps;
+    std::vector<uint8_t> luts;             // [..][3][256]
+    std::vector<uint16_t> qtables;         // [..][2][64]
+    uint64_t seed = 0;
+};
+int corrupt_spec_make(const char* who, int32_t n, const bod_corrupt_op* ops, int32_t ops_per_frame, const uint32_t* frame_ids,
+                      const uint16_t* taps, int32_t n_taps, const uint8_t* luts, int32_t n_luts, const uint16_t* qtables,
+                      int32_t n_qtables, uint64_t seed, CorruptSpec* out, char* errbuf, size_t errcap);
+struct CorruptSlot {                       // one route's device side: record / table blob, ping-pong scratch, both grow on demand
+    std::vector<char> host;
+    char* dev = nullptr; size_t dev_cap = 0;
+    uint8_t* scratch = nullptr; size_t scratch_cap = 0;
+    hipEvent_t copied = nullptr;           // the copy of `host` has left the host (its next rewrite waits for it)
+    size_t sums_off = 0, sums_bytes = 0, taps_off = 0, luts_off = 0, q_off = 0, frame_bytes = 0;
+    int32_t wgs[4][4] = {};                // per op slot: workgroups per frame of the pointwise, conv, pixelate and JPEG kernels
+    uint32_t kinds[4] = {};                // per op slot: bit k set when a frame runs kind k there
+    void release();
+};
+// Host half: lays the batch out for src_hw[n][2], rewrites slot.host and grows the device buffers (synchronising `stream` first when
+// it has to free one).  Nothing is enqueued.
+int corrupt_prepare(CorruptSlot& slot, const char* who, const CorruptSpec& spec, const int32_t* src_hw, hipStream_t stream,
+                    char* errbuf, size_t errcap);
+// Device half, after corrupt_prepare: the frames at `buf` run through their chains on `stream`; *result is where they end up
+// (`buf` after an even number of op slots, slot.scratch after an odd one).
+int corrupt_enqueue(CorruptSlot& slot, const char* who, const CorruptSpec& spec, uint8_t* buf, hipStream_t stream, uint8_t** result,
+                    char* errbuf, size_t errcap);

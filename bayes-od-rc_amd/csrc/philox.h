@@ -76,3 +76,6 @@ BOD_HD DropPair dropout_run_windows(const Philox4& r, int u) {
 #define BOD_SCORE_TAG 0x005C04E5u
 // energy-score TRAINING normals (loss_kernels.hip, proper_losses.py): counter = (sample, anchor, BOD_LOSS_TAG, image id)
 #define BOD_LOSS_TAG 0x0010555Eu
+// frame corruptions (corrupt_kernels.hip, corruptions.py): counter = (x, y, BOD_CORRUPT_TAG | op slot, frame id) for a pixel,
+// (ix, iy, BOD_CORRUPT_TAG | op slot | octave << 4, frame id) for a lattice point of the fog field (octaves 2..7)
+#define BOD_CORRUPT_TAG 0x00C02200u

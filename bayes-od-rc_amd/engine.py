@@ -246,6 +246,20 @@ class Engine(object):
         done when this returns: ``files`` need not be kept."""
         return self._jpeg_upload(files, means, aspect_resize, aug, threads, int(buffer))
 
+    def set_upload_corruption(self, chains, frame_ids=None, seed=0, ops_arrays=None):
+        """Corrupt the frames of the NEXT packed upload on the device (``bod_set_upload_corruption``): ``chains``
+        is one ``corruptions.Chain`` for the whole batch or a list of one per frame, ``frame_ids`` [batch] the ids the random ops
+        key their numbers on (default 0, 1, ..).  One-shot: the next ``upload_frames_u8_ragged[_async]``,
+        ``upload_frames_u8_augmented[_async]`` or ``upload_frames_jpeg[_async]`` consumes it; the image buffer ends up bit for bit
+        as after the upload of ``corrupt_frames(...)``'s output.  ``None`` clears a pending one; ``ops_arrays`` gives
+        already packed (ops, taps, luts, qtables) arrays instead of chains.  A uniform ``upload_frames_u8``
+        with one pending raises ``ValueError`` and leaves it pending."""
+        if chains is None and ops_arrays is None:
+            self._chk(self.lib.bod_set_upload_corruption(self.h, None, 0, None, None, 0, None, 0, None, 0, 0))
+            return
+        args, _keep = _corruption_args(chains, self.B, frame_ids, ops_arrays)
+        self._chk(self.lib.bod_set_upload_corruption(self.h, *args, int(seed) & 0xFFFFFFFFFFFFFFFF))
+
     def _device_images(self, image_buffer):
         ptr = self.lib.bod_device_images(self.h) if image_buffer is None else self.lib.bod_device_images_buffer(self.h, int(image_buffer))
         if not ptr:
@@ -1290,6 +1304,50 @@ def decode_jpeg_rgb(files, device=0, threads=None):
         out.append(rgb[off:off + 3 * h * w].reshape(h, w, 3))
         off += 3 * h * w
     return out
+
+
+def _corruption_args(chains, n, frame_ids, ops_arrays=None):
+    """(ops, ops_per_frame, frame_ids, taps, n_taps, luts, n_luts, qtables, n_qtables) as the corruption entry points take them,
+    and the arrays that must outlive the call.  ``ops_arrays``: already packed (ops [n,P], taps, luts, qtables) instead of chains."""
+    from . import corruptions
+    ops, taps, luts, qts = corruptions.pack(chains, n) if ops_arrays is None else ops_arrays
+    ops = np.ascontiguousarray(ops, corruptions.OP_DTYPE)
+    taps = np.ascontiguousarray(taps, np.uint16).reshape(-1)
+    luts = np.ascontiguousarray(luts, np.uint8).reshape(-1, 3, 256)
+    qts = np.ascontiguousarray(qts, np.uint16).reshape(-1, 2, 64)
+    if ops.ndim != 2 or ops.shape[0] != n:
+        raise ValueError("expected ops of shape (%d, ops_per_frame), got %s" % (n, ops.shape))
+    ids = None
+    if frame_ids is not None:
+        ids = np.ascontiguousarray(np.asarray(frame_ids, np.int64) & 0xFFFFFFFF, np.uint32).reshape(-1)
+        if ids.size != n:
+            raise ValueError("expected %d frame ids, got %d" % (n, ids.size))
+    args = (ops.ctypes.data_as(C.POINTER(_lib.BodCorruptOp)), int(ops.shape[1]),
+            None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_uint32)),
+            taps.ctypes.data_as(C.POINTER(C.c_uint16)) if taps.size else None, int(taps.size),
+            luts.ctypes.data_as(C.POINTER(C.c_uint8)) if luts.size else None, int(luts.shape[0]),
+            qts.ctypes.data_as(C.POINTER(C.c_uint16)) if qts.size else None, int(qts.shape[0]))
+    return args, (ops, ids, taps, luts, qts)
+
+
+def corrupt_frames(frames, chains, frame_ids=None, seed=0, device=0, ops_arrays=None):
+    """The corruption stage alone (``bod_corrupt_frames_u8``): ``frames`` is a list of uint8 [h,w,3] arrays of
+    any sizes, ``chains`` one ``corruptions.Chain`` for all of them or a list of one per frame, ``frame_ids`` the ids the random
+    ops key their numbers on (default 0, 1, ..).  Returns the corrupted frames as a list of uint8 [h,w,3] arrays.  A frame's result
+    depends on its bytes, its chain, its id and the seed alone."""
+    lib = _lib.load()
+    buf, sizes = pack_ragged(frames)
+    n = sizes.shape[0]
+    args, _keep = _corruption_args(chains, n, frame_ids, ops_arrays)
+    out = np.empty_like(buf)
+    st = lib.bod_corrupt_frames_u8(int(device), n, buf.ctypes.data_as(C.POINTER(C.c_uint8)), iptr(sizes), *args,
+                                   int(seed) & 0xFFFFFFFFFFFFFFFF, out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    _lib.check(lib, None, st)
+    res, off = [], 0
+    for h, w in sizes:
+        res.append(out[off:off + 3 * h * w].reshape(h, w, 3))
+        off += 3 * h * w
+    return res
 
 
 def score_pairs(means, covs, targets, num_samples=1000, seed=0, first_row_id=0, device=0):

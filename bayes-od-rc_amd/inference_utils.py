@@ -207,11 +207,14 @@ class BayesOdPipeline(object):
         self.engine = self.model.engine_for(self._hw, batch=self._batch, mc_samples=self.model.mc_dropout_samples, **self._kw)
         return self.engine
 
-    def upload_mixed(self, frames, means, aspect_resize=True):
+    def upload_mixed(self, frames, means, aspect_resize=True, corruption=None):
         """``batch`` uint8 frames of mixed source sizes into the engine, for ``__call__(None, ...)``: every frame is rescaled by
-        its own S = orig / net (inference_utils.py:147-167 takes it per sample), so no ``bind(orig_size=...)`` per size."""
+        its own S = orig / net (inference_utils.py:147-167 takes it per sample), so no ``bind(orig_size=...)`` per size.
+        ``corruption``: (chain, frame ids, seed) -- the frames are corrupted on the device on their way in."""
         self.bind()
         from . import datasets
+        if corruption is not None:
+            self.engine.set_upload_corruption(corruption[0], frame_ids=corruption[1], seed=corruption[2])
         datasets.upload_frames(self.engine, frames, means, aspect_resize=aspect_resize)     # (--device_jpeg: frames may be JPEG files)
 
     def __call__(self, images=None, seed=0, first_image_id=0):
@@ -295,8 +298,10 @@ class EnsemblePipeline(object):
                 eng.update_config(self._config(m, first=i == 0))
         return self.engine
 
-    def upload_mixed(self, frames, means, aspect_resize=True):
+    def upload_mixed(self, frames, means, aspect_resize=True, corruption=None):
         from . import datasets
+        if corruption is not None:
+            self.engine.set_upload_corruption(corruption[0], frame_ids=corruption[1], seed=corruption[2])
         datasets.upload_frames(self.engine, frames, means, aspect_resize=aspect_resize)
 
     def __call__(self, images=None, seed=0, first_image_id=0):

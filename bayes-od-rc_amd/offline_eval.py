@@ -18,6 +18,12 @@ The reference scripts hard-code their paths and print a table; here the same com
 ``scores`` reports proper scoring rules and calibration of the predictive distributions (scoring_rules.py: NLL, energy
 score, PIT calibration error, the covariance scale that minimises the NLL, classification NLL / Brier / ECE).
 
+    python -m bayes_od_rc_amd.offline_eval shift --labels val.json --predictions clean=<tree> fog3=<tree> [..] [--gpu-device N] [--json]
+
+``shift`` runs the ``scores`` computation on every named tree -- a clean run and runs under ``run_inference --corrupt
+NAME:SEVERITY`` -- and prints one table: every scalar ``scores`` metric per name and its difference to the
+first name's.
+
 ``--predictions`` is the directory holding ``data/ mean/ cov/ cat_param/`` (run_inference.py:90-115); labels are
 BDD-format records ``{name, category, bbox: [x1, y1, x2, y2]}`` or, for KITTI, the label_2 text files (converted to the
 same records by ``kitti_records``).  Host NumPy like the reference.
@@ -226,13 +232,64 @@ def pdq_report(gt_records, tree, frames, img_shape, categories=BDD_CATEGORIES, c
     return out
 
 
+def _scalar_metrics(report, prefix=''):
+    """The report's numbers as a flat {name: value} (nested dicts joined with '.'; lists such as histograms left out)."""
+    flat = {}
+    for k, v in report.items():
+        if isinstance(v, dict):
+            flat.update(_scalar_metrics(v, prefix + k + '.'))
+        elif v is None or (isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)):
+            flat[prefix + k] = None if v is None else float(v)
+    return flat
+
+
+def shift_report(gt_records, trees, **score_kw):
+    """The ``scores`` report of every (name, tree) of ``trees`` -- the same labels, say a clean run and runs under
+    ``run_inference --corrupt`` -- and every scalar metric's difference to the first name's.  Returns {'names', 'reports': {name:
+    scores report}, 'metrics': {name: {metric: value}}, 'delta': {name: {metric: value - first name's, None where either is}}}."""
+    from . import scoring_rules                       # (imports this module)
+    trees = list(trees)
+    if not trees:
+        raise ValueError('shift needs at least one NAME=TREE')
+    names = [n for n, _ in trees]
+    if len(set(names)) != len(names):
+        raise ValueError('shift: the names must differ: %s' % ', '.join(names))
+    reports, metrics = {}, {}
+    for name, tree in trees:
+        frames = sorted(f[:-4] for f in os.listdir(os.path.join(tree, 'mean')) if f.endswith('.npy'))
+        reports[name] = scoring_rules.scores_report(gt_records, tree, frames, **score_kw)
+        metrics[name] = _scalar_metrics(reports[name])
+    base = metrics[names[0]]
+    delta = {n: {k: (None if v is None or base.get(k) is None else v - base[k]) for k, v in metrics[n].items()} for n in names}
+    return {'names': names, 'reports': reports, 'metrics': metrics, 'delta': delta}
+
+
+def format_shift_table(out):
+    """One row per name and metric column pair: the value, and its difference to the first name's in brackets."""
+    names = out['names']
+    keys = [k for k in out['metrics'][names[0]]]
+    width = max(len(k) for k in keys + ['metric'])
+    lines = ['%-*s  %s' % (width, 'metric', '  '.join('%24s' % n[:24] for n in names))]
+
+    def cell(name, k):
+        v, d = out['metrics'][name].get(k), out['delta'][name].get(k)
+        if v is None:
+            return '%24s' % '-'
+        return '%24s' % ('%.6g' % v if name == names[0] or d is None else '%.6g (%+.4g)' % (v, d))
+    for k in keys:
+        lines.append('%-*s  %s' % (width, k, '  '.join(cell(n, k) for n in names)))
+    return '\n'.join(lines)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('metric', choices=('ap', 'mue', 'pdq', 'scores'))
+    ap.add_argument('metric', choices=('ap', 'mue', 'pdq', 'scores', 'shift'))
     ap.add_argument('--labels', required=True, help='BDD-format ground-truth json, or (with --dataset kitti) the label_2 directory')
     ap.add_argument('--dataset', default='bdd', choices=('bdd', 'kitti'))
     ap.add_argument('--difficulty', default='all', choices=('easy', 'moderate', 'hard', 'all'))
-    ap.add_argument('--predictions', required=True, help='directory with data/ mean/ cov/ cat_param/')
+    ap.add_argument('--predictions', required=True, nargs='+', metavar='TREE', help='directory with data/ mean/ cov/ cat_param/; '
+                    'shift: NAME=TREE [NAME=TREE ...], the first one being the reference (the clean run)')
+    ap.add_argument('--json', action='store_true', help='shift: print the whole result as JSON after the table')
     ap.add_argument('--entropy', default='gaussian', choices=('gaussian', 'categorical'))
     ap.add_argument('--compute-method', default='Categorical', choices=('Categorical', 'All'))
     ap.add_argument('--image-size', type=int, nargs=2, default=(720, 1280), metavar=('H', 'W'))
@@ -244,6 +301,29 @@ def main(argv=None):
     ap.add_argument('--score-threshold', type=float, default=0.5445, metavar='T', help='scores: lowest best-class score of a detection')
     ap.add_argument('--parts', action='store_true', help='scores: also score the epistemic / aleatoric covariance parts')
     args = ap.parse_args(argv)
+    if args.metric == 'shift':
+        if args.dataset == 'kitti':
+            raise SystemExit('shift --dataset kitti: convert the labels to records with kitti_records() and call shift_report()')
+        trees = []
+        for item in args.predictions:
+            name, sep, tree = item.partition('=')
+            if not sep or not name or not tree:
+                ap.error('shift: --predictions takes NAME=TREE, got %r' % item)
+            trees.append((name, tree))
+        with open(args.labels) as fp:
+            gt = json.load(fp)
+        try:
+            out = shift_report(gt, trees, score_threshold=args.score_threshold, cov_scale=args.cov_scale, num_samples=args.samples,
+                               seed=args.seed, device=args.gpu_device, parts=args.parts)
+        except ValueError as e:
+            ap.error(str(e))
+        print(format_shift_table(out))
+        if args.json:
+            print(json.dumps(out, indent=1))
+        return out
+    if len(args.predictions) != 1:
+        ap.error('%s takes one --predictions directory' % args.metric)
+    args.predictions = args.predictions[0]
     if args.dataset == 'kitti':
         if args.metric == 'ap':
             out = ap_report(*kitti_records(args.labels, args.predictions, args.difficulty))

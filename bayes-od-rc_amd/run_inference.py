@@ -151,7 +151,9 @@ def _test_model_on_dataset(config, args, model):
     pipes = {}
     pending = []
     device_jpeg = bool(getattr(args, 'device_jpeg', False))
-    mixed = bool(getattr(args, 'mixed_sizes', False)) or device_jpeg          # --device_jpeg forms its batches as --mixed_sizes does
+    corrupt = _corruption(args)              # --corrupt NAME:SEVERITY: frames are corrupted on the device at upload
+    # --device_jpeg and --corrupt form their batches as --mixed_sizes does
+    mixed = bool(getattr(args, 'mixed_sizes', False)) or device_jpeg or corrupt is not None
     handler.defer_decode = device_jpeg       # JPEG files travel as bytes and are decoded on the device at upload
 
     def emit(dets):
@@ -177,7 +179,10 @@ def _test_model_on_dataset(config, args, model):
                 use_full_covar=test_config['use_full_covar'], dataset_name=test_dataset, orig_size=hw,
                 anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class)
         pipe = pipes[key]
-        pipe.upload_mixed([p[1] for p in pending], constants.MEANS_DICT[handler.im_normalization], aspect_resize=kitti)
+        # (a frame's corruption is keyed on its dataset index: the same whatever batch or run it falls into)
+        corruption = None if corrupt is None else (corrupt[0], [p[2] for p in pending], corrupt[1])
+        pipe.upload_mixed([p[1] for p in pending], constants.MEANS_DICT[handler.im_normalization], aspect_resize=kitti,
+                          corruption=corruption)
         emit(pipe(None, seed=args.seed, first_image_id=pending[0][2]))
 
     def flush():
@@ -213,6 +218,15 @@ def _test_model_on_dataset(config, args, model):
     return writer.root
 
 
+def _corruption(args):
+    """--corrupt NAME:SEVERITY [--corrupt_seed S] -> (chain, seed), or None."""
+    spec = getattr(args, 'corrupt', None)
+    if not spec:
+        return None
+    from . import corruptions
+    return corruptions.make(*corruptions.parse(spec)), int(getattr(args, 'corrupt_seed', 0) or 0)
+
+
 def main(argv=None):
     here = os.path.dirname(os.path.abspath(__file__))
     ap = argparse.ArgumentParser()
@@ -245,7 +259,21 @@ def main(argv=None):
                     '(class_entropy/<frame>.npy [K,4]: total, aleatoric, epistemic_mc, epistemic_spatial; the last three sum to the '
                     'first) beside cov/; works with --ensemble, --mc_passes, --tta_flip and --covariance_parts; yaml key: '
                     'testing_config.class_uncertainty')
+    ap.add_argument('--corrupt', type=str, default=None, metavar='NAME:SEVERITY', help='with --dataset: corrupt every frame on the '
+                    'GPU before preprocessing, to score uncertainty under dataset shift (gaussian_noise, impulse_noise, defocus_blur, '
+                    'motion_blur, gaussian_blur, pixelate, jpeg_compression, contrast, brightness, low_light, fog; severity 1..5); '
+                    'batches as under --mixed_sizes; works with --device_jpeg, --ensemble, --tta_flip and the parts flags')
+    ap.add_argument('--corrupt_seed', type=int, default=0, help='seed of the random corruptions; a frame\'s noise depends on it and '
+                    'on the frame\'s dataset index alone')
     args = ap.parse_args(argv)
+    if args.corrupt:
+        if not args.dataset:
+            ap.error('--corrupt requires --dataset')
+        from . import corruptions
+        try:
+            corruptions.parse(args.corrupt)
+        except ValueError as e:
+            ap.error('--corrupt: %s' % e)
     config = config_utils.load_yaml(args.yaml_path)
     config = config_utils.setup(config, args)
     if args.device_jpeg and not args.dataset:

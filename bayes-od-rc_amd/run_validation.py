@@ -85,7 +85,7 @@ def flush_buckets(carry, batch):
             rest = rest[batch:]
 
 
-def validate_batch(model, config, batch, mixed_sizes=False):
+def validate_batch(model, config, batch, mixed_sizes=False, corruption=None):
     """``len(batch)`` ground-truth-only samples of one source size (``mixed_sizes``: of any sizes, uploaded ragged) through
     ``Engine.validate_boxes`` on a handle of that batch size.  Returns per frame ``(total_loss, loss_dict, class rows [K,C], corners [K,4])``: the values ``val_single_step`` +
     ``post_process_predictions`` give for the frame alone, plus the regularisation term (run_validation.py:252-258)."""
@@ -101,6 +101,10 @@ def validate_batch(model, config, batch, mixed_sizes=False):
     eng = model.engine_for(hw, batch=len(batch), mc_samples=1, nms_config=VALIDATION_NMS)
     if not eng._anchors_set:
         eng.set_anchors(np.asarray(batch[0][constants.ANCHORS_KEY], np.float32))
+    if corruption is not None:              # (chain, frame ids, seed): the next packed upload corrupts the frames
+        if not (deferred or (mixed_sizes and 'image_uint8' in batch[0])):
+            raise ValueError('a corruption needs the packed upload of uint8 frames (the --dataset route with mixed sizes)')
+        eng.set_upload_corruption(corruption[0], frame_ids=corruption[1], seed=corruption[2])
     if deferred:
         from . import datasets
         means = constants.MEANS_DICT[dataset_config.get('im_normalization', 'ImageNet')]
@@ -175,7 +179,7 @@ def _validate_batched(model, config, samples, sample_ids, out_dir, categories, b
     return records, [totals[i] for i in sorted(totals)], sums, ndet
 
 
-def _validate_mixed(model, config, samples, sample_ids, out_dir, categories, batch):
+def _validate_mixed(model, config, samples, sample_ids, out_dir, categories, batch, corruption=None):
     """``--mixed_sizes``: the batched route without buckets -- one pass in dataset order, ``batch`` frames of whatever source
     sizes per call, one tail batch.  Same return value as ``_validate_batched``."""
     dataset = config['dataset_config']['dataset']
@@ -186,7 +190,8 @@ def _validate_mixed(model, config, samples, sample_ids, out_dir, categories, bat
         if not frames:
             break
         first = len(totals)
-        for j, (total, loss_dict, classes, corners) in enumerate(validate_batch(model, config, frames, mixed_sizes=True)):
+        kw = {} if corruption is None else {'corruption': (corruption[0], list(range(first, first + len(frames))), corruption[1])}
+        for j, (total, loss_dict, classes, corners) in enumerate(validate_batch(model, config, frames, mixed_sizes=True, **kw)):
             totals.append(float(total))
             for k, v in loss_dict.items():
                 sums[k] = sums.get(k, 0.0) + float(v)
@@ -226,7 +231,8 @@ def _put_back(head, rest):
     yield from rest
 
 
-def validate_checkpoint(config, checkpoint_path, samples, sample_ids, predictions_dir, categories=None, batch=8, mixed_sizes=False):
+def validate_checkpoint(config, checkpoint_path, samples, sample_ids, predictions_dir, categories=None, batch=8, mixed_sizes=False,
+                        corruption=None):
     """One checkpoint over the validation frames.  Returns {'ckpt_id', 'mean_total_loss', 'mean_losses', 'num_frames',
     'num_detections', 'predictions'} ('predictions' = the BDD records, or None for KITTI).  ``samples``: an iterable of
     sample dicts, or a callable that returns one (a streamed split is read once per checkpoint).  Samples without dense
@@ -241,7 +247,10 @@ def validate_checkpoint(config, checkpoint_path, samples, sample_ids, prediction
     head = list(itertools.islice(stream, 1))
     batched = bool(head) and constants.ANCHORS_CLASS_TARGETS_KEY not in head[0]        # the test Trainer.train_single_step uses
     route = (_validate_mixed if mixed_sizes else _validate_batched) if batched else _validate_per_frame
-    records, totals, sums, ndet = route(model, config, _put_back(head, stream), sample_ids, out_dir, categories, int(batch))
+    if corruption is not None and route is not _validate_mixed:
+        raise ValueError('a corruption (chain, seed) needs mixed_sizes and samples without dense targets')
+    kw = {} if corruption is None else {'corruption': corruption}
+    records, totals, sums, ndet = route(model, config, _put_back(head, stream), sample_ids, out_dir, categories, int(batch), **kw)
     if dataset != 'kitti':
         with open(os.path.join(out_dir, 'predictions.json'), 'w') as fp:
             json.dump(records, fp, indent=4, separators=(',', ': '))
@@ -261,7 +270,7 @@ def list_checkpoints(checkpoint_dir):
 
 
 def validate(config, samples, sample_ids, categories=None, gt_records=None, poll_seconds=None, max_polls=None, batch=8,
-             mixed_sizes=False):
+             mixed_sizes=False, corruption=None):
     """The loop of run_validation.py:86-228: every checkpoint not yet listed in evaluated_ckpts.txt, in id order; with
     ``poll_seconds`` keep waiting for new ones (``max_polls`` bounds the waiting, for tests).  ``samples`` / ``batch`` / ``mixed_sizes``: see
     ``validate_checkpoint``."""
@@ -278,7 +287,8 @@ def validate(config, samples, sample_ids, categories=None, gt_records=None, poll
             if ckpt_id in done or ckpt_id <= last_id:
                 continue
             print('\nRunning checkpoint ' + str(ckpt_id) + '\n')
-            r = validate_checkpoint(config, path, samples, sample_ids, predictions_dir, categories, batch=batch, mixed_sizes=mixed_sizes)
+            kw = {} if corruption is None else {'corruption': corruption}      # (chain, seed): frames keyed on their dataset index
+            r = validate_checkpoint(config, path, samples, sample_ids, predictions_dir, categories, batch=batch, mixed_sizes=mixed_sizes, **kw)
             if gt_records is not None and r['predictions'] is not None:
                 from .offline_eval import ap_report
                 r['ap'] = ap_report(gt_records, r['predictions']) if r['predictions'] else None
@@ -311,9 +321,22 @@ def main(argv=None):
     ap.add_argument('--device_jpeg', action='store_true', help='with --dataset: baseline JPEG files are decoded inside the library '
                     '(Huffman decoding on host threads, the rest on the GPU) instead of by PIL; batches as under --mixed_sizes; a batch '
                     'with any other file in it takes the PIL route; the results are identical either way')
+    ap.add_argument('--corrupt', type=str, default=None, metavar='NAME:SEVERITY', help='with --dataset: corrupt every frame on the '
+                    'GPU before preprocessing (run_inference --help lists the names; severity 1..5); batches as under --mixed_sizes')
+    ap.add_argument('--corrupt_seed', type=int, default=0, help='seed of the random corruptions (a frame\'s noise depends on it and '
+                    'on the frame\'s dataset index alone)')
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error('--batch must be at least 1')
+    corruption = None
+    if args.corrupt:
+        if not args.dataset:
+            ap.error('--corrupt requires --dataset')
+        from . import corruptions
+        try:
+            corruption = (corruptions.make(*corruptions.parse(args.corrupt)), int(args.corrupt_seed))
+        except ValueError as e:
+            ap.error('--corrupt: %s' % e)
     if args.device_jpeg and not args.dataset:
         ap.error('--device_jpeg requires --dataset')
     config = config_utils.setup(config_utils.load_yaml(args.yaml_path), args)
@@ -333,8 +356,9 @@ def main(argv=None):
         samples = synthetic_samples(args.synthetic, args.image_size, dataset_config['anchor_generator'], num_classes, seed=args.seed)
         sample_ids = ['synthetic_%04d.jpg' % i for i in range(len(samples))]
         categories = ['car', 'truck', 'bus', 'person', 'rider', 'bike', 'motor'][:num_classes]
+    kw = {} if corruption is None else {'corruption': corruption}
     return validate(config, samples, sample_ids, categories=categories, poll_seconds=args.poll or None, batch=args.batch,
-                    mixed_sizes=bool((args.mixed_sizes or args.device_jpeg) and args.dataset))
+                    mixed_sizes=bool((args.mixed_sizes or args.device_jpeg or corruption is not None) and args.dataset), **kw)
 
 
 if __name__ == '__main__':

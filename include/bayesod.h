@@ -376,6 +376,66 @@ bod_status bod_upload_frames_jpeg(bod_handle h, const uint8_t* const* data, cons
 bod_status bod_upload_frames_jpeg_async(bod_handle h, const uint8_t* const* data, const int64_t* len,
                                         const float* rgb_means, int32_t aspect_resize, const bod_augment* aug,
                                         int32_t threads, int32_t* src_hw_out, int32_t buffer);
+/* Corruptions of the packed uint8 RGB source frames on the device: dataset shift for scoring uncertainty.  A
+ * frame's corruption is a chain of ops_per_frame (1..4) ops applied in order to its h*w*3 bytes; ops[n][ops_per_frame] holds one
+ * chain per frame (pad a shorter chain with BOD_CORRUPT_NONE, which leaves the bytes alone).  Every op but GAUSSIAN_NOISE is
+ * integer arithmetic, or fp32 with a fixed operation order (no contraction): its result is defined to the bit.
+ *   LUT            v' = luts[table][c][v]                                     (luts: uint8 [n_luts][3][256])
+ *   CONTRAST       m_c = (float)((double)(sum of channel c over the frame) / (double)(h*w));
+ *                  v' = rintf(min(max((v - m_c) * f0 + m_c, 0), 255)), subtract, multiply and add as three fp32 operations
+ *   IMPULSE_NOISE  words x, y, z of the pixel's Philox call serve R, G, B: word < u0 ? ((word & 1) ? 255 : 0) : v
+ *                  (u0 = min(floor(p * 2^32), 2^32 - 1) for a probability p)
+ *   GAUSSIAN_NOISE u(t) = ((t >> 9) + 0.5) * 2^-23;  n0, n1 = sqrtf(-2 logf(u(x))) * (cosf, sinf)(6.2831855f * u(y)), n2 the cosine
+ *                  branch of (z, w);  v'_c = rintf(min(max(v_c + f0 * n_c, 0), 255)), multiply and add as two fp32 operations
+ *   CONV2D         v'(y, x) = (sum over ky, kx of taps[tap_offset + ky*ksize + kx] * v(clamp(y + ky - r), clamp(x + kx - r)) + 2^14) >> 15,
+ *                  r = ksize / 2, coordinates clamped to the frame; ksize odd, 1..25; the ksize^2 uint16 taps sum to exactly 2^15
+ *   PIXELATE       every u0 x u0 block anchored at (0, 0), ragged at the right / bottom edge, becomes (sum + n/2) / n over its n
+ *                  pixels, per channel, integer division
+ *   JPEG           8x8-block-local baseline round trip at 4:4:4: libjpeg's jccolor forward colour, edge blocks replicating the
+ *                  last column then the last row, samples - 128, jfdctint ("islow") forward DCT, quantisation
+ *                  sign(x) * ((|x| + (8q >> 1)) / 8q) by qtables[table] (uint16 [n_qtables][2][64], luma then chroma, natural
+ *                  order), then the decoder's dequantisation, inverse DCT, clamp and YCbCr -> RGB.  Equal to libjpeg(-turbo)'s
+ *                  save-then-load bytes at subsampling 4:4:4.
+ *   FOG            octaves s = 7..2, lattice spacing S = 2^s; the lattice value v(s, iy, ix) is the top 16 bits of word x of a
+ *                  Philox call; fx = x & (S-1), fy = y & (S-1), b_s = (v00*(S-fx) + v01*fx)*(S-fy) + (v10*(S-fx) + v11*fx)*fy;
+ *                  F = sum over s of (b_s >> 2s) >> (7 - s);  t = (u0 * F) >> 17;  v' = (v*(256 - t) + 255*t + 128) >> 8
+ * Random numbers: philox4x32_10 with key (seed low, seed high) and counter
+ *   (x, y, BOD_CORRUPT_TAG | slot, frame id)                    IMPULSE_NOISE, GAUSSIAN_NOISE: pixel (y, x)
+ *   (ix, iy, BOD_CORRUPT_TAG | slot | s << 4, frame id)         FOG: lattice point (iy, ix) of octave s
+ * with BOD_CORRUPT_TAG = 0x00C02200 and slot = the op's index 0..3 in its chain: a frame's result depends on its bytes, its
+ * chain, its id and the seed alone -- not on its place in the batch, the batch's other frames or how frames are split over calls
+ * (a chain split over two calls keeps its slots when the other call's slots hold BOD_CORRUPT_NONE). */
+enum { BOD_CORRUPT_NONE = 0, BOD_CORRUPT_LUT = 1, BOD_CORRUPT_CONTRAST = 2, BOD_CORRUPT_IMPULSE_NOISE = 3,
+       BOD_CORRUPT_GAUSSIAN_NOISE = 4, BOD_CORRUPT_CONV2D = 5, BOD_CORRUPT_PIXELATE = 6, BOD_CORRUPT_JPEG = 7, BOD_CORRUPT_FOG = 8 };
+typedef struct bod_corrupt_op {   /* 32 bytes */
+    int32_t  kind;                /* BOD_CORRUPT_* */
+    float    f0;                  /* CONTRAST: the factor k (finite); GAUSSIAN_NOISE: sigma in grey levels, 0..128; else unused */
+    uint32_t u0;                  /* IMPULSE_NOISE: threshold T; PIXELATE: block size f, 2..64; FOG: strength a, 0..256; else unused */
+    int32_t  tap_offset;          /* CONV2D: first tap of the kernel in `taps` */
+    int32_t  ksize;               /* CONV2D: K (odd, 1..25) */
+    int32_t  table;               /* LUT: index into luts; JPEG: index into qtables */
+    int32_t  reserved[2];         /* 0 */
+} bod_corrupt_op;
+/* The stage alone (stand-alone device entry, as bod_jpeg_decode_rgb): n frames packed back to back (frame b at byte 3 * sum of
+ * h_i * w_i over i < b) with sizes src_hw[n][2], their chains and ids frame_ids[n] (NULL: 0, 1, ..) -> rgb_packed_out, same
+ * packing.  taps / luts / qtables may be NULL when their count is 0.  Errors through bod_last_error(NULL). */
+bod_status bod_corrupt_frames_u8(int32_t device, int32_t n, const uint8_t* rgb_packed_in, const int32_t* src_hw,
+                                 const bod_corrupt_op* ops, int32_t ops_per_frame, const uint32_t* frame_ids,
+                                 const uint16_t* taps, int32_t n_taps, const uint8_t* luts, int32_t n_luts,
+                                 const uint16_t* qtables, int32_t n_qtables, uint64_t seed, uint8_t* rgb_packed_out);
+/* One-shot: the same description for the handle's `batch` frames, copied before return and consumed by the handle's NEXT packed
+ * upload -- bod_upload_frames_u8_ragged[_async], bod_upload_frames_u8_augmented[_async] or bod_upload_frames_jpeg[_async].  The
+ * stage runs on that upload's stream after the copy (or the JPEG colour kernel) and before the preprocess kernel, under the same
+ * events and buffer ownership: the image buffer ends up bit for bit as after the upload of bod_corrupt_frames_u8's output.  The
+ * corrupted frame never exists on the host.  ops == NULL clears a pending description.  A uniform bod_upload_frames_u8[_async]
+ * with one pending fails with BOD_ERR_INVALID_ARG and consumes nothing; an upload that fails leaves it pending.
+ * Both entries validate before anything is enqueued: BOD_ERR_INVALID_ARG naming the frame and the op for an unknown kind,
+ * ops_per_frame outside 1..4, an even ksize or one outside 1..25, taps that do not sum to 2^15, tap_offset + ksize^2 past n_taps,
+ * a block size outside 2..64, a table index past its table, a zero quantisation entry, a sigma that is not finite or
+ * outside [0, 128], a contrast factor that is not finite, a fog strength above 256; the handle stays as it was. */
+bod_status bod_set_upload_corruption(bod_handle h, const bod_corrupt_op* ops, int32_t ops_per_frame, const uint32_t* frame_ids,
+                                     const uint16_t* taps, int32_t n_taps, const uint8_t* luts, int32_t n_luts,
+                                     const uint16_t* qtables, int32_t n_qtables, uint64_t seed);
 const float* bod_device_images_buffer(bod_handle h, int32_t buffer);
 const float* bod_device_images(bod_handle h);
 bod_status bod_synchronize(bod_handle h);

@@ -137,6 +137,24 @@ bod_status bod_upload_frames_jpeg(bod_handle h, const uint8_t* const* data, cons
 bod_status bod_upload_frames_jpeg_async(bod_handle h, const uint8_t* const* data, const int64_t* len,
                                         const float* rgb_means, int32_t aspect_resize, const bod_augment* aug,
                                         int32_t threads, int32_t* src_hw_out, int32_t buffer);
+enum { BOD_CORRUPT_NONE = 0, BOD_CORRUPT_LUT = 1, BOD_CORRUPT_CONTRAST = 2, BOD_CORRUPT_IMPULSE_NOISE = 3,
+       BOD_CORRUPT_GAUSSIAN_NOISE = 4, BOD_CORRUPT_CONV2D = 5, BOD_CORRUPT_PIXELATE = 6, BOD_CORRUPT_JPEG = 7, BOD_CORRUPT_FOG = 8 };
+typedef struct bod_corrupt_op {
+    int32_t  kind;
+    float    f0;
+    uint32_t u0;
+    int32_t  tap_offset;
+    int32_t  ksize;
+    int32_t  table;
+    int32_t  reserved[2];
+} bod_corrupt_op;
+bod_status bod_corrupt_frames_u8(int32_t device, int32_t n, const uint8_t* rgb_packed_in, const int32_t* src_hw,
+                                 const bod_corrupt_op* ops, int32_t ops_per_frame, const uint32_t* frame_ids,
+                                 const uint16_t* taps, int32_t n_taps, const uint8_t* luts, int32_t n_luts,
+                                 const uint16_t* qtables, int32_t n_qtables, uint64_t seed, uint8_t* rgb_packed_out);
+bod_status bod_set_upload_corruption(bod_handle h, const bod_corrupt_op* ops, int32_t ops_per_frame, const uint32_t* frame_ids,
+                                     const uint16_t* taps, int32_t n_taps, const uint8_t* luts, int32_t n_luts,
+                                     const uint16_t* qtables, int32_t n_qtables, uint64_t seed);
 const float* bod_device_images_buffer(bod_handle h, int32_t buffer);
 const float* bod_device_images(bod_handle h);
 bod_status bod_synchronize(bod_handle h);
