@@ -76,6 +76,10 @@ class BodFoldLayer(C.Structure):
 
 BOD_DGRAD_FLIP, BOD_DGRAD_ROWS, BOD_DGRAD_COL2IM = 0, 1, 2       # routes of bod_stage_conv_dgrad
 
+# forms of bod_stage_stem
+(BOD_STEM_AUTO, BOD_STEM_F32_POOL_F32, BOD_STEM_F32_POOL_SPLIT, BOD_STEM_SEG64_POOL, BOD_STEM_ROW_POOL, BOD_STEM_FUSED_8,
+ BOD_STEM_FUSED_4, BOD_STEM_FUSED_SPLIT) = range(8)
+
 BOD_LOSS_ONE_IMAGE_ID = 1                          # flag in bod_loss_options.reserved[0]
 
 
@@ -162,6 +166,9 @@ SIGNATURES = {
     "bod_stage_conv_dgrad": (C.c_int, [C.c_int32, C.c_int32, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _I]),
     "bod_stage_stem_pool_backward": (C.c_int, [C.c_int32, C.c_int32, _F, _F, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _F]),
+    "bod_stage_stem": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, _F, _F, C.c_int32, C.c_int32,
+                                 C.c_float, _F, _F, _I]),
+    "bod_stage_stem_pool": (C.c_int, [C.c_int32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_float, _F]),
     "bod_stage_fold_pack": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(BodFoldLayer)]),
     "bod_stage_conv": (C.c_int, [C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F,
                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F,

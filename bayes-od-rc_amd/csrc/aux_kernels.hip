@@ -23,11 +23,10 @@ constexpr int ST_SEG = 64;                      // output pixels per task (4 wav
 constexpr int ST_ROWF = 2 * ST_SEG * 3 + 5 * 3 + 5;   // 404 floats: (2*63+7) pixels * 3 ch = 399, + the 3 zero-weight k slots, padded
 constexpr int ST_KSTEPS = 42;                   // 7 rows x 24 (21 real + 3 zero) / 4
 
-template <bool OUT_F32>
 __global__ __launch_bounds__(256, 1) void stem_conv_kernel(const float* __restrict__ img,
                                                            const float* __restrict__ w,
                                                            const float* __restrict__ bias,
-                                                           void* __restrict__ out_,
+                                                           float* __restrict__ out,
                                                            int B, int H, int W, int oh, int ow) {
     __shared__ float patch[2][7][ST_ROWF];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -88,22 +87,13 @@ __global__ __launch_bounds__(256, 1) void stem_conv_kernel(const float* __restri
         }
         const int seg = task % segs, oy = (task / segs) % oh, b = task / (segs * oh);
         const int ox = seg * ST_SEG + wave * 16 + li;
-        if (ox < ow && OUT_F32) {
-            float* o = reinterpret_cast<float*>(out_) + (((size_t)b * oh + oy) * ow + ox) * 64 + lq * 4;
+        if (ox < ow) {
+            float* o = out + (((size_t)b * oh + oy) * ow + ox) * 64 + lq * 4;
 #pragma unroll
             for (int f = 0; f < 4; ++f)
                 *reinterpret_cast<float4*>(o + f * 16) =
                     make_float4(fmaxf(acc[f][0] + bv[f][0], 0.f), fmaxf(acc[f][1] + bv[f][1], 0.f),
                                 fmaxf(acc[f][2] + bv[f][2], 0.f), fmaxf(acc[f][3] + bv[f][3], 0.f));
-        } else if (ox < ow) {
-            uint16_t* o = reinterpret_cast<uint16_t*>(out_) + (((size_t)b * oh + oy) * ow + ox) * 64 + lq * 4;
-#pragma unroll
-            for (int f = 0; f < 4; ++f) {
-                uint2 pk;
-                pk.x = f32_to_bf16_a(fmaxf(acc[f][0] + bv[f][0], 0.f)) | (f32_to_bf16_a(fmaxf(acc[f][1] + bv[f][1], 0.f)) << 16);
-                pk.y = f32_to_bf16_a(fmaxf(acc[f][2] + bv[f][2], 0.f)) | (f32_to_bf16_a(fmaxf(acc[f][3] + bv[f][3], 0.f)) << 16);
-                *reinterpret_cast<uint2*>(o + f * 16) = pk;
-            }
         }
         if (nxt < ntasks) commit(buf ^ 1);
         __syncthreads();
@@ -642,7 +632,7 @@ __global__ __launch_bounds__(512, 1) void stem_pool_fused_split_kernel(const flo
                 for (int f = 0; f < FW; ++f) acc[f][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alr[t][f], bq.v, acc[f][p], 0, 0, 0);
             }
         }
-        // bias + ReLU in fp32 (stem_conv_kernel<true>'s epilogue), then the window's running maximum
+        // bias + ReLU in fp32 (stem_conv_kernel's epilogue), then the window's running maximum
 #pragma unroll
         for (int f = 0; f < FW; ++f) {
             const f32x4_t bv = *reinterpret_cast<const f32x4_t*>(bias + (chh * FW + f) * 16 + lq * 4);      // (per row: registers are short here)
@@ -708,8 +698,21 @@ __global__ __launch_bounds__(512, 1) void stem_pool_fused_split_kernel(const flo
     }
 }
 
-hipError_t launch_stem_pool_fused(const float* img, const float* w, const float* bias, void* pooled, int split, int B, int H, int W, int oh,
-                                  int ow, int ph, int pw, int pool_pitch, int pool_plane, hipStream_t s) {
+// which fused kernel the pipeline runs: the rule (environment reads) apart from the launch, so that a test can name the form
+StemFusedForm stem_pool_fused_form(int split) {
+    if (split) return STEM_FUSED_SPLIT;
+    // BOD_STEM_WAVES=4: the four-wave form (round 3), A/B aid -- bit-identical pooled plane
+    static const bool eight = [] { const char* e = getenv("BOD_STEM_WAVES"); return !e || atoi(e) != 4; }();
+    return eight ? STEM_FUSED_8 : STEM_FUSED_4;
+}
+// the shapes every fused kernel is built for (stem_pool_fused_applies adds the switches and the batch floor)
+bool stem_pool_fused_fits(const float* img, int W, int ow) {
+    return ow <= SR_SEG && (W & 3) == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0;
+}
+
+hipError_t launch_stem_pool_fused_form(StemFusedForm form, const float* img, const float* w, const float* bias, void* pooled, int B, int H,
+                                       int W, int oh, int ow, int ph, int pw, int pool_pitch, int pool_plane, hipStream_t s) {
+    if (!stem_pool_fused_fits(img, W, ow)) return hipErrorInvalidValue;
     static PerDeviceOnce once;
     bool& attr_set = *once.slot();
     if (!attr_set) {
@@ -719,20 +722,20 @@ hipError_t launch_stem_pool_fused(const float* img, const float* w, const float*
         if (e != hipSuccess) return e;
         attr_set = true;
     }
-    if (split) {
+    if (form == STEM_FUSED_SPLIT)
         hipLaunchKernelGGL(stem_pool_fused_split_kernel, dim3(B), dim3(512), SFS_LDS_BYTES, s, img, w, bias, reinterpret_cast<uint16_t*>(pooled), B, H, W,
                            oh, ow, ph, pw, pool_pitch, pool_plane);
-        return hipGetLastError();
-    }
-    // BOD_STEM_WAVES=4: the four-wave form (round 3), A/B aid -- bit-identical pooled plane
-    static const bool eight = [] { const char* e = getenv("BOD_STEM_WAVES"); return !e || atoi(e) != 4; }();
-    if (eight)
+    else if (form == STEM_FUSED_8)
         hipLaunchKernelGGL(stem_pool_fused_kernel<2>, dim3(B), dim3(512), SF_LDS_BYTES, s, img, w, bias, reinterpret_cast<uint16_t*>(pooled), B, H, W, oh, ow,
                            ph, pw, pool_pitch, pool_plane);
     else
         hipLaunchKernelGGL(stem_pool_fused_kernel<1>, dim3(B), dim3(256), SF_LDS_BYTES, s, img, w, bias, reinterpret_cast<uint16_t*>(pooled), B, H, W, oh, ow,
                            ph, pw, pool_pitch, pool_plane);
     return hipGetLastError();
+}
+hipError_t launch_stem_pool_fused(const float* img, const float* w, const float* bias, void* pooled, int split, int B, int H, int W, int oh,
+                                  int ow, int ph, int pw, int pool_pitch, int pool_plane, hipStream_t s) {
+    return launch_stem_pool_fused_form(stem_pool_fused_form(split), img, w, bias, pooled, B, H, W, oh, ow, ph, pw, pool_pitch, pool_plane, s);
 }
 // the fused kernel's shapes: one 256-pixel segment per stem row, 16-byte aligned rows, enough images to fill the chip's CUs
 // (one workgroup per image walks down its frame: with fewer images than CUs part of the chip idles for the whole launch -- measured
@@ -741,22 +744,30 @@ hipError_t launch_stem_pool_fused(const float* img, const float* w, const float*
 bool stem_pool_fused_applies(const float* img, int B, int W, int ow, int n_cu) {
     static const bool on = [] { const char* e = getenv("BOD_STEM_POOL_FUSED"); return !e || atoi(e) != 0; }();
     static const int min_b = [] { const char* e = getenv("BOD_STEM_POOL_FUSED_MIN_B"); return e ? atoi(e) : 0; }();
-    return on && ow <= SR_SEG && (W & 3) == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0 && B >= (min_b > 0 ? min_b : (n_cu > 0 ? n_cu : 256));
+    return on && stem_pool_fused_fits(img, W, ow) && B >= (min_b > 0 ? min_b : (n_cu > 0 ? n_cu : 256));
 }
 
-hipError_t launch_stem_conv(const float* img, const float* w, const float* bias, void* out, int out_f32,
-                            int B, int H, int W, int oh, int ow, hipStream_t s) {
+// which stem kernel the pipeline runs (the rule apart from the launch, as above)
+bool stem_conv_row_fits(const float* img, int W) {                                      // (16-byte row loads: rows of W*3 floats from a 16-byte aligned base)
+    return (W & 3) == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0;
+}
+StemConvForm stem_conv_form(const float* img, int out_f32, int W) {
+    if (out_f32) return STEM_CONV_F32;
+    static const bool old_stem = getenv("BOD_STEM_SEG64") && atoi(getenv("BOD_STEM_SEG64")) == 1;   // A/B aid: the 64-pixel-task kernel (bit-identical outputs)
+    return old_stem || !stem_conv_row_fits(img, W) ? STEM_CONV_SEG64 : STEM_CONV_ROW;
+}
+
+hipError_t launch_stem_conv_form(StemConvForm form, const float* img, const float* w, const float* bias, void* out,
+                                 int B, int H, int W, int oh, int ow, hipStream_t s) {
     const int segs = (ow + ST_SEG - 1) / ST_SEG;
     const int ntasks = B * oh * segs;
     const int grid = ntasks < 1024 ? ntasks : 1024;
-    if (out_f32) hipLaunchKernelGGL(stem_conv_kernel<true>, dim3(grid), dim3(256), 0, s, img, w, bias, out, B, H, W, oh, ow);
+    if (form == STEM_CONV_F32) hipLaunchKernelGGL(stem_conv_kernel, dim3(grid), dim3(256), 0, s, img, w, bias, reinterpret_cast<float*>(out), B, H, W, oh, ow);
+    else if (form == STEM_CONV_SEG64)
+        hipLaunchKernelGGL(stem_conv_bf16_kernel, dim3(ntasks < 768 ? ntasks : 768), dim3(256), 0, s, img, w, bias,
+                           reinterpret_cast<uint16_t*>(out), B, H, W, oh, ow);
     else {
-        static const bool old_stem = getenv("BOD_STEM_SEG64") && atoi(getenv("BOD_STEM_SEG64")) == 1;   // A/B aid: the 64-pixel-task kernel (bit-identical outputs)
-        if (old_stem || (W & 3) || (reinterpret_cast<uintptr_t>(img) & 15)) {            // (16-byte row loads: rows of W*3 floats from a 16-byte aligned base)
-            hipLaunchKernelGGL(stem_conv_bf16_kernel, dim3(ntasks < 768 ? ntasks : 768), dim3(256), 0, s, img, w, bias,
-                               reinterpret_cast<uint16_t*>(out), B, H, W, oh, ow);
-            return hipGetLastError();
-        }
+        if (!stem_conv_row_fits(img, W)) return hipErrorInvalidValue;
         static PerDeviceOnce once;
         bool& attr_set = *once.slot();
         if (!attr_set) {
@@ -769,6 +780,10 @@ hipError_t launch_stem_conv(const float* img, const float* w, const float* bias,
                            reinterpret_cast<uint16_t*>(out), B, H, W, oh, ow);
     }
     return hipGetLastError();
+}
+hipError_t launch_stem_conv(const float* img, const float* w, const float* bias, void* out, int out_f32,
+                            int B, int H, int W, int oh, int ow, hipStream_t s) {
+    return launch_stem_conv_form(stem_conv_form(img, out_f32, W), img, w, bias, out, B, H, W, oh, ow, s);
 }
 
 // fp32 variant of the pooling kernel below (thread = output pixel x 4-channel group)

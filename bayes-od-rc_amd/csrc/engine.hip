@@ -1505,6 +1505,11 @@ struct MarkerRange {                    // scope = one range
     MarkerRange(const MarkerRange&) = delete;
     MarkerRange& operator=(const MarkerRange&) = delete;
 };
+// BOD_STEM_SPLIT_FUSED=0: the (hi, lo) precisions keep the fp32 stem and the pooling launch (read by the forward pass and bod_stage_stem)
+static bool stem_split_fused_enabled() {
+    static const bool on = [] { const char* e = getenv("BOD_STEM_SPLIT_FUSED"); return !e || atoi(e) != 0; }();
+    return on;
+}
 // stage of a forward op, from its name: conv1 / pool1 -> stem, resK* -> resK, C?_reduced / P? -> fpn, head_tower_layer_k(...) -> itself
 static std::string op_stage(const std::string& name) {
     if (name.rfind("conv1", 0) == 0 || name.rfind("pool1", 0) == 0) return "bod:stem";
@@ -1598,8 +1603,7 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
                 const Op* pool = op_i < h->ops.size() && h->ops[op_i].kind == Op::POOL ? &h->ops[op_i] : nullptr;
                 // Round 6: the (hi, lo) precisions take the same walk on three bf16 products (their stem was the exact fp32 kernel + a
                 // pooling launch: 5.2 ms per 256 frames against 0.8); BOD_STEM_SPLIT_FUSED=0: as before.
-                static const bool split_fused = [] { const char* e = getenv("BOD_STEM_SPLIT_FUSED"); return !e || atoi(e) != 0; }();
-                stem_pool_fused = pool && !h->train && (h->split ? split_fused : h->es == 2) && !trace &&
+                stem_pool_fused = pool && !h->train && (h->split ? stem_split_fused_enabled() : h->es == 2) && !trace &&
                                   stem_pool_fused_applies(dev_images, c.batch, c.image_w, h->sw, is_front ? cus_front : cus_back);
                 if (stem_pool_fused)
                     HIPCHK(h, launch_stem_pool_fused(dev_images, h->stem_w, h->stem_b, pool->conv.g[0].out, h->split ? 1 : 0, c.batch, c.image_h,

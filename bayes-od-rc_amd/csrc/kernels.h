@@ -165,6 +165,14 @@ hipError_t launch_pairs_to_hx(const void* in, void* out, long npix, int C, hipSt
 // 7x7 s2 VALID conv (fp32 image, fp32 folded weights [7][7][3][64]) + bias + ReLU -> bf16 [B,oh,ow,64]
 hipError_t launch_stem_conv(const float* img, const float* w, const float* bias, void* out, int out_f32,
                             int B, int H, int W, int oh, int ow, hipStream_t s);
+// launch_stem_conv = the rule (stem_conv_form: precision, BOD_STEM_SEG64, row alignment) + the launch of that form.  fp32: exact fp32
+// MFMA, 64-pixel tasks; SEG64 / ROW: the bf16 kernels on 64-pixel and on 256-pixel row tasks (bit-identical planes).  The row kernel
+// needs W % 4 == 0 and a 16-byte aligned image (stem_conv_row_fits; hipErrorInvalidValue otherwise, nothing launched)
+enum StemConvForm { STEM_CONV_F32 = 0, STEM_CONV_SEG64 = 1, STEM_CONV_ROW = 2 };
+bool stem_conv_row_fits(const float* img, int W);
+StemConvForm stem_conv_form(const float* img, int out_f32, int W);
+hipError_t launch_stem_conv_form(StemConvForm form, const float* img, const float* w, const float* bias, void* out,
+                                 int B, int H, int W, int oh, int ow, hipStream_t s);
 // ZeroPadding2D((1,2)) + MaxPool 3x3 s2 VALID on [B,ih,iw,64] -> padded-plane output.  mode 0: bf16 -> bf16; 1: fp32 -> fp32;
 // 2: fp32 -> (hi, lo) bf16 pairs (bf16x3 precision)
 // stem + zero-pad + max-pool in one kernel (bf16 inference, stem rows of <= 256 pixels; aux_kernels.hip)
@@ -172,6 +180,13 @@ bool stem_pool_fused_applies(const float* img, int B, int W, int ow, int n_cu);
 // split = 1: the (hi, lo) precisions -- three bf16 products, fp32 pooling, pooled pixels stored as pairs (aux_kernels.hip)
 hipError_t launch_stem_pool_fused(const float* img, const float* w, const float* bias, void* pooled, int split, int B, int H, int W, int oh,
                                   int ow, int ph, int pw, int pool_pitch, int pool_plane, hipStream_t s);
+// launch_stem_pool_fused = the rule (stem_pool_fused_form: split, BOD_STEM_WAVES) + the launch of that form.  Every form needs
+// stem_pool_fused_fits: ow <= 256, W % 4 == 0, a 16-byte aligned image (hipErrorInvalidValue otherwise, nothing launched)
+enum StemFusedForm { STEM_FUSED_8 = 0, STEM_FUSED_4 = 1, STEM_FUSED_SPLIT = 2 };
+bool stem_pool_fused_fits(const float* img, int W, int ow);
+StemFusedForm stem_pool_fused_form(int split);
+hipError_t launch_stem_pool_fused_form(StemFusedForm form, const float* img, const float* w, const float* bias, void* pooled, int B, int H,
+                                       int W, int oh, int ow, int ph, int pw, int pool_pitch, int pool_plane, hipStream_t s);
 hipError_t launch_stem_pool(const void* in, void* out, int mode, int B, int ih, int iw, int oh, int ow,
                             int out_pitch, int out_plane, hipStream_t s);
 

@@ -1178,6 +1178,141 @@ bod_status bod_stage_stem_pool_backward(int32_t device, int32_t precision, const
     return sc.done(run());
 }
 
+// ------------------------------------------------------------------------------------------------
+// Stage entry points of the stem and stem-pool kernels (include/bayesod.h, DESIGN.md 9.14).  Output planes live between two
+// guard regions, everything filled with the caller's sentinel: an element a kernel leaves out, and a store past either end, show.
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t STAGE_GUARD = 4096;                    // guard elements on either side of a plane
+struct GuardedPlane {
+    char* base = nullptr;
+    size_t n = 0, es = 0;
+    char* plane() const { return base + STAGE_GUARD * es; }
+};
+bool stage_sentinel_ok(float v) { return std::isfinite(v) && bf2f(f2bf(v)) == v; }
+bod_status guarded_alloc(bod_context* h, size_t n, bool f32, float sentinel, GuardedPlane* g) {
+    g->n = n; g->es = f32 ? 4 : 2;
+    const size_t total = n + 2 * STAGE_GUARD;
+    BODCHK(h->dalloc(&g->base, total * g->es, false));
+    std::vector<float> hf(f32 ? total : 0, sentinel);
+    std::vector<uint16_t> hb(f32 ? 0 : total, f2bf(sentinel));
+    HIPCHK(h, hipMemcpyAsync(g->base, f32 ? (const void*)hf.data() : (const void*)hb.data(), total * g->es, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BOD_OK;
+}
+// plane -> dst (may be NULL) as fp32; BOD_ERR_HIP when a guard element no longer holds the sentinel
+bod_status guarded_download(bod_context* h, const GuardedPlane& g, float sentinel, const char* what, float* dst) {
+    const size_t total = g.n + 2 * STAGE_GUARD;
+    std::vector<char> hb(total * g.es);
+    HIPCHK(h, hipMemcpyAsync(hb.data(), g.base, hb.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    auto at = [&](size_t i) {
+        if (g.es == 4) { float f; std::memcpy(&f, &hb[i * 4], 4); return f; }
+        uint16_t u; std::memcpy(&u, &hb[i * 2], 2); return bf2f(u);
+    };
+    for (size_t i = 0; i < STAGE_GUARD; ++i)
+        if (at(i) != sentinel || at(STAGE_GUARD + g.n + i) != sentinel)
+            return h->fail(BOD_ERR_HIP, "%s: a kernel wrote outside its plane (guard element %zu %s it)", what, i, at(i) != sentinel ? "before" : "after");
+    if (dst) for (size_t i = 0; i < g.n; ++i) dst[i] = at(STAGE_GUARD + i);
+    return BOD_OK;
+}
+}  // namespace
+
+bod_status bod_stage_stem(int32_t device, int32_t form, int32_t precision, const float* images, int32_t B, int32_t H, int32_t W,
+                          const float* w, const float* bias, int32_t misalign, int32_t n_cu, float sentinel, float* stem_out,
+                          float* pooled, int32_t* form_ran) {
+    StageScope sc;
+    bod_context* h = sc.h;
+    const bool f32 = precision == BOD_PRECISION_FP32, x3 = precision == BOD_PRECISION_BF16X3;
+    h->es = f32 ? 4 : 2;
+    auto bad = [&](const char* what) { return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_stem: %s", what)); };
+    if (precision != BOD_PRECISION_BF16 && !f32 && !x3) return bad("precision must be BOD_PRECISION_BF16, BOD_PRECISION_FP32 or BOD_PRECISION_BF16X3");
+    if (!images || !w || !bias || !form_ran) return bad("images, w, bias and form_ran must not be NULL");
+    if (form < BOD_STEM_AUTO || form > BOD_STEM_FUSED_SPLIT) return bad("unknown form");
+    if (B < 1 || H < 7 || W < 7 || (int64_t)B * H * W > (1 << 22)) return bad("need B >= 1, H, W >= 7 and at most 2^22 input pixels");
+    if (!stage_sentinel_ok(sentinel)) return bad("the sentinel must be finite and exact in bf16");
+    static const int form_precision[8] = {-1, BOD_PRECISION_FP32, BOD_PRECISION_BF16X3, BOD_PRECISION_BF16, BOD_PRECISION_BF16,
+                                          BOD_PRECISION_BF16, BOD_PRECISION_BF16, BOD_PRECISION_BF16X3};
+    if (form != BOD_STEM_AUTO && form_precision[form] != precision) return bad("this form does not run in this precision");
+    // the stem / pool geometry of bod_create
+    const int oh = (H - 7) / 2 + 1, ow = (W - 7) / 2 + 1;
+    const int ph = (oh + 2 - 3) / 2 + 1, pw = (ow + 4 - 3) / 2 + 1;
+    const int pool_pitch = pw + 2, pool_plane = (ph + 2) * (pw + 2);
+    auto is_fused = [](int f) { return f == BOD_STEM_FUSED_8 || f == BOD_STEM_FUSED_4 || f == BOD_STEM_FUSED_SPLIT; };
+    if ((form == BOD_STEM_ROW_POOL || is_fused(form)) && ((W & 3) != 0 || misalign))
+        return bad("the row and fused kernels need W % 4 == 0 and a 16-byte aligned image");
+    if (is_fused(form) && ow > 256) return bad("the fused kernels take stem rows of at most 256 pixels");
+    if (const bod_status s = sc.open(device)) return sc.done(s);
+    auto run = [&]() -> bod_status {
+        const size_t n_img = (size_t)B * H * W * 3;
+        float *d_imgbuf = nullptr, *d_w = nullptr, *d_b = nullptr;
+        BODCHK(h->dalloc(&d_imgbuf, n_img + 4));
+        const float* d_img = d_imgbuf + (misalign ? 1 : 0);
+        if ((reinterpret_cast<uintptr_t>(d_img) & 15) != (misalign ? 4u : 0u)) return h->fail(BOD_ERR_HIP, "bod_stage_stem: device allocation is not 16-byte aligned");
+        BODCHK(h->dalloc(&d_w, (size_t)147 * 64, false));
+        BODCHK(h->dalloc(&d_b, (size_t)64, false));
+        HIPCHK(h, hipMemcpyAsync(const_cast<float*>(d_img), images, n_img * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_w, w, (size_t)147 * 64 * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_b, bias, 64 * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        int f = form;
+        if (f == BOD_STEM_AUTO) {                      // the forward pass's rule (Op::STEM) for an inference handle that is not traced
+            const bool fused = !f32 && (x3 ? stem_split_fused_enabled() : true) && stem_pool_fused_applies(d_img, B, W, ow, n_cu);
+            if (f32) f = BOD_STEM_F32_POOL_F32;
+            else if (fused) f = x3 ? BOD_STEM_FUSED_SPLIT : (stem_pool_fused_form(0) == STEM_FUSED_8 ? BOD_STEM_FUSED_8 : BOD_STEM_FUSED_4);
+            else if (x3) f = BOD_STEM_F32_POOL_SPLIT;
+            else f = stem_conv_form(d_img, 0, W) == STEM_CONV_ROW ? BOD_STEM_ROW_POOL : BOD_STEM_SEG64_POOL;
+        }
+        // whatever chose the form: nothing is launched on a shape the kernel is not built for
+        if ((f == BOD_STEM_ROW_POOL && !stem_conv_row_fits(d_img, W)) || (is_fused(f) && !stem_pool_fused_fits(d_img, W, ow)))
+            return h->fail(BOD_ERR_INVALID_ARG, "bod_stage_stem: form %d does not fit this image (W %d, ow %d, misalign %d)", f, W, ow, misalign);
+        const bool pairs = f == BOD_STEM_F32_POOL_SPLIT || f == BOD_STEM_FUSED_SPLIT;
+        const bool stem_f32 = f == BOD_STEM_F32_POOL_F32 || f == BOD_STEM_F32_POOL_SPLIT;
+        GuardedPlane gs, gp;
+        BODCHK(guarded_alloc(h, (size_t)B * pool_plane * (pairs ? 128 : 64), f == BOD_STEM_F32_POOL_F32, sentinel, &gp));
+        if (is_fused(f)) {
+            const StemFusedForm ff = f == BOD_STEM_FUSED_SPLIT ? STEM_FUSED_SPLIT : f == BOD_STEM_FUSED_8 ? STEM_FUSED_8 : STEM_FUSED_4;
+            HIPCHK(h, launch_stem_pool_fused_form(ff, d_img, d_w, d_b, gp.plane(), B, H, W, oh, ow, ph, pw, pool_pitch, pool_plane, h->stream));
+        } else {
+            BODCHK(guarded_alloc(h, (size_t)B * oh * ow * 64, stem_f32, sentinel, &gs));
+            const StemConvForm cf = stem_f32 ? STEM_CONV_F32 : f == BOD_STEM_ROW_POOL ? STEM_CONV_ROW : STEM_CONV_SEG64;
+            HIPCHK(h, launch_stem_conv_form(cf, d_img, d_w, d_b, gs.plane(), B, H, W, oh, ow, h->stream));
+            HIPCHK(h, launch_stem_pool(gs.plane(), gp.plane(), f == BOD_STEM_F32_POOL_SPLIT ? 2 : (stem_f32 ? 1 : 0), B, oh, ow, ph, pw, pool_pitch,
+                                       pool_plane, h->stream));
+            BODCHK(guarded_download(h, gs, sentinel, "bod_stage_stem (stem plane)", stem_out));
+        }
+        BODCHK(guarded_download(h, gp, sentinel, "bod_stage_stem (pooled plane)", pooled));
+        *form_ran = f;
+        return BOD_OK;
+    };
+    return sc.done(run());
+}
+
+bod_status bod_stage_stem_pool(int32_t device, int32_t mode, const float* stem, int32_t B, int32_t ih, int32_t iw, float sentinel,
+                               float* pooled) {
+    StageScope sc;
+    bod_context* h = sc.h;
+    const bool in_f32 = mode != 0;
+    h->es = in_f32 ? 4 : 2;
+    auto bad = [&](const char* what) { return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_stem_pool: %s", what)); };
+    if (mode < 0 || mode > 2) return bad("mode must be 0 (bf16 -> bf16), 1 (fp32 -> fp32) or 2 (fp32 -> pairs)");
+    if (!stem || !pooled) return bad("stem and pooled must not be NULL");
+    if (B < 1 || ih < 1 || iw < 1 || (int64_t)B * ih * iw > (1 << 22)) return bad("need B, ih, iw >= 1 and at most 2^22 stem pixels");
+    if (!stage_sentinel_ok(sentinel)) return bad("the sentinel must be finite and exact in bf16");
+    const int oh = (ih + 2 - 3) / 2 + 1, ow = (iw + 4 - 3) / 2 + 1;
+    const int pool_pitch = ow + 2, pool_plane = (oh + 2) * (ow + 2);
+    if (const bod_status s = sc.open(device)) return sc.done(s);
+    auto run = [&]() -> bod_status {
+        void* d_stem = nullptr;
+        BODCHK(stage_upload(h, stem, (size_t)B * ih * iw * 64, in_f32, &d_stem));
+        GuardedPlane gp;
+        BODCHK(guarded_alloc(h, (size_t)B * pool_plane * (mode == 2 ? 128 : 64), mode == 1, sentinel, &gp));
+        HIPCHK(h, launch_stem_pool(d_stem, gp.plane(), mode, B, ih, iw, oh, ow, pool_pitch, pool_plane, h->stream));
+        return guarded_download(h, gp, sentinel, "bod_stage_stem_pool", pooled);
+    };
+    return sc.done(run());
+}
+
 bod_status bod_stage_fold_pack(int32_t device, int32_t count, const bod_fold_layer* layers) {
     StageScope sc;
     bod_context* h = sc.h;

@@ -1149,6 +1149,60 @@ def stage_stem_pool_backward(stem_out, dpool, precision="bf16", device=0):
     return dz
 
 
+STEM_FORMS = {"auto": _lib.BOD_STEM_AUTO, "f32+pool_f32": _lib.BOD_STEM_F32_POOL_F32, "f32+pool_split": _lib.BOD_STEM_F32_POOL_SPLIT,
+              "seg64+pool": _lib.BOD_STEM_SEG64_POOL, "row+pool": _lib.BOD_STEM_ROW_POOL, "fused8": _lib.BOD_STEM_FUSED_8,
+              "fused4": _lib.BOD_STEM_FUSED_4, "fused_split": _lib.BOD_STEM_FUSED_SPLIT}
+STEM_FORM_PRECISION = {"f32+pool_f32": "fp32", "f32+pool_split": "bf16x3", "seg64+pool": "bf16", "row+pool": "bf16", "fused8": "bf16",
+                       "fused4": "bf16", "fused_split": "bf16x3"}
+STEM_SENTINEL = -65536.0
+
+
+def stem_geometry(h, w):
+    """(oh, ow, ph, pw) of the stem and its pooled plane for an H x W frame, as handle creation derives them."""
+    oh, ow = (h - 7) // 2 + 1, (w - 7) // 2 + 1
+    return oh, ow, (oh - 1) // 2 + 1, (ow + 1) // 2 + 1
+
+
+def stage_stem(images, w, bias, form="auto", precision=None, misalign=False, n_cu=0, sentinel=STEM_SENTINEL, device=0):
+    """One form of the stem through the library's launchers (``bod_stage_stem``): images [B,H,W,3], w [7,7,3,64] (folded), bias [64].
+    form: a key of STEM_FORMS; precision is implied by an explicit form and required ('fp32', 'bf16', 'bf16x3') with 'auto'.
+    Returns dict(form: the key of the form that ran, stem: [B,oh,ow,64] float32 or None for a fused form, pooled:
+    [B,ph+2,pw+2,64 or 128] float32 with its border); both device planes were prefilled with ``sentinel``."""
+    lib = _lib.load()
+    images, w, bias = as_f32(images), as_f32(w), as_f32(bias)
+    if images.ndim != 4 or images.shape[3] != 3 or w.shape != (7, 7, 3, 64) or bias.shape != (64,):
+        raise ValueError("stage_stem: images [B,H,W,3], w [7,7,3,64], bias [64]")
+    if precision is None:
+        precision = STEM_FORM_PRECISION[form]           # KeyError for 'auto': the rule needs a precision
+    b, h, wd, _ = images.shape
+    oh, ow, ph, pw = stem_geometry(h, wd)
+    if min(oh, ow) < 1:
+        raise ValueError("stage_stem: H and W must be at least 7")
+    stem = np.full((b, oh, ow, 64), np.nan, np.float32)
+    pooled = np.full((b, ph + 2, pw + 2, 128 if precision == "bf16x3" else 64), np.nan, np.float32)
+    ran = C.c_int32(-1)
+    st = lib.bod_stage_stem(device, STEM_FORMS[form], PRECISIONS[precision], fptr(images), b, h, wd, fptr(w), fptr(bias), int(bool(misalign)),
+                            int(n_cu), float(sentinel), fptr(stem), fptr(pooled), C.byref(ran))
+    _lib.check(lib, None, st)
+    name = {v: k for k, v in STEM_FORMS.items()}[ran.value]
+    return {"form": name, "stem": None if name.startswith("fused") else stem, "pooled": pooled}
+
+
+def stage_stem_pool(stem, mode, sentinel=STEM_SENTINEL, device=0):
+    """The stem's zero-pad + 3x3 s2 max-pool alone (``bod_stage_stem_pool``) on stem [B,ih,iw,64]; mode 0 bf16 -> bf16, 1 fp32 ->
+    fp32, 2 fp32 -> (hi, lo) pairs.  Returns the pooled plane with its border, [B,oh+2,ow+2,64 (mode 2: 128)] float32."""
+    lib = _lib.load()
+    stem = as_f32(stem)
+    if stem.ndim != 4 or stem.shape[3] != 64:
+        raise ValueError("stage_stem_pool: stem [B,ih,iw,64]")
+    b, ih, iw, _ = stem.shape
+    oh, ow = (ih - 1) // 2 + 1, (iw + 1) // 2 + 1
+    pooled = np.full((b, oh + 2, ow + 2, 128 if int(mode) == 2 else 64), np.nan, np.float32)
+    st = lib.bod_stage_stem_pool(device, int(mode), fptr(stem), b, ih, iw, float(sentinel), fptr(pooled))
+    _lib.check(lib, None, st)
+    return pooled
+
+
 def stage_fold_pack(layers, device=0):
     """Batch-norm folding and the three bf16 weight packings of every layer in ONE launch (``bod_stage_fold_pack``).  layers:
     dicts with kernel [taps,cin,cout] (or HWIO), cout_pad, optional bias and gamma / beta / mean / var.  Returns one dict per

@@ -511,6 +511,43 @@ bod_status bod_stage_conv_dgrad(int32_t device, int32_t route, const float* dz, 
 bod_status bod_stage_stem_pool_backward(int32_t device, int32_t precision, const float* stem_out, const float* dpool, int64_t dpool_elems,
                                         int32_t B, int32_t ih, int32_t iw, float* dz);
 
+/* Stage entry points of the stem and stem-pool kernels (tests/test_gpu_stem_kernels.py), built like the
+ * ones above: a throw-away context, host arrays in and out, the library's own launchers, every size, pointer and
+ * precondition checked on the host before anything is launched (BOD_ERR_INVALID_ARG), errors via bod_last_error(NULL).
+ *
+ * bod_stage_stem runs ONE form of the stem on images [B,H,W,3] fp32, w [7][7][3][64] fp32 (folded) and bias [64].
+ * Geometry as bod_create derives it: oh = (H-7)/2+1, ow = (W-7)/2+1, ph = (oh-1)/2+1, pw = (ow+1)/2+1.
+ * form = BOD_STEM_AUTO follows the pipeline's rule for `precision` (BOD_PRECISION_FP32, _BF16 or _BF16X3): the fused
+ * kernel where stem_pool_fused_applies says so for this image pointer, W, B and n_cu (the stream's compute-unit share,
+ * as the forward pass passes it; <= 0: the rule's default of 256), else launch_stem_conv's choice and the pooling
+ * launch.  An explicit form names the kernels and must fit `precision`:
+ *   BOD_STEM_F32_POOL_F32     fp32 stem, stem_pool_f32_kernel                 (FP32)
+ *   BOD_STEM_F32_POOL_SPLIT   fp32 stem, stem_pool_split_kernel               (BF16X3; pooled pixels are 128 slots)
+ *   BOD_STEM_SEG64_POOL       64-pixel bf16 stem, stem_pool_kernel            (BF16)
+ *   BOD_STEM_ROW_POOL         row bf16 stem, stem_pool_kernel                 (BF16; W % 4 == 0, aligned image)
+ *   BOD_STEM_FUSED_8 / _4     stem + pool in one kernel on 8 / 4 waves        (BF16; as ROW, and ow <= 256)
+ *   BOD_STEM_FUSED_SPLIT      the fused kernel of the (hi, lo) precisions     (BF16X3; as the fused forms; 128 slots)
+ * An explicit form whose precondition does not hold is refused.  misalign != 0 places the device image 4 bytes past a
+ * 16-byte boundary (BOD_STEM_AUTO then has to fall back to the 64-pixel kernel).  Requires H, W >= 7 and at most 2^22
+ * input pixels.
+ * stem_out [B,oh,ow,64] (may be NULL) receives the stem plane of the forms that write one (the fused forms leave it
+ * untouched); pooled [B,ph+2,pw+2,64 or 128] (may be NULL) the pooled plane INCLUDING its one-pixel border, the 128
+ * slots of a pair pixel in storage order.  bf16 values come back widened to fp32.  Both device planes are filled
+ * with `sentinel` (a value bf16 holds exactly, e.g. -65536) before the launch and lie between two guard regions of the same
+ * fill; a guard that changed is BOD_ERR_HIP.  *form_ran: the explicit form that ran. */
+enum { BOD_STEM_AUTO = 0, BOD_STEM_F32_POOL_F32 = 1, BOD_STEM_F32_POOL_SPLIT = 2, BOD_STEM_SEG64_POOL = 3, BOD_STEM_ROW_POOL = 4,
+       BOD_STEM_FUSED_8 = 5, BOD_STEM_FUSED_4 = 6, BOD_STEM_FUSED_SPLIT = 7 };
+bod_status bod_stage_stem(int32_t device, int32_t form, int32_t precision, const float* images, int32_t B, int32_t H, int32_t W,
+                          const float* w, const float* bias, int32_t misalign, int32_t n_cu, float sentinel, float* stem_out,
+                          float* pooled, int32_t* form_ran);
+
+/* launch_stem_pool alone on a caller-supplied stem plane stem [B,ih,iw,64]: mode 0 bf16 -> bf16 (the plane is rounded
+ * to bf16 on the way in), 1 fp32 -> fp32, 2 fp32 -> (hi, lo) pairs.  pooled [B,oh+2,ow+2,64 (mode 2: 128)] with
+ * oh = (ih-1)/2+1, ow = (iw+1)/2+1 comes back with its border; the device plane is prefilled with `sentinel` and guarded as
+ * above.  At most 2^22 stem pixels. */
+bod_status bod_stage_stem_pool(int32_t device, int32_t mode, const float* stem, int32_t B, int32_t ih, int32_t iw, float sentinel,
+                               float* pooled);
+
 /* Fold batch-norm into the master weights and pack them, all `count` layers in ONE launch_fold_pack_all launch, bf16
  * mode.  Inputs: kernel [taps][cin][cout], bias / gamma / beta / mean / var [cout] or NULL (the four batch-norm arrays
  * together).  Outputs, each optional except b_fwd: w_fwd [cout_pad][taps][cin], w_bwd [(tap, ci)][cout_pad] and w_flip

@@ -176,6 +176,13 @@ bod_status bod_stage_conv_dgrad(int32_t device, int32_t route, const float* dz, 
                                 int32_t ksplit, int32_t groups, float* din, int32_t* info2);
 bod_status bod_stage_stem_pool_backward(int32_t device, int32_t precision, const float* stem_out, const float* dpool, int64_t dpool_elems,
                                         int32_t B, int32_t ih, int32_t iw, float* dz);
+enum { BOD_STEM_AUTO = 0, BOD_STEM_F32_POOL_F32 = 1, BOD_STEM_F32_POOL_SPLIT = 2, BOD_STEM_SEG64_POOL = 3, BOD_STEM_ROW_POOL = 4,
+       BOD_STEM_FUSED_8 = 5, BOD_STEM_FUSED_4 = 6, BOD_STEM_FUSED_SPLIT = 7 };
+bod_status bod_stage_stem(int32_t device, int32_t form, int32_t precision, const float* images, int32_t B, int32_t H, int32_t W,
+                          const float* w, const float* bias, int32_t misalign, int32_t n_cu, float sentinel, float* stem_out,
+                          float* pooled, int32_t* form_ran);
+bod_status bod_stage_stem_pool(int32_t device, int32_t mode, const float* stem, int32_t B, int32_t ih, int32_t iw, float sentinel,
+                               float* pooled);
 typedef struct bod_fold_layer {
     const float* kernel; const float* bias; const float* gamma; const float* beta; const float* mean; const float* var;
     int32_t taps, cin, cout, cout_pad;
