@@ -59,6 +59,12 @@ class BodJpegInfo(C.Structure):
                 ("restart_interval", C.c_int32), ("supported", C.c_int32), ("coef_count", C.c_int64)]
 
 
+class BodPngInfo(C.Structure):
+    """struct bod_png_info: what a PNG file's header says."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("bit_depth", C.c_int32), ("color_type", C.c_int32), ("channels", C.c_int32),
+                ("interlace", C.c_int32), ("supported", C.c_int32), ("raw_bytes", C.c_int64)]
+
+
 class BodCorruptOp(C.Structure):
     """bod_corrupt_op: one op of a frame's corruption chain (``corruptions.OP_DTYPE`` is the same layout as a NumPy dtype)."""
     _fields_ = [("kind", C.c_int32), ("f0", C.c_float), ("u0", C.c_uint32), ("tap_offset", C.c_int32), ("ksize", C.c_int32),
@@ -156,6 +162,16 @@ SIGNATURES = {
                                         C.POINTER(C.c_uint16), C.c_int32, C.c_uint64, C.POINTER(C.c_uint8)]),
     "bod_set_upload_corruption": (C.c_int, [_H, C.POINTER(BodCorruptOp), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint16),
                                             C.c_int32, C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_uint16), C.c_int32, C.c_uint64]),
+    "bod_png_info": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(BodPngInfo)]),
+    "bod_png_inflate": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_uint8), C.c_int64]),
+    "bod_png_decode_rgb": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int32,
+                                     C.POINTER(C.c_uint8), C.c_int64, _I]),
+    "bod_bench_png_decode": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "bod_upload_frames_png": (C.c_int, [_H, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), _F, C.c_int32, C.POINTER(BodAugment),
+                                        C.c_int32, _I]),
+    "bod_upload_frames_png_async": (C.c_int, [_H, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), _F, C.c_int32, C.POINTER(BodAugment),
+                                              C.c_int32, _I, C.c_int32]),
     "bod_device_images_buffer": (C.c_void_p, [_H, C.c_int32]),
     "bod_device_images": (C.c_void_p, [_H]),
     "bod_synchronize": (C.c_int, [_H]),

@@ -26,6 +26,8 @@ SOURCES = [
     ("train_kernels.hip", []),
     # integer code only (the JPEG inverse DCT, upsampling and colour conversion: DESIGN.md 9.11)
     ("jpeg_kernels.hip", []),
+    # integer code only (the PNG scanline filters' reconstruction: DESIGN.md 9.15)
+    ("png_kernels.hip", []),
     # frame corruptions: integer code, and fp32 ops whose order a NumPy restatement repeats
     ("corrupt_kernels.hip", ["-ffp-contract=off"]),
     ("engine.hip", []),

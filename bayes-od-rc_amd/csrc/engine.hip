@@ -5,10 +5,12 @@
 #include "../../include/bayesod.h"
 #include "kernels.h"
 #include "jpeg_entropy.h"
+#include "png_inflate.h"
 
 #include <algorithm>
 #include <array>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <condition_variable>
 #include <deque>
@@ -260,6 +262,24 @@ struct JpegSlot {
     }
 };
 
+// One PNG batch in flight (bod_upload_frames_png[_async], bod_png_decode_rgb), as JpegSlot: `pinned` holds the [n]
+// PngFrame records and, 128-byte aligned behind them, the filtered scanlines the host threads inflate; one copy takes both to `dev`.
+struct PngSlot {
+    char* pinned = nullptr; size_t pinned_cap = 0;
+    char* dev = nullptr; size_t dev_cap = 0;
+    hipEvent_t copied = nullptr;
+    // of the batch decoded last
+    int32_t n = 0, rows_per_band = 0;
+    size_t stage_bytes = 0, raw_base = 0;
+    int64_t rgb_bytes = 0;
+    void release() {
+        if (pinned) hipHostFree(pinned);
+        if (dev) hipFree(dev);
+        if (copied) hipEventDestroy(copied);
+        *this = PngSlot();
+    }
+};
+
 struct bod_context {
     bod_config cfg{};
     std::string err;
@@ -312,6 +332,7 @@ struct bod_context {
     RaggedTable rag_sync, rag_b[2];
     RaggedTable aug_sync, aug_b[2];       // the augmented uploads' own (their records are PreprocAugFrame, without factors)
     JpegSlot jpeg_slot[3];                              // JPEG uploads: one per image buffer, [2] the synchronous route's
+    PngSlot png_slot[3];                                // PNG uploads: the same
     // frame corruptions: the one-shot description bod_set_upload_corruption left for the next packed upload, and
     // each route's tables and scratch (indexed as jpeg_slot)
     CorruptSpec corrupt_pending;
@@ -2026,6 +2047,7 @@ bod_status bod_destroy(bod_handle h) {
     for (int k = 0; k < 2; ++k) { if (h->rag_b[k].dev) hipFree(h->rag_b[k].dev); if (h->ev_tab[k]) hipEventDestroy(h->ev_tab[k]); if (h->kscale_cur[k]) hipFree(h->kscale_cur[k]); }
     if (h->copy) { hipStreamSynchronize(h->copy); hipStreamDestroy(h->copy); }
     for (JpegSlot& js : h->jpeg_slot) js.release();
+    for (PngSlot& ps : h->png_slot) ps.release();
     for (CorruptSlot& cs : h->corrupt_slot) cs.release();
     for (int k = 0; k < 2; ++k) {
         if (h->d_u8_b[k]) hipFree(h->d_u8_b[k]);
@@ -2420,6 +2442,101 @@ static bod_status jpeg_enqueue(JpegSlot& s, const char* who, uint8_t* rgb_dst, h
     return BOD_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// PNG frames: chunk parsing and inflate on host threads (png_inflate.h), the scanline filters on the device
+// (png_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+// Host half of a batch, as jpeg_host_decode: parse every header, lay the batch out, wait until the previous copy has left the slot's
+// pinned staging, then inflate the files into it on `threads` threads (at most 16, at most one per frame).  Nothing is enqueued and
+// nothing of a handle changes here; `data` is no longer needed afterwards.  src_hw: [n][2].
+static bod_status png_host_decode(PngSlot& s, const char* who, int32_t n, const uint8_t* const* data, const int64_t* len, int32_t threads,
+                                  int32_t* src_hw, std::string* err) try {
+    std::vector<PngHeader> hd((size_t)n);
+    std::vector<PngFrame> fr((size_t)n);
+    int64_t raw = 0, rgb = 0;
+    int32_t max_h = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!data[i] || len[i] < 0) JPEG_FAIL(BOD_ERR_INVALID_ARG, "%s: frame %d has no data", who, i);
+        PngHeader& h = hd[(size_t)i];
+        if (png_parse(data[i], len[i], &h) != PNG_OK) JPEG_FAIL(BOD_ERR_INVALID_ARG, "%s: frame %d is corrupt: %s", who, i, h.msg);
+        if (!h.supported) JPEG_FAIL(BOD_ERR_INVALID_ARG, "%s: frame %d is not a supported PNG: %s", who, i, h.msg);
+        PngFrame& f = fr[(size_t)i];
+        f = PngFrame{};
+        f.raw_off = raw; f.rgb_off = rgb;
+        f.height = h.height; f.width = h.width; f.channels = h.channels;
+        raw += h.raw_bytes;                                        // (each at most 65535 * (1 + 4 * 65535): n of them stay far inside int64)
+        rgb += (int64_t)3 * h.height * h.width;
+        max_h = std::max(max_h, h.height);
+        src_hw[2 * i] = h.height; src_hw[2 * i + 1] = h.width;
+    }
+    const size_t raw_base = ((size_t)n * sizeof(PngFrame) + 127) & ~(size_t)127;
+    const size_t stage_bytes = raw_base + (size_t)raw;
+    if (s.copied && hipEventSynchronize(s.copied) != hipSuccess) JPEG_FAIL(BOD_ERR_HIP, "%s: waiting for the previous scanline copy failed", who);
+    if (stage_bytes > s.pinned_cap) {
+        if (s.pinned) hipHostFree(s.pinned);
+        s.pinned = nullptr; s.pinned_cap = 0;
+        if (hipHostMalloc(reinterpret_cast<void**>(&s.pinned), stage_bytes, hipHostMallocDefault) != hipSuccess) {
+            s.pinned = nullptr;
+            JPEG_FAIL(BOD_ERR_OOM, "%s: %zu bytes of pinned scanline staging", who, stage_bytes);
+        }
+        s.pinned_cap = stage_bytes;
+    }
+    uint8_t* raw_host = reinterpret_cast<uint8_t*>(s.pinned + raw_base);
+    std::vector<int> status((size_t)n, PNG_OK);
+    std::vector<std::array<char, 192>> msgs((size_t)n);
+    std::atomic<int> next{0};
+    auto work = [&]() {
+        for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
+            msgs[(size_t)i][0] = 0;
+            status[(size_t)i] = png_decode(data[i], len[i], hd[(size_t)i], raw_host + fr[(size_t)i].raw_off, msgs[(size_t)i].data(), msgs[(size_t)i].size());
+        }
+    };
+    const int workers = std::max(1, std::min(std::min(threads, 16), n));
+    {
+        // the calling thread is one of the workers: whatever could not be started is decoded here
+        std::vector<std::thread> pool;
+        pool.reserve((size_t)workers);
+        try { for (int k = 1; k < workers; ++k) pool.emplace_back(work); } catch (const std::system_error&) {}
+        work();
+        for (std::thread& t : pool) t.join();
+    }
+    for (int i = 0; i < n; ++i)
+        if (status[(size_t)i] != PNG_OK) JPEG_FAIL(BOD_ERR_INVALID_ARG, "%s: frame %d is corrupt: %s", who, i, msgs[(size_t)i].data());
+    std::memcpy(s.pinned, fr.data(), (size_t)n * sizeof(PngFrame));
+    s.n = n; s.stage_bytes = stage_bytes; s.raw_base = raw_base; s.rgb_bytes = rgb;
+    s.rows_per_band = std::min(PNG_MAX_BAND_ROWS, (max_h + 63) / 64 * 64);       // one thread per row; taller frames go band by band
+    return BOD_OK;
+} catch (const std::bad_alloc&) {
+    JPEG_FAIL(BOD_ERR_OOM, "%s: out of host memory for %d frame headers", who, n);
+}
+
+static PngArgs png_args(const PngSlot& s, uint8_t* rgb_dst) {
+    PngArgs a{};
+    a.frames = reinterpret_cast<const PngFrame*>(s.dev);
+    a.raw = reinterpret_cast<const uint8_t*>(s.dev + s.raw_base);
+    a.rgb = rgb_dst; a.n = s.n; a.rows_per_band = s.rows_per_band;
+    return a;
+}
+
+// Device half: one copy of the records + filtered scanlines, then the kernel, which leaves the packed RGB frames at rgb_dst (room
+// for s.rgb_bytes).  The slot's device buffer grows here; `stream` is the only stream that ever touches it.
+static bod_status png_enqueue(PngSlot& s, const char* who, uint8_t* rgb_dst, hipStream_t stream, std::string* err) {
+    if (s.stage_bytes > s.dev_cap) {
+        if (hipStreamSynchronize(stream) != hipSuccess) JPEG_FAIL(BOD_ERR_HIP, "%s: hipStreamSynchronize failed", who);
+        if (s.dev) hipFree(s.dev);
+        s.dev = nullptr; s.dev_cap = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&s.dev), s.stage_bytes) != hipSuccess) { s.dev = nullptr; JPEG_FAIL(BOD_ERR_OOM, "%s: %zu bytes of scanlines", who, s.stage_bytes); }
+        s.dev_cap = s.stage_bytes;
+    }
+    if (!s.copied && hipEventCreateWithFlags(&s.copied, hipEventDisableTiming) != hipSuccess) { s.copied = nullptr; JPEG_FAIL(BOD_ERR_HIP, "%s: hipEventCreate failed", who); }
+    const PngArgs a = png_args(s, rgb_dst);
+    hipError_t e = hipMemcpyAsync(s.dev, s.pinned, s.stage_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipEventRecord(s.copied, stream);
+    if (e == hipSuccess) e = launch_png_unfilter(a, stream);
+    if (e != hipSuccess) JPEG_FAIL(BOD_ERR_HIP, "%s: PNG device stage failed: %s", who, hipGetErrorString(e));
+    return BOD_OK;
+}
+
 // Frame corruptions: the pending one-shot description of bod_set_upload_corruption in a packed upload.  The host half
 // runs before anything of the upload is enqueued; the device half runs between the frames' arrival and the preprocess kernel and
 // consumes the description.
@@ -2439,9 +2556,10 @@ static bod_status corrupt_run_pending(bod_handle h, const char* who, CorruptSlot
 }
 
 // The synchronous upload of a packed batch: the ragged route (aug == nullptr) or the augmented one, which differ in their table and
-// their kernel only.  js != nullptr: the packed frames come from a decoded JPEG batch (jpeg_host_decode) instead of rgb_packed.
+// their kernel only.  js != nullptr: the packed frames come from a decoded JPEG batch (jpeg_host_decode) instead of rgb_packed;
+// ps != nullptr: from an inflated PNG batch (png_host_decode).
 static bod_status upload_packed(bod_handle h, const char* who, const uint8_t* rgb_packed, const int32_t* src_hw, const float* rgb_means,
-                                int32_t aspect_resize, const bod_augment* aug, JpegSlot* js = nullptr) {
+                                int32_t aspect_resize, const bod_augment* aug, JpegSlot* js = nullptr, PngSlot* ps = nullptr) {
     MarkerRange mr_api("bod:upload");
     BODCHK(join_overlap(h));
     const bod_config& c = h->cfg;
@@ -2464,6 +2582,10 @@ static bod_status upload_packed(bod_handle h, const char* who, const uint8_t* rg
     if (js) {
         std::string err;
         const bod_status st = jpeg_enqueue(*js, who, h->d_frames_u8, h->stream, &err);
+        if (st != BOD_OK) return h->fail(st, "%s", err.c_str());
+    } else if (ps) {
+        std::string err;
+        const bod_status st = png_enqueue(*ps, who, h->d_frames_u8, h->stream, &err);
         if (st != BOD_OK) return h->fail(st, "%s", err.c_str());
     } else {
         HIPCHK(h, hipMemcpyAsync(h->d_frames_u8, rgb_packed, bytes, hipMemcpyHostToDevice, h->stream));
@@ -2543,7 +2665,7 @@ bod_status bod_upload_frames_u8_async(bod_handle h, const uint8_t* rgb, int32_t 
 // The pipelined upload of a packed batch, ragged (aug == nullptr) or augmented.
 static bod_status upload_packed_async(bod_handle h, const char* who, const uint8_t* rgb_packed, const int32_t* src_hw,
                                       const float* rgb_means, int32_t aspect_resize, const bod_augment* aug, int32_t buffer,
-                                      JpegSlot* js = nullptr) {
+                                      JpegSlot* js = nullptr, PngSlot* ps = nullptr) {
     MarkerRange mr_api("bod:upload");
     if (buffer < 0 || buffer > 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: buffer must be 0 or 1", who);
     const bod_config& c = h->cfg;
@@ -2588,6 +2710,10 @@ static bod_status upload_packed_async(bod_handle h, const char* who, const uint8
     if (js) {
         std::string err;
         const bod_status st = jpeg_enqueue(*js, who, h->d_u8_b[buffer], h->copy, &err);
+        if (st != BOD_OK) return h->fail(st, "%s", err.c_str());
+    } else if (ps) {
+        std::string err;
+        const bod_status st = png_enqueue(*ps, who, h->d_u8_b[buffer], h->copy, &err);
         if (st != BOD_OK) return h->fail(st, "%s", err.c_str());
     } else {
         HIPCHK(h, hipMemcpyAsync(h->d_u8_b[buffer], rgb_packed, bytes, hipMemcpyHostToDevice, h->copy));
@@ -2648,6 +2774,61 @@ bod_status bod_upload_frames_jpeg_async(bod_handle h, const uint8_t* const* data
                                         int32_t aspect_resize, const bod_augment* aug, int32_t threads, int32_t* src_hw_out, int32_t buffer) {
     if (h && (buffer < 0 || buffer > 1)) return h->fail(BOD_ERR_INVALID_ARG, "bod_upload_frames_jpeg_async: buffer must be 0 or 1");
     return upload_jpeg(h, "bod_upload_frames_jpeg_async", data, len, rgb_means, aspect_resize, aug, threads, src_hw_out, buffer);
+}
+
+// The PNG upload routes, as upload_jpeg: the host inflate first (nothing of the handle has changed when it fails, and `data` is free
+// once it is done), then the ragged or augmented upload with the inflated batch in the place of the packed host frames.
+static bod_status upload_png(bod_handle h, const char* who, const uint8_t* const* data, const int64_t* len, const float* rgb_means,
+                             int32_t aspect_resize, const bod_augment* aug, int32_t threads, int32_t* src_hw_out, int32_t buffer) {
+    if (!h || !data || !len || !rgb_means) return BOD_ERR_INVALID_ARG;
+    if (buffer < -1 || buffer > 1) return h->fail(BOD_ERR_INVALID_ARG, "%s: buffer must be 0 or 1", who);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    PngSlot& ps = h->png_slot[buffer < 0 ? 2 : buffer];
+    std::vector<int32_t> hw((size_t)h->cfg.batch * 2);
+    std::string err;
+    const bod_status st = png_host_decode(ps, who, h->cfg.batch, data, len, threads, hw.data(), &err);
+    if (st != BOD_OK) return h->fail(st, "%s", err.c_str());
+    if (src_hw_out) std::memcpy(src_hw_out, hw.data(), hw.size() * sizeof(int32_t));
+    if (buffer < 0) return upload_packed(h, who, nullptr, hw.data(), rgb_means, aspect_resize, aug, nullptr, &ps);
+    return upload_packed_async(h, who, nullptr, hw.data(), rgb_means, aspect_resize, aug, buffer, nullptr, &ps);
+}
+
+bod_status bod_upload_frames_png(bod_handle h, const uint8_t* const* data, const int64_t* len, const float* rgb_means,
+                                 int32_t aspect_resize, const bod_augment* aug, int32_t threads, int32_t* src_hw_out) {
+    return upload_png(h, "bod_upload_frames_png", data, len, rgb_means, aspect_resize, aug, threads, src_hw_out, -1);
+}
+
+bod_status bod_upload_frames_png_async(bod_handle h, const uint8_t* const* data, const int64_t* len, const float* rgb_means,
+                                       int32_t aspect_resize, const bod_augment* aug, int32_t threads, int32_t* src_hw_out, int32_t buffer) {
+    if (h && (buffer < 0 || buffer > 1)) return h->fail(BOD_ERR_INVALID_ARG, "bod_upload_frames_png_async: buffer must be 0 or 1");
+    return upload_png(h, "bod_upload_frames_png_async", data, len, rgb_means, aspect_resize, aug, threads, src_hw_out, buffer);
+}
+
+// Header and inflate stage alone (bayesod.h): host only, no handle, no device.
+bod_status bod_png_info(const uint8_t* data, int64_t len, struct bod_png_info* out) {
+    if (!data || !out || len < 0) { g_create_error = "bod_png_info: NULL argument"; return BOD_ERR_INVALID_ARG; }
+    std::memset(out, 0, sizeof *out);
+    PngHeader h;
+    if (png_parse(data, len, &h) != PNG_OK) { g_create_error = std::string("bod_png_info: ") + h.msg; return BOD_ERR_INVALID_ARG; }
+    out->width = h.width; out->height = h.height; out->bit_depth = h.bit_depth; out->color_type = h.color_type;
+    out->channels = h.channels; out->interlace = h.interlace; out->supported = h.supported; out->raw_bytes = h.raw_bytes;
+    g_create_error = h.supported ? "" : std::string("bod_png_info: ") + h.msg;
+    return BOD_OK;
+}
+
+bod_status bod_png_inflate(const uint8_t* data, int64_t len, uint8_t* raw, int64_t raw_capacity) {
+    static const char* who = "bod_png_inflate";
+    if (!data || !raw || len < 0) { g_create_error = std::string(who) + ": NULL argument"; return BOD_ERR_INVALID_ARG; }
+    PngHeader h;
+    if (png_parse(data, len, &h) != PNG_OK) { g_create_error = std::string(who) + ": " + h.msg; return BOD_ERR_INVALID_ARG; }
+    if (!h.supported) { g_create_error = std::string(who) + ": not a supported PNG: " + h.msg; return BOD_ERR_INVALID_ARG; }
+    if (h.raw_bytes > raw_capacity) {
+        g_create_error = std::string(who) + ": the scanlines take " + std::to_string(h.raw_bytes) + " bytes, the buffer holds " + std::to_string(raw_capacity);
+        return BOD_ERR_INVALID_ARG;
+    }
+    char msg[192] = {0};
+    if (png_decode(data, len, h, raw, msg, sizeof msg) != PNG_OK) { g_create_error = std::string(who) + ": " + msg; return BOD_ERR_INVALID_ARG; }
+    return BOD_OK;
 }
 
 // Header and entropy stage alone (bayesod.h): host only, no handle, no device.
@@ -3961,6 +4142,78 @@ bod_status bod_jpeg_decode_rgb(int32_t device, int32_t n, const uint8_t* const* 
         hipStreamSynchronize(s);
         if (d_rgb) hipFree(d_rgb);
         js.release();
+        if (st != BOD_OK) snprintf(err, cap, "%s", e.c_str());
+        return st;
+    });
+}
+
+// The PNG decoder alone (bayesod.h): n files -> packed RGB on the host.  Stateless; its buffers live for the call.
+bod_status bod_png_decode_rgb(int32_t device, int32_t n, const uint8_t* const* data, const int64_t* len, int32_t threads,
+                              uint8_t* rgb_packed, int64_t rgb_capacity, int32_t* src_hw) {
+    static const char* who = "bod_png_decode_rgb";
+    if (n < 1 || !data || !len || !rgb_packed || !src_hw) { g_create_error = std::string(who) + ": NULL argument or no frame"; return BOD_ERR_INVALID_ARG; }
+    return pdq_call(device, [&](hipStream_t s, char* err, size_t cap) -> int {
+        PngSlot ps;
+        std::string e;
+        uint8_t* d_rgb = nullptr;
+        bod_status st = png_host_decode(ps, who, n, data, len, threads, src_hw, &e);
+        if (st == BOD_OK && ps.rgb_bytes > rgb_capacity) {
+            e = std::string(who) + ": the frames take " + std::to_string(ps.rgb_bytes) + " bytes, the buffer holds " + std::to_string(rgb_capacity);
+            st = BOD_ERR_INVALID_ARG;
+        }
+        if (st == BOD_OK && hipMalloc(reinterpret_cast<void**>(&d_rgb), (size_t)ps.rgb_bytes) != hipSuccess) {
+            d_rgb = nullptr; e = std::string(who) + ": out of device memory for the frames"; st = BOD_ERR_OOM;
+        }
+        if (st == BOD_OK) st = png_enqueue(ps, who, d_rgb, s, &e);
+        if (st == BOD_OK && (hipMemcpyAsync(rgb_packed, d_rgb, (size_t)ps.rgb_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                             hipStreamSynchronize(s) != hipSuccess)) {
+            e = std::string(who) + ": copying the frames back failed: " + hipGetErrorString(hipGetLastError()); st = BOD_ERR_HIP;
+        }
+        hipStreamSynchronize(s);
+        if (d_rgb) hipFree(d_rgb);
+        ps.release();
+        if (st != BOD_OK) snprintf(err, cap, "%s", e.c_str());
+        return st;
+    });
+}
+
+// The PNG decoder's two halves timed apart (bayesod.h; tests/tools/bench_png.py): the host half as the uploads run it, on the
+// library's own worker threads, by the host clock; png_unfilter_kernel alone by events around each launch.
+bod_status bod_bench_png_decode(int32_t device, int32_t n, const uint8_t* const* data, const int64_t* len, int32_t threads, int32_t iters,
+                                double* host_ms, double* kernel_ms) {
+    static const char* who = "bod_bench_png_decode";
+    if (n < 1 || iters < 1 || !data || !len || !host_ms || !kernel_ms) { g_create_error = std::string(who) + ": NULL argument, no frame or no iteration"; return BOD_ERR_INVALID_ARG; }
+    return pdq_call(device, [&](hipStream_t s, char* err, size_t cap) -> int {
+        PngSlot ps;
+        std::string e;
+        uint8_t* d_rgb = nullptr;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        std::vector<int32_t> hw((size_t)n * 2);
+        bod_status st = BOD_OK;
+        for (int i = 0; i < iters && st == BOD_OK; ++i) {
+            const auto t0 = std::chrono::steady_clock::now();
+            st = png_host_decode(ps, who, n, data, len, threads, hw.data(), &e);
+            host_ms[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        if (st == BOD_OK && hipMalloc(reinterpret_cast<void**>(&d_rgb), (size_t)ps.rgb_bytes) != hipSuccess) {
+            d_rgb = nullptr; e = std::string(who) + ": out of device memory for the frames"; st = BOD_ERR_OOM;
+        }
+        if (st == BOD_OK) st = png_enqueue(ps, who, d_rgb, s, &e);             // the copy, and one launch that is not timed
+        if (st == BOD_OK && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)) { e = std::string(who) + ": hipEventCreate failed"; st = BOD_ERR_HIP; }
+        for (int i = 0; i < iters && st == BOD_OK; ++i) {
+            float ms = 0.f;
+            hipError_t he = hipEventRecord(ev[0], s);
+            if (he == hipSuccess) he = launch_png_unfilter(png_args(ps, d_rgb), s);
+            if (he == hipSuccess) he = hipEventRecord(ev[1], s);
+            if (he == hipSuccess) he = hipEventSynchronize(ev[1]);
+            if (he == hipSuccess) he = hipEventElapsedTime(&ms, ev[0], ev[1]);
+            if (he != hipSuccess) { e = std::string(who) + ": timing the kernel failed: " + hipGetErrorString(he); st = BOD_ERR_HIP; }
+            kernel_ms[i] = ms;
+        }
+        hipStreamSynchronize(s);
+        for (hipEvent_t v : ev) if (v) hipEventDestroy(v);
+        if (d_rgb) hipFree(d_rgb);
+        ps.release();
         if (st != BOD_OK) snprintf(err, cap, "%s", e.c_str());
         return st;
     });

@@ -418,6 +418,28 @@ struct JpegArgs {
 hipError_t launch_jpeg_idct(const JpegArgs& a, hipStream_t s);
 hipError_t launch_jpeg_color(const JpegArgs& a, hipStream_t s);
 
+// PNG frames (png_kernels.hip): the host's inflate (png_inflate.h) leaves each frame's filtered scanlines -- per row a
+// filter-type byte the host has checked to be 0..4, then width * channels bytes --, the kernel reconstructs them (PNG specification,
+// section 9) into the packed uint8 RGB frames the ragged / augmented preprocess kernels read.  One record per frame, written and
+// validated on the host; every device address and every loop bound comes from it.
+struct PngFrame {              // 32 B
+    int64_t raw_off;           // first byte of the frame's filtered scanlines in the batch's buffer
+    int64_t rgb_off;           // first byte of the frame in the packed RGB buffer (PreprocFrame::offset)
+    int32_t height, width;
+    int32_t channels;          // 1 gray, 2 gray + alpha, 3 RGB, 4 RGBA (8 bits each): the filters' bytes per pixel
+    int32_t pad;
+};
+static_assert(sizeof(PngFrame) == 32, "PngFrame layout");
+struct PngArgs {
+    const PngFrame* frames;    // [n], device memory
+    const uint8_t* raw;        // the filtered scanlines of all frames
+    uint8_t* rgb;              // packed uint8 RGB frames
+    int32_t n;
+    int32_t rows_per_band;     // threads of a workgroup, one per row of a band: a multiple of 64, at most PNG_MAX_BAND_ROWS
+};
+constexpr int PNG_MAX_BAND_ROWS = 1024;
+hipError_t launch_png_unfilter(const PngArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------------
 // Loss forward (loss_kernels.hip)
 // ------------------------------------------------------------------------------------------------

@@ -29,6 +29,8 @@ IMAGE_UINT8_KEY = 'image_uint8'
 BOXES_2D_GT_SOURCE_KEY = 'boxes_2d_gt_source'
 # defer_decode: the raw bytes of a JPEG file the library decodes itself (Engine.upload_frames_jpeg), in place of IMAGE_UINT8_KEY
 IMAGE_JPEG_KEY = 'image_jpeg'
+# defer_png: the same for a PNG file (Engine.upload_frames_png)
+IMAGE_PNG_KEY = 'image_png'
 
 
 def check_data_dirs(folders):
@@ -52,50 +54,76 @@ def _decode(path):
         return np.asarray(im.convert('RGB'), dtype=np.uint8)
 
 
-def _deferred_jpeg(path):
-    """(file bytes, [h, w, 3]) when the file is a JPEG the library decodes on the device (``engine.jpeg_info``), else None: a PNG, a
-    progressive or CMYK JPEG, a corrupt header take the PIL path."""
+def _deferred_file(path, jpeg, png):
+    """(sample key, file bytes, [h, w, 3]) when the file is one the library decodes on the device -- a JPEG (``jpeg``:
+    ``engine.jpeg_info``) or a PNG (``png``: ``engine.png_info``) of the supported subset --, else None: any other file, a
+    progressive or CMYK JPEG, a palette, 16-bit or interlaced PNG, a corrupt header take the PIL path.  The file is read once."""
+    if not (jpeg or png):
+        return None
     from . import engine
     with open(path, 'rb') as fp:
         data = fp.read()
-    try:
-        info = engine.jpeg_info(data)
-    except ValueError:
-        return None
-    if not info['supported']:
-        return None
-    return data, np.asarray([info['height'], info['width'], 3], dtype=np.int32)
+    for wanted, key, probe in ((jpeg, IMAGE_JPEG_KEY, engine.jpeg_info), (png, IMAGE_PNG_KEY, engine.png_info)):
+        if not wanted:
+            continue
+        try:
+            info = probe(data)
+        except ValueError:
+            continue
+        if info['supported']:
+            return key, data, np.asarray([info['height'], info['width'], 3], dtype=np.int32)
+    return None
 
 
-class DeferredJpeg(object):
-    """A JPEG file waiting for the device decoder: its bytes and the (h, w, 3) shape its header gives."""
+class DeferredFile(object):
+    """An image file waiting for a device decoder: its bytes and the (h, w, 3) shape its header gives."""
 
     def __init__(self, data, shape):
         self.data, self.shape = data, tuple(int(v) for v in shape)
 
     def decode(self):
-        """The host route of a batch that cannot go up as JPEG: PIL's decode, which the device decoder equals byte for byte."""
+        """The host route of a batch that cannot go up as files of one kind: PIL's decode, which the device decoders equal byte for
+        byte."""
         import io
         from PIL import Image
         with Image.open(io.BytesIO(self.data)) as im:
             return np.asarray(im.convert('RGB'), dtype=np.uint8)
 
 
+class DeferredJpeg(DeferredFile):
+    """A JPEG file waiting for the device decoder."""
+
+
+class DeferredPng(DeferredFile):
+    """A PNG file waiting for the device decoder."""
+
+
+def sample_is_deferred(sample):
+    """Whether the sample carries a file's bytes for the device decoders in place of a decoded frame."""
+    return sample.get(IMAGE_JPEG_KEY) is not None or sample.get(IMAGE_PNG_KEY) is not None
+
+
 def sample_frame(sample):
-    """A sample's frame, whichever way it carries it: the uint8 RGB array, or a ``DeferredJpeg`` (``defer_decode`` handlers)."""
+    """A sample's frame, whichever way it carries it: the uint8 RGB array, a ``DeferredJpeg`` (``defer_decode`` handlers) or a
+    ``DeferredPng`` (``defer_png`` handlers)."""
     if sample.get(IMAGE_JPEG_KEY) is not None:
         return DeferredJpeg(sample[IMAGE_JPEG_KEY], sample[constants.ORIGINAL_IM_SIZE_KEY])
+    if sample.get(IMAGE_PNG_KEY) is not None:
+        return DeferredPng(sample[IMAGE_PNG_KEY], sample[constants.ORIGINAL_IM_SIZE_KEY])
     return sample[IMAGE_UINT8_KEY]
 
 
 def upload_frames(engine, frames, means, aspect_resize=True, aug=None):
-    """One batch of ``sample_frame`` results into the engine: all ``DeferredJpeg`` -> ``Engine.upload_frames_jpeg`` (decoded on
-    the device); with at least one decoded frame among them the JPEG members are decoded with PIL and the batch goes up by
-    ``upload_frames_u8_ragged`` (``aug``: ``upload_frames_u8_augmented``).  The image buffer is bit-identical either way."""
+    """One batch of ``sample_frame`` results into the engine: all ``DeferredPng`` -> ``Engine.upload_frames_png``, all
+    ``DeferredJpeg`` -> ``Engine.upload_frames_jpeg`` (decoded on the device); any other mixture has its deferred members decoded
+    with PIL and goes up by ``upload_frames_u8_ragged`` (``aug``: ``upload_frames_u8_augmented``).  The image buffer is
+    bit-identical either way."""
     frames = list(frames)
+    if frames and all(isinstance(f, DeferredPng) for f in frames):
+        return engine.upload_frames_png([f.data for f in frames], means, aspect_resize=aspect_resize, aug=aug)
     if frames and all(isinstance(f, DeferredJpeg) for f in frames):
         return engine.upload_frames_jpeg([f.data for f in frames], means, aspect_resize=aspect_resize, aug=aug)
-    frames = [f.decode() if isinstance(f, DeferredJpeg) else f for f in frames]
+    frames = [f.decode() if isinstance(f, DeferredFile) else f for f in frames]
     if aug is not None:
         return engine.upload_frames_u8_augmented(frames, aug, means, aspect_resize=aspect_resize)
     return engine.upload_frames_u8_ragged(frames, means, aspect_resize=aspect_resize)
@@ -109,6 +137,8 @@ class DatasetHandler(object):
         # True: a sample of a JPEG file the library decodes (engine.jpeg_info) carries the file's bytes under IMAGE_JPEG_KEY and no
         # IMAGE_UINT8_KEY / host-normalised image; the decode runs on the device at upload.  Other files: as before.
         self.defer_decode = False
+        # True: the same for a PNG file the library decodes (engine.png_info), under IMAGE_PNG_KEY
+        self.defer_png = False
 
 
 class BddDatasetHandler(DatasetHandler):
@@ -163,16 +193,16 @@ class BddDatasetHandler(DatasetHandler):
         return onehot, boxes.astype(np.float32), False
 
     def create_sample_dict(self, im_path, sample_id):
-        deferred = _deferred_jpeg(im_path) if self.defer_decode else None
+        deferred = _deferred_file(im_path, self.defer_decode, self.defer_png)
         if deferred is not None:
-            data, shape = deferred
+            key, data, shape = deferred
             cls_gt, box_gt, _ = self._read_labels(sample_id)
             placeholder = np.zeros(tuple(shape), np.float32)     # shape carrier: the pixels are produced on the device
             sample = create_sample_dict(placeholder, self.anchor_gen_config, box_gt, cls_gt, is_testing=self.is_testing,
                                         dense_targets=self.dense_targets)
             sample[constants.IMAGE_NORMALIZED_KEY] = None
             sample[constants.ORIGINAL_IM_SIZE_KEY] = shape
-            sample[IMAGE_JPEG_KEY] = data
+            sample[key] = data
             return sample
         rgb = _decode(im_path)
         norm = normalize_frame(rgb, self.im_normalization)
@@ -246,9 +276,9 @@ class KittiDatasetHandler(DatasetHandler):
     def create_sample_dict(self, im_path, label_path):
         """Anchors / targets are generated for the RESIZED frame (resize_shape); GT boxes are divided by the
         original size and multiplied by the final size as the reference does (:132-135)."""
-        deferred = _deferred_jpeg(im_path) if self.defer_decode else None
+        deferred = _deferred_file(im_path, self.defer_decode, self.defer_png)
         rgb = None if deferred is not None else _decode(im_path)
-        shape = deferred[1] if deferred is not None else np.asarray(rgb.shape, dtype=np.int32)
+        shape = deferred[2] if deferred is not None else np.asarray(rgb.shape, dtype=np.int32)
         cls_gt, box_gt, _ = self._read_labels(label_path)
         oh, ow = int(shape[0]), int(shape[1])
         nh, nw = self.resize_shape
@@ -260,7 +290,7 @@ class KittiDatasetHandler(DatasetHandler):
         sample[constants.IMAGE_NORMALIZED_KEY] = None
         sample[constants.ORIGINAL_IM_SIZE_KEY] = shape
         if deferred is not None:
-            sample[IMAGE_JPEG_KEY] = deferred[0]
+            sample[deferred[0]] = deferred[1]
         else:
             sample[IMAGE_UINT8_KEY] = rgb
         sample[BOXES_2D_GT_SOURCE_KEY] = box_gt_source

@@ -260,6 +260,37 @@ class Engine(object):
         args, _keep = _corruption_args(chains, self.B, frame_ids, ops_arrays)
         self._chk(self.lib.bod_set_upload_corruption(self.h, *args, int(seed) & 0xFFFFFFFFFFFFFFFF))
 
+    def _png_upload(self, files, means, aspect_resize, aug, threads, buffer):
+        from . import constants
+        ptrs, lens = _jpeg_files(files, self.B, "PNG")
+        m = np.ascontiguousarray(constants.MEANS_DICT['ImageNet'] if means is None else means, dtype=np.float32)
+        rec = None if aug is None else augment_records(aug, self.B)
+        recp = None if rec is None else rec.ctypes.data_as(C.POINTER(_lib.BodAugment))
+        src_hw = np.zeros((self.B, 2), np.int32)
+        threads = min(16, self.B) if threads is None else int(threads)
+        if buffer is None:
+            st = self.lib.bod_upload_frames_png(self.h, ptrs, lens, fptr(m), int(bool(aspect_resize)), recp, threads, iptr(src_hw))
+        else:
+            st = self.lib.bod_upload_frames_png_async(self.h, ptrs, lens, fptr(m), int(bool(aspect_resize)), recp, threads,
+                                                      iptr(src_hw), int(buffer))
+        self._chk(st)
+        return src_hw
+
+    def upload_frames_png(self, files, means=None, aspect_resize=True, aug=None, threads=None):
+        """``upload_frames_u8_ragged`` (``aug=None``) or ``upload_frames_u8_augmented`` of PNG files decoded inside the library
+        (``bod_upload_frames_png``): ``files`` is a list of ``batch`` ``bytes`` objects, each an 8-bit gray, RGB,
+        gray + alpha or RGBA PNG file without interlacing.  The inflate runs on ``threads`` host threads outside the GIL (default
+        ``min(16, batch)``), the scanline filters on the device; the image buffer ends up bit for bit as after the upload of PIL's
+        ``convert('RGB')`` decode of the files.  Returns the frames' sizes, int32 [batch, 2] (h, w).  ``ValueError`` naming the
+        frame for a corrupt or unsupported file (``png_info`` tells in advance); the handle and the frames it held stay as they
+        were."""
+        return self._png_upload(files, means, aspect_resize, aug, threads, None)
+
+    def upload_frames_png_async(self, files, buffer, means=None, aspect_resize=True, aug=None, threads=None):
+        """Pipelined form (``bod_upload_frames_png_async``), used like ``upload_frames_u8_ragged_async``.  The host inflate is
+        done when this returns: ``files`` need not be kept."""
+        return self._png_upload(files, means, aspect_resize, aug, threads, int(buffer))
+
     def _device_images(self, image_buffer):
         ptr = self.lib.bod_device_images(self.h) if image_buffer is None else self.lib.bod_device_images_buffer(self.h, int(image_buffer))
         if not ptr:
@@ -1289,14 +1320,14 @@ def pdq_frames(img_hw, num_gt, gt_boxes, num_det, det_boxes, det_corner_covs, de
     return fgs, bgs, dbgs, heat
 
 
-def _jpeg_files(files, batch=None):
-    """A list of bytes objects as the (const uint8_t* const*, const int64_t*) pair of the JPEG entry points."""
+def _jpeg_files(files, batch=None, kind="JPEG"):
+    """A list of bytes objects as the (const uint8_t* const*, const int64_t*) pair of the JPEG (and PNG) entry points."""
     files = list(files)
     if batch is not None and len(files) != batch:
-        raise ValueError("expected %d JPEG files, got %d" % (batch, len(files)))
+        raise ValueError("expected %d %s files, got %d" % (batch, kind, len(files)))
     for i, f in enumerate(files):
         if not isinstance(f, bytes):
-            raise ValueError("JPEG file %d must be a bytes object, got %s" % (i, type(f).__name__))
+            raise ValueError("%s file %d must be a bytes object, got %s" % (kind, i, type(f).__name__))
     ptrs = (C.c_char_p * len(files))(*files)
     lens = (C.c_int64 * len(files))(*[len(f) for f in files])
     return ptrs, lens
@@ -1402,6 +1433,74 @@ def corrupt_frames(frames, chains, frame_ids=None, seed=0, device=0, ops_arrays=
         res.append(out[off:off + 3 * h * w].reshape(h, w, 3))
         off += 3 * h * w
     return res
+
+
+def png_info(data):
+    """What a PNG file's header says (``bod_png_info``; host only): a dict of width, height, bit_depth, color_type, channels (bytes
+    per pixel of the filtered scanlines), interlace, raw_bytes, supported, and ``reason`` -- why not, for a well-formed file outside
+    the subset the library decodes (palette, 16-bit, interlaced, tRNS, ...; a file without the PNG signature, such as a JPEG, is
+    reported the same way).  ``ValueError`` for a corrupt header or chunk layout."""
+    lib = _lib.load()
+    if not isinstance(data, bytes):
+        raise ValueError("a PNG file must be a bytes object, got %s" % type(data).__name__)
+    info = _lib.BodPngInfo()
+    _lib.check(lib, None, lib.bod_png_info(data, len(data), C.byref(info)))
+    out = {name: int(getattr(info, name)) for name, _ in _lib.BodPngInfo._fields_}
+    out["supported"] = bool(info.supported)
+    reason = lib.bod_last_error(None)
+    out["reason"] = "" if info.supported else (reason.decode() if reason else "")
+    return out
+
+
+def png_inflate(data):
+    """The host half of the decoder alone (``bod_png_inflate``): the filtered scanlines, uint8 [height, 1 + width * channels] --
+    per row the filter-type byte, then the filtered bytes.  Equal to ``zlib.decompress`` of the file's concatenated IDAT chunks."""
+    lib = _lib.load()
+    info = png_info(data)
+    if not info["supported"]:
+        raise ValueError(info["reason"])
+    raw = np.empty(info["raw_bytes"], np.uint8)
+    _lib.check(lib, None, lib.bod_png_inflate(data, len(data), raw.ctypes.data_as(C.POINTER(C.c_uint8)), raw.size))
+    return raw.reshape(info["height"], 1 + info["width"] * info["channels"])
+
+
+def decode_png_rgb(files, device=0, threads=None):
+    """PNG files -> a list of uint8 [h, w, 3] RGB frames, decoded by the library (``bod_png_decode_rgb``: inflate on ``threads``
+    host threads, default ``min(16, len(files))``, the scanline filters on the device).  Equal to PIL's ``convert('RGB')``."""
+    lib = _lib.load()
+    ptrs, lens = _jpeg_files(files, kind="PNG")
+    n = len(lens)
+    if n == 0:
+        return []
+    total = 0
+    for i in range(n):
+        info = png_info(files[i])
+        if not info["supported"]:
+            raise ValueError("bod_png_decode_rgb: frame %d is not a supported PNG: %s" % (i, info["reason"]))
+        total += 3 * info["width"] * info["height"]
+    rgb = np.empty(total, np.uint8)
+    src_hw = np.zeros((n, 2), np.int32)
+    st = lib.bod_png_decode_rgb(int(device), n, ptrs, lens, min(16, n) if threads is None else int(threads),
+                                rgb.ctypes.data_as(C.POINTER(C.c_uint8)), rgb.size, iptr(src_hw))
+    _lib.check(lib, None, st)
+    out, off = [], 0
+    for h, w in src_hw:
+        out.append(rgb[off:off + 3 * h * w].reshape(h, w, 3))
+        off += 3 * h * w
+    return out
+
+
+def bench_png_decode(files, threads=16, iters=5, device=0):
+    """The PNG decoder's two halves timed apart (``bod_bench_png_decode``; tests/tools/bench_png.py): (host_ms [iters] -- the host
+    half of an upload of ``files`` on ``threads`` of the library's worker threads, by the host clock --, kernel_ms [iters] --
+    ``png_unfilter_kernel`` alone on the batch, by events)."""
+    lib = _lib.load()
+    ptrs, lens = _jpeg_files(files, kind="PNG")
+    host, kernel = np.zeros(int(iters), np.float64), np.zeros(int(iters), np.float64)
+    st = lib.bod_bench_png_decode(int(device), len(lens), ptrs, lens, int(threads), int(iters),
+                                  host.ctypes.data_as(C.POINTER(C.c_double)), kernel.ctypes.data_as(C.POINTER(C.c_double)))
+    _lib.check(lib, None, st)
+    return host, kernel
 
 
 def score_pairs(means, covs, targets, num_samples=1000, seed=0, first_row_id=0, device=0):

@@ -151,10 +151,12 @@ def _test_model_on_dataset(config, args, model):
     pipes = {}
     pending = []
     device_jpeg = bool(getattr(args, 'device_jpeg', False))
+    device_png = bool(getattr(args, 'device_png', False))
     corrupt = _corruption(args)              # --corrupt NAME:SEVERITY: frames are corrupted on the device at upload
-    # --device_jpeg and --corrupt form their batches as --mixed_sizes does
-    mixed = bool(getattr(args, 'mixed_sizes', False)) or device_jpeg or corrupt is not None
+    # --device_jpeg, --device_png and --corrupt form their batches as --mixed_sizes does
+    mixed = bool(getattr(args, 'mixed_sizes', False)) or device_jpeg or device_png or corrupt is not None
     handler.defer_decode = device_jpeg       # JPEG files travel as bytes and are decoded on the device at upload
+    handler.defer_png = device_png           # PNG files likewise
 
     def emit(dets):
         for (name, _, _), (classes, boxes_vuhw, covs, counts, *parts) in zip(pending, dets):
@@ -246,6 +248,10 @@ def main(argv=None):
     ap.add_argument('--device_jpeg', action='store_true', help='with --dataset: baseline JPEG files are decoded inside the library '
                     '(Huffman decoding on host threads, the rest on the GPU) instead of by PIL; batches as under --mixed_sizes; a batch '
                     'with any other file in it takes the PIL route; the outputs are identical either way')
+    ap.add_argument('--device_png', action='store_true', help='with --dataset: 8-bit gray / RGB / RGBA PNG files (KITTI) are decoded '
+                    'inside the library (inflate on host threads, the scanline filters on the GPU) instead of by PIL; batches as under '
+                    '--mixed_sizes; composes with --device_jpeg; a batch that is not all PNG (or all JPEG) takes the PIL route; the '
+                    'outputs are identical either way')
     ap.add_argument('--ensemble', type=str, nargs='+', default=None, help='weight files of an ensemble: every member runs the '
                     'yaml\'s mc_dropout_samples samples and ONE posterior is formed from all of them (overrides --weights)')
     ap.add_argument('--mc_passes', type=int, default=1, help='with --ensemble or --tta_flip: forwards per member (k passes of n '
@@ -278,6 +284,8 @@ def main(argv=None):
     config = config_utils.setup(config, args)
     if args.device_jpeg and not args.dataset:
         ap.error('--device_jpeg requires --dataset')
+    if args.device_png and not args.dataset:
+        ap.error('--device_png requires --dataset')
     try:
         return test_model(config, args)
     except ValueError as e:

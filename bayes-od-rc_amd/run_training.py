@@ -86,8 +86,8 @@ class Trainer(object):
         samples have no host image (IMAGE_NORMALIZED_KEY is None): their uint8 frames are resized and normalised on the device."""
         if self.augmentation is not None:
             return self._train_step_augmented(sample_dicts, learning_rate)
-        if any(s.get('image_jpeg') is not None for s in sample_dicts):     # --device_jpeg: JPEG files decoded at upload (DESIGN.md 9.11)
-            from . import datasets
+        from . import datasets
+        if any(datasets.sample_is_deferred(s) for s in sample_dicts):      # --device_jpeg / --device_png: files decoded at upload (DESIGN.md 9.11, 9.15)
             datasets.upload_frames(self.engine, [datasets.sample_frame(s) for s in sample_dicts], constants.MEANS_DICT[self.im_normalization],
                                    aspect_resize='boxes_2d_gt_source' in sample_dicts[0])
             imgs = None
@@ -271,10 +271,11 @@ def train(config, args):
         # one minibatch at a time
         handler = datasets.build_dataset(dataset_config, 'train')
         handler.dense_targets = False
-        device_jpeg = bool(getattr(args, 'device_jpeg', False))
+        device_jpeg, device_png = bool(getattr(args, 'device_jpeg', False)), bool(getattr(args, 'device_png', False))
         handler.defer_decode = device_jpeg       # JPEG files travel as bytes and are decoded on the device at upload
+        handler.defer_png = device_png           # PNG files likewise
         # (the augmented upload takes equal and mixed sizes alike: no buckets needed; --device_jpeg forms its minibatches the same way)
-        stream = stream_minibatches(handler, mb, mixed_sizes=bool(getattr(args, 'mixed_sizes', False)) or augmentation is not None or device_jpeg)
+        stream = stream_minibatches(handler, mb, mixed_sizes=bool(getattr(args, 'mixed_sizes', False)) or augmentation is not None or device_jpeg or device_png)
         pending = next(stream)                                        # the first minibatch also tells the frame size
         first = pending[0][constants.IMAGE_NORMALIZED_KEY]
         if hasattr(handler, 'resize_shape'):
@@ -426,9 +427,15 @@ def main(argv=None):
     ap.add_argument('--device_jpeg', action='store_true', help='with --dataset: baseline JPEG files are decoded inside the library '
                     '(Huffman decoding on host threads, the rest on the GPU) instead of by PIL; minibatches as under --mixed_sizes; '
                     '--augment passes its records through; a minibatch with any other file in it takes the PIL route')
+    ap.add_argument('--device_png', action='store_true', help='with --dataset: 8-bit gray / RGB / RGBA PNG files (KITTI) are decoded '
+                    'inside the library (inflate on host threads, the scanline filters on the GPU) instead of by PIL; minibatches as '
+                    'under --mixed_sizes; composes with --device_jpeg; --augment passes its records through; a minibatch that is not '
+                    'all PNG (or all JPEG) takes the PIL route')
     args = ap.parse_args(argv)
     if args.device_jpeg and not args.dataset:
         ap.error('--device_jpeg requires --dataset')
+    if args.device_png and not args.dataset:
+        ap.error('--device_png requires --dataset')
     config = config_utils.setup(config_utils.load_yaml(args.yaml_path), args)
     return train(config, args)
 

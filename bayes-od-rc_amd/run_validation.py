@@ -91,7 +91,8 @@ def validate_batch(model, config, batch, mixed_sizes=False, corruption=None):
     ``post_process_predictions`` give for the frame alone, plus the regularisation term (run_validation.py:252-258)."""
     dataset_config = config['dataset_config']
     first = batch[0][constants.IMAGE_NORMALIZED_KEY]
-    deferred = any(s.get('image_jpeg') is not None for s in batch)      # --device_jpeg: JPEG files decoded at upload (DESIGN.md 9.11)
+    # --device_jpeg / --device_png: files decoded at upload (DESIGN.md 9.11, 9.15)
+    deferred = any(s.get('image_jpeg') is not None or s.get('image_png') is not None for s in batch)
     # KITTI: the pixels are produced on the device (a deferred BDD JPEG has no host image either: the handler's extra key tells)
     on_device_resize = first is None and 'boxes_2d_gt_source' in batch[0] if deferred else first is None
     if on_device_resize:
@@ -325,6 +326,10 @@ def main(argv=None):
                     'GPU before preprocessing (run_inference --help lists the names; severity 1..5); batches as under --mixed_sizes')
     ap.add_argument('--corrupt_seed', type=int, default=0, help='seed of the random corruptions (a frame\'s noise depends on it and '
                     'on the frame\'s dataset index alone)')
+    ap.add_argument('--device_png', action='store_true', help='with --dataset: 8-bit gray / RGB / RGBA PNG files (KITTI) are decoded '
+                    'inside the library (inflate on host threads, the scanline filters on the GPU) instead of by PIL; batches as under '
+                    '--mixed_sizes; composes with --device_jpeg; a batch that is not all PNG (or all JPEG) takes the PIL route; the '
+                    'results are identical either way')
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error('--batch must be at least 1')
@@ -339,6 +344,8 @@ def main(argv=None):
             ap.error('--corrupt: %s' % e)
     if args.device_jpeg and not args.dataset:
         ap.error('--device_jpeg requires --dataset')
+    if args.device_png and not args.dataset:
+        ap.error('--device_png requires --dataset')
     config = config_utils.setup(config_utils.load_yaml(args.yaml_path), args)
     dataset_config = config['dataset_config']
     categories = None
@@ -348,6 +355,7 @@ def main(argv=None):
         handler = datasets.build_dataset(dataset_config, args.data_split)
         handler.dense_targets = False
         handler.defer_decode = bool(args.device_jpeg)
+        handler.defer_png = bool(args.device_png)
         samples, sample_ids = handler.create_dataset, list(handler.sample_ids)
         categories = handler.training_data_config['categories'] if dataset_config['dataset'] == 'bdd' else None
     else:
@@ -358,7 +366,7 @@ def main(argv=None):
         categories = ['car', 'truck', 'bus', 'person', 'rider', 'bike', 'motor'][:num_classes]
     kw = {} if corruption is None else {'corruption': corruption}
     return validate(config, samples, sample_ids, categories=categories, poll_seconds=args.poll or None, batch=args.batch,
-                    mixed_sizes=bool((args.mixed_sizes or args.device_jpeg or corruption is not None) and args.dataset), **kw)
+                    mixed_sizes=bool((args.mixed_sizes or args.device_jpeg or args.device_png or corruption is not None) and args.dataset), **kw)
 
 
 if __name__ == '__main__':

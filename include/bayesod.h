@@ -436,6 +436,53 @@ bod_status bod_corrupt_frames_u8(int32_t device, int32_t n, const uint8_t* rgb_p
 bod_status bod_set_upload_corruption(bod_handle h, const bod_corrupt_op* ops, int32_t ops_per_frame, const uint32_t* frame_ids,
                                      const uint16_t* taps, int32_t n_taps, const uint8_t* luts, int32_t n_luts,
                                      const uint16_t* qtables, int32_t n_qtables, uint64_t seed);
+/* PNG frames decoded inside the library, the JPEG entries' counterpart for KITTI's files.  Chunk parsing and the
+ * zlib inflate run on host threads (no zlib is linked); the reconstruction of the filtered scanlines (PNG specification section 9:
+ * None, Sub, Up, Average, Paeth) runs on the device and writes the uint8 RGB frames into the staging buffer the ragged / augmented
+ * preprocess kernels read: the decoded frame never exists on the host.  PNG is lossless: the frames equal PIL's
+ * Image.open(..).convert('RGB') byte for byte (RGBA loses its alpha, gray and gray + alpha give the gray byte three times).
+ * Supported: bit depth 8, colour type 0 (gray), 2 (RGB), 4 (gray + alpha) or 6 (RGBA), interlace method 0, no tRNS and no acTL
+ * chunk.  Palette images, bit depths 1, 2, 4 and 16, Adam7 interlacing and files with a tRNS or acTL chunk are well-formed but NOT
+ * supported: bod_png_info reports them with supported = 0 and the reason in bod_last_error(NULL) (so does a file without the PNG
+ * signature: a JPEG), the other entry points refuse them with BOD_ERR_INVALID_ARG.  A bad CRC-32 of a critical chunk or Adler-32,
+ * a truncated file or stream, a stream that gives more or fewer bytes than height * (1 + width * channels), a filter-type byte
+ * beyond 4, a width or height of 0 or beyond 65535 are BOD_ERR_INVALID_ARG (bod_png_info checks the header and the chunk layout;
+ * what lies inside IDAT is checked where it is inflated).
+ * (The struct has no typedef: in C a typedef would share the function's name space.) */
+struct bod_png_info {
+    int32_t width, height, bit_depth, color_type;
+    int32_t channels;                /* bytes per pixel of the filtered scanlines: 1, 3, 2 or 4 for colour type 0, 2, 4, 6 */
+    int32_t interlace;
+    int32_t supported;               /* 0: well-formed but outside the supported subset (the message says why) */
+    int64_t raw_bytes;               /* height * (1 + width * channels): what bod_png_inflate writes */
+};
+/* Header and inflate stage alone: host only, no handle, no device (as bod_jpeg_info); errors through bod_last_error(NULL).
+ * bod_png_inflate writes the filtered scanlines: per row one filter-type byte (0..4), then width * channels bytes. */
+bod_status bod_png_info(const uint8_t* data, int64_t len, struct bod_png_info* out);
+bod_status bod_png_inflate(const uint8_t* data, int64_t len, uint8_t* raw, int64_t raw_capacity);
+/* The decoder alone (as bod_jpeg_decode_rgb): n files -> packed RGB on the host (frame b at byte 3 * sum of h_i * w_i over i < b)
+ * + src_hw[n][2].  `threads` host threads inflate the files (capped at 16 and at n; <= 0 means 1). */
+bod_status bod_png_decode_rgb(int32_t device, int32_t n, const uint8_t* const* data, const int64_t* len,
+                              int32_t threads, uint8_t* rgb_packed, int64_t rgb_capacity, int32_t* src_hw);
+/* Measurement entry (as bod_bench_head_conv; tests/tools/bench_png.py): the decoder's two halves timed apart on n files.
+ * host_ms[iters]: the host half as the uploads run it -- headers, layout, inflate on `threads` of the library's worker threads
+ * into pinned staging -- by the host clock (the first iteration also allocates the staging).  kernel_ms[iters]:
+ * png_unfilter_kernel alone on the batch, by events around each launch, after one launch that is not timed. */
+bod_status bod_bench_png_decode(int32_t device, int32_t n, const uint8_t* const* data, const int64_t* len,
+                                int32_t threads, int32_t iters, double* host_ms, double* kernel_ms);
+/* The upload routes, word for word bod_upload_frames_jpeg[_async] with PNG files: inflated on `threads` host threads into pinned
+ * staging the handle owns (one per image buffer; the host waits for the previous copy out of it first), then the copy, the
+ * unfilter kernel and the ragged (aug == NULL) or augmented preprocess kernel run on the upload's stream.  Everything else is
+ * bod_upload_frames_u8_ragged[_async] / bod_upload_frames_u8_augmented[_async] of the decoded frames, bit for bit (geometry
+ * errors, per-frame KITTI factors, bod_set_upload_corruption).  The host stage finishes before the call returns: `data` is free
+ * on return.  A corrupt or unsupported frame gives BOD_ERR_INVALID_ARG naming the frame and the reason; nothing is enqueued, the
+ * handle and the frames it held stay as they were. */
+bod_status bod_upload_frames_png(bod_handle h, const uint8_t* const* data, const int64_t* len,
+                                 const float* rgb_means, int32_t aspect_resize, const bod_augment* aug,
+                                 int32_t threads, int32_t* src_hw_out);
+bod_status bod_upload_frames_png_async(bod_handle h, const uint8_t* const* data, const int64_t* len,
+                                       const float* rgb_means, int32_t aspect_resize, const bod_augment* aug,
+                                       int32_t threads, int32_t* src_hw_out, int32_t buffer);
 const float* bod_device_images_buffer(bod_handle h, int32_t buffer);
 const float* bod_device_images(bod_handle h);
 bod_status bod_synchronize(bod_handle h);

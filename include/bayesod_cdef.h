@@ -155,6 +155,25 @@ bod_status bod_corrupt_frames_u8(int32_t device, int32_t n, const uint8_t* rgb_p
 bod_status bod_set_upload_corruption(bod_handle h, const bod_corrupt_op* ops, int32_t ops_per_frame, const uint32_t* frame_ids,
                                      const uint16_t* taps, int32_t n_taps, const uint8_t* luts, int32_t n_luts,
                                      const uint16_t* qtables, int32_t n_qtables, uint64_t seed);
+struct bod_png_info {
+    int32_t width, height, bit_depth, color_type;
+    int32_t channels;
+    int32_t interlace;
+    int32_t supported;
+    int64_t raw_bytes;
+};
+bod_status bod_png_info(const uint8_t* data, int64_t len, struct bod_png_info* out);
+bod_status bod_png_inflate(const uint8_t* data, int64_t len, uint8_t* raw, int64_t raw_capacity);
+bod_status bod_png_decode_rgb(int32_t device, int32_t n, const uint8_t* const* data, const int64_t* len,
+                              int32_t threads, uint8_t* rgb_packed, int64_t rgb_capacity, int32_t* src_hw);
+bod_status bod_bench_png_decode(int32_t device, int32_t n, const uint8_t* const* data, const int64_t* len,
+                                int32_t threads, int32_t iters, double* host_ms, double* kernel_ms);
+bod_status bod_upload_frames_png(bod_handle h, const uint8_t* const* data, const int64_t* len,
+                                 const float* rgb_means, int32_t aspect_resize, const bod_augment* aug,
+                                 int32_t threads, int32_t* src_hw_out);
+bod_status bod_upload_frames_png_async(bod_handle h, const uint8_t* const* data, const int64_t* len,
+                                       const float* rgb_means, int32_t aspect_resize, const bod_augment* aug,
+                                       int32_t threads, int32_t* src_hw_out, int32_t buffer);
 const float* bod_device_images_buffer(bod_handle h, int32_t buffer);
 const float* bod_device_images(bod_handle h);
 bod_status bod_synchronize(bod_handle h);
