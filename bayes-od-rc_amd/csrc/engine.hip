@@ -4,6 +4,7 @@
 // -> RetinaNetModel.call.
 #include "../../include/bayesod.h"
 #include "kernels.h"
+#include "plane_tables.h"
 #include "jpeg_entropy.h"
 #include "png_inflate.h"
 
@@ -363,6 +364,7 @@ struct bod_context {
     bool plan_halo = false;                              // ... and box layer 1 / covariance layer 2 over the tail's 3x3 halo
     SparseTailArgs sparse{};
     int plan_tail_rows = 0;                              // rows per tile of the sparse tail launch (bod_plan_info_n slot 9; 0: no sparse tail)
+    int plan_stage_end = 0;                              // last block of stages 2-4 on the pixels the next stage reads (slot 10): 0 off, 1 the `2c`, 2 + stage 4's `2b`
     bool agg_sparse = false;                             // the last forward's agg[1] / agg[2] are sparse
     // Statistics handles (bod_config.mc_statistics): the accumulator of the bod_stat_* entry points -- a second set of the three
     // agg[] arrays holding the merged statistics of stat_k samples.  agg[] itself receives every bod_stat_forward's fresh record (from
@@ -512,31 +514,33 @@ bod_status new_plane(bod_context* h, Plane* p, int B, int hh, int ww, int C) {
     return h->dalloc(&p->d, (size_t)B * p->bstride * C * h->es);
 }
 
-// row table for plane -> plane convolutions. org_* = padded coordinate of the window origin of
-// output (0,0); res optional (nearest-upsampled when its size differs).
-bod_status make_table(bod_context* h, const std::string& key, int B, const Plane& in, const Plane& out,
-                      int stride, int org_y, int org_x, const Plane* res, const RowEnt** tbl) {
+// row table for plane -> plane convolutions (plane_tables.h). org_* = padded coordinate of the window origin of
+// output (0,0); res optional (nearest-upsampled when its size differs); out_step 2: the output pixels
+// (2y, 2x) only -- no allocation of its own: the table lives in the second halves of the dense table's entries (dense_key; built here
+// if no conv has asked for it yet) and is taken half an entry further on (plane_tables.h, plane_step_view).  *M = rows of the table.
+PlaneGeom plane_geom(const Plane& p) { return PlaneGeom{p.base, p.bstride, p.pitch, p.h, p.w}; }
+
+bod_status make_table(bod_context* h, const std::string& key, const std::string& dense_key, int B, const Plane& in, const Plane& out,
+                      int stride, int org_y, int org_x, const Plane* res, int out_step, const RowEnt** tbl, int* M) {
+    *M = B * plane_step_count(out.h, out_step) * plane_step_count(out.w, out_step);
     auto it = h->tables.find(key);
     if (it != h->tables.end()) { *tbl = it->second; return BOD_OK; }
-    std::vector<RowEnt> rows((size_t)B * out.h * out.w);
-    size_t r = 0;
-    for (int b = 0; b < B; ++b)
-        for (int y = 0; y < out.h; ++y)
-            for (int x = 0; x < out.w; ++x) {
-                RowEnt e{};
-                e.in_off = (int32_t)(in.base + b * in.bstride + (int64_t)(y * stride + org_y) * in.pitch + (x * stride + org_x));
-                e.in_pitch = in.pitch;
-                e.out_off = (int32_t)(out.base + b * out.bstride + (int64_t)(y + 1) * out.pitch + (x + 1));
-                if (res) {
-                    int ry = y, rx = x;
-                    if (res->h != out.h || res->w != out.w) {
-                        ry = std::min((int)std::floor((y + 0.5) * ((double)res->h / out.h)), res->h - 1);
-                        rx = std::min((int)std::floor((x + 0.5) * ((double)res->w / out.w)), res->w - 1);
-                    }
-                    e.res_off = (int32_t)(res->base + b * res->bstride + (int64_t)(ry + 1) * res->pitch + (rx + 1));
-                }
-                rows[r++] = e;
-            }
+    std::vector<RowEnt> rows;
+    const PlaneGeom gi = plane_geom(in), go = plane_geom(out), gr = res ? plane_geom(*res) : PlaneGeom{};
+    plane_row_table(B, gi, go, stride, org_y, org_x, res ? &gr : nullptr, out_step, rows);
+    if (out_step != 1) {
+        const RowEnt* dense = nullptr;
+        int Md = 0;
+        BODCHK(make_table(h, dense_key, dense_key, B, in, out, stride, org_y, org_x, res, 1, &dense, &Md));
+        RowEnt* view = const_cast<RowEnt*>(dense);          // (a 1 x 1 plane: the step-2 table is the dense table)
+        if (rows.size() < (size_t)Md) {
+            view = const_cast<RowEnt*>(plane_step_view(dense));
+            HIPCHK(h, hipMemcpy2D(view, sizeof(RowEnt), rows.data(), sizeof(RowEnt), PLANE_STEP_VIEW_BYTES, rows.size(), hipMemcpyHostToDevice));
+        }
+        h->tables[key] = view;
+        *tbl = view;
+        return BOD_OK;
+    }
     RowEnt* d = nullptr;
     BODCHK(h->dalloc(&d, rows.size(), false));
     HIPCHK(h, hipMemcpyAsync(d, rows.data(), rows.size() * sizeof(RowEnt), hipMemcpyHostToDevice, h->stream));
@@ -651,7 +655,7 @@ void to_split_args(ConvArgs* a) {
 // conv + folded BN (+residual) (+ReLU) between two planes
 bod_status add_conv(bod_context* h, const std::string& name, const std::string& bn, const Plane& in,
                     const Plane& out, int stride, bool same, bool relu, const Plane* res,
-                    char* out_relu = nullptr) {
+                    char* out_relu = nullptr, int out_step = 1, bool even_rows = false) {
     PackedConv pc;
     BODCHK(pack_conv(h, name, bn, 64, &pc));
     if (pc.cin != in.C || pc.cout != out.C)
@@ -661,16 +665,18 @@ bod_status add_conv(bod_context* h, const std::string& name, const std::string& 
     int oy = 1, ox = 1;
     if (same) { oy = 1 - same_pad_before(in.h, kh, stride); ox = 1 - same_pad_before(in.w, pc.kw, stride); }
     // the table depends on plane geometry only (offsets are relative to each buffer's base)
-    char key[256];
-    snprintf(key, sizeof key, "pp:%lld,%lld,%d:%lld,%lld,%d,%d,%d:%d:%d:%d:%lld,%lld,%d,%d,%d", (long long)in.base,
-             (long long)in.bstride, in.pitch, (long long)out.base, (long long)out.bstride, out.pitch, out.h, out.w,
-             stride, oy, ox, res ? (long long)res->base : -1LL, res ? (long long)res->bstride : 0LL,
-             res ? res->pitch : 0, res ? res->h : 0, res ? res->w : 0);
+    char key[256], dense_key[256];
+    for (int k = 0; k < 2; ++k)
+        snprintf(k ? dense_key : key, sizeof key, "pp:%lld,%lld,%d:%lld,%lld,%d,%d,%d:%d:%d:%d:%lld,%lld,%d,%d,%d:%d", (long long)in.base,
+                 (long long)in.bstride, in.pitch, (long long)out.base, (long long)out.bstride, out.pitch, out.h, out.w,
+                 stride, oy, ox, res ? (long long)res->base : -1LL, res ? (long long)res->bstride : 0LL,
+                 res ? res->pitch : 0, res ? res->h : 0, res ? res->w : 0, k ? 1 : out_step);
     const RowEnt* tbl = nullptr;
     const int B = h->cfg.batch;
-    BODCHK(make_table(h, key, B, in, out, stride, oy, ox, res, &tbl));
+    int M = 0;
+    BODCHK(make_table(h, key, dense_key, B, in, out, stride, oy, ox, res, out_step, &tbl, &M));
     Op op; op.kind = Op::CONV;
-    op.conv = base_args(pc, tbl, B * out.h * out.w, in.C, out.C);
+    op.conv = base_args(pc, tbl, M, in.C, out.C);
     op.conv.g[0] = ConvGroup{in.d, pc.w, pc.bias, out.d, res ? res->d : nullptr, out_relu, 0, 0, nullptr, nullptr, nullptr, 0, 0};
     op.conv.flags = relu ? CONV_RELU : 0;
     op.flops = 2.0 * op.conv.M * pc.cout * pc.taps * pc.cin;
@@ -682,7 +688,9 @@ bod_status add_conv(bod_context* h, const std::string& name, const std::string& 
     // stage 3-5 at batch 1): enough splits for >= ~256 workgroups, each keeping >= 4 K-tiles.
     static const bool splitk_on = [] { const char* e = getenv("BOD_CONV_SPLITK"); return !e || atoi(e) != 0; }();
     if (splitk_on && (h->es == 2 || h->split)) {
-        const long tiles = (long)((op.conv.M + 127) / 128) * (pc.cout_pad % 128 == 0 ? pc.cout_pad / 128 : pc.cout_pad / 64);
+        // (counted on the whole plane also where the table holds a part of it -- out_step, even_rows: a pixel's summation order must
+        //  not depend on BOD_STAGE_END_PIXELS)
+        const long tiles = (long)((B * out.h * out.w + 127) / 128) * (pc.cout_pad % 128 == 0 ? pc.cout_pad / 128 : pc.cout_pad / 64);
         const int chunks = pc.cin * (h->split ? 2 : 1) / 64;          // K-tiles per tap (bf16x3: 32 channels per K-tile)
         int S = 1;
         while (tiles * S < 256 && S * 2 <= 16 && chunks % (S * 2) == 0 && (long)pc.taps * (chunks / (S * 2)) >= 4) S *= 2;
@@ -701,12 +709,18 @@ bod_status add_conv(bod_context* h, const std::string& name, const std::string& 
         pc.cin == 256 && pc.cout == 256 && pc.cout_pad == 256 && !res && !out_relu && in.h == out.h && in.w == out.w) {
         ConvArgs probe = op.conv;
         if (conv_igemm_uses_full_cout_tile(probe)) {
-            const std::string xkey = std::string(key) + ":xr";
+            // even_rows (the `2b` of stage 4's last block, build_plan): tiles of the even output rows only, all x -- runs stay
+            // x-adjacent and tiles full; the odd rows are read by nobody (plane_tables.h).  Only where the launch keeps the 256x256
+            // tile with half the rows (the kernel's launch rule, conv_igemm.hip, sees the table's M): otherwise every row as before.
+            bool even = even_rows;
+            if (even) { ConvArgs half = op.conv; half.M = B * plane_step_count(out.h, 2) * out.w; even = conv_igemm_uses_full_cout_tile(half); }
+            const std::string xkey = std::string(key) + (even ? ":xr:even" : ":xr");
             auto it = h->xr_tables.find(xkey);
             if (it == h->xr_tables.end()) {
                 std::vector<RowEnt> rows((size_t)op.conv.M), tiled;
                 std::vector<ExtRow> ext;
                 HIPCHK(h, hipMemcpy(rows.data(), tbl, rows.size() * sizeof(RowEnt), hipMemcpyDeviceToHost));
+                if (even) { std::vector<RowEnt> dense; dense.swap(rows); plane_rows_of_even_y(dense, B, out.h, out.w, rows); }
                 if (!xr_tile_rows(rows, tiled, ext)) return h->fail(BOD_ERR_INVALID_ARG, "row-reuse tiling of '%s': extended rows out of order", name.c_str());
                 bod_context::XrTable t;
                 t.m = (int)tiled.size();
@@ -717,6 +731,7 @@ bod_status add_conv(bod_context* h, const std::string& name, const std::string& 
                 it = h->xr_tables.emplace(xkey, t).first;
             }
             op.conv.rows = it->second.rows; op.conv.ext = it->second.ext; op.conv.M = it->second.m; op.conv.xreuse = 2;
+            if (even) op.flops = 2.0 * B * plane_step_count(out.h, 2) * out.w * pc.cout * pc.taps * pc.cin;
         }
     }
     h->ops.push_back(op);
@@ -834,6 +849,15 @@ bod_status build_plan(bod_context* h) {
     const char* blocks[6] = {"", "", "abc", "abcd", c.backbone_depth == 101 ? "abcdefghijklmnopqrstuvw" : "abcdef", "abc"};
     const int f1s[6] = {0, 0, 64, 128, 256, 512};
     Plane taps[6];
+    // The last block of stages 2, 3 and 4 (res2c, res3d, res4f / res4w) has ONE reader: the next stage's ConvBlock, whose `2a` and
+    // `branch1` are 1x1, stride 2, VALID -- pixel (2y, 2x) and nothing else (the FPN taps are the block-'a' outputs, below).  Its `2c`
+    // therefore runs on a table of those pixels alone (plane_tables.h, out_step = 2): a quarter of the rows, written to the same
+    // positions of the same plane, so the next stage's launches are untouched; the other pixels keep stale values nobody reads.
+    // Stage 4's `2b` (row-reuse tiles) computes the even rows only.  Inference handles; BOD_STAGE_END_PIXELS=0: the whole planes
+    // (A/B, bit-identical downstream), =1: the `2c` alone.  bod_plan_info_n slot 10.
+    int stage_end = train_mode ? 0 : 2;
+    if (const char* e = getenv("BOD_STAGE_END_PIXELS")) stage_end = std::min(stage_end, std::max(atoi(e), 0));
+    h->plan_stage_end = stage_end;
     for (int st = 2; st <= 5; ++st) {
         const int f1 = f1s[st], f3 = f1 * 4, hh = h->ch[st], ww = h->cw[st];
         const int first_stride = st == 2 ? 1 : 2;
@@ -987,8 +1011,9 @@ bod_status build_plan(bod_context* h) {
             } else {
                 if (!pw_t1_ready) BODCHK(add_conv(h, c_ + "2a", b_ + "2a", x, t1, 1, false, true, nullptr));
                 pw_t1_ready = false;
-                BODCHK(add_conv(h, c_ + "2b", b_ + "2b", t1, t2, 1, true, true, nullptr));
-                BODCHK(add_conv(h, c_ + "2c", b_ + "2c", t2, out, 1, false, true, &x));
+                const bool stage_end_blk = bl[1] == 0 && st <= 4;          // read at the pixels (2y, 2x) only (above)
+                BODCHK(add_conv(h, c_ + "2b", b_ + "2b", t1, t2, 1, true, true, nullptr, nullptr, 1, stage_end_blk && stage_end >= 2 && st == 4));
+                BODCHK(add_conv(h, c_ + "2c", b_ + "2c", t2, out, 1, false, true, &x, nullptr, stage_end_blk && stage_end >= 1 ? 2 : 1));
                 BODCHK(fuse_next_2a(bl));
             }
             x = out;
@@ -4405,11 +4430,12 @@ bod_status bod_plan_info(bod_handle h, int32_t* info8) {
 
 bod_status bod_plan_info_n(bod_handle h, int32_t* info, int32_t n) {
     if (!h || !info || n < 0) return BOD_ERR_INVALID_ARG;
-    int32_t all[10];
+    int32_t all[11];
     BODCHK(bod_plan_info(h, all));
     all[8] = h->plan_halo;
     all[9] = h->plan_tail_rows;
-    for (int i = 0; i < n && i < 10; ++i) info[i] = all[i];
+    all[10] = h->plan_stage_end;
+    for (int i = 0; i < n && i < 11; ++i) info[i] = all[i];
     return BOD_OK;
 }
 

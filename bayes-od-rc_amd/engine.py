@@ -863,12 +863,13 @@ class Engine(object):
 
     def plan_info(self):
         """{'aggregating', 'fused_head_outputs', 'row_reuse', 'fan_out_row_reuse', 'ops', 'plane_row_reuse_layers', 'tower_mx',
-        'sparse_tail', 'sparse_halo', 'sparse_tail_rows'} of the forward plan (bod_plan_info_n)."""
-        info = (C.c_int32 * 10)()
-        self._chk(self.lib.bod_plan_info_n(self.h, info, 10))
+        'sparse_tail', 'sparse_halo', 'sparse_tail_rows', 'stage_end_pixels'} of the forward plan (bod_plan_info_n)."""
+        info = (C.c_int32 * 11)()
+        self._chk(self.lib.bod_plan_info_n(self.h, info, 11))
         return {"aggregating": bool(info[0]), "fused_head_outputs": bool(info[1]), "row_reuse": bool(info[2]),
                 "fan_out_row_reuse": bool(info[3]), "ops": int(info[4]), "plane_row_reuse_layers": int(info[5]), "tower_mx": bool(info[6]), "tower_mx_format": int(info[6]),
-                "sparse_tail": bool(info[7]), "sparse_halo": bool(info[8]), "sparse_tail_rows": int(info[9])}
+                "sparse_tail": bool(info[7]), "sparse_halo": bool(info[8]), "sparse_tail_rows": int(info[9]),
+                "stage_end_pixels": int(info[10])}
 
     @property
     def aggregating(self):

@@ -903,9 +903,11 @@ bod_status bod_device_detection_class_parts(bod_handle h, int32_t slot, void** p
  * (BOD_PRECISION_F16MX / BOD_PRECISION_F16MX4), [7] = 1 when the box / covariance heads' last layers run over the pixels with a kept
  * anchor only (the sparse tail; BOD_SPARSE_TAIL=0: dense). */
 bod_status bod_plan_info(bod_handle h, int32_t* info8);
-/* bod_plan_info with more slots: fills info[0 .. min(n, 10) - 1]; [0..7] as above, [8] = 1 when box layer 1 and covariance layer 2
+/* bod_plan_info with more slots: fills info[0 .. min(n, 11) - 1]; [0..7] as above, [8] = 1 when box layer 1 and covariance layer 2
  * also run only over the 3x3 dilation of the sparse tail's pixels (the sparse halo; BOD_SPARSE_HALO=0: dense, as before), [9] = rows
- * per tile of the sparse tail's launch: 192, or 256 with BOD_SPARSE_TAIL_ROWS=256 (0 without a sparse tail). */
+ * per tile of the sparse tail's launch: 192, or 256 with BOD_SPARSE_TAIL_ROWS=256 (0 without a sparse tail), [10] = the last block of
+ * ResNet stages 2-4 on the pixels the next stage reads: 0 whole planes (training handles, BOD_STAGE_END_PIXELS=0), 1 the `2c` layers,
+ * 2 the `2c` layers and stage 4's `2b`. */
 bod_status bod_plan_info_n(bod_handle h, int32_t* info, int32_t n);
 
 /* ---- mergeable MC statistics (handles created with mc_statistics = 1): ensembles of several weight sets, more samples than one
