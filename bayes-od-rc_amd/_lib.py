@@ -71,6 +71,14 @@ class BodCorruptOp(C.Structure):
                 ("table", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class BodRenderOptions(C.Structure):
+    """bod_render_options: view, line width, labels and contour radius of bod_render_frames_u8."""
+    _fields_ = [("view", C.c_int32), ("line_width", C.c_int32), ("labels", C.c_int32), ("r2", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+BOD_RENDER_OVERLAY, BOD_RENDER_HEAT = 0, 1
+
+
 class BodFoldLayer(C.Structure):
     """bod_fold_layer: one layer of bod_stage_fold_pack (inputs, geometry, host output arrays)."""
     _fields_ = [("kernel", C.POINTER(C.c_float)), ("bias", C.POINTER(C.c_float)), ("gamma", C.POINTER(C.c_float)),
@@ -162,6 +170,9 @@ SIGNATURES = {
                                         C.POINTER(C.c_uint16), C.c_int32, C.c_uint64, C.POINTER(C.c_uint8)]),
     "bod_set_upload_corruption": (C.c_int, [_H, C.POINTER(BodCorruptOp), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint16),
                                             C.c_int32, C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_uint16), C.c_int32, C.c_uint64]),
+    "bod_render_frames_u8": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_uint8), _I, _I, _I, _F, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                       _I, _I, C.POINTER(BodRenderOptions), C.POINTER(C.c_uint8), _I]),
+    "bod_render_font": (C.c_int, [C.POINTER(C.c_uint8), _I]),
     "bod_png_info": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(BodPngInfo)]),
     "bod_png_inflate": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_uint8), C.c_int64]),
     "bod_png_decode_rgb": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int32,

@@ -30,6 +30,8 @@ SOURCES = [
     ("png_kernels.hip", []),
     # frame corruptions: integer code, and fp32 ops whose order a NumPy restatement repeats
     ("corrupt_kernels.hip", ["-ffp-contract=off"]),
+    # rendering: integer code, and the ellipse coverage in fp32 whose operation order a NumPy restatement repeats
+    ("render_kernels.hip", ["-ffp-contract=off"]),
     ("engine.hip", []),
 ]
 # -fno-slp-vectorize (round 6): NO packed fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) in any kernel of

@@ -7,6 +7,7 @@
 #include "plane_tables.h"
 #include "jpeg_entropy.h"
 #include "png_inflate.h"
+#include "render_font.h"
 
 #include <algorithm>
 #include <array>
@@ -4139,6 +4140,31 @@ bod_status bod_set_upload_corruption(bod_handle h, const bod_corrupt_op* ops, in
                                      n_qtables, seed, &spec, err, sizeof err);
     if (st != BOD_OK) return h->fail((bod_status)st, "%s", err);
     h->corrupt_pending = std::move(spec);
+    return BOD_OK;
+}
+
+// The rendering stage (bayesod.h; render_kernels.hip).  Stateless; arguments are checked before a device is looked for.
+bod_status bod_render_frames_u8(int32_t device, int32_t n, const uint8_t* rgb_packed_in, const int32_t* src_hw, const int32_t* num_det,
+                                const int32_t* det_boxes, const float* det_corner_covs, const uint8_t* det_colors, const uint8_t* det_text,
+                                const int32_t* num_gt, const int32_t* gt_boxes, const bod_render_options* opt, uint8_t* rgb_packed_out,
+                                int32_t* skipped_ellipses) {
+    {
+        char err[512] = {0};
+        const int st = render_validate(n, rgb_packed_in, src_hw, num_det, det_boxes, det_corner_covs, det_colors, det_text, num_gt, gt_boxes, opt,
+                                       rgb_packed_out, err, sizeof err);
+        g_create_error = err;
+        if (st != BOD_OK || n == 0) return (bod_status)st;
+    }
+    return pdq_call(device, [&](hipStream_t s, char* err, size_t cap) -> int {
+        return render_frames_run(n, rgb_packed_in, src_hw, num_det, det_boxes, det_corner_covs, det_colors, det_text, num_gt, gt_boxes, opt,
+                                 rgb_packed_out, skipped_ellipses, s, err, cap);
+    });
+}
+
+bod_status bod_render_font(uint8_t* glyph_rows, int32_t* count) {
+    if (!count) { g_create_error = "bod_render_font: count is NULL"; return BOD_ERR_INVALID_ARG; }
+    *count = RENDER_FONT_COUNT;
+    if (glyph_rows) memcpy(glyph_rows, RENDER_FONT, sizeof RENDER_FONT);
     return BOD_OK;
 }
 

@@ -617,6 +617,19 @@ int pdq_corner_heatmaps_run(int H, int W, int n, const double* means_yx, const d
 int pdq_frames_run(int H, int W, int F, const int32_t* num_gt, const int32_t* gt_boxes, const int32_t* num_det, const int32_t* det_boxes,
                    const double* det_corner_covs, double* fg_loss, double* bg_loss, double* det_bg_loss, float* heatmaps, hipStream_t s,
                    char* errbuf, size_t errcap);
+// bod_pdq_frames' box heatmaps of one frame's rows, left on the device in d_heat [nd][H][W] (NULL: validate only); *bad_row names a
+// refused row.  The rendering stage's HEAT view composes them (render_kernels.hip).
+int pdq_box_heatmaps_device(int H, int W, int nd, const int32_t* det_boxes, const float* det_corner_covs, float* d_heat, int* bad_row,
+                            hipStream_t s, char* errbuf, size_t errcap);
+// Rendering (render_kernels.hip): host drivers of bod_render_frames_u8, same conventions.  render_validate needs no
+// device and runs first.
+int render_validate(int32_t n, const uint8_t* rgb_in, const int32_t* src_hw, const int32_t* num_det, const int32_t* det_boxes,
+                    const float* det_corner_covs, const uint8_t* det_colors, const uint8_t* det_text, const int32_t* num_gt,
+                    const int32_t* gt_boxes, const bod_render_options* opt, uint8_t* rgb_out, char* errbuf, size_t errcap);
+int render_frames_run(int32_t n, const uint8_t* rgb_in, const int32_t* src_hw, const int32_t* num_det, const int32_t* det_boxes,
+                      const float* det_corner_covs, const uint8_t* det_colors, const uint8_t* det_text, const int32_t* num_gt,
+                      const int32_t* gt_boxes, const bod_render_options* opt, uint8_t* rgb_out, int32_t* skipped_ellipses, hipStream_t s,
+                      char* errbuf, size_t errcap);
 // Scoring rules (score_kernels.hip): host driver of bod_score_pairs, same conventions; rows are staged in internal batches.
 int score_pairs_run(long long n, const double* means, const double* covs, const double* targets, int num_samples, unsigned long long seed,
                     unsigned long long first_row_id, double* out, int32_t* status, hipStream_t s, char* errbuf, size_t errcap);

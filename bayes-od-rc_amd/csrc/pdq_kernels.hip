@@ -631,3 +631,62 @@ int pdq_frames_run(int H, int W, int F, const int32_t* num_gt, const int32_t* gt
                 trace_ms[2]);
     return BOD_OK;
 }
+
+// The box heatmaps of pdq_frames_run alone, left on the device, for the rendering stage's HEAT view (render_kernels.hip): rows
+// [0, nd) of one frame's detections (corner covariances as float32, widened exactly) -> d_heat [nd][H][W], made by the same
+// setup_corner / launch_corners / pdq_rows_kernel as bod_pdq_frames' heatmaps (a frame without ground truths).  d_heat == NULL only
+// validates.  On a refused row *bad_row names it.  Synchronises the stream before its scratch is freed.
+int pdq_box_heatmaps_device(int H, int W, int nd, const int32_t* det_boxes, const float* det_corner_covs, float* d_heat, int* bad_row,
+                            hipStream_t s, char* errbuf, size_t errcap) {
+    Err err{errbuf, errcap};
+    *bad_row = -1;
+    if (H < 1 || W < 1 || nd < 0 || nd > 32767 || (nd > 0 && (!det_boxes || !det_corner_covs)))
+        return err.fail(BOD_ERR_INVALID_ARG, "bad argument");
+    if (W > PDQ_MAX_W) return err.fail(BOD_ERR_INVALID_ARG, "image width %d above %d", W, PDQ_MAX_W);
+    if (nd == 0) return BOD_OK;
+    std::vector<PdqCorner> corners((size_t)(2 * nd));
+    std::vector<int> roi_init((size_t)(8 * nd));
+    std::vector<PdqDet> dets((size_t)nd);
+    size_t maps = 0;
+    for (int d = 0; d < nd; ++d) {
+        const int32_t* b = det_boxes + 4 * d;
+        const float* cv = det_corner_covs + 8 * d;               // [2][2][2], (x, y) order: as pdq_frames_run
+        const double tl[4] = {cv[3], cv[2], cv[1], cv[0]};
+        const double br[4] = {cv[7], cv[5], cv[6], cv[4]};
+        *bad_row = d;
+        int st = setup_corner(H, W, (double)b[1], (double)b[0], tl, &corners[2 * d], &roi_init[8 * d], err, 2 * d);
+        if (st != BOD_OK) return st;
+        st = setup_corner(H, W, (double)H - ((double)b[3] + 1), (double)W - ((double)b[2] + 1), br, &corners[2 * d + 1], &roi_init[8 * d + 4],
+                          err, 2 * d + 1);
+        if (st != BOD_OK) return st;
+        for (int k = 0; k < 2; ++k) {
+            PdqCorner& c = corners[2 * d + k];
+            c.map_off = (long long)maps;
+            maps += (size_t)c.nh * c.nw + c.nh + c.nw;
+        }
+        dets[d] = PdqDet{0, d};
+    }
+    *bad_row = -1;
+    if (!d_heat) return BOD_OK;
+    const PdqFrame frame{0, 0, 0, nd, 0, 0};
+    DevArena arena;
+    PdqCorner* d_corners; int* d_rois; float* d_maps; double* d_cc; PdqDet* d_dets; PdqFrame* d_frames; PdqGt* d_gts;
+    double *d_seg, *d_rowtot;
+    PDQ_HIP(arena.alloc(&d_corners, (size_t)2 * nd)); PDQ_HIP(arena.alloc(&d_rois, (size_t)8 * nd));
+    PDQ_HIP(arena.alloc(&d_maps, maps)); PDQ_HIP(arena.alloc(&d_cc, (size_t)2 * nd));
+    PDQ_HIP(arena.alloc(&d_dets, (size_t)nd)); PDQ_HIP(arena.alloc(&d_frames, 1)); PDQ_HIP(arena.alloc(&d_gts, 1));
+    PDQ_HIP(arena.alloc(&d_seg, 2)); PDQ_HIP(arena.alloc(&d_rowtot, (size_t)nd * H));
+    PDQ_HIP(hipMemcpyAsync(d_corners, corners.data(), sizeof(PdqCorner) * 2 * nd, hipMemcpyHostToDevice, s));
+    PDQ_HIP(hipMemcpyAsync(d_rois, roi_init.data(), sizeof(int) * 8 * nd, hipMemcpyHostToDevice, s));
+    PDQ_HIP(hipMemsetAsync(d_cc, 0, sizeof(double) * 2 * nd, s));
+    PDQ_HIP(hipMemcpyAsync(d_dets, dets.data(), sizeof(PdqDet) * nd, hipMemcpyHostToDevice, s));
+    PDQ_HIP(hipMemcpyAsync(d_frames, &frame, sizeof(PdqFrame), hipMemcpyHostToDevice, s));
+    int st = launch_corners(corners.data(), 2 * nd, d_corners, d_rois, d_maps, d_cc, s, err);
+    if (st == BOD_OK) {
+        hipLaunchKernelGGL(pdq_rows_kernel, dim3(H, nd), dim3(PDQ_BLOCK), (size_t)2 * W * sizeof(double), s, d_corners, d_rois, d_maps, d_cc,
+                           d_dets, d_frames, d_gts, H, W, d_seg, d_rowtot, d_heat);
+        if (hipGetLastError() != hipSuccess) st = err.fail(BOD_ERR_HIP, "the heatmap launch failed");
+    }
+    if (hipStreamSynchronize(s) != hipSuccess && st == BOD_OK) st = err.fail(BOD_ERR_HIP, "the heatmap kernels failed");
+    return st;
+}

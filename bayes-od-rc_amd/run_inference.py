@@ -80,6 +80,10 @@ def test_model(config, args):
                 mapped = inference_utils.map_dataset_classes(training_dataset, test_dataset, classes)
             writer.write('%06d' % (lo + b), boxes, mapped, boxes_vuhw, covs, classes, counts, categories, **parts)
             n_done += 1
+        if getattr(args, 'render', None):     # (normalised BGR frames back to the uint8 RGB they were made from)
+            from . import constants
+            rgb = np.clip(np.rint(chunk[:, :, :, ::-1] + np.asarray(constants.MEANS_DICT['ImageNet'], np.float32)), 0, 255).astype(np.uint8)
+            _render_batch(args, writer.root, ['%06d' % (lo + b) for b in range(len(chunk))], list(rgb), categories)
         sys.stdout.write('\r{}'.format(n_done) + ' /' + str(len(frames)))
     writer.close()
     elapsed = time.time() - start
@@ -166,6 +170,7 @@ def _test_model_on_dataset(config, args, model):
             if training_dataset != test_dataset and boxes.size > 0:
                 mapped = inference_utils.map_dataset_classes(training_dataset, test_dataset, classes)
             writer.write(name, boxes, mapped, boxes_vuhw, covs, classes, counts, categories, **parts)
+        _render_batch(args, writer.root, [p[0] for p in pending], [p[1] for p in pending], categories)
         del pending[:]
 
     def flush_mixed():
@@ -220,6 +225,21 @@ def _test_model_on_dataset(config, args, model):
     return writer.root
 
 
+def _render_batch(args, tree, names, frames, categories):
+    """--render DIR: the batch whose records were just written, drawn on the GPU (one bod_render_frames_u8 call per
+    view for the whole batch, mixed sizes included) and written as DIR/<frame>_<view>.png.  The source frames are the host's: a frame
+    that travelled as a file for --device_jpeg / --device_png is decoded here by PIL, and --corrupt is not shown."""
+    out = getattr(args, 'render', None)
+    if not out or not names:
+        return
+    from . import show_predictions
+    view = getattr(args, 'render_view', 'overlay')
+    frames = [f.decode() if hasattr(f, 'decode') else np.ascontiguousarray(f, np.uint8) for f in frames]
+    show_predictions.render_tree_frames(tree, list(names), frames, ('overlay', 'heat') if view == 'both' else (view,), out,
+                                        device=int(args.gpu_device), min_score=float(getattr(args, 'render_min_score', 0.5)),
+                                        categories=list(categories))
+
+
 def _corruption(args):
     """--corrupt NAME:SEVERITY [--corrupt_seed S] -> (chain, seed), or None."""
     spec = getattr(args, 'corrupt', None)
@@ -271,6 +291,12 @@ def main(argv=None):
                     'batches as under --mixed_sizes; works with --device_jpeg, --ensemble, --tta_flip and the parts flags')
     ap.add_argument('--corrupt_seed', type=int, default=0, help='seed of the random corruptions; a frame\'s noise depends on it and '
                     'on the frame\'s dataset index alone')
+    ap.add_argument('--render', type=str, default=None, metavar='DIR', help='also draw every batch\'s detections onto its source '
+                    'frames on the GPU right after its records are written (boxes, labels and a 2-sigma ellipse on each corner) and '
+                    'write DIR/<frame>_<view>.png; the stand-alone tool is python -m bayes_od_rc_amd.show_predictions')
+    ap.add_argument('--render_view', choices=('overlay', 'heat', 'both'), default='overlay', help='with --render: the overlay, the '
+                    'jet-coloured spatial-probability map, or both')
+    ap.add_argument('--render_min_score', type=float, default=0.5, help='with --render: detections below this score are not drawn')
     args = ap.parse_args(argv)
     if args.corrupt:
         if not args.dataset:

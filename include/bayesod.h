@@ -436,6 +436,63 @@ bod_status bod_corrupt_frames_u8(int32_t device, int32_t n, const uint8_t* rgb_p
 bod_status bod_set_upload_corruption(bod_handle h, const bod_corrupt_op* ops, int32_t ops_per_frame, const uint32_t* frame_ids,
                                      const uint16_t* taps, int32_t n_taps, const uint8_t* luts, int32_t n_luts,
                                      const uint16_t* qtables, int32_t n_qtables, uint64_t seed);
+/* Rendering (render_kernels.hip): detections and their corner uncertainty drawn onto uint8 RGB frames on the device.
+ * A stand-alone stage like bod_corrupt_frames_u8, with the same packing: frame b starts at byte 3 * sum of h_i * w_i over i < b, sizes
+ * src_hw[n][2] (1..65535 each).  Frame f owns rows [sum of num_det[i] over i < f, + num_det[f]) of the det_* arrays and likewise of
+ * gt_boxes.  The drawing rules are this library's own and are defined to the byte: tests/render_reference.py restates them in NumPy.
+ *
+ * Pixel (x, y) is the integer lattice point.  Every blend is v' = (v*(256 - A) + colour*A + 128) >> 8 per channel, A in 0..256.
+ * Primitives are applied strictly in the order below, within a pass in ascending row index (painter's order), so a frame's result
+ * depends on its bytes and its rows alone: not on the batch, the tiling or the launch shape.  Boxes may lie partly or wholly outside
+ * the frame; drawing is clipped.
+ *
+ * BOD_RENDER_OVERLAY
+ *   pass 0  every ground-truth box: the ring of width 1 in colour (0, 255, 0).
+ *   pass A  per detection: the ring of width 1 in the detection's colour; if `labels` and the text has L > 0 glyphs (det_text row: up
+ *           to 16 glyph indices, 0xFF ends it), a black filled rectangle over x in [x0, x0 + 6L], y in [y0, y0 + 8], then the set bit
+ *           (row r, column j) of glyph i at (x0 + 1 + 6i + j, y0 + 1 + r) in the detection's colour.  All of pass A has A = 256.
+ *   pass B  per detection: the top-left ellipse at centre (x0, y0), the bottom-right ellipse at centre (x1, y1), then the ring of
+ *           width max(t - 1, 1), t = line_width.
+ *   Ring of width w on (x0, y0, x1, y1), with a = w / 2 and b = (w + 1) / 2 (integer division): a pixel is covered (A = 256) iff
+ *           x in [x0 - a, x1 + a] and y in [y0 - a, y1 + a] and not (x in [x0 + b, x1 - b] and y in [y0 + b, y1 - b]).  A box with
+ *           x1 < x0 or y1 < y0 draws nothing.
+ *   Ellipse of a corner covariance, a = S_xx, b = S_xy, c = S_yy (fp32): skipped, and counted in skipped_ellipses[frame], unless a, b, c
+ *           are finite, a > 0, c > 0 and det = a*c - b*b > 0 (fp32, two products and a difference).  Extents, computed in double:
+ *           ex = ceil(1.5 * sqrt(r2 * a)) + t + 1, ey = ceil(1.5 * sqrt(r2 * c)) + t + 1, each capped at 4096; the coverage is 0 by
+ *           definition outside |dx| <= ex, |dy| <= ey (dx = x - centre x, dy = y - centre y).  Inside, in fp32 without contraction:
+ *               gx = (c*dx - b*dy) / det;  gy = (a*dy - b*dx) / det;  q = dx*gx + dy*gy;
+ *               if (!(q > 0)) A = 0; else { m = sqrtf(q); g = sqrtf(gx*gx + gy*gy); dist = fabsf(m - sqrtf(r2)) * m / g;
+ *                                           cov = fminf(fmaxf((0.5f*t + 0.5f) - dist, 0), 1); A = (int)(cov * 256.0f); }
+ *           (+, -, *, / and sqrtf only, all correctly rounded; fmaxf / fminf return the operand that is not a NaN), in the detection's
+ *           colour.  dist is the first-order distance to the contour of squared Mahalanobis radius r2.
+ * BOD_RENDER_HEAT
+ *   A per-pixel index plane starts at 0.  Detections in ascending order: wherever the detection's box heatmap h -- exactly the float32
+ *   map bod_pdq_frames(.., heatmaps) yields for that row on a frame of this size, made by the same device code -- is nonzero,
+ *   index = (int)(h * 255.0f); the last nonzero write wins.  Colour of index i, with x = 4i: R = clip(min(x - 382, 1147 - x), 0, 255),
+ *   G = clip(min(x - 127, 892 - x), 0, 255), B = clip(min(x + 128, 637 - x), 0, 255).  Output = (26*v + 230*colour + 128) >> 8.
+ *   Rows bod_pdq_frames refuses (and a frame wider than 4000) are refused here the same way, before anything is drawn.  Detections are
+ *   taken in chunks of at most 4096 rows whose heatmaps fit 64 MiB (at least one row): the device scratch of the view is at most
+ *   3 * max(64 MiB, 4*h*w bytes) plus 1 KiB + 16*h + 8*w bytes per chunk row, whatever D is.
+ * Font: 5x7 glyphs for a-z, 0-9, '.', ' ', '%', '-', '_' (41 glyphs, indices in this order).  bod_render_font writes them as
+ *   glyph_rows[count][7], low 5 bits of a byte, bit 4 = the leftmost column (glyph_rows may be NULL to ask for count alone).
+ * Errors through bod_last_error(NULL).  BOD_ERR_INVALID_ARG, naming the frame and the row where there is one: n < 0, a NULL array with
+ * a nonzero count, a negative count, a frame size outside 1..65535, line_width outside 1..7, r2 not finite or not > 0, an unknown
+ * view, a glyph index >= count that is not 0xFF.  n == 0 is BOD_OK.  opt == NULL: OVERLAY, line_width 2, labels on, r2 6.180074f. */
+enum { BOD_RENDER_OVERLAY = 0, BOD_RENDER_HEAT = 1 };
+typedef struct bod_render_options {   /* 32 bytes */
+    int32_t view;          /* BOD_RENDER_* */
+    int32_t line_width;    /* t, 1..7: ellipses use t, the second-pass box max(t-1,1), the first-pass box 1 */
+    int32_t labels;        /* 0/1 */
+    float   r2;            /* squared Mahalanobis radius of the contour; default 6.180074f
+                              (= chi2.ppf(2*Phi(2)-1, 2): the 2-sigma contour the reference's demo draws) */
+    int32_t reserved[4];   /* 0 */
+} bod_render_options;
+bod_status bod_render_frames_u8(int32_t device, int32_t n, const uint8_t* rgb_packed_in, const int32_t* src_hw,
+                                const int32_t* num_det, const int32_t* det_boxes, const float* det_corner_covs,
+                                const uint8_t* det_colors, const uint8_t* det_text, const int32_t* num_gt,
+                                const int32_t* gt_boxes, const bod_render_options* opt, uint8_t* rgb_packed_out,
+                                int32_t* skipped_ellipses);
+bod_status bod_render_font(uint8_t* glyph_rows, int32_t* count);
 /* PNG frames decoded inside the library, the JPEG entries' counterpart for KITTI's files.  Chunk parsing and the
  * zlib inflate run on host threads (no zlib is linked); the reconstruction of the filtered scanlines (PNG specification section 9:
  * None, Sub, Up, Average, Paeth) runs on the device and writes the uint8 RGB frames into the staging buffer the ragged / augmented

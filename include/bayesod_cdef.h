@@ -155,6 +155,20 @@ bod_status bod_corrupt_frames_u8(int32_t device, int32_t n, const uint8_t* rgb_p
 bod_status bod_set_upload_corruption(bod_handle h, const bod_corrupt_op* ops, int32_t ops_per_frame, const uint32_t* frame_ids,
                                      const uint16_t* taps, int32_t n_taps, const uint8_t* luts, int32_t n_luts,
                                      const uint16_t* qtables, int32_t n_qtables, uint64_t seed);
+enum { BOD_RENDER_OVERLAY = 0, BOD_RENDER_HEAT = 1 };
+typedef struct bod_render_options {
+    int32_t view;
+    int32_t line_width;
+    int32_t labels;
+    float   r2;
+    int32_t reserved[4];
+} bod_render_options;
+bod_status bod_render_frames_u8(int32_t device, int32_t n, const uint8_t* rgb_packed_in, const int32_t* src_hw,
+                                const int32_t* num_det, const int32_t* det_boxes, const float* det_corner_covs,
+                                const uint8_t* det_colors, const uint8_t* det_text, const int32_t* num_gt,
+                                const int32_t* gt_boxes, const bod_render_options* opt, uint8_t* rgb_packed_out,
+                                int32_t* skipped_ellipses);
+bod_status bod_render_font(uint8_t* glyph_rows, int32_t* count);
 struct bod_png_info {
     int32_t width, height, bit_depth, color_type;
     int32_t channels;
