@@ -216,19 +216,20 @@ class Engine(object):
             self._ragged_keep = {}
         self._ragged_keep[int(buffer)] = buf
 
-    def _jpeg_upload(self, files, means, aspect_resize, aug, threads, buffer):
+    def _encoded_upload(self, kind, files, means, aspect_resize, aug, threads, buffer):
+        """The JPEG / PNG uploads (``kind``: "jpeg" or "png"), synchronous (``buffer=None``) or pipelined."""
         from . import constants
-        ptrs, lens = _jpeg_files(files, self.B)
+        ptrs, lens = _encoded_files(files, self.B, kind.upper())
         m = np.ascontiguousarray(constants.MEANS_DICT['ImageNet'] if means is None else means, dtype=np.float32)
         rec = None if aug is None else augment_records(aug, self.B)
         recp = None if rec is None else rec.ctypes.data_as(C.POINTER(_lib.BodAugment))
         src_hw = np.zeros((self.B, 2), np.int32)
         threads = min(16, self.B) if threads is None else int(threads)
+        args = (self.h, ptrs, lens, fptr(m), int(bool(aspect_resize)), recp, threads, iptr(src_hw))
         if buffer is None:
-            st = self.lib.bod_upload_frames_jpeg(self.h, ptrs, lens, fptr(m), int(bool(aspect_resize)), recp, threads, iptr(src_hw))
+            st = getattr(self.lib, "bod_upload_frames_%s" % kind)(*args)
         else:
-            st = self.lib.bod_upload_frames_jpeg_async(self.h, ptrs, lens, fptr(m), int(bool(aspect_resize)), recp, threads,
-                                                       iptr(src_hw), int(buffer))
+            st = getattr(self.lib, "bod_upload_frames_%s_async" % kind)(*args, int(buffer))
         self._chk(st)
         return src_hw
 
@@ -239,12 +240,12 @@ class Engine(object):
         the image buffer ends up bit for bit as after the upload of PIL's ``convert('RGB')`` decode of the files.  Returns the
         frames' sizes, int32 [batch, 2] (h, w).  ``ValueError`` naming the frame for a corrupt or unsupported file
         (``jpeg_info`` tells in advance); the handle and the frames it held stay as they were."""
-        return self._jpeg_upload(files, means, aspect_resize, aug, threads, None)
+        return self._encoded_upload("jpeg", files, means, aspect_resize, aug, threads, None)
 
     def upload_frames_jpeg_async(self, files, buffer, means=None, aspect_resize=True, aug=None, threads=None):
         """Pipelined form (``bod_upload_frames_jpeg_async``), used like ``upload_frames_u8_ragged_async``.  The host decode is
         done when this returns: ``files`` need not be kept."""
-        return self._jpeg_upload(files, means, aspect_resize, aug, threads, int(buffer))
+        return self._encoded_upload("jpeg", files, means, aspect_resize, aug, threads, int(buffer))
 
     def set_upload_corruption(self, chains, frame_ids=None, seed=0, ops_arrays=None):
         """Corrupt the frames of the NEXT packed upload on the device (``bod_set_upload_corruption``): ``chains``
@@ -260,22 +261,6 @@ class Engine(object):
         args, _keep = _corruption_args(chains, self.B, frame_ids, ops_arrays)
         self._chk(self.lib.bod_set_upload_corruption(self.h, *args, int(seed) & 0xFFFFFFFFFFFFFFFF))
 
-    def _png_upload(self, files, means, aspect_resize, aug, threads, buffer):
-        from . import constants
-        ptrs, lens = _jpeg_files(files, self.B, "PNG")
-        m = np.ascontiguousarray(constants.MEANS_DICT['ImageNet'] if means is None else means, dtype=np.float32)
-        rec = None if aug is None else augment_records(aug, self.B)
-        recp = None if rec is None else rec.ctypes.data_as(C.POINTER(_lib.BodAugment))
-        src_hw = np.zeros((self.B, 2), np.int32)
-        threads = min(16, self.B) if threads is None else int(threads)
-        if buffer is None:
-            st = self.lib.bod_upload_frames_png(self.h, ptrs, lens, fptr(m), int(bool(aspect_resize)), recp, threads, iptr(src_hw))
-        else:
-            st = self.lib.bod_upload_frames_png_async(self.h, ptrs, lens, fptr(m), int(bool(aspect_resize)), recp, threads,
-                                                      iptr(src_hw), int(buffer))
-        self._chk(st)
-        return src_hw
-
     def upload_frames_png(self, files, means=None, aspect_resize=True, aug=None, threads=None):
         """``upload_frames_u8_ragged`` (``aug=None``) or ``upload_frames_u8_augmented`` of PNG files decoded inside the library
         (``bod_upload_frames_png``): ``files`` is a list of ``batch`` ``bytes`` objects, each an 8-bit gray, RGB,
@@ -284,12 +269,12 @@ class Engine(object):
         ``convert('RGB')`` decode of the files.  Returns the frames' sizes, int32 [batch, 2] (h, w).  ``ValueError`` naming the
         frame for a corrupt or unsupported file (``png_info`` tells in advance); the handle and the frames it held stay as they
         were."""
-        return self._png_upload(files, means, aspect_resize, aug, threads, None)
+        return self._encoded_upload("png", files, means, aspect_resize, aug, threads, None)
 
     def upload_frames_png_async(self, files, buffer, means=None, aspect_resize=True, aug=None, threads=None):
         """Pipelined form (``bod_upload_frames_png_async``), used like ``upload_frames_u8_ragged_async``.  The host inflate is
         done when this returns: ``files`` need not be kept."""
-        return self._png_upload(files, means, aspect_resize, aug, threads, int(buffer))
+        return self._encoded_upload("png", files, means, aspect_resize, aug, threads, int(buffer))
 
     def _device_images(self, image_buffer):
         ptr = self.lib.bod_device_images(self.h) if image_buffer is None else self.lib.bod_device_images_buffer(self.h, int(image_buffer))
@@ -1321,7 +1306,7 @@ def pdq_frames(img_hw, num_gt, gt_boxes, num_det, det_boxes, det_corner_covs, de
     return fgs, bgs, dbgs, heat
 
 
-def _jpeg_files(files, batch=None, kind="JPEG"):
+def _encoded_files(files, batch=None, kind="JPEG"):
     """A list of bytes objects as the (const uint8_t* const*, const int64_t*) pair of the JPEG (and PNG) entry points."""
     files = list(files)
     if batch is not None and len(files) != batch:
@@ -1366,30 +1351,35 @@ def jpeg_entropy_decode(data):
     return coefs, quant
 
 
-def decode_jpeg_rgb(files, device=0, threads=None):
-    """JPEG files -> a list of uint8 [h, w, 3] RGB frames, decoded by the library (``bod_jpeg_decode_rgb``: Huffman decoding on
-    ``threads`` host threads, default ``min(16, len(files))``, everything else on the device).  Equal to PIL's ``convert('RGB')``."""
+def _decode_rgb(kind, files, device, threads):
+    """``decode_jpeg_rgb`` / ``decode_png_rgb`` (``kind``: "jpeg" or "png")."""
     lib = _lib.load()
-    ptrs, lens = _jpeg_files(files)
+    ptrs, lens = _encoded_files(files, kind=kind.upper())
     n = len(lens)
     if n == 0:
         return []
     total = 0
     for i in range(n):
-        info = jpeg_info(files[i])
+        info = (jpeg_info if kind == "jpeg" else png_info)(files[i])
         if not info["supported"]:
-            raise ValueError("bod_jpeg_decode_rgb: frame %d is not a supported JPEG: %s" % (i, info["reason"]))
+            raise ValueError("bod_%s_decode_rgb: frame %d is not a supported %s: %s" % (kind, i, kind.upper(), info["reason"]))
         total += 3 * info["width"] * info["height"]
     rgb = np.empty(total, np.uint8)
     src_hw = np.zeros((n, 2), np.int32)
-    st = lib.bod_jpeg_decode_rgb(int(device), n, ptrs, lens, min(16, n) if threads is None else int(threads),
-                                 rgb.ctypes.data_as(C.POINTER(C.c_uint8)), rgb.size, iptr(src_hw))
+    st = getattr(lib, "bod_%s_decode_rgb" % kind)(int(device), n, ptrs, lens, min(16, n) if threads is None else int(threads),
+                                                  rgb.ctypes.data_as(C.POINTER(C.c_uint8)), rgb.size, iptr(src_hw))
     _lib.check(lib, None, st)
     out, off = [], 0
     for h, w in src_hw:
         out.append(rgb[off:off + 3 * h * w].reshape(h, w, 3))
         off += 3 * h * w
     return out
+
+
+def decode_jpeg_rgb(files, device=0, threads=None):
+    """JPEG files -> a list of uint8 [h, w, 3] RGB frames, decoded by the library (``bod_jpeg_decode_rgb``: Huffman decoding on
+    ``threads`` host threads, default ``min(16, len(files))``, everything else on the device).  Equal to PIL's ``convert('RGB')``."""
+    return _decode_rgb("jpeg", files, device, threads)
 
 
 def _corruption_args(chains, n, frame_ids, ops_arrays=None):
@@ -1468,27 +1458,7 @@ def png_inflate(data):
 def decode_png_rgb(files, device=0, threads=None):
     """PNG files -> a list of uint8 [h, w, 3] RGB frames, decoded by the library (``bod_png_decode_rgb``: inflate on ``threads``
     host threads, default ``min(16, len(files))``, the scanline filters on the device).  Equal to PIL's ``convert('RGB')``."""
-    lib = _lib.load()
-    ptrs, lens = _jpeg_files(files, kind="PNG")
-    n = len(lens)
-    if n == 0:
-        return []
-    total = 0
-    for i in range(n):
-        info = png_info(files[i])
-        if not info["supported"]:
-            raise ValueError("bod_png_decode_rgb: frame %d is not a supported PNG: %s" % (i, info["reason"]))
-        total += 3 * info["width"] * info["height"]
-    rgb = np.empty(total, np.uint8)
-    src_hw = np.zeros((n, 2), np.int32)
-    st = lib.bod_png_decode_rgb(int(device), n, ptrs, lens, min(16, n) if threads is None else int(threads),
-                                rgb.ctypes.data_as(C.POINTER(C.c_uint8)), rgb.size, iptr(src_hw))
-    _lib.check(lib, None, st)
-    out, off = [], 0
-    for h, w in src_hw:
-        out.append(rgb[off:off + 3 * h * w].reshape(h, w, 3))
-        off += 3 * h * w
-    return out
+    return _decode_rgb("png", files, device, threads)
 
 
 def bench_png_decode(files, threads=16, iters=5, device=0):
@@ -1496,7 +1466,7 @@ def bench_png_decode(files, threads=16, iters=5, device=0):
     half of an upload of ``files`` on ``threads`` of the library's worker threads, by the host clock --, kernel_ms [iters] --
     ``png_unfilter_kernel`` alone on the batch, by events)."""
     lib = _lib.load()
-    ptrs, lens = _jpeg_files(files, kind="PNG")
+    ptrs, lens = _encoded_files(files, kind="PNG")
     host, kernel = np.zeros(int(iters), np.float64), np.zeros(int(iters), np.float64)
     st = lib.bod_bench_png_decode(int(device), len(lens), ptrs, lens, int(threads), int(iters),
                                   host.ctypes.data_as(C.POINTER(C.c_double)), kernel.ctypes.data_as(C.POINTER(C.c_double)))
