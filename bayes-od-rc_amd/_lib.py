@@ -18,7 +18,9 @@ if os.environ.get("BOD_LIB_OVERRIDE"):
 
 BOD_OK, BOD_ERR_INVALID_ARG, BOD_ERR_HIP, BOD_ERR_OOM, BOD_ERR_NOT_READY, BOD_ERR_NO_DEVICE = range(6)
 BOD_PARTS_COVARIANCE, BOD_PARTS_CLASS = 1, 2      # bits of bod_config.covariance_parts
-BOD_VIEW_IDENTITY, BOD_VIEW_HFLIP = 0, 1          # views of a statistics handle (bod_stat_forward_view / bod_stat_merge_view)
+BOD_MERGE_BAYES, BOD_MERGE_CENTRE, BOD_MERGE_MIXTURE = 0, 1, 2      # bod_set_merge_method
+MERGE_METHODS = {"bayes": BOD_MERGE_BAYES, "centre": BOD_MERGE_CENTRE, "mixture": BOD_MERGE_MIXTURE}
+BOD_VIEW_IDENTITY, BOD_VIEW_HFLIP = 0, 1         # views of a statistics handle (bod_stat_forward_view / bod_stat_merge_view)
 
 
 class BodConfig(C.Structure):
@@ -261,6 +263,11 @@ SIGNATURES = {
     "bod_get_detection_class_parts_batch": (C.c_int, [_H, _F]),
     "bod_collect_class_parts": (C.c_int, [_H, C.c_int32, _F]),
     "bod_device_detection_class_parts": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
+    "bod_set_merge_method": (C.c_int, [_H, C.c_int32]),
+    "bod_get_merge_method": (C.c_int, [_H, _I]),
+    "bod_get_detection_merge_terms": (C.c_int, [_H, C.c_int32, _F, _F, _I]),
+    "bod_get_detection_merge_terms_batch": (C.c_int, [_H, C.c_int32, _F, _F, _I]),
+    "bod_device_detection_merge_terms": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
     "bod_stat_get_entropy": (C.c_int, [_H, _F]),
     "bod_stat_set_entropy": (C.c_int, [_H, _F]),
     "bod_stat_device_entropy": (C.c_int, [_H, C.POINTER(C.c_void_p)]),

@@ -401,6 +401,13 @@ struct bod_context {
     float* out_cparts_s[2] = {nullptr, nullptr}; float* out_cparts = nullptr;
     std::vector<char> cparts_ok, det_cparts_ok[2];
     bool cparts_staged[2] = {false, false};
+    // How run_cluster merges a cluster (bod_set_merge_method).  The term buffers -- within / between [B,K,16] and
+    // members [B,K] per record slot -- exist from the first non-default setter call on; merge_terms_ok[slot]: the slot's last
+    // cluster stage wrote them (it ran as CENTRE or MIXTURE).
+    int merge_method = BOD_MERGE_BAYES;
+    float* merge_within_s[2] = {nullptr, nullptr}; float* merge_between_s[2] = {nullptr, nullptr};
+    int32_t* merge_members_s[2] = {nullptr, nullptr};
+    bool merge_terms_ok[2] = {false, false};
     hipStream_t side = nullptr;
     // ---- CU-partitioned pipeline overlap (bod_config.pipeline_overlap; bod_infer_async only).  The memory-bound front of batch i+1
     // (stem, backbone, FPN) runs on its own stream, masked to the last `ov_front_slots` CU slots of every XCD, while the MFMA-bound
@@ -1847,7 +1854,13 @@ bod_status run_cluster(bod_context* h, hipStream_t st) {
     a.affinity = h->affinity_img >= 0 ? h->affinity : nullptr; a.affinity_img = h->affinity_img;
     h->affinity_img = -1;                         // consumed by this call
     a.out_scores = h->out_scores; a.out_means = h->out_means; a.out_covs = h->out_covs; a.out_counts = h->out_counts;
-    HIPCHK(h, launch_cluster_fuse(a, st));
+    if (h->merge_method == BOD_MERGE_BAYES) {
+        HIPCHK(h, launch_cluster_fuse(a, st));
+    } else {
+        const MergeTerms terms{h->merge_within_s[h->slot], h->merge_between_s[h->slot], h->merge_members_s[h->slot]};
+        HIPCHK(h, launch_cluster_merge(a, h->merge_method, terms, st));
+    }
+    h->merge_terms_ok[h->slot] = h->merge_method != BOD_MERGE_BAYES;
     if (h->parts) { HIPCHK(h, launch_cluster_parts(a, h->parts, h->out_parts, st)); h->det_parts_ok[h->slot] = h->parts_ok; }
     if (h->cparts) { HIPCHK(h, launch_cluster_class_parts(a, h->cparts, h->out_cparts, st)); h->det_cparts_ok[h->slot] = h->cparts_ok; }
     h->cluster_done = true;
@@ -2666,6 +2679,94 @@ bod_status bod_device_detection_class_parts(bod_handle h, int32_t sidx, void** p
     BODCHK(class_parts_handle(h, "bod_device_detection_class_parts"));
     if (!p || sidx < 0 || sidx > 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_device_detection_class_parts: slot %d / NULL", sidx);
     *p = h->out_cparts_s[sidx];
+    return BOD_OK;
+}
+
+bod_status bod_set_merge_method(bod_handle h, int32_t method) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    if (method != BOD_MERGE_BAYES && method != BOD_MERGE_CENTRE && method != BOD_MERGE_MIXTURE)
+        return h->fail(BOD_ERR_INVALID_ARG, "bod_set_merge_method: unknown method %d (BOD_MERGE_BAYES = 0, BOD_MERGE_CENTRE = 1, BOD_MERGE_MIXTURE = 2)", method);
+    if (h->cfg.training) return h->fail(BOD_ERR_INVALID_ARG, "bod_set_merge_method: a training handle has no cluster stage");
+    if (method != BOD_MERGE_BAYES && h->cfg.covariance_parts != 0)
+        return h->fail(BOD_ERR_INVALID_ARG, "bod_set_merge_method: the handle was created with bod_config.covariance_parts = %d; the covariance and "
+                       "class-entropy parts are defined for the Bayesian fuse (BOD_MERGE_BAYES) only", h->cfg.covariance_parts);
+    if (method != BOD_MERGE_BAYES && !h->merge_members_s[1]) {
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        const size_t BK = (size_t)h->cfg.batch * h->cfg.nms_max_output_size;
+        for (int sidx = 0; sidx < 2; ++sidx) {
+            BODCHK(h->dalloc(&h->merge_within_s[sidx], BK * 16));
+            BODCHK(h->dalloc(&h->merge_between_s[sidx], BK * 16));
+            BODCHK(h->dalloc(&h->merge_members_s[sidx], BK));
+        }
+    }
+    h->merge_method = method;
+    return BOD_OK;
+}
+
+bod_status bod_get_merge_method(bod_handle h, int32_t* method) {
+    if (!h || !method) return BOD_ERR_INVALID_ARG;
+    *method = h->merge_method;
+    return BOD_OK;
+}
+
+bod_status bod_get_detection_merge_terms(bod_handle h, int32_t img, float* within, float* between, int32_t* members) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(join_overlap(h));
+    if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+    if (img < 0 || img >= h->cfg.batch) return h->fail(BOD_ERR_INVALID_ARG, "image index out of range");
+    if (!h->merge_terms_ok[h->slot]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_merge_terms: the last cluster stage ran as BOD_MERGE_BAYES, which has no merge terms");
+    int32_t num = 0;
+    HIPCHK(h, hipMemcpyAsync(&num, h->nms_nsel + img, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t k = (size_t)std::max(num, 0), o = (size_t)img * h->cfg.nms_max_output_size;
+    BODCHK(d2h(h, within, h->merge_within_s[h->slot] + o * 16, k * 16));
+    BODCHK(d2h(h, between, h->merge_between_s[h->slot] + o * 16, k * 16));
+    BODCHK(d2h(h, members, h->merge_members_s[h->slot] + o, k));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BOD_OK;
+}
+
+bod_status bod_get_detection_merge_terms_batch(bod_handle h, int32_t slot, float* within, float* between, int32_t* members) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    if (slot < -1 || slot > 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_get_detection_merge_terms_batch: slot %d", slot);
+    const size_t B = (size_t)h->cfg.batch, K = (size_t)h->cfg.nms_max_output_size;
+    std::vector<int32_t> num(B);
+    if (slot < 0) {
+        BODCHK(join_overlap(h));
+        if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+        const int sidx = h->slot;
+        if (!h->merge_terms_ok[sidx]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_merge_terms_batch: the last cluster stage ran as BOD_MERGE_BAYES, which has no merge terms");
+        HIPCHK(h, hipMemcpyAsync(num.data(), h->nms_nsel_s[sidx], B * 4, hipMemcpyDeviceToHost, h->stream));
+        BODCHK(d2h(h, within, h->merge_within_s[sidx], B * K * 16));
+        BODCHK(d2h(h, between, h->merge_between_s[sidx], B * K * 16));
+        BODCHK(d2h(h, members, h->merge_members_s[sidx], B * K));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    } else {
+        // a bod_infer_async ticket: wait for that batch as bod_collect does (its event, not a stream the next batch may be queued on),
+        // then plain blocking copies -- the pinned staging of the records is sized at create and stays as it is
+        if (!h->done_stream[slot]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_merge_terms_batch: slot %d holds no batch of bod_infer_async", slot);
+        if (!h->merge_terms_ok[slot]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_merge_terms_batch: slot %d's cluster stage ran as BOD_MERGE_BAYES, which has no merge terms", slot);
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        HIPCHK(h, hipEventSynchronize(h->ev_done[slot]));
+        HIPCHK(h, hipMemcpy(num.data(), h->nms_nsel_s[slot], B * 4, hipMemcpyDeviceToHost));
+        if (within) HIPCHK(h, hipMemcpy(within, h->merge_within_s[slot], B * K * 64, hipMemcpyDeviceToHost));
+        if (between) HIPCHK(h, hipMemcpy(between, h->merge_between_s[slot], B * K * 64, hipMemcpyDeviceToHost));
+        if (members) HIPCHK(h, hipMemcpy(members, h->merge_members_s[slot], B * K * 4, hipMemcpyDeviceToHost));
+    }
+    // rows beyond an image's count are whatever an earlier batch left: zero them on the way out, like the record rows
+    for (size_t b = 0; b < B; ++b)
+        for (size_t k = (size_t)std::min<int64_t>(std::max(num[b], 0), (int64_t)K); k < K; ++k) {
+            if (within) std::memset(within + (b * K + k) * 16, 0, 64);
+            if (between) std::memset(between + (b * K + k) * 16, 0, 64);
+            if (members) members[b * K + k] = 0;
+        }
+    return BOD_OK;
+}
+
+bod_status bod_device_detection_merge_terms(bod_handle h, int32_t sidx, void** p) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    if (!p || sidx < 0 || sidx > 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_device_detection_merge_terms: slot %d / NULL", sidx);
+    p[0] = h->merge_within_s[sidx]; p[1] = h->merge_between_s[sidx]; p[2] = h->merge_members_s[sidx];
     return BOD_OK;
 }
 

@@ -305,6 +305,11 @@ struct ClusterArgs {
     float* out_scores; float* out_means; float* out_covs; float* out_counts;
 };
 hipError_t launch_cluster_fuse(const ClusterArgs& a, hipStream_t s);
+// The other ways to merge a cluster (bayesod.h, bod_set_merge_method): method = BOD_MERGE_CENTRE or
+// BOD_MERGE_MIXTURE in place of cluster_fuse_kernel, same ClusterArgs, grid and membership test.  Writes the five detection arrays
+// and the terms: within / between [B,max_out,16], members [B,max_out].
+struct MergeTerms { float* within; float* between; int32_t* members; };
+hipError_t launch_cluster_merge(const ClusterArgs& a, int method, MergeTerms out, hipStream_t s);
 hipError_t launch_iou_matrix(const float* corners, int M, float* out, hipStream_t s);
 // Covariance parts (bod_config.covariance_parts): every covariance the two fusion steps store, split into what the fused
 // mean inherits from the epistemic noise, from the aleatoric noise and from the prior -- three symmetric 4x4 terms that sum to it.

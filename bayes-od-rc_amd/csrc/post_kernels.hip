@@ -10,6 +10,7 @@
 //                           KITTI rescale, score ranking, corners                    (:25-29,:53-202)
 //   K4 nms_kernel           NonMaxSuppressionV5 (soft-NMS), one wavefront per image   (:204-212)
 //   K5 cluster_fuse_kernel  bayes_od_clustering, one workgroup per (image, centre)   (:285-364)
+//      cluster_merge_kernel in its place under bod_set_merge_method: the NMS pick / the Gaussian mixture (no reference counterpart)
 //   K6 iou_matrix_kernel    box_utils.bbox_iou_vuvu (only for API compatibility)     (:214-215)
 #include "kernels.h"
 #include "philox.h"
@@ -1687,6 +1688,127 @@ hipError_t launch_cluster_class_parts(const ClusterArgs& a, const float* cparts,
     if (!cparts || !out_cparts || (a.C != 4 && a.C != 8)) return hipErrorInvalidValue;
     if (a.C == 8) hipLaunchKernelGGL(cluster_class_parts_kernel<8>, dim3(a.max_out, a.B), dim3(CL_BLOCK), 0, s, a, cparts, out_cparts);
     else hipLaunchKernelGGL(cluster_class_parts_kernel<4>, dim3(a.max_out, a.B), dim3(CL_BLOCK), 0, s, a, cparts, out_cparts);
+    return hipGetLastError();
+}
+
+// The NMS pick and the equal-weight Gaussian mixture of a cluster (bayesod.h, bod_set_merge_method), in place of
+// cluster_fuse_kernel: same grid, same membership expression, the same reduction (wave butterflies, one LDS exchange of the four
+// waves' partials, thread 0 finishes), and no 4x4 inverse.  The members' means enter shifted by the centre's, d_i = mu_i - mu_c.
+// BOD_MERGE_CENTRE (uniform over the grid) only counts the members.
+template <int C>
+__global__ __launch_bounds__(CL_BLOCK) void cluster_merge_kernel(ClusterArgs a, int method, MergeTerms out) {
+    constexpr int Q = 25 + 2 * C;                     // sum Sigma_i [10], sum d_i d_i^T [10], sum d_i [4], scores [C], counts [C], members
+    __shared__ float red[4 * Q];
+    const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    if (k >= a.num_selected[b]) return;
+    const int M = a.num_kept[b];
+    const int centre = a.selected[(size_t)b * a.max_out + k];
+    const size_t base = (size_t)b * a.A;
+    const float4* boxes = reinterpret_cast<const float4*>(a.corners) + base;
+    const float4 cbox = boxes[centre];
+    const bool mix = method == BOD_MERGE_MIXTURE;
+    float mc[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) mc[r] = a.means[(base + centre) * 4 + r];
+    float acc[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) acc[q] = 0.f;
+    const float* aff = (a.affinity && b == a.affinity_img) ? a.affinity + (size_t)k * a.A : nullptr;
+    for (int i = tid; i < M; i += CL_BLOCK) {
+        if (!((aff ? aff[i] : iou_plus1(boxes[i], cbox)) > a.thr)) continue;
+        acc[Q - 1] += 1.f;                            // (at most A < 2^24: exact)
+        if (!mix) continue;
+        float d[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) d[r] = a.means[(base + i) * 4 + r] - mc[r];
+        int t = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int q = 0; q <= r; ++q) {
+                acc[t] += a.covs[(base + i) * 16 + r * 4 + q];
+                acc[10 + t] += d[r] * d[q];
+                ++t;
+            }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[20 + r] += d[r];
+        float row[C], rs = 0.f;
+#pragma unroll
+        for (int j = 0; j < C; ++j) { row[j] = a.counts[(base + i) * C + j]; rs += row[j]; }
+#pragma unroll
+        for (int j = 0; j < C; ++j) { acc[24 + j] += row[j] / rs; acc[24 + C + j] += row[j]; }
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+    auto wsum = [](float v) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        return v;
+    };
+    if (mix) {                                        // (block-uniform)
+#pragma unroll
+        for (int q = 0; q < Q - 1; ++q) {
+            const float r = wsum(acc[q]);
+            if (lane == 0) red[wave * Q + q] = r;
+        }
+    }
+    {
+        const float r = wsum(acc[Q - 1]);
+        if (lane == 0) red[wave * Q + Q - 1] = r;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const size_t ob = (size_t)b * a.max_out + k;
+    const float fn = (red[Q - 1] + red[2 * Q - 1]) + (red[3 * Q - 1] + red[4 * Q - 1]);
+    out.members[ob] = (int)fn;
+    if (!mix || !(fn > 0.f)) {
+        // the centre's own posterior row; a caller's affinity may leave a mixture without members: the same row
+        float row[C], rs = 0.f;
+#pragma unroll
+        for (int j = 0; j < C; ++j) { row[j] = a.counts[(base + centre) * C + j]; rs += row[j]; }
+#pragma unroll
+        for (int j = 0; j < C; ++j) { a.out_scores[ob * C + j] = row[j] / rs; a.out_counts[ob * C + j] = row[j]; }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) a.out_means[ob * 4 + r] = mc[r];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const float v = a.covs[(base + centre) * 16 + q];
+            a.out_covs[ob * 16 + q] = v; out.within[ob * 16 + q] = v; out.between[ob * 16 + q] = 0.f;
+        }
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < Q - 1; ++q) acc[q] = (red[q] + red[Q + q]) + (red[2 * Q + q] + red[3 * Q + q]);
+    float dbar[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { dbar[r] = acc[20 + r] / fn; a.out_means[ob * 4 + r] = mc[r] + dbar[r]; }
+    {
+        int t = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int q = 0; q <= r; ++q) {
+                const float w = acc[t] / fn;
+                const float bt = acc[10 + t] / fn - dbar[r] * dbar[q];
+                const float cv = w + bt;
+                out.within[ob * 16 + r * 4 + q] = w; out.within[ob * 16 + q * 4 + r] = w;
+                out.between[ob * 16 + r * 4 + q] = bt; out.between[ob * 16 + q * 4 + r] = bt;
+                a.out_covs[ob * 16 + r * 4 + q] = cv; a.out_covs[ob * 16 + q * 4 + r] = cv;
+                ++t;
+            }
+    }
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+        a.out_scores[ob * C + j] = acc[24 + j] / fn;
+        a.out_counts[ob * C + j] = acc[24 + C + j] / fn;
+    }
+}
+
+hipError_t launch_cluster_merge(const ClusterArgs& a, int method, MergeTerms out, hipStream_t s) {
+    if ((method != BOD_MERGE_CENTRE && method != BOD_MERGE_MIXTURE) || !out.within || !out.between || !out.members) return hipErrorInvalidValue;
+    dim3 grid(a.max_out, a.B);
+    if (a.C == 8) hipLaunchKernelGGL(cluster_merge_kernel<8>, grid, dim3(CL_BLOCK), 0, s, a, method, out);
+    else if (a.C == 4) hipLaunchKernelGGL(cluster_merge_kernel<4>, grid, dim3(CL_BLOCK), 0, s, a, method, out);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -158,9 +158,10 @@ def all_gather_samples(local, full, group=None):
 class SampleShardedEngine(object):
     """Pair of handles for the sample-sharded mode on this rank's GPU: ``fwd`` computes this rank's n samples,
     ``post`` (no weights: raw buffers only) receives the gathered ensemble and runs posterior / soft-NMS /
-    cluster-fuse.  ``make_config_kwargs`` are those of engine.make_config for the FULL ensemble."""
+    cluster-fuse.  ``make_config_kwargs`` are those of engine.make_config for the FULL ensemble.  ``merge_method``: how ``post``
+    merges a cluster ('bayes', 'centre', 'mixture': ``Engine.set_merge_method``)."""
 
-    def __init__(self, image_hw, weights, anchors, mc_samples, device=0, batch=1, group=None, **make_config_kwargs):
+    def __init__(self, image_hw, weights, anchors, mc_samples, device=0, batch=1, group=None, merge_method='bayes', **make_config_kwargs):
         from .engine import Engine, make_config
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -171,6 +172,7 @@ class SampleShardedEngine(object):
         self.fwd.load_weights(weights)
         self.post = Engine(make_config(image_hw, batch=batch, mc_samples=mc_samples, device=device, **make_config_kwargs))
         self.post.set_anchors(anchors)
+        self.post.set_merge_method(merge_method)
         self._local = raw_views(self.fwd)
         self._full = raw_views(self.post, mark_ready=False)
 
@@ -344,9 +346,10 @@ class StatShardedEngine(object):
     """The sample-sharded mode on statistics: ONE statistics handle per rank computes its n = N / world samples
     (``stat_forward`` with sample base rank * n), one all-gather exchanges the 34-float records, every rank resets and folds
     the W records in rank order (identical bits on all ranks), and posterior / soft-NMS / cluster-fuse run replicated.
-    ``make_config_kwargs`` are those of engine.make_config for the FULL ensemble."""
+    ``make_config_kwargs`` are those of engine.make_config for the FULL ensemble.  ``merge_method``: how the handle merges a
+    cluster ('bayes', 'centre', 'mixture': ``Engine.set_merge_method``)."""
 
-    def __init__(self, image_hw, weights, anchors, mc_samples, device=0, batch=1, group=None, **make_config_kwargs):
+    def __init__(self, image_hw, weights, anchors, mc_samples, device=0, batch=1, group=None, merge_method='bayes', **make_config_kwargs):
         from .engine import Engine, make_config
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -356,6 +359,7 @@ class StatShardedEngine(object):
                                          mc_statistics=True, **make_config_kwargs))
         self.engine.load_weights(weights)
         self.engine.set_anchors(anchors)
+        self.engine.set_merge_method(merge_method)
         self._local = stat_views(self.engine)
         self._gathered = None                     # kept alive until the folds that read it have run
 

@@ -14,6 +14,14 @@ _KINDS = {"kernel": 0, "bias": 1, "gamma": 2, "beta": 3, "mean": 4, "var": 5}
 # three MFMA products, the 1e-3 end-to-end parity mode on the bf16 matrix pipe
 PRECISIONS = {"bf16": 0, "fp32": 1, "bf16x3": 2, "f16mx": 3, "f16mx4": 4}
 VIEWS = {"identity": _lib.BOD_VIEW_IDENTITY, "hflip": _lib.BOD_VIEW_HFLIP}      # test-time views of a statistics handle
+MERGE_METHODS = _lib.MERGE_METHODS                # how a cluster becomes a detection (bod_set_merge_method)
+
+
+def merge_method_id(method):
+    """'bayes' / 'centre' / 'mixture' -> BOD_MERGE_*; ValueError names the choices for anything else."""
+    if not isinstance(method, str) or method not in MERGE_METHODS:
+        raise ValueError("merge_method must be one of %s, got %r" % (sorted(MERGE_METHODS), method))
+    return MERGE_METHODS[method]
 
 
 def make_config(image_hw, batch=1, mc_samples=10, num_classes=8, anchors_per_location=9, device=0,
@@ -669,6 +677,46 @@ class Engine(object):
 
     def cluster_fuse(self):
         self._chk(self.lib.bod_cluster_fuse(self.h))
+
+    # -- how a cluster becomes a detection (include/bayesod.h, bod_set_merge_method) ----------
+    def set_merge_method(self, method):
+        """'bayes' (the default: the Bayesian fuse), 'centre' (the NMS pick: the centre's own posterior) or 'mixture' (the
+        equal-weight Gaussian mixture of the members), for the next cluster_fuse / infer / infer_async (``bod_set_merge_method``)."""
+        self._chk(self.lib.bod_set_merge_method(self.h, merge_method_id(method)))
+
+    @property
+    def merge_method(self):
+        m = C.c_int32(0)
+        self._chk(self.lib.bod_get_merge_method(self.h, C.byref(m)))
+        return {v: k for k, v in _lib.MERGE_METHODS.items()}[int(m.value)]
+
+    def get_detection_merge_terms(self, image_index=0):
+        """(within [K,4,4], between [K,4,4], members [K]) of every detection of ``get_detections(image_index)`` after a 'centre' or
+        'mixture' cluster stage; covs = within + between (``bod_get_detection_merge_terms``)."""
+        within = np.empty((self.K, 4, 4), np.float32)
+        between = np.empty((self.K, 4, 4), np.float32)
+        members = np.empty(self.K, np.int32)
+        n = C.c_int32(0)
+        self._chk(self.lib.bod_get_detection_merge_terms(self.h, image_index, fptr(within), fptr(between), iptr(members)))
+        self._chk(self.lib.bod_get_detections(self.h, image_index, C.byref(n), None, None, None, None))
+        n = n.value
+        return within[:n].copy(), between[:n].copy(), members[:n].copy()
+
+    def get_detection_merge_terms_batch(self, slot=-1):
+        """{'within' [B,K,4,4], 'between' [B,K,4,4], 'members' [B,K]}, padded with zero rows like ``get_detections_batch``;
+        ``slot``: a ticket of ``infer_async`` (waits for that batch), -1 after a synchronous call
+        (``bod_get_detection_merge_terms_batch``)."""
+        out = {"within": np.empty((self.B, self.K, 4, 4), np.float32), "between": np.empty((self.B, self.K, 4, 4), np.float32),
+               "members": np.empty((self.B, self.K), np.int32)}
+        self._chk(self.lib.bod_get_detection_merge_terms_batch(self.h, int(slot), fptr(out["within"]), fptr(out["between"]),
+                                                               iptr(out["members"])))
+        return out
+
+    def device_detection_merge_terms_pointers(self, slot=0):
+        ptrs = (C.c_void_p * 3)()
+        self._chk(self.lib.bod_device_detection_merge_terms(self.h, slot, ptrs))
+        shapes = [(self.B, self.K, 16), (self.B, self.K, 16), (self.B, self.K)]
+        return {n: (int(p or 0), s) for n, p, s in zip(("within", "between", "members"), ptrs, shapes)}
 
     def get_detections(self, image_index=0):
         k = self.K

@@ -76,7 +76,8 @@ def bayes_od_inference(model, sample_dict, bayes_od_config, nms_config, use_full
 
 
 def bayes_od_clustering(predicted_boxes_class_counts, predicted_boxes_means, predicted_boxes_covs,
-                        cluster_centers, affinity_matrix=None, affinity_threshold=0.7, engine=None, class_parts=None):
+                        cluster_centers, affinity_matrix=None, affinity_threshold=0.7, engine=None, class_parts=None,
+                        merge_method='bayes', return_merge_terms=False):
     """Bayesian cluster-and-fuse on the device (reference :285-364).
 
     Returns (final_scores [K,C], final_means [K,4,1], final_covs [K,4,4] (x70), final_counts [K,C]).
@@ -90,8 +91,18 @@ def bayes_od_clustering(predicted_boxes_class_counts, predicted_boxes_means, pre
     ``class_parts``: the rows' class_entropy_parts [M,3+C] as ``bayes_od_inference(..., class_parts=True)`` returns them (total,
     aleatoric, epistemic, mean_probs[C]); a fifth value follows, final_class_parts [K,4] = total, aleatoric, epistemic_mc,
     epistemic_spatial entropy of every detection's MC class distribution.  An ``engine`` must then have been made with the option.
+    ``merge_method``: 'bayes' (the reference's fusion), 'centre' (the NMS pick: each centre's own row, no factor 70) or 'mixture'
+    (the equal-weight Gaussian mixture of the members, no factor 70) -- ``Engine.set_merge_method``; set on every call, the
+    default included, because the stand-alone handle is shared between calls.  ``return_merge_terms=True`` (not with 'bayes')
+    appends merge_within [K,4,4], merge_between [K,4,4] and merge_members [K]: final_covs = within + between.  Neither goes
+    with ``class_parts``.
     """
-    from .engine import Engine, make_config
+    from .engine import Engine, make_config, merge_method_id
+    merge_method_id(merge_method)
+    if merge_method != 'bayes' and class_parts is not None:
+        raise ValueError("merge_method=%r does not go with class_parts: the class-entropy parts are defined for the Bayesian fuse only" % merge_method)
+    if return_merge_terms and merge_method == 'bayes':
+        raise ValueError("return_merge_terms needs merge_method 'centre' or 'mixture': the Bayesian fuse has no merge terms")
     counts = np.ascontiguousarray(predicted_boxes_class_counts, dtype=np.float32)
     means = np.ascontiguousarray(predicted_boxes_means, dtype=np.float32).reshape(-1, 4)
     covs = np.ascontiguousarray(predicted_boxes_covs, dtype=np.float32).reshape(-1, 4, 4)
@@ -107,11 +118,14 @@ def bayes_od_clustering(predicted_boxes_class_counts, predicted_boxes_means, pre
     if k == 0 or m == 0:
         out = (np.zeros((0, c), np.float32), np.zeros((0, 4, 1), np.float32),
                np.zeros((0, 4, 4), np.float32), np.zeros((0, c), np.float32))
+        if return_merge_terms:
+            out += (np.zeros((0, 4, 4), np.float32), np.zeros((0, 4, 4), np.float32), np.zeros(0, np.int32))
         return out + (np.zeros((0, 4), np.float32),) if class_parts is not None else out
     eng = engine if engine is not None else _standalone_engine(m, c, k, class_parts is not None)
     cfg = eng.cfg
     cfg.nms_iou_threshold = float(affinity_threshold)
     eng.update_config(cfg)
+    eng.set_merge_method(merge_method)
     eng.set_posterior(0, counts, means, covs, np.zeros(m, np.float32))
     if class_parts is not None:
         eng.set_posterior_class_parts(0, class_parts[:, 3:], class_parts[:, :3])
@@ -126,6 +140,8 @@ def bayes_od_clustering(predicted_boxes_class_counts, predicted_boxes_means, pre
     eng.cluster_fuse()
     scores, fmeans, fcovs, fcounts = eng.get_detections(0)
     out = (scores, fmeans[:, :, None], fcovs, fcounts)
+    if return_merge_terms:
+        out += eng.get_detection_merge_terms(0)
     return out + (eng.get_detection_class_parts(0),) if class_parts is not None else out
 
 
@@ -179,13 +195,24 @@ def _detections(engine):
     return dets
 
 
+def _checked_merge_method(merge_method, covariance_parts=False, class_parts=False):
+    from .engine import merge_method_id
+    merge_method_id(merge_method)
+    if merge_method != 'bayes' and (covariance_parts or class_parts):
+        raise ValueError("merge_method=%r does not go with covariance_parts / class_parts: the parts are defined for the Bayesian "
+                         "fuse only" % merge_method)
+    return merge_method
+
+
 class BayesOdPipeline(object):
     """Batched, fully device-resident form of the reference's per-image loop body
     (src/retina_net/experiments/run_inference.py:137-161): forward -> posterior -> soft-NMS ->
     cluster-and-fuse for ``batch`` images per call, no host round trip in between."""
 
     def __init__(self, model, image_hw, batch, bayes_od_config, nms_config, use_full_covar=True,
-                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, covariance_parts=False, class_parts=False):
+                 dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, covariance_parts=False, class_parts=False,
+                 merge_method='bayes'):
+        self._merge = _checked_merge_method(merge_method, covariance_parts, class_parts)
         self._kw = dict(bayes_od_config=bayes_od_config, nms_config=nms_config, use_full_covar=use_full_covar,
                         dataset_name=dataset_name, nms_variant=nms_variant, orig_size=orig_size)
         if covariance_parts:
@@ -205,7 +232,12 @@ class BayesOdPipeline(object):
         if orig_size is not None:
             self._kw['orig_size'] = tuple(orig_size)
         self.engine = self.model.engine_for(self._hw, batch=self._batch, mc_samples=self.model.mc_dropout_samples, **self._kw)
+        self.engine.set_merge_method(self._merge)          # (the handle is shared: set on every bind, the default included)
         return self.engine
+
+    def merge_terms(self):
+        """Per image (within [K,4,4], between [K,4,4], members [K]) of the last call's detections ('centre' / 'mixture' only)."""
+        return [self.engine.get_detection_merge_terms(b) for b in range(self.engine.B)]
 
     def upload_mixed(self, frames, means, aspect_resize=True, corruption=None):
         """``batch`` uint8 frames of mixed source sizes into the engine, for ``__call__(None, ...)``: every frame is rescaled by
@@ -241,8 +273,9 @@ class EnsemblePipeline(object):
 
     def __init__(self, models, image_hw, batch, bayes_od_config, nms_config, samples_per_member, passes=1, use_full_covar=True,
                  dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, views=('identity',), covariance_parts=False,
-                 class_parts=False):
+                 class_parts=False, merge_method='bayes'):
         from .engine import Engine, make_config
+        self._merge = _checked_merge_method(merge_method, covariance_parts, class_parts)
         models = list(models)
         if not models:
             raise ValueError("EnsemblePipeline needs at least one model")
@@ -275,6 +308,7 @@ class EnsemblePipeline(object):
             eng.load_weights(m._weights)
             self.engines.append(eng)
         self.engine = self.engines[0]             # uploads, the merged accumulator and the Bayesian stages live here
+        self.engine.set_merge_method(self._merge)
         if anchors is not None:
             self.set_anchors(anchors)
 
@@ -325,6 +359,10 @@ class EnsemblePipeline(object):
         self.engine.nms()
         self.engine.cluster_fuse()
         return _detections(self.engine)
+
+    def merge_terms(self):
+        """Per image (within [K,4,4], between [K,4,4], members [K]) of the last call's detections ('centre' / 'mixture' only)."""
+        return [self.engine.get_detection_merge_terms(b) for b in range(self.engine.B)]
 
 
 def post_process_predictions(sample_dict, prediction_dict, dataset_name='bdd', engine=None, nms_config=None):

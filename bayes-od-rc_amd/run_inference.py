@@ -28,6 +28,7 @@ def test_model(config, args):
     want_class = _want_class_parts(config, args)          # decided once: the writer and every pipeline get the same answer
     if test_config['uncertainty_method'] != 'bayes_od':
         raise ValueError("only uncertainty_method 'bayes_od' is supported (as in the reference release)")
+    merge = check_merge_options(config, args)             # likewise; refuses what does not go together before anything is built
     dataset_config = config['dataset_config']
     training_dataset = dataset_config['dataset']
     test_dataset = test_config['test_dataset']
@@ -59,19 +60,22 @@ def test_model(config, args):
         if b not in pipes:
             pipes[b] = _make_pipeline(model, args, hw, b, test_config['bayes_od_config'], nms_config,
                                       use_full_covar=test_config['use_full_covar'],
-                                      dataset_name=test_dataset, orig_size=orig, anchors=anchors, class_parts=want_class)
+                                      dataset_name=test_dataset, orig_size=orig, anchors=anchors, class_parts=want_class,
+                                      merge_method=merge)
         return pipes[b]
     predictions_dir = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'], 'predictions')
     writer = writers.PredictionWriter(predictions_dir, test_dataset, test_config['ckpt_idx'],
                                       test_config['uncertainty_method'],
-                                      test_config['bayes_od_config']['fusion_method'], cov_parts=_want_parts(args),
-                                      class_parts=want_class)
+                                      writer_fusion_name(test_config['bayes_od_config']['fusion_method'], merge),
+                                      cov_parts=_want_parts(args), class_parts=want_class)
     categories = dataset_config[training_dataset]['training_data_config']['categories']
     start = time.time()
     n_done = 0
     for lo in range(0, len(frames), batch):              # every frame, like the reference's loop (run_inference.py:137)
         chunk = frames[lo:lo + batch]
         dets = pipe_for(len(chunk))(chunk, seed=args.seed, first_image_id=lo)
+        if _want_merge_terms(args):
+            _write_merge_terms(writer.root, ['%06d' % (lo + b) for b in range(len(chunk))], pipe_for(len(chunk)).merge_terms())
         for b, (classes, boxes_vuhw, covs, counts, *parts) in enumerate(dets):
             parts = _part_kwargs(_want_parts(args), want_class, parts)
             boxes = box_utils.vuhw_to_vuvu_np(boxes_vuhw) if boxes_vuhw.size else boxes_vuhw
@@ -101,6 +105,57 @@ def _ensemble_members(config, args):
         m.load_weights(path)
         members.append(m)
     return members
+
+
+MERGE_TERM_DIRS = ('merge_within', 'merge_between', 'merge_members')
+
+
+def resolve_merge_method(config, flag=None):
+    """How a cluster becomes a detection: --merge_method if given, else the yaml's testing_config.bayes_od_config.merge_method,
+    else 'bayes'.  ValueError for a name that is none of 'bayes', 'centre', 'mixture'."""
+    from .engine import MERGE_METHODS
+    name = flag
+    if name is None:
+        name = ((config.get('testing_config') or {}).get('bayes_od_config') or {}).get('merge_method')
+    if name is None:
+        name = 'bayes'
+    if name not in MERGE_METHODS:
+        raise ValueError("merge_method must be one of %s, got %r" % (sorted(MERGE_METHODS), name))
+    return name
+
+
+def writer_fusion_name(fusion_method, merge_method):
+    """The ``fusion_method`` PredictionWriter names the tree after: the yaml's for the default method (today's path), and
+    '<fusion_method>-<merge_method>' for another, so the trees of one checkpoint sit side by side."""
+    return fusion_method if merge_method == 'bayes' else '%s-%s' % (fusion_method, merge_method)
+
+
+def check_merge_options(config, args):
+    """The resolved merge method; ValueError for a combination the library refuses: a non-default method with the covariance or
+    class-entropy parts (they are defined for the Bayesian fuse only), --merge_terms with the default method (it has none)."""
+    merge = resolve_merge_method(config, getattr(args, 'merge_method', None))
+    if merge != 'bayes' and _want_parts(args):
+        raise ValueError("--merge_method %s does not go with --covariance_parts: the covariance parts are defined for the Bayesian "
+                         "fuse only" % merge)
+    if merge != 'bayes' and _want_class_parts(config, args):
+        raise ValueError("--merge_method %s does not go with --class_uncertainty: the class-entropy parts are defined for the "
+                         "Bayesian fuse only" % merge)
+    if merge == 'bayes' and _want_merge_terms(args):
+        raise ValueError("--merge_terms needs --merge_method centre or mixture: the Bayesian fuse has no merge terms")
+    return merge
+
+
+def _want_merge_terms(args):
+    return bool(getattr(args, 'merge_terms', False))
+
+
+def _write_merge_terms(root, names, terms):
+    """--merge_terms: merge_within/<frame>.npy [K,4,4], merge_between/<frame>.npy [K,4,4], merge_members/<frame>.npy [K] beside cov/."""
+    for d in MERGE_TERM_DIRS:
+        os.makedirs(os.path.join(root, d), exist_ok=True)
+    for name, arrays in zip(names, terms):
+        for d, a in zip(MERGE_TERM_DIRS, arrays):
+            np.save(os.path.join(root, d, name + '.npy'), a)
 
 
 def _want_parts(args):
@@ -142,13 +197,15 @@ def _test_model_on_dataset(config, args, model):
     from . import constants, datasets
     test_config = config['testing_config']
     want_class = _want_class_parts(config, args)
+    merge = check_merge_options(config, args)
     dataset_config = config['dataset_config']
     training_dataset, test_dataset = dataset_config['dataset'], test_config['test_dataset']
     handler = datasets.build_dataset(dict(dataset_config, dataset=test_dataset), 'test')
     kitti = test_dataset == 'kitti'
     predictions_dir = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'], 'predictions')
     writer = writers.PredictionWriter(predictions_dir, test_dataset, test_config['ckpt_idx'],
-                                      test_config['uncertainty_method'], test_config['bayes_od_config']['fusion_method'],
+                                      test_config['uncertainty_method'],
+                                      writer_fusion_name(test_config['bayes_od_config']['fusion_method'], merge),
                                       cov_parts=_want_parts(args), class_parts=want_class)
     categories = dataset_config[training_dataset]['training_data_config']['categories']
     gen = FpnAnchorGenerator(dataset_config['anchor_generator'])
@@ -162,7 +219,9 @@ def _test_model_on_dataset(config, args, model):
     handler.defer_decode = device_jpeg       # JPEG files travel as bytes and are decoded on the device at upload
     handler.defer_png = device_png           # PNG files likewise
 
-    def emit(dets):
+    def emit(dets, pipe):
+        if _want_merge_terms(args):
+            _write_merge_terms(writer.root, [p[0] for p in pending], pipe.merge_terms())
         for (name, _, _), (classes, boxes_vuhw, covs, counts, *parts) in zip(pending, dets):
             parts = _part_kwargs(_want_parts(args), want_class, parts)
             boxes = box_utils.vuhw_to_vuvu_np(boxes_vuhw) if boxes_vuhw.size else boxes_vuhw
@@ -184,13 +243,13 @@ def _test_model_on_dataset(config, args, model):
             pipes[key] = _make_pipeline(
                 model, args, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
                 use_full_covar=test_config['use_full_covar'], dataset_name=test_dataset, orig_size=hw,
-                anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class)
+                anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class, merge_method=merge)
         pipe = pipes[key]
         # (a frame's corruption is keyed on its dataset index: the same whatever batch or run it falls into)
         corruption = None if corrupt is None else (corrupt[0], [p[2] for p in pending], corrupt[1])
         pipe.upload_mixed([p[1] for p in pending], constants.MEANS_DICT[handler.im_normalization], aspect_resize=kitti,
                           corruption=corruption)
-        emit(pipe(None, seed=args.seed, first_image_id=pending[0][2]))
+        emit(pipe(None, seed=args.seed, first_image_id=pending[0][2]), pipe)
 
     def flush():
         if mixed:
@@ -205,11 +264,11 @@ def _test_model_on_dataset(config, args, model):
             pipes[key] = _make_pipeline(
                 model, args, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
                 use_full_covar=test_config['use_full_covar'], dataset_name=test_dataset, orig_size=src_hw,
-                anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class)
+                anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class, merge_method=merge)
         pipe = pipes[key]
         pipe.bind(orig_size=src_hw)      # the handle may be shared with a pipe of another source size: re-apply the KITTI scale
         pipe.engine.upload_frames_u8(frames, constants.MEANS_DICT[handler.im_normalization], aspect_resize=kitti)
-        emit(pipe(None, seed=args.seed, first_image_id=pending[0][2]))
+        emit(pipe(None, seed=args.seed, first_image_id=pending[0][2]), pipe)
 
     start, n_done = time.time(), 0
     for idx, sample in enumerate(handler.create_dataset()):
@@ -285,6 +344,13 @@ def main(argv=None):
                     '(class_entropy/<frame>.npy [K,4]: total, aleatoric, epistemic_mc, epistemic_spatial; the last three sum to the '
                     'first) beside cov/; works with --ensemble, --mc_passes, --tta_flip and --covariance_parts; yaml key: '
                     'testing_config.class_uncertainty')
+    ap.add_argument('--merge_method', choices=('bayes', 'centre', 'mixture'), default=None, help='how a cluster of kept anchors becomes a '
+                    'detection: bayes (default) multiplies the members\' Gaussians; centre reports the centre\'s own posterior, what plain '
+                    'NMS would; mixture is the equal-weight Gaussian mixture of the members.  The tree of a non-default method is '
+                    'bayes_od_<fusion_method>-<merge_method>; yaml key: testing_config.bayes_od_config.merge_method (the flag wins); not '
+                    'with --covariance_parts / --class_uncertainty')
+    ap.add_argument('--merge_terms', action='store_true', help='with --merge_method centre / mixture: also write merge_within/, '
+                    'merge_between/ ([K,4,4] each; cov = within + between) and merge_members/ ([K]) beside cov/')
     ap.add_argument('--corrupt', type=str, default=None, metavar='NAME:SEVERITY', help='with --dataset: corrupt every frame on the '
                     'GPU before preprocessing, to score uncertainty under dataset shift (gaussian_noise, impulse_noise, defocus_blur, '
                     'motion_blur, gaussian_blur, pixelate, jpeg_compression, contrast, brightness, low_light, fog; severity 1..5); '
@@ -310,6 +376,10 @@ def main(argv=None):
     config = config_utils.setup(config, args)
     if args.device_jpeg and not args.dataset:
         ap.error('--device_jpeg requires --dataset')
+    try:
+        check_merge_options(config, args)
+    except ValueError as e:
+        ap.error(str(e))
     if args.device_png and not args.dataset:
         ap.error('--device_png requires --dataset')
     try:

@@ -952,6 +952,47 @@ bod_status bod_get_detection_class_parts_batch(bod_handle h, float* rows);
 bod_status bod_collect_class_parts(bod_handle h, int32_t slot, float* rows);
 bod_status bod_device_detection_class_parts(bod_handle h, int32_t slot, void** ptr);
 
+/* ---- how a cluster becomes a detection: the Bayesian fuse, the NMS pick, or the equal-weight Gaussian mixture ----
+ * bod_cluster_fuse multiplies the members' Gaussians and scales the result by 70 (BOD_MERGE_BAYES, the default and the method of
+ * bayes_od_clustering).  The two other methods give the other side of that comparison on the same posterior and the same clusters.
+ * Membership is the same for all three: the rows i < num_kept whose affinity to centre k is > nms_iou_threshold, the affinity being
+ * the IoU of the posterior means evaluated on the fly or the one-shot columns of bod_set_affinity.
+ * With n the member count, c the centre's row, mu_i / Sigma_i / counts_i the members' posterior rows and d_i = mu_i - mu_c (the
+ * shift by the centre keeps the second moments well conditioned in fp32):
+ *   BOD_MERGE_BAYES    today's kernel and results; nothing below is written.
+ *   BOD_MERGE_CENTRE   what plain NMS reports, the centre's own posterior:  mean = mu_c, cov = Sigma_c (no factor 70),
+ *                      counts = counts_c, scores_j = counts_cj / sum_j counts_cj (summed for j ascending).
+ *                      Terms: within = Sigma_c, between = 0, members = n.
+ *   BOD_MERGE_MIXTURE  the moment-matched mixture of the members with weight 1/n each:
+ *                        dbar = (1/n) sum d_i,  mean = mu_c + dbar,
+ *                        within  = (1/n) sum Sigma_i,
+ *                        between = (1/n) sum d_i d_i^T - dbar dbar^T   (evaluated on the lower triangle and mirrored; within likewise),
+ *                        cov = within + between (no factor 70),
+ *                        scores = (1/n) sum counts_i / sum_j(counts_ij),  counts = (1/n) sum counts_i.
+ *                      `between` is the spread of the members' means: the "output redundancy" spatial uncertainty.
+ *   n == 0 (only under a caller's affinity whose column excludes every row, the centre included): both new methods return the
+ *   centre's row as BOD_MERGE_CENTRE does, with members = 0.  (BOD_MERGE_BAYES divides by zero there, as before.)
+ * fp32 throughout, no fused multiply-add; the sums over the members are re-associated (256 threads, wave butterflies).
+ * bod_set_merge_method: takes effect with the next bod_cluster_fuse, bod_infer or bod_infer_async enqueued (so it also serves
+ * statistics handles: bod_stat_posterior -> bod_nms -> bod_cluster_fuse).  BOD_ERR_INVALID_ARG, with a message, for an unknown
+ * value, for a training = 1 handle, and for a non-default method on a handle whose covariance_parts is non-zero: the covariance and
+ * class-entropy parts kernels are defined for the Bayesian fuse only, and extending them is out of scope.  After a refusal the
+ * handle's method is unchanged.  The first non-default call allocates the term buffers (2 slots x batch x max_detections x 33 words).
+ * bod_get_detection_merge_terms / _batch: within [K][16], between [K][16], members [K] of one image / the same with
+ * [batch][max_detections] in front (rows beyond an image's count zero), rows as bod_get_detections[_batch]; NULLs skipped.
+ * _batch's slot = -1 is the slot synchronous calls use; slot 0 / 1 is a bod_infer_async ticket: the call waits for that batch as
+ * bod_collect does, does not release the slot, and may come before bod_collect or after it, until the next bod_infer_async that
+ * reuses the slot.  BOD_ERR_NOT_READY when the slot's last cluster stage ran as BOD_MERGE_BAYES (or none has run).
+ * bod_device_detection_merge_terms: device addresses {within, between, members} of a slot (see bod_device_detections); NULLs
+ * before the first non-default bod_set_merge_method.
+ * The five detection arrays, bod_record_width and bod_gather_detections do not know the method: the terms are not in the records. */
+enum { BOD_MERGE_BAYES = 0, BOD_MERGE_CENTRE = 1, BOD_MERGE_MIXTURE = 2 };
+bod_status bod_set_merge_method(bod_handle h, int32_t method);
+bod_status bod_get_merge_method(bod_handle h, int32_t* method);
+bod_status bod_get_detection_merge_terms(bod_handle h, int32_t image_index, float* within, float* between, int32_t* members);
+bod_status bod_get_detection_merge_terms_batch(bod_handle h, int32_t slot, float* within, float* between, int32_t* members);
+bod_status bod_device_detection_merge_terms(bod_handle h, int32_t slot, void** ptrs3);
+
 /* What the handle's plan looks like (tests / bench report it; nothing on the hot path reads it).  info8[0] = 1 when the MC
  * statistics are reduced inside the last tower layers' tiles (no [B,N,A,.] tensors on the bod_infer path), [1] = 1 when the 1x1
  * head output convs are fused into the last tower layers' epilogues, [2] = 1 when the per-sample tower layers run on the

@@ -309,6 +309,12 @@ bod_status bod_get_detection_class_parts(bod_handle h, int32_t image_index, floa
 bod_status bod_get_detection_class_parts_batch(bod_handle h, float* rows);
 bod_status bod_collect_class_parts(bod_handle h, int32_t slot, float* rows);
 bod_status bod_device_detection_class_parts(bod_handle h, int32_t slot, void** ptr);
+enum { BOD_MERGE_BAYES = 0, BOD_MERGE_CENTRE = 1, BOD_MERGE_MIXTURE = 2 };
+bod_status bod_set_merge_method(bod_handle h, int32_t method);
+bod_status bod_get_merge_method(bod_handle h, int32_t* method);
+bod_status bod_get_detection_merge_terms(bod_handle h, int32_t image_index, float* within, float* between, int32_t* members);
+bod_status bod_get_detection_merge_terms_batch(bod_handle h, int32_t slot, float* within, float* between, int32_t* members);
+bod_status bod_device_detection_merge_terms(bod_handle h, int32_t slot, void** ptrs3);
 bod_status bod_plan_info(bod_handle h, int32_t* info8);
 bod_status bod_plan_info_n(bod_handle h, int32_t* info, int32_t n);
 bod_status bod_stat_reset(bod_handle h);
