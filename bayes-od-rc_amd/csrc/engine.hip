@@ -5,6 +5,7 @@
 #include "../../include/bayesod.h"
 #include "kernels.h"
 #include "plane_tables.h"
+#include "record_state.h"
 #include "jpeg_entropy.h"
 #include "png_inflate.h"
 #include "render_font.h"
@@ -267,6 +268,25 @@ struct DecodeSlot {
     }
 };
 
+// One buffer of detection records and everything that belongs to it.  The device arrays are [B,K,.] (nms_nsel [B]); the pinned copy
+// is laid out by RecordLayout (record_state.h).
+struct RecordSlot {
+    int32_t* nms_sel = nullptr; int32_t* nms_nsel = nullptr;           // cluster centres and their count per image
+    float* scores = nullptr; float* means = nullptr; float* covs = nullptr; float* counts = nullptr;
+    float* parts = nullptr; float* cparts = nullptr;                   // [B,K,3,16] / [B,K,4] on handles with covariance / class-entropy parts
+    // merge terms, from the first non-default bod_set_merge_method on: within / between [B,K,16], members [B,K]; merge_terms_ok: the
+    // slot's last cluster stage wrote them (it ran as CENTRE or MIXTURE)
+    float* merge_within = nullptr; float* merge_between = nullptr; int32_t* merge_members = nullptr;
+    bool merge_terms_ok = false;
+    std::vector<char> parts_ok, cparts_ok;                             // per image: the handle's parts_ok / cparts_ok at the slot's cluster-fuse
+    // a ticket of bod_infer_async
+    char* host_stage = nullptr;                // pinned host copy of the records (filled on the stream that finished them)
+    hipEvent_t done = nullptr;
+    hipStream_t done_stream = nullptr;         // the stream that recorded `done`: a ticket's gather follows on it
+    bool pending = false;                      // not collected yet
+    bool parts_staged = false, cparts_staged = false;                  // host_stage holds the parts of a ticket
+};
+
 struct bod_context {
     bod_config cfg{};
     std::string err;
@@ -294,8 +314,8 @@ struct bod_context {
     std::map<std::string, HostTensor> host_w;           // "name/kind"
     std::map<std::string, PackedConv> packed;
     float* stem_w = nullptr; float* stem_b = nullptr;
-    bool weights_ready = false, anchors_ready = false, forward_done = false, posterior_done = false,
-         nms_done = false, cluster_done = false;
+    bool weights_ready = false, anchors_ready = false;
+    StageState stage;                                   // which of forward / posterior / nms / cluster has run (record_state.h)
 
     // activations
     float* d_images = nullptr;
@@ -378,19 +398,14 @@ struct bod_context {
     float* nms_scores = nullptr; int32_t* nms_begin = nullptr;
     // detection records are double-buffered ("slots") so the latency-bound NMS + cluster-fuse of one
     // batch can run on a side stream underneath the next batch's convolutions
-    int32_t* nms_sel_s[2] = {nullptr, nullptr}; int32_t* nms_nsel_s[2] = {nullptr, nullptr};
-    float* out_scores_s[2] = {nullptr, nullptr}; float* out_means_s[2] = {nullptr, nullptr};
-    float* out_covs_s[2] = {nullptr, nullptr}; float* out_counts_s[2] = {nullptr, nullptr};
-    int32_t* nms_sel = nullptr; int32_t* nms_nsel = nullptr;          // = current slot
-    float* out_scores = nullptr; float* out_means = nullptr; float* out_covs = nullptr; float* out_counts = nullptr;
+    RecordSlot rec[2];
     int slot = 0;
+    RecordSlot& cur() { return rec[slot]; }             // the slot run_nms / run_cluster write and the synchronous getters read
     // Covariance parts (bod_config.covariance_parts; nullptr / empty on every other handle): the per-anchor lower triangles behind
     // pb.covs, the detections' [B,K,3,16] double-buffered with the records.  parts_ok[img]: the image's rows of `parts` belong to its
-    // posterior (false between bod_set_posterior and bod_set_posterior_parts); det_parts_ok[slot][img]: ... at the slot's cluster-fuse.
+    // posterior (false between bod_set_posterior and bod_set_posterior_parts); rec[slot].parts_ok[img]: ... at the slot's cluster-fuse.
     float* parts = nullptr;
-    float* out_parts_s[2] = {nullptr, nullptr}; float* out_parts = nullptr;
-    std::vector<char> parts_ok, det_parts_ok[2];
-    bool parts_staged[2] = {false, false};              // host_stage[slot] holds the parts of a bod_infer_async ticket
+    std::vector<char> parts_ok;
     // Class-entropy parts (bod_config.covariance_parts bit BOD_PARTS_CLASS; nullptr / empty on every other handle).  ent: the fresh
     // sum_n H(softmax) [B,A] of the last forward (AGG_CLS_ENT epilogue, or stat_from_raw_kernel); stat_ent: its accumulator on a
     // statistics handle, holding stat_ent_k of the record's stat_k samples; cparts: [B,A,3+C] per kept slot; the detections'
@@ -398,16 +413,10 @@ struct bod_context {
     bool class_parts = false;
     float* ent = nullptr; float* stat_ent = nullptr; int stat_ent_k = 0;
     float* cparts = nullptr;
-    float* out_cparts_s[2] = {nullptr, nullptr}; float* out_cparts = nullptr;
-    std::vector<char> cparts_ok, det_cparts_ok[2];
-    bool cparts_staged[2] = {false, false};
-    // How run_cluster merges a cluster (bod_set_merge_method).  The term buffers -- within / between [B,K,16] and
-    // members [B,K] per record slot -- exist from the first non-default setter call on; merge_terms_ok[slot]: the slot's last
-    // cluster stage wrote them (it ran as CENTRE or MIXTURE).
+    std::vector<char> cparts_ok;
+    // How run_cluster merges a cluster (bod_set_merge_method).  The slots' term buffers exist from the first
+    // non-default setter call on.
     int merge_method = BOD_MERGE_BAYES;
-    float* merge_within_s[2] = {nullptr, nullptr}; float* merge_between_s[2] = {nullptr, nullptr};
-    int32_t* merge_members_s[2] = {nullptr, nullptr};
-    bool merge_terms_ok[2] = {false, false};
     hipStream_t side = nullptr;
     // ---- CU-partitioned pipeline overlap (bod_config.pipeline_overlap; bod_infer_async only).  The memory-bound front of batch i+1
     // (stem, backbone, FPN) runs on its own stream, masked to the last `ov_front_slots` CU slots of every XCD, while the MFMA-bound
@@ -426,22 +435,12 @@ struct bod_context {
     int first_head_op = 0;                              // index of the first head launch in ops: everything before it is the front
     bool in_overlap_call = false;
     int n_cu = 256;                                     // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-    hipEvent_t ev_posterior = nullptr; hipEvent_t ev_done[2] = {nullptr, nullptr};
+    hipEvent_t ev_posterior = nullptr;
     int dev_op_lo = 0, dev_op_hi = 1 << 30;                   // BOD_FORWARD_OPS=lo:hi (development: tests/tools/selfcheck_probe.py): forward runs ops [lo, hi) only
-    hipStream_t done_stream[2] = {nullptr, nullptr};          // the stream that finished a slot's records (bod_infer_async): a ticket's gather follows on it
-    bool side_pending[2] = {false, false};
-    char* host_stage[2] = {nullptr, nullptr};     // pinned host copy of a slot's records (filled on the side stream)
     float* rec_send = nullptr; float* rec_recv = nullptr; size_t rec_recv_elems = 0;      // bod_gather_detections: packed records, gathered blocks
     hipEvent_t ev_gather = nullptr; hipStream_t gather_stream = nullptr;                  // last use of rec_send / rec_recv and the stream it went to
-    void select_slot(int sidx) {
-        slot = sidx;
-        nms_sel = nms_sel_s[sidx]; nms_nsel = nms_nsel_s[sidx];
-        out_scores = out_scores_s[sidx]; out_means = out_means_s[sidx];
-        out_covs = out_covs_s[sidx]; out_counts = out_counts_s[sidx];
-        out_parts = out_parts_s[sidx]; out_cparts = out_cparts_s[sidx];
-    }
     float* iou_scratch = nullptr; int64_t iou_cap = 0;
-    float* affinity = nullptr; int affinity_img = -1;   // bod_set_affinity: centre columns of a caller-supplied affinity matrix (one-shot)
+    float* affinity = nullptr;                           // bod_set_affinity: centre columns of a caller-supplied affinity matrix (one-shot; stage.affinity_img)
 
     // profiling
     bool profiling = false; int prof_which = 0;
@@ -482,6 +481,78 @@ struct bod_context {
 
 namespace {
 
+// The throw-away context of the stateless entry points (bod_stage_*, bod_loss_*, bod_anchor_targets): it owns the call's stream and
+// temporary device buffers; done() leaves the message where bod_last_error(NULL) finds it.
+struct StageScope {
+    bod_context ctx;
+    bod_context* h = &ctx;
+    bod_status done(bod_status s) {
+        if (s != BOD_OK) g_create_error = h->err;
+        if (h->stream) hipStreamSynchronize(h->stream);
+        for (void* p : h->allocs) hipFree(p);
+        if (h->stream) hipStreamDestroy(h->stream);
+        h->allocs.clear(); h->stream = nullptr;
+        return s;
+    }
+    bod_status open(int32_t device) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+            return h->fail(BOD_ERR_NO_DEVICE, "no HIP device %d: libbayesod_hip has no CPU fallback", device);
+        if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
+            return h->fail(BOD_ERR_HIP, "cannot set up device %d", device);
+        return BOD_OK;
+    }
+};
+
+// Forward row table of a convolution that reads a zero-bordered plane (pitch, bstride) -- one row per output pixel in (b, y, x)
+// order, in_off = the pixel's window origin (conv_out_geometry: oy, ox).  The other fields are zero: a caller that needs them
+// fills them in a second pass.
+std::vector<RowEnt> forward_row_table(int B, int OH, int OW, int stride, int oy, int ox, int pitch, int64_t bstride) {
+    std::vector<RowEnt> rows((size_t)B * OH * OW);
+    size_t r = 0;
+    for (int b = 0; b < B; ++b)
+        for (int y = 0; y < OH; ++y)
+            for (int xx = 0; xx < OW; ++xx) {
+                RowEnt e{};
+                e.in_off = (int32_t)(b * bstride + (int64_t)(y * stride + oy) * pitch + (xx * stride + ox));
+                e.in_pitch = pitch;
+                rows[r++] = e;
+            }
+    return rows;
+}
+
+// every batch still in a record slot finishes in front of what `st` gets next (the posterior's buffers are its readers' inputs)
+bod_status wait_pending_slots(bod_context* h, hipStream_t st) {
+    for (RecordSlot& r : h->rec)
+        if (r.pending) HIPCHK(h, hipStreamWaitEvent(st, r.done, 0));
+    return BOD_OK;
+}
+
+RecordLayout record_layout(const bod_context* h) {
+    return RecordLayout((size_t)h->cfg.batch, (size_t)h->cfg.nms_max_output_size, h->cfg.num_classes,
+                        (h->cfg.covariance_parts & BOD_PARTS_COVARIANCE) != 0, h->class_parts);
+}
+
+// A slot's pinned staging buffer, segment by segment, for every segment `ptr` names: filled from the device arrays there on `st`
+// (from_device), or copied out to the caller's arrays there.
+bod_status copy_staged(bod_context* h, const RecordSlot& r, void* const ptr[RecordLayout::SEGS], bool from_device, hipStream_t st) {
+    const RecordLayout L = record_layout(h);
+    for (int s = 0; s < RecordLayout::SEGS; ++s) {
+        const size_t n = L.bytes((RecordLayout::Seg)s);
+        if (!ptr[s] || n == 0) continue;
+        if (from_device) HIPCHK(h, hipMemcpyAsync(r.host_stage + L.off[s], ptr[s], n, hipMemcpyDeviceToHost, st));
+        else std::memcpy(ptr[s], r.host_stage + L.off[s], n);
+    }
+    return BOD_OK;
+}
+
+// the current slot's detection count of one image, on the host
+bod_status slot_count(bod_context* h, int32_t img, int32_t* num) {
+    HIPCHK(h, hipMemcpyAsync(num, h->cur().nms_nsel + img, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BOD_OK;
+}
+
 const char* kHeadPrefix[3] = {"pyramid_classification", "pyramid_regression", "pyramid_cov"};
 const int kHeadConvs[3] = {4, 3, 4};     // RegHeader.call uses 3 towers convs (multitask_headers.py:209-230)
 
@@ -492,12 +563,6 @@ void cu_slot_mask(int lo, int hi, uint32_t mask[8]) {
     for (int w = 0; w < 8; ++w) mask[w] = 0u;
     for (int slot = lo; slot < hi; ++slot)
         for (int xcd = 0; xcd < 8; ++xcd) { const int bit = slot * 8 + xcd; mask[bit >> 5] |= 1u << (bit & 31); }
-}
-
-int same_pad_before(int in, int k, int s) {
-    const int out = (in + s - 1) / s;
-    const int total = std::max((out - 1) * s + k - in, 0);
-    return total / 2;
 }
 
 bod_status new_plane(bod_context* h, Plane* p, int B, int hh, int ww, int C) {
@@ -654,8 +719,8 @@ bod_status add_conv(bod_context* h, const std::string& name, const std::string& 
         return h->fail(BOD_ERR_INVALID_ARG, "conv '%s': weight shape [%d->%d] does not match planes [%d->%d]",
                        name.c_str(), pc.cin, pc.cout, in.C, out.C);
     const int kh = pc.taps / pc.kw;
-    int oy = 1, ox = 1;
-    if (same) { oy = 1 - same_pad_before(in.h, kh, stride); ox = 1 - same_pad_before(in.w, pc.kw, stride); }
+    int OH, OW, oy, ox;                        // (the output plane is the caller's: only the window origin is taken from here)
+    conv_out_geometry(in.h, in.w, kh, pc.kw, stride, same, &OH, &OW, &oy, &ox);
     // the table depends on plane geometry only (offsets are relative to each buffer's base)
     char key[256], dense_key[256];
     for (int k = 0; k < 2; ++k)
@@ -1470,31 +1535,28 @@ bod_status alloc_post(bod_context* h) {
     BODCHK(h->dalloc(&h->nms_scores, BApad));
     BODCHK(h->dalloc(&h->nms_begin, BApad));
     const size_t BK = (size_t)c.batch * c.nms_max_output_size;
-    for (int sidx = 0; sidx < 2; ++sidx) {
-        BODCHK(h->dalloc(&h->nms_sel_s[sidx], BK));
-        BODCHK(h->dalloc(&h->nms_nsel_s[sidx], (size_t)c.batch));
-        BODCHK(h->dalloc(&h->out_scores_s[sidx], BK * c.num_classes));
-        BODCHK(h->dalloc(&h->out_means_s[sidx], BK * 4));
-        BODCHK(h->dalloc(&h->out_covs_s[sidx], BK * 16));
-        BODCHK(h->dalloc(&h->out_counts_s[sidx], BK * c.num_classes));
-        if (c.covariance_parts & BOD_PARTS_COVARIANCE) BODCHK(h->dalloc(&h->out_parts_s[sidx], BK * 48));
-        if (h->class_parts) BODCHK(h->dalloc(&h->out_cparts_s[sidx], BK * 4));
-        const size_t stage_bytes = ((size_t)c.batch + BK * (2 * (size_t)c.num_classes + 20 + ((c.covariance_parts & BOD_PARTS_COVARIANCE) ? 48 : 0) +
-                                                            (h->class_parts ? 4 : 0))) * 4;
-        if (hipHostMalloc(reinterpret_cast<void**>(&h->host_stage[sidx]), stage_bytes, hipHostMallocDefault) != hipSuccess)
+    const bool cov_parts = (c.covariance_parts & BOD_PARTS_COVARIANCE) != 0;
+    const size_t stage_bytes = record_layout(h).total();
+    for (RecordSlot& r : h->rec) {
+        BODCHK(h->dalloc(&r.nms_sel, BK));
+        BODCHK(h->dalloc(&r.nms_nsel, (size_t)c.batch));
+        BODCHK(h->dalloc(&r.scores, BK * c.num_classes));
+        BODCHK(h->dalloc(&r.means, BK * REC_MEAN));
+        BODCHK(h->dalloc(&r.covs, BK * REC_COV));
+        BODCHK(h->dalloc(&r.counts, BK * c.num_classes));
+        if (cov_parts) { BODCHK(h->dalloc(&r.parts, BK * REC_PARTS)); r.parts_ok.assign((size_t)c.batch, 0); }
+        if (h->class_parts) { BODCHK(h->dalloc(&r.cparts, BK * REC_CPARTS)); r.cparts_ok.assign((size_t)c.batch, 0); }
+        if (hipHostMalloc(reinterpret_cast<void**>(&r.host_stage), stage_bytes, hipHostMallocDefault) != hipSuccess)
             return h->fail(BOD_ERR_OOM, "pinned host staging buffer (%zu bytes)", stage_bytes);
     }
-    if (c.covariance_parts & BOD_PARTS_COVARIANCE) {
+    if (cov_parts) {
         BODCHK(h->dalloc(&h->parts, BA * BOD_PARTS_TRI));
         h->parts_ok.assign((size_t)c.batch, 0);
-        for (int sidx = 0; sidx < 2; ++sidx) h->det_parts_ok[sidx].assign((size_t)c.batch, 0);
     }
     if (h->class_parts) {
         BODCHK(h->dalloc(&h->cparts, BA * (3 + (size_t)c.num_classes)));
         h->cparts_ok.assign((size_t)c.batch, 0);
-        for (int sidx = 0; sidx < 2; ++sidx) h->det_cparts_ok[sidx].assign((size_t)c.batch, 0);
     }
-    h->select_slot(0);
     BODCHK(h->dalloc(&h->d_images, (size_t)c.batch * c.image_h * c.image_w * 3));
     h->d_images_b[0] = h->d_images;
     return BOD_OK;
@@ -1658,8 +1720,7 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
             case Op::KEEP: {
                 // the posterior's keep flags, then the sparse tail's row table from them -- on the device, no host round trip.  The
                 // flags and counts are the posterior's buffers: ordered behind the readers of an earlier call as run_posterior is.
-                for (int sidx = 0; sidx < 2; ++sidx)
-                    if (h->side_pending[sidx]) HIPCHK(h, hipStreamWaitEvent(st, h->ev_done[sidx], 0));
+                BODCHK(wait_pending_slots(h, st));
                 PostCfg pc = post_cfg(h, seed, first_image);
                 pc.aggregated = 1;
                 PostBuffers pb = h->pb;
@@ -1749,7 +1810,7 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
         }
         for (hipEvent_t& e : tev) hipEventDestroy(e);
     }
-    h->forward_done = true; h->posterior_done = h->nms_done = h->cluster_done = false; h->affinity_img = -1;
+    h->stage.forward_ran();
     h->last_seed = seed; h->last_first_image = first_image;
     if (!only_flavoured) h->last_sample_base = c.mc_sample_base;
     if (flavour == FLAVOUR_AGG) { h->agg_valid = true; h->raw_valid = false; h->agg_sparse = h->plan_sparse; }
@@ -1765,21 +1826,19 @@ bod_status materialise_raw(bod_context* h) {
     BODCHK(ensure_raw(h));
     const bool prof = h->profiling;
     h->profiling = false;
-    const bool fd = h->forward_done, pd = h->posterior_done, nd = h->nms_done, cd = h->cluster_done;
-    const int aff = h->affinity_img;
+    const StageState stage = h->stage;
     const int32_t base = h->cfg.mc_sample_base;
     h->cfg.mc_sample_base = h->last_sample_base;
     const bod_status st = run_forward(h, h->cur_images, h->last_seed, h->last_first_image, FLAVOUR_RAW, true);
     h->cfg.mc_sample_base = base;
     h->profiling = prof;
-    h->forward_done = fd; h->posterior_done = pd; h->nms_done = nd; h->cluster_done = cd; h->affinity_img = aff;
+    h->stage = stage;
     return st;
 }
 
 bod_status run_posterior(bod_context* h, uint64_t seed, uint32_t first_image) {
     if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called");
-    for (int sidx = 0; sidx < 2; ++sidx)
-        if (h->side_pending[sidx]) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_done[sidx], 0));
+    BODCHK(wait_pending_slots(h, h->stream));
     MarkerRange mr("bod:posterior");
     PostCfg pc = post_cfg(h, seed, first_image);
     PostBuffers pb = h->pb;
@@ -1806,15 +1865,14 @@ bod_status run_posterior(bod_context* h, uint64_t seed, uint32_t first_image) {
     if (h->cfg.ranking_method == BOD_RANK_JOINT_ENTROPY && h->cfg.gaussian_isotropic && h->cfg.dirichlet_non_informative)
         HIPCHK(h, launch_joint_entropy_rank(pc, pb, h->stream));
     if (h->profiling) { HIPCHK(h, hipEventRecord(e1, h->stream)); h->ev_post.emplace_back(e0, e1); }
-    h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;
+    h->stage.posterior_ran();
     return BOD_OK;
 }
 
 // validation_utils.post_process_predictions up to the NMS input, on MC sample 0 of the raw head outputs (bod_validation_post)
 bod_status run_validation_post(bod_context* h) {
     BODCHK(materialise_raw(h));
-    for (int sidx = 0; sidx < 2; ++sidx)
-        if (h->side_pending[sidx]) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_done[sidx], 0));
+    BODCHK(wait_pending_slots(h, h->stream));
     PostCfg pc = post_cfg(h, 0, 0);
     PostBuffers pb = h->pb;
     pb.cls = h->raw[0]; pb.box = h->raw[1]; pb.cov = h->raw[2]; pb.anchors = h->d_anchors;
@@ -1827,7 +1885,7 @@ bod_status run_validation_post(bod_context* h) {
         HIPCHK(h, hipMemsetAsync(h->cparts, 0, (size_t)h->cfg.batch * h->A * (3 + h->cfg.num_classes) * sizeof(float), h->stream));
         std::fill(h->cparts_ok.begin(), h->cparts_ok.end(), 1);
     }
-    h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;
+    h->stage.posterior_ran();
     return BOD_OK;
 }
 
@@ -1836,10 +1894,10 @@ bod_status run_nms(bod_context* h, hipStream_t st) {
     const bod_config& c = h->cfg;
     NmsArgs a{};
     a.B = c.batch; a.A = h->A; a.num_kept = h->pb.num_kept; a.corners = h->pb.corners; a.ranking = h->pb.ranking;
-    a.work_scores = h->nms_scores; a.work_begin = h->nms_begin; a.selected = h->nms_sel; a.num_selected = h->nms_nsel;
+    a.work_scores = h->nms_scores; a.work_begin = h->nms_begin; a.selected = h->cur().nms_sel; a.num_selected = h->cur().nms_nsel;
     a.max_out = c.nms_max_output_size; a.iou_thr = c.nms_iou_threshold; a.sigma = c.nms_soft_sigma; a.variant = c.nms_variant;
     HIPCHK(h, launch_nms(a, st));
-    h->nms_done = true; h->cluster_done = false; h->affinity_img = -1;      // new centres: a pending bod_set_affinity was sized for the old ones
+    h->stage.nms_ran();
     return BOD_OK;
 }
 
@@ -1848,22 +1906,23 @@ bod_status run_cluster(bod_context* h, hipStream_t st) {
     const bod_config& c = h->cfg;
     ClusterArgs a{};
     a.B = c.batch; a.A = h->A; a.C = c.num_classes; a.max_out = c.nms_max_output_size;
-    a.num_kept = h->pb.num_kept; a.selected = h->nms_sel; a.num_selected = h->nms_nsel;
+    RecordSlot& r = h->cur();
+    a.num_kept = h->pb.num_kept; a.selected = r.nms_sel; a.num_selected = r.nms_nsel;
     a.corners = h->pb.corners; a.counts = h->pb.counts; a.means = h->pb.means; a.covs = h->pb.covs;
     a.thr = c.nms_iou_threshold;
-    a.affinity = h->affinity_img >= 0 ? h->affinity : nullptr; a.affinity_img = h->affinity_img;
-    h->affinity_img = -1;                         // consumed by this call
-    a.out_scores = h->out_scores; a.out_means = h->out_means; a.out_covs = h->out_covs; a.out_counts = h->out_counts;
+    a.affinity = h->stage.affinity_img >= 0 ? h->affinity : nullptr; a.affinity_img = h->stage.affinity_img;
+    h->stage.affinity_img = -1;                   // consumed by this call
+    a.out_scores = r.scores; a.out_means = r.means; a.out_covs = r.covs; a.out_counts = r.counts;
     if (h->merge_method == BOD_MERGE_BAYES) {
         HIPCHK(h, launch_cluster_fuse(a, st));
     } else {
-        const MergeTerms terms{h->merge_within_s[h->slot], h->merge_between_s[h->slot], h->merge_members_s[h->slot]};
+        const MergeTerms terms{r.merge_within, r.merge_between, r.merge_members};
         HIPCHK(h, launch_cluster_merge(a, h->merge_method, terms, st));
     }
-    h->merge_terms_ok[h->slot] = h->merge_method != BOD_MERGE_BAYES;
-    if (h->parts) { HIPCHK(h, launch_cluster_parts(a, h->parts, h->out_parts, st)); h->det_parts_ok[h->slot] = h->parts_ok; }
-    if (h->cparts) { HIPCHK(h, launch_cluster_class_parts(a, h->cparts, h->out_cparts, st)); h->det_cparts_ok[h->slot] = h->cparts_ok; }
-    h->cluster_done = true;
+    r.merge_terms_ok = h->merge_method != BOD_MERGE_BAYES;
+    if (h->parts) { HIPCHK(h, launch_cluster_parts(a, h->parts, r.parts, st)); r.parts_ok = h->parts_ok; }
+    if (h->cparts) { HIPCHK(h, launch_cluster_class_parts(a, h->cparts, r.cparts, st)); r.cparts_ok = h->cparts_ok; }
+    h->stage.cluster_ran();
     return BOD_OK;
 }
 
@@ -2026,8 +2085,8 @@ bod_status bod_create(const bod_config* cfg, bod_handle* out) {
         }
     }
     if (hipEventCreateWithFlags(&h->ev_posterior, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_done[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_done[1], hipEventDisableTiming) != hipSuccess)
+        hipEventCreateWithFlags(&h->rec[0].done, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&h->rec[1].done, hipEventDisableTiming) != hipSuccess)
         return bail(h->fail(BOD_ERR_HIP, "hipEventCreate failed"));
     if (c.mc_statistics && hipEventCreateWithFlags(&h->ev_stat, hipEventDisableTiming) != hipSuccess)
         return bail(h->fail(BOD_ERR_HIP, "hipEventCreate failed"));
@@ -2053,10 +2112,10 @@ bod_status bod_destroy(bod_handle h) {
     if (h->side) { hipStreamSynchronize(h->side); hipStreamDestroy(h->side); }
     if (h->ev_posterior) hipEventDestroy(h->ev_posterior);
     if (h->ev_stat) hipEventDestroy(h->ev_stat);
-    for (int sidx = 0; sidx < 2; ++sidx) if (h->ev_done[sidx]) hipEventDestroy(h->ev_done[sidx]);
+    for (RecordSlot& r : h->rec) if (r.done) hipEventDestroy(r.done);
     train_destroy(h);
     val_destroy(h);
-    for (int sidx = 0; sidx < 2; ++sidx) if (h->host_stage[sidx]) hipHostFree(h->host_stage[sidx]);
+    for (RecordSlot& r : h->rec) if (r.host_stage) hipHostFree(r.host_stage);
     if (h->rec_recv && h->rec_recv != h->rec_send) hipFree(h->rec_recv);
     if (h->rec_send) hipFree(h->rec_send);
     if (h->ev_gather) hipEventDestroy(h->ev_gather);
@@ -2229,7 +2288,7 @@ bod_status bod_synchronize(bod_handle h) {
     if (h->copy) HIPCHK(h, hipStreamSynchronize(h->copy));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipStreamSynchronize(h->side));
-    h->side_pending[0] = h->side_pending[1] = false;
+    h->rec[0].pending = h->rec[1].pending = false;
     return BOD_OK;
 }
 
@@ -2248,7 +2307,7 @@ bod_status bod_forward(bod_handle h, const float* images, int32_t on_device, uin
 bod_status bod_get_raw(bod_handle h, float* cls, float* box, float* cov) {
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->forward_done) return h->fail(BOD_ERR_NOT_READY, "bod_forward has not run");
+    if (!h->stage.forward) return h->fail(BOD_ERR_NOT_READY, "bod_forward has not run");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     BODCHK(materialise_raw(h));
     const bod_config& c = h->cfg;
@@ -2275,7 +2334,7 @@ bod_status bod_set_raw(bod_handle h, const float* cls, const float* box, const f
     if (box) HIPCHK(h, hipMemcpyAsync(h->raw[1], box, n * 16, hipMemcpyHostToDevice, h->stream));
     if (cov && c.has_covar_head) HIPCHK(h, hipMemcpyAsync(h->raw[2], cov, n * 40, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->forward_done = true; h->posterior_done = h->nms_done = h->cluster_done = false; h->affinity_img = -1;
+    h->stage.forward_ran();
     h->raw_valid = true; h->agg_valid = false;
     return BOD_OK;
 }
@@ -2283,7 +2342,7 @@ bod_status bod_set_raw(bod_handle h, const float* cls, const float* box, const f
 bod_status bod_get_pyramid(bod_handle h, int32_t l, float* out) {
     if (!h || !out) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->forward_done || !h->pyramid.d) return h->fail(BOD_ERR_NOT_READY, "bod_forward has not run");
+    if (!h->stage.forward || !h->pyramid.d) return h->fail(BOD_ERR_NOT_READY, "bod_forward has not run");
     if (l < 0 || l >= h->nlev) return h->fail(BOD_ERR_INVALID_ARG, "level index %d out of range", l);
     const int B = h->cfg.batch;
     std::vector<char> tmp((size_t)B * h->Ppad * 256 * h->es);
@@ -2311,7 +2370,7 @@ bod_status bod_get_pyramid(bod_handle h, int32_t l, float* out) {
 bod_status bod_posterior(bod_handle h, uint64_t seed, uint32_t first_image_id) {
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->forward_done) return h->fail(BOD_ERR_NOT_READY, "bod_forward / bod_set_raw has not run");
+    if (!h->stage.forward) return h->fail(BOD_ERR_NOT_READY, "bod_forward / bod_set_raw has not run");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     return run_posterior(h, seed, first_image_id);
 }
@@ -2319,7 +2378,7 @@ bod_status bod_posterior(bod_handle h, uint64_t seed, uint32_t first_image_id) {
 bod_status bod_validation_post(bod_handle h) {
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->forward_done) return h->fail(BOD_ERR_NOT_READY, "bod_forward / bod_set_raw has not run");
+    if (!h->stage.forward) return h->fail(BOD_ERR_NOT_READY, "bod_forward / bod_set_raw has not run");
     if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     return run_validation_post(h);
@@ -2328,7 +2387,7 @@ bod_status bod_validation_post(bod_handle h) {
 bod_status bod_get_num_kept(bod_handle h, int32_t* out) {
     if (!h || !out) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
+    if (!h->stage.posterior) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
     BODCHK(d2h(h, out, h->pb.num_kept, (size_t)h->cfg.batch));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BOD_OK;
@@ -2344,7 +2403,7 @@ static bod_status image_m(bod_handle h, int32_t img, int32_t* m) {
 bod_status bod_get_posterior(bod_handle h, int32_t img, float* counts, float* score, float* means, float* covs, float* ranking, int32_t* anchor_index) {
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
+    if (!h->stage.posterior) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
     int32_t m = 0;
     BODCHK(image_m(h, img, &m));
     const size_t o = (size_t)img * h->A, C = h->cfg.num_classes;
@@ -2379,7 +2438,7 @@ bod_status bod_set_posterior(bod_handle h, int32_t img, int32_t m, const float* 
     }
     HIPCHK(h, hipMemcpyAsync(h->pb.num_kept + img, &m, 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;
+    h->stage.posterior_ran();
     if (h->parts) h->parts_ok[img] = 0;               // the rows' parts are the previous posterior's until bod_set_posterior_parts
     if (h->cparts) h->cparts_ok[img] = 0;             // ... until bod_set_posterior_class_parts
     return BOD_OK;
@@ -2403,7 +2462,7 @@ static void parts_expand(const float* tri, size_t m, float* full) {
 bod_status bod_get_posterior_parts(bod_handle h, int32_t img, float* parts) {
     BODCHK(parts_handle(h, "bod_get_posterior_parts"));
     BODCHK(join_overlap(h));
-    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
+    if (!h->stage.posterior) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
     int32_t m = 0;
     BODCHK(image_m(h, img, &m));
     if (!h->parts_ok[img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_posterior_parts: image %d was injected with bod_set_posterior; bod_set_posterior_parts has not followed", img);
@@ -2418,7 +2477,7 @@ bod_status bod_get_posterior_parts(bod_handle h, int32_t img, float* parts) {
 bod_status bod_set_posterior_parts(bod_handle h, int32_t img, int32_t m, const float* parts) {
     BODCHK(parts_handle(h, "bod_set_posterior_parts"));
     BODCHK(join_overlap(h));
-    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior / bod_set_posterior has not run");
+    if (!h->stage.posterior) return h->fail(BOD_ERR_NOT_READY, "bod_posterior / bod_set_posterior has not run");
     int32_t mm = 0;
     BODCHK(image_m(h, img, &mm));
     if (m != mm || (m > 0 && !parts)) return h->fail(BOD_ERR_INVALID_ARG, "bod_set_posterior_parts: got %d rows, image %d has %d", m, img, mm);
@@ -2430,14 +2489,14 @@ bod_status bod_set_posterior_parts(bod_handle h, int32_t img, int32_t m, const f
     }
     if (m > 0) HIPCHK(h, hipMemcpyAsync(h->parts + (size_t)img * h->A * BOD_PARTS_TRI, tri.data(), tri.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->parts_ok[img] = 1; h->cluster_done = false;
+    h->parts_ok[img] = 1; h->stage.parts_set();
     return BOD_OK;
 }
 
 bod_status bod_nms(bod_handle h) {
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
+    if (!h->stage.posterior) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     return run_nms(h, h->stream);
 }
@@ -2445,11 +2504,10 @@ bod_status bod_nms(bod_handle h) {
 bod_status bod_get_nms(bod_handle h, int32_t img, int32_t* indices, int32_t* num) {
     if (!h || !num) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->nms_done) return h->fail(BOD_ERR_NOT_READY, "bod_nms has not run");
+    if (!h->stage.nms) return h->fail(BOD_ERR_NOT_READY, "bod_nms has not run");
     if (img < 0 || img >= h->cfg.batch) return h->fail(BOD_ERR_INVALID_ARG, "image index out of range");
-    HIPCHK(h, hipMemcpyAsync(num, h->nms_nsel + img, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    BODCHK(d2h(h, indices, h->nms_sel + (size_t)img * h->cfg.nms_max_output_size, (size_t)*num));
+    BODCHK(slot_count(h, img, num));
+    BODCHK(d2h(h, indices, h->cur().nms_sel + (size_t)img * h->cfg.nms_max_output_size, (size_t)*num));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BOD_OK;
 }
@@ -2457,7 +2515,7 @@ bod_status bod_get_nms(bod_handle h, int32_t img, int32_t* indices, int32_t* num
 bod_status bod_set_nms(bod_handle h, int32_t img, const int32_t* indices, int32_t n) {
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior / bod_set_posterior has not run");
+    if (!h->stage.posterior) return h->fail(BOD_ERR_NOT_READY, "bod_posterior / bod_set_posterior has not run");
     if (img < 0 || img >= h->cfg.batch || n < 0 || n > h->cfg.nms_max_output_size || (n > 0 && !indices))
         return h->fail(BOD_ERR_INVALID_ARG, "bod_set_nms: bad image index or count (max %d)", h->cfg.nms_max_output_size);
     int32_t m = 0;
@@ -2465,17 +2523,17 @@ bod_status bod_set_nms(bod_handle h, int32_t img, const int32_t* indices, int32_
     for (int i = 0; i < n; ++i)
         if (indices[i] < 0 || indices[i] >= m) return h->fail(BOD_ERR_INVALID_ARG, "cluster centre %d out of range [0,%d)", indices[i], m);
     if (n > 0)
-        HIPCHK(h, hipMemcpyAsync(h->nms_sel + (size_t)img * h->cfg.nms_max_output_size, indices, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->nms_nsel + img, &n, 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->cur().nms_sel + (size_t)img * h->cfg.nms_max_output_size, indices, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->cur().nms_nsel + img, &n, 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->nms_done = true; h->cluster_done = false; h->affinity_img = -1;      // new centres: a pending bod_set_affinity was sized for the old ones
+    h->stage.nms_ran();
     return BOD_OK;
 }
 
 bod_status bod_get_iou_matrix(bod_handle h, int32_t img, float* iou) {
     if (!h || !iou) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
+    if (!h->stage.posterior) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
     int32_t m = 0;
     BODCHK(image_m(h, img, &m));
     if (m == 0) return BOD_OK;
@@ -2496,13 +2554,12 @@ bod_status bod_get_iou_matrix(bod_handle h, int32_t img, float* iou) {
 bod_status bod_set_affinity(bod_handle h, int32_t img, const float* centre_columns, int32_t k, int32_t m) {
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->nms_done) return h->fail(BOD_ERR_NOT_READY, "bod_nms / bod_set_nms has not run");
+    if (!h->stage.nms) return h->fail(BOD_ERR_NOT_READY, "bod_nms / bod_set_nms has not run");
     if (img < 0 || img >= h->cfg.batch || !centre_columns) return h->fail(BOD_ERR_INVALID_ARG, "bod_set_affinity: bad image index / NULL");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     int32_t mm = 0, kk = 0;
     BODCHK(image_m(h, img, &mm));
-    HIPCHK(h, hipMemcpyAsync(&kk, h->nms_nsel + img, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    BODCHK(slot_count(h, img, &kk));
     if (m != mm || k != kk)
         return h->fail(BOD_ERR_INVALID_ARG, "bod_set_affinity: got %d columns of %d rows, the image has %d centres and %d boxes", k, m, kk, mm);
     if (!h->affinity && hipMalloc((void**)&h->affinity, (size_t)h->cfg.nms_max_output_size * h->A * 4) != hipSuccess)
@@ -2510,14 +2567,14 @@ bod_status bod_set_affinity(bod_handle h, int32_t img, const float* centre_colum
     for (int r = 0; r < k && m > 0; ++r)          // row r -> affinity[r][0..m): one plain copy per centre (k <= max_detections)
         HIPCHK(h, hipMemcpyAsync(h->affinity + (size_t)r * h->A, centre_columns + (size_t)r * m, (size_t)m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->affinity_img = img;
+    h->stage.affinity_set(img);
     return BOD_OK;
 }
 
 bod_status bod_cluster_fuse(bod_handle h) {
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->nms_done) return h->fail(BOD_ERR_NOT_READY, "bod_nms has not run");
+    if (!h->stage.nms) return h->fail(BOD_ERR_NOT_READY, "bod_nms has not run");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     return run_cluster(h, h->stream);
 }
@@ -2525,15 +2582,15 @@ bod_status bod_cluster_fuse(bod_handle h) {
 bod_status bod_get_detections(bod_handle h, int32_t img, int32_t* num, float* scores, float* means, float* covs, float* counts) {
     if (!h || !num) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+    if (!h->stage.cluster) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
     if (img < 0 || img >= h->cfg.batch) return h->fail(BOD_ERR_INVALID_ARG, "image index out of range");
-    HIPCHK(h, hipMemcpyAsync(num, h->nms_nsel + img, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    BODCHK(slot_count(h, img, num));
     const size_t k = (size_t)*num, o = (size_t)img * h->cfg.nms_max_output_size, C = h->cfg.num_classes;
-    BODCHK(d2h(h, scores, h->out_scores + o * C, k * C));
-    BODCHK(d2h(h, means, h->out_means + o * 4, k * 4));
-    BODCHK(d2h(h, covs, h->out_covs + o * 16, k * 16));
-    BODCHK(d2h(h, counts, h->out_counts + o * C, k * C));
+    const RecordSlot& r = h->cur();
+    BODCHK(d2h(h, scores, r.scores + o * C, k * C));
+    BODCHK(d2h(h, means, r.means + o * REC_MEAN, k * REC_MEAN));
+    BODCHK(d2h(h, covs, r.covs + o * REC_COV, k * REC_COV));
+    BODCHK(d2h(h, counts, r.counts + o * C, k * C));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BOD_OK;
 }
@@ -2541,13 +2598,14 @@ bod_status bod_get_detections(bod_handle h, int32_t img, int32_t* num, float* sc
 bod_status bod_get_detections_batch(bod_handle h, int32_t* num, float* scores, float* means, float* covs, float* counts) {
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+    if (!h->stage.cluster) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
     const size_t BK = (size_t)h->cfg.batch * h->cfg.nms_max_output_size, C = h->cfg.num_classes;
-    BODCHK(d2h(h, num, h->nms_nsel, (size_t)h->cfg.batch));
-    BODCHK(d2h(h, scores, h->out_scores, BK * C));
-    BODCHK(d2h(h, means, h->out_means, BK * 4));
-    BODCHK(d2h(h, covs, h->out_covs, BK * 16));
-    BODCHK(d2h(h, counts, h->out_counts, BK * C));
+    const RecordSlot& r = h->cur();
+    BODCHK(d2h(h, num, r.nms_nsel, (size_t)h->cfg.batch));
+    BODCHK(d2h(h, scores, r.scores, BK * C));
+    BODCHK(d2h(h, means, r.means, BK * REC_MEAN));
+    BODCHK(d2h(h, covs, r.covs, BK * REC_COV));
+    BODCHK(d2h(h, counts, r.counts, BK * C));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BOD_OK;
 }
@@ -2555,13 +2613,12 @@ bod_status bod_get_detections_batch(bod_handle h, int32_t* num, float* scores, f
 bod_status bod_get_detection_parts(bod_handle h, int32_t img, float* parts) {
     BODCHK(parts_handle(h, "bod_get_detection_parts"));
     BODCHK(join_overlap(h));
-    if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+    if (!h->stage.cluster) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
     if (img < 0 || img >= h->cfg.batch) return h->fail(BOD_ERR_INVALID_ARG, "image index out of range");
-    if (!h->det_parts_ok[h->slot][img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_parts: image %d was fused without its posterior's parts (bod_set_posterior_parts)", img);
+    if (!h->cur().parts_ok[img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_parts: image %d was fused without its posterior's parts (bod_set_posterior_parts)", img);
     int32_t num = 0;
-    HIPCHK(h, hipMemcpyAsync(&num, h->nms_nsel + img, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    BODCHK(d2h(h, parts, h->out_parts + (size_t)img * h->cfg.nms_max_output_size * 48, (size_t)num * 48));
+    BODCHK(slot_count(h, img, &num));
+    BODCHK(d2h(h, parts, h->cur().parts + (size_t)img * h->cfg.nms_max_output_size * REC_PARTS, (size_t)num * REC_PARTS));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BOD_OK;
 }
@@ -2569,10 +2626,10 @@ bod_status bod_get_detection_parts(bod_handle h, int32_t img, float* parts) {
 bod_status bod_get_detection_parts_batch(bod_handle h, float* parts) {
     BODCHK(parts_handle(h, "bod_get_detection_parts_batch"));
     BODCHK(join_overlap(h));
-    if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+    if (!h->stage.cluster) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
     for (int img = 0; img < h->cfg.batch; ++img)
-        if (!h->det_parts_ok[h->slot][img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_parts_batch: image %d was fused without its posterior's parts (bod_set_posterior_parts)", img);
-    BODCHK(d2h(h, parts, h->out_parts, (size_t)h->cfg.batch * h->cfg.nms_max_output_size * 48));
+        if (!h->cur().parts_ok[img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_parts_batch: image %d was fused without its posterior's parts (bod_set_posterior_parts)", img);
+    BODCHK(d2h(h, parts, h->cur().parts, (size_t)h->cfg.batch * h->cfg.nms_max_output_size * REC_PARTS));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BOD_OK;
 }
@@ -2580,7 +2637,7 @@ bod_status bod_get_detection_parts_batch(bod_handle h, float* parts) {
 bod_status bod_device_detection_parts(bod_handle h, int32_t sidx, void** p) {
     BODCHK(parts_handle(h, "bod_device_detection_parts"));
     if (!p || sidx < 0 || sidx > 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_device_detection_parts: slot %d / NULL", sidx);
-    *p = h->out_parts_s[sidx];
+    *p = h->rec[sidx].parts;
     return BOD_OK;
 }
 
@@ -2593,7 +2650,7 @@ static bod_status class_parts_handle(bod_handle h, const char* who) {
 bod_status bod_get_posterior_class_parts(bod_handle h, int32_t img, float* rows) {
     BODCHK(class_parts_handle(h, "bod_get_posterior_class_parts"));
     BODCHK(join_overlap(h));
-    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
+    if (!h->stage.posterior) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
     int32_t m = 0;
     BODCHK(image_m(h, img, &m));
     if (!h->cparts_ok[img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_posterior_class_parts: image %d was injected with bod_set_posterior; bod_set_posterior_class_parts has not followed", img);
@@ -2610,7 +2667,7 @@ bod_status bod_get_posterior_class_parts(bod_handle h, int32_t img, float* rows)
 bod_status bod_get_posterior_mean_probs(bod_handle h, int32_t img, float* mean_probs) {
     BODCHK(class_parts_handle(h, "bod_get_posterior_mean_probs"));
     BODCHK(join_overlap(h));
-    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
+    if (!h->stage.posterior) return h->fail(BOD_ERR_NOT_READY, "bod_posterior has not run");
     int32_t m = 0;
     BODCHK(image_m(h, img, &m));
     if (!h->cparts_ok[img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_posterior_mean_probs: image %d was injected with bod_set_posterior; bod_set_posterior_class_parts has not followed", img);
@@ -2627,7 +2684,7 @@ bod_status bod_get_posterior_mean_probs(bod_handle h, int32_t img, float* mean_p
 bod_status bod_set_posterior_class_parts(bod_handle h, int32_t img, int32_t m, const float* mean_probs, const float* rows) {
     BODCHK(class_parts_handle(h, "bod_set_posterior_class_parts"));
     BODCHK(join_overlap(h));
-    if (!h->posterior_done) return h->fail(BOD_ERR_NOT_READY, "bod_posterior / bod_set_posterior has not run");
+    if (!h->stage.posterior) return h->fail(BOD_ERR_NOT_READY, "bod_posterior / bod_set_posterior has not run");
     int32_t mm = 0;
     BODCHK(image_m(h, img, &mm));
     if (m != mm || (m > 0 && (!mean_probs || !rows))) return h->fail(BOD_ERR_INVALID_ARG, "bod_set_posterior_class_parts: got %d rows, image %d has %d", m, img, mm);
@@ -2639,20 +2696,19 @@ bod_status bod_set_posterior_class_parts(bod_handle h, int32_t img, int32_t m, c
     }
     if (m > 0) HIPCHK(h, hipMemcpyAsync(h->cparts + (size_t)img * h->A * Q, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->cparts_ok[img] = 1; h->cluster_done = false;
+    h->cparts_ok[img] = 1; h->stage.parts_set();
     return BOD_OK;
 }
 
 bod_status bod_get_detection_class_parts(bod_handle h, int32_t img, float* rows) {
     BODCHK(class_parts_handle(h, "bod_get_detection_class_parts"));
     BODCHK(join_overlap(h));
-    if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+    if (!h->stage.cluster) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
     if (img < 0 || img >= h->cfg.batch) return h->fail(BOD_ERR_INVALID_ARG, "image index out of range");
-    if (!h->det_cparts_ok[h->slot][img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_class_parts: image %d was fused without its posterior's class parts (bod_set_posterior_class_parts)", img);
+    if (!h->cur().cparts_ok[img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_class_parts: image %d was fused without its posterior's class parts (bod_set_posterior_class_parts)", img);
     int32_t num = 0;
-    HIPCHK(h, hipMemcpyAsync(&num, h->nms_nsel + img, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    BODCHK(d2h(h, rows, h->out_cparts + (size_t)img * h->cfg.nms_max_output_size * 4, (size_t)num * 4));
+    BODCHK(slot_count(h, img, &num));
+    BODCHK(d2h(h, rows, h->cur().cparts + (size_t)img * h->cfg.nms_max_output_size * REC_CPARTS, (size_t)num * REC_CPARTS));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BOD_OK;
 }
@@ -2660,25 +2716,23 @@ bod_status bod_get_detection_class_parts(bod_handle h, int32_t img, float* rows)
 bod_status bod_get_detection_class_parts_batch(bod_handle h, float* rows) {
     BODCHK(class_parts_handle(h, "bod_get_detection_class_parts_batch"));
     BODCHK(join_overlap(h));
-    if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+    if (!h->stage.cluster) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
     for (int img = 0; img < h->cfg.batch; ++img)
-        if (!h->det_cparts_ok[h->slot][img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_class_parts_batch: image %d was fused without its posterior's class parts (bod_set_posterior_class_parts)", img);
+        if (!h->cur().cparts_ok[img]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_class_parts_batch: image %d was fused without its posterior's class parts (bod_set_posterior_class_parts)", img);
     // rows beyond an image's count are whatever an earlier batch left: zero them on the way out, like the record rows
     const size_t B = (size_t)h->cfg.batch, K = (size_t)h->cfg.nms_max_output_size;
     std::vector<int32_t> num(B);
-    HIPCHK(h, hipMemcpyAsync(num.data(), h->nms_nsel, B * 4, hipMemcpyDeviceToHost, h->stream));
-    BODCHK(d2h(h, rows, h->out_cparts, B * K * 4));
+    HIPCHK(h, hipMemcpyAsync(num.data(), h->cur().nms_nsel, B * 4, hipMemcpyDeviceToHost, h->stream));
+    BODCHK(d2h(h, rows, h->cur().cparts, B * K * REC_CPARTS));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (size_t b = 0; rows && b < B; ++b)
-        for (size_t k = (size_t)std::max(num[b], 0); k < K; ++k)
-            for (int q = 0; q < 4; ++q) rows[(b * K + k) * 4 + q] = 0.f;
+    zero_rows_past_count(rows, num.data(), B, K, REC_CPARTS);
     return BOD_OK;
 }
 
 bod_status bod_device_detection_class_parts(bod_handle h, int32_t sidx, void** p) {
     BODCHK(class_parts_handle(h, "bod_device_detection_class_parts"));
     if (!p || sidx < 0 || sidx > 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_device_detection_class_parts: slot %d / NULL", sidx);
-    *p = h->out_cparts_s[sidx];
+    *p = h->rec[sidx].cparts;
     return BOD_OK;
 }
 
@@ -2690,13 +2744,13 @@ bod_status bod_set_merge_method(bod_handle h, int32_t method) {
     if (method != BOD_MERGE_BAYES && h->cfg.covariance_parts != 0)
         return h->fail(BOD_ERR_INVALID_ARG, "bod_set_merge_method: the handle was created with bod_config.covariance_parts = %d; the covariance and "
                        "class-entropy parts are defined for the Bayesian fuse (BOD_MERGE_BAYES) only", h->cfg.covariance_parts);
-    if (method != BOD_MERGE_BAYES && !h->merge_members_s[1]) {
+    if (method != BOD_MERGE_BAYES && !h->rec[1].merge_members) {
         HIPCHK(h, hipSetDevice(h->cfg.device));
         const size_t BK = (size_t)h->cfg.batch * h->cfg.nms_max_output_size;
-        for (int sidx = 0; sidx < 2; ++sidx) {
-            BODCHK(h->dalloc(&h->merge_within_s[sidx], BK * 16));
-            BODCHK(h->dalloc(&h->merge_between_s[sidx], BK * 16));
-            BODCHK(h->dalloc(&h->merge_members_s[sidx], BK));
+        for (RecordSlot& r : h->rec) {
+            BODCHK(h->dalloc(&r.merge_within, BK * REC_COV));
+            BODCHK(h->dalloc(&r.merge_between, BK * REC_COV));
+            BODCHK(h->dalloc(&r.merge_members, BK));
         }
     }
     h->merge_method = method;
@@ -2712,16 +2766,15 @@ bod_status bod_get_merge_method(bod_handle h, int32_t* method) {
 bod_status bod_get_detection_merge_terms(bod_handle h, int32_t img, float* within, float* between, int32_t* members) {
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+    if (!h->stage.cluster) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
     if (img < 0 || img >= h->cfg.batch) return h->fail(BOD_ERR_INVALID_ARG, "image index out of range");
-    if (!h->merge_terms_ok[h->slot]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_merge_terms: the last cluster stage ran as BOD_MERGE_BAYES, which has no merge terms");
+    if (!h->cur().merge_terms_ok) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_merge_terms: the last cluster stage ran as BOD_MERGE_BAYES, which has no merge terms");
     int32_t num = 0;
-    HIPCHK(h, hipMemcpyAsync(&num, h->nms_nsel + img, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    BODCHK(slot_count(h, img, &num));
     const size_t k = (size_t)std::max(num, 0), o = (size_t)img * h->cfg.nms_max_output_size;
-    BODCHK(d2h(h, within, h->merge_within_s[h->slot] + o * 16, k * 16));
-    BODCHK(d2h(h, between, h->merge_between_s[h->slot] + o * 16, k * 16));
-    BODCHK(d2h(h, members, h->merge_members_s[h->slot] + o, k));
+    BODCHK(d2h(h, within, h->cur().merge_within + o * REC_COV, k * REC_COV));
+    BODCHK(d2h(h, between, h->cur().merge_between + o * REC_COV, k * REC_COV));
+    BODCHK(d2h(h, members, h->cur().merge_members + o, k));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BOD_OK;
 }
@@ -2733,40 +2786,39 @@ bod_status bod_get_detection_merge_terms_batch(bod_handle h, int32_t slot, float
     std::vector<int32_t> num(B);
     if (slot < 0) {
         BODCHK(join_overlap(h));
-        if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
-        const int sidx = h->slot;
-        if (!h->merge_terms_ok[sidx]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_merge_terms_batch: the last cluster stage ran as BOD_MERGE_BAYES, which has no merge terms");
-        HIPCHK(h, hipMemcpyAsync(num.data(), h->nms_nsel_s[sidx], B * 4, hipMemcpyDeviceToHost, h->stream));
-        BODCHK(d2h(h, within, h->merge_within_s[sidx], B * K * 16));
-        BODCHK(d2h(h, between, h->merge_between_s[sidx], B * K * 16));
-        BODCHK(d2h(h, members, h->merge_members_s[sidx], B * K));
+        if (!h->stage.cluster) return h->fail(BOD_ERR_NOT_READY, "bod_cluster_fuse has not run");
+        const RecordSlot& r = h->cur();
+        if (!r.merge_terms_ok) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_merge_terms_batch: the last cluster stage ran as BOD_MERGE_BAYES, which has no merge terms");
+        HIPCHK(h, hipMemcpyAsync(num.data(), r.nms_nsel, B * 4, hipMemcpyDeviceToHost, h->stream));
+        BODCHK(d2h(h, within, r.merge_within, B * K * REC_COV));
+        BODCHK(d2h(h, between, r.merge_between, B * K * REC_COV));
+        BODCHK(d2h(h, members, r.merge_members, B * K));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     } else {
         // a bod_infer_async ticket: wait for that batch as bod_collect does (its event, not a stream the next batch may be queued on),
         // then plain blocking copies -- the pinned staging of the records is sized at create and stays as it is
-        if (!h->done_stream[slot]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_merge_terms_batch: slot %d holds no batch of bod_infer_async", slot);
-        if (!h->merge_terms_ok[slot]) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_merge_terms_batch: slot %d's cluster stage ran as BOD_MERGE_BAYES, which has no merge terms", slot);
+        const RecordSlot& r = h->rec[slot];
+        if (!r.done_stream) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_merge_terms_batch: slot %d holds no batch of bod_infer_async", slot);
+        if (!r.merge_terms_ok) return h->fail(BOD_ERR_NOT_READY, "bod_get_detection_merge_terms_batch: slot %d's cluster stage ran as BOD_MERGE_BAYES, which has no merge terms", slot);
         HIPCHK(h, hipSetDevice(h->cfg.device));
-        HIPCHK(h, hipEventSynchronize(h->ev_done[slot]));
-        HIPCHK(h, hipMemcpy(num.data(), h->nms_nsel_s[slot], B * 4, hipMemcpyDeviceToHost));
-        if (within) HIPCHK(h, hipMemcpy(within, h->merge_within_s[slot], B * K * 64, hipMemcpyDeviceToHost));
-        if (between) HIPCHK(h, hipMemcpy(between, h->merge_between_s[slot], B * K * 64, hipMemcpyDeviceToHost));
-        if (members) HIPCHK(h, hipMemcpy(members, h->merge_members_s[slot], B * K * 4, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipEventSynchronize(r.done));
+        HIPCHK(h, hipMemcpy(num.data(), r.nms_nsel, B * 4, hipMemcpyDeviceToHost));
+        if (within) HIPCHK(h, hipMemcpy(within, r.merge_within, B * K * REC_COV * 4, hipMemcpyDeviceToHost));
+        if (between) HIPCHK(h, hipMemcpy(between, r.merge_between, B * K * REC_COV * 4, hipMemcpyDeviceToHost));
+        if (members) HIPCHK(h, hipMemcpy(members, r.merge_members, B * K * 4, hipMemcpyDeviceToHost));
     }
     // rows beyond an image's count are whatever an earlier batch left: zero them on the way out, like the record rows
-    for (size_t b = 0; b < B; ++b)
-        for (size_t k = (size_t)std::min<int64_t>(std::max(num[b], 0), (int64_t)K); k < K; ++k) {
-            if (within) std::memset(within + (b * K + k) * 16, 0, 64);
-            if (between) std::memset(between + (b * K + k) * 16, 0, 64);
-            if (members) members[b * K + k] = 0;
-        }
+    zero_rows_past_count(within, num.data(), B, K, REC_COV);
+    zero_rows_past_count(between, num.data(), B, K, REC_COV);
+    zero_rows_past_count(members, num.data(), B, K, 1);
     return BOD_OK;
 }
 
 bod_status bod_device_detection_merge_terms(bod_handle h, int32_t sidx, void** p) {
     if (!h) return BOD_ERR_INVALID_ARG;
     if (!p || sidx < 0 || sidx > 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_device_detection_merge_terms: slot %d / NULL", sidx);
-    p[0] = h->merge_within_s[sidx]; p[1] = h->merge_between_s[sidx]; p[2] = h->merge_members_s[sidx];
+    const RecordSlot& r = h->rec[sidx];
+    p[0] = r.merge_within; p[1] = r.merge_between; p[2] = r.merge_members;
     return BOD_OK;
 }
 
@@ -2776,14 +2828,14 @@ bod_status bod_device_raw(bod_handle h, void** p, int32_t mark_ready) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (mark_ready) BODCHK(ensure_raw(h)); else BODCHK(materialise_raw(h));
     p[0] = h->raw[0]; p[1] = h->raw[1]; p[2] = h->cfg.has_covar_head ? h->raw[2] : nullptr;
-    if (mark_ready) { h->kscale_now = nullptr; h->forward_done = true; h->posterior_done = h->nms_done = h->cluster_done = false; h->affinity_img = -1; h->raw_valid = true; h->agg_valid = false; }
+    if (mark_ready) { h->kscale_now = nullptr; h->stage.forward_ran(); h->raw_valid = true; h->agg_valid = false; }
     return BOD_OK;
 }
 
 bod_status bod_device_detections(bod_handle h, int32_t sidx, void** p) {
     if (!h || !p || sidx < 0 || sidx > 1) return BOD_ERR_INVALID_ARG;
-    p[0] = h->nms_nsel_s[sidx]; p[1] = h->out_scores_s[sidx]; p[2] = h->out_means_s[sidx];
-    p[3] = h->out_covs_s[sidx]; p[4] = h->out_counts_s[sidx];
+    const RecordSlot& r = h->rec[sidx];
+    p[0] = r.nms_nsel; p[1] = r.scores; p[2] = r.means; p[3] = r.covs; p[4] = r.counts;
     return BOD_OK;
 }
 
@@ -2810,7 +2862,8 @@ bod_status bod_infer_async(bod_handle h, const float* images, int32_t on_device,
     if (h->cfg.mc_samples < 2) return h->fail(BOD_ERR_INVALID_ARG, "bayes_od needs mc_samples >= 2 (sample covariance divides by N-1)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int sidx = h->slot ^ 1;
-    if (h->side_pending[sidx])
+    RecordSlot& r = h->rec[sidx];
+    if (r.pending)
         return h->fail(BOD_ERR_NOT_READY, "slot %d still holds uncollected detections: call bod_collect first", sidx);
     // pipeline_overlap handles: this call's front goes to h->front, everything else to h->back (h->stream for the call's duration);
     // both are first ordered behind whatever the full-chip stream still holds (an upload, a synchronous call's tail)
@@ -2828,7 +2881,7 @@ bod_status bod_infer_async(bod_handle h, const float* images, int32_t on_device,
     BODCHK(run_forward(h, dev, seed, first_image_id, infer_flavour(h), false, ov));
     BODCHK(run_posterior(h, seed, first_image_id));           // waits for the side stream's previous readers
     HIPCHK(h, hipEventRecord(h->ev_posterior, h->stream));
-    h->select_slot(sidx);
+    h->slot = sidx;
     // Round 5: soft-NMS + cluster-and-fuse (and the copies of the records) run on the MAIN stream, behind the posterior, not on the side
     // stream beside the next call's stem.  With them on the side stream a call's detections were not reproducible: one detection in ~60
     // frames with its fused mean moved by up to 0.4 px (same counts and scores: one cluster member more or less) -- in 3-14 of 12 runs of
@@ -2847,20 +2900,13 @@ bod_status bod_infer_async(bod_handle h, const float* images, int32_t on_device,
     // The records follow the kernels on the side stream into pinned host memory, so bod_collect only waits for
     // this slot's event: it must never queue work behind the NEXT batch's side-stream kernels (that would
     // stall the host until the next batch has finished and drain the pipeline).
-    {
-        const size_t B = (size_t)h->cfg.batch, BK = B * h->cfg.nms_max_output_size, C = h->cfg.num_classes;
-        char* hs = h->host_stage[sidx];
-        HIPCHK(h, hipMemcpyAsync(hs, h->nms_nsel_s[sidx], B * 4, hipMemcpyDeviceToHost, sd)); hs += B * 4;
-        HIPCHK(h, hipMemcpyAsync(hs, h->out_scores_s[sidx], BK * C * 4, hipMemcpyDeviceToHost, sd)); hs += BK * C * 4;
-        HIPCHK(h, hipMemcpyAsync(hs, h->out_means_s[sidx], BK * 16, hipMemcpyDeviceToHost, sd)); hs += BK * 16;
-        HIPCHK(h, hipMemcpyAsync(hs, h->out_covs_s[sidx], BK * 64, hipMemcpyDeviceToHost, sd)); hs += BK * 64;
-        HIPCHK(h, hipMemcpyAsync(hs, h->out_counts_s[sidx], BK * C * 4, hipMemcpyDeviceToHost, sd)); hs += BK * C * 4;
-        if (h->parts) { HIPCHK(h, hipMemcpyAsync(hs, h->out_parts_s[sidx], BK * 48 * 4, hipMemcpyDeviceToHost, sd)); h->parts_staged[sidx] = true; hs += BK * 48 * 4; }
-        if (h->cparts) { HIPCHK(h, hipMemcpyAsync(hs, h->out_cparts_s[sidx], BK * 4 * 4, hipMemcpyDeviceToHost, sd)); h->cparts_staged[sidx] = true; }
-    }
-    HIPCHK(h, hipEventRecord(h->ev_done[sidx], sd));
-    h->done_stream[sidx] = sd;
-    h->side_pending[sidx] = true;
+    void* const dev_arrays[RecordLayout::SEGS] = {r.nms_nsel, r.scores, r.means, r.covs, r.counts, r.parts, r.cparts};
+    BODCHK(copy_staged(h, r, dev_arrays, true, sd));
+    if (r.parts) r.parts_staged = true;
+    if (r.cparts) r.cparts_staged = true;
+    HIPCHK(h, hipEventRecord(r.done, sd));
+    r.done_stream = sd;
+    r.pending = true;
     *slot_out = sidx;
     return BOD_OK;
 }
@@ -2868,43 +2914,32 @@ bod_status bod_infer_async(bod_handle h, const float* images, int32_t on_device,
 bod_status bod_collect(bod_handle h, int32_t sidx, int32_t* num, float* scores, float* means, float* covs, float* counts) {
     MarkerRange mr_api("bod:collect");
     if (!h) return BOD_ERR_INVALID_ARG;
-    if (sidx < 0 || sidx > 1 || !h->side_pending[sidx]) return h->fail(BOD_ERR_NOT_READY, "slot %d has no pending batch", sidx);
-    const size_t B = (size_t)h->cfg.batch, BK = B * h->cfg.nms_max_output_size, C = h->cfg.num_classes;
-    HIPCHK(h, hipEventSynchronize(h->ev_done[sidx]));
-    const char* hs = h->host_stage[sidx];
-    if (num) std::memcpy(num, hs, B * 4);
-    hs += B * 4;
-    if (scores) std::memcpy(scores, hs, BK * C * 4);
-    hs += BK * C * 4;
-    if (means) std::memcpy(means, hs, BK * 16);
-    hs += BK * 16;
-    if (covs) std::memcpy(covs, hs, BK * 64);
-    hs += BK * 64;
-    if (counts) std::memcpy(counts, hs, BK * C * 4);
-    h->side_pending[sidx] = false;
+    if (sidx < 0 || sidx > 1 || !h->rec[sidx].pending) return h->fail(BOD_ERR_NOT_READY, "slot %d has no pending batch", sidx);
+    RecordSlot& r = h->rec[sidx];
+    HIPCHK(h, hipEventSynchronize(r.done));
+    void* const out[RecordLayout::SEGS] = {num, scores, means, covs, counts, nullptr, nullptr};
+    BODCHK(copy_staged(h, r, out, false, nullptr));
+    r.pending = false;
     return BOD_OK;
 }
 
 bod_status bod_collect_parts(bod_handle h, int32_t sidx, float* parts) {
     BODCHK(parts_handle(h, "bod_collect_parts"));
-    if (sidx < 0 || sidx > 1 || !h->parts_staged[sidx]) return h->fail(BOD_ERR_NOT_READY, "bod_collect_parts: slot %d holds no batch of bod_infer_async", sidx);
-    const size_t B = (size_t)h->cfg.batch, BK = B * h->cfg.nms_max_output_size, C = h->cfg.num_classes;
-    HIPCHK(h, hipEventSynchronize(h->ev_done[sidx]));
-    if (parts) std::memcpy(parts, h->host_stage[sidx] + (B + BK * (2 * C + 20)) * 4, BK * 48 * 4);
-    return BOD_OK;
+    if (sidx < 0 || sidx > 1 || !h->rec[sidx].parts_staged) return h->fail(BOD_ERR_NOT_READY, "bod_collect_parts: slot %d holds no batch of bod_infer_async", sidx);
+    HIPCHK(h, hipEventSynchronize(h->rec[sidx].done));
+    void* const out[RecordLayout::SEGS] = {nullptr, nullptr, nullptr, nullptr, nullptr, parts, nullptr};
+    return copy_staged(h, h->rec[sidx], out, false, nullptr);
 }
 
 bod_status bod_collect_class_parts(bod_handle h, int32_t sidx, float* rows) {
     BODCHK(class_parts_handle(h, "bod_collect_class_parts"));
-    if (sidx < 0 || sidx > 1 || !h->cparts_staged[sidx]) return h->fail(BOD_ERR_NOT_READY, "bod_collect_class_parts: slot %d holds no batch of bod_infer_async", sidx);
-    const size_t B = (size_t)h->cfg.batch, K = (size_t)h->cfg.nms_max_output_size, BK = B * K, C = h->cfg.num_classes;
-    HIPCHK(h, hipEventSynchronize(h->ev_done[sidx]));
-    if (!rows) return BOD_OK;
-    std::memcpy(rows, h->host_stage[sidx] + (B + BK * (2 * C + 20 + (h->parts ? 48 : 0))) * 4, BK * 4 * 4);
-    const int32_t* num = reinterpret_cast<const int32_t*>(h->host_stage[sidx]);      // rows beyond an image's count: zero
-    for (size_t b = 0; b < B; ++b)
-        for (size_t k = (size_t)std::max(num[b], 0); k < K; ++k)
-            for (int q = 0; q < 4; ++q) rows[(b * K + k) * 4 + q] = 0.f;
+    if (sidx < 0 || sidx > 1 || !h->rec[sidx].cparts_staged) return h->fail(BOD_ERR_NOT_READY, "bod_collect_class_parts: slot %d holds no batch of bod_infer_async", sidx);
+    const RecordSlot& r = h->rec[sidx];
+    HIPCHK(h, hipEventSynchronize(r.done));
+    void* const out[RecordLayout::SEGS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rows};
+    BODCHK(copy_staged(h, r, out, false, nullptr));
+    // rows beyond an image's count: zero (the counts lead the staging buffer)
+    zero_rows_past_count(rows, reinterpret_cast<const int32_t*>(r.host_stage), (size_t)h->cfg.batch, (size_t)h->cfg.nms_max_output_size, REC_CPARTS);
     return BOD_OK;
 }
 
@@ -2913,8 +2948,8 @@ bod_status bod_stage_conv(int32_t device, const float* x, int32_t B, int32_t H, 
                           int32_t stride, int32_t same_padding, int32_t relu, const float* residual,
                           float dropout_rate, uint64_t seed, int32_t layer_id, uint32_t image_id,
                           int32_t round_output_bf16, int32_t precision, float* out) {
-    bod_context ctx;                      // scratch context: owns the temporary device buffers
-    bod_context* h = &ctx;
+    StageScope sc;                        // scratch context: owns the temporary device buffers
+    bod_context* h = sc.h;
     const int mxfmt = precision == BOD_PRECISION_F16MX ? 1 : precision == BOD_PRECISION_F16MX4 ? 2 : 0;
     const bool mxp = mxfmt != 0;                 // f16mx tower kernel; round_output_bf16 = data path under test (bayesod.h)
     const int mx_mode = mxp ? round_output_bf16 : 0;
@@ -2922,37 +2957,20 @@ bod_status bod_stage_conv(int32_t device, const float* x, int32_t B, int32_t H, 
     if (mxp) round_output_bf16 = 1;
     h->es = (f32 || x3) ? 4 : 2;
     h->split = x3; h->mx = mxfmt;
-    auto done = [&](bod_status s) {
-        if (s != BOD_OK) g_create_error = h->err;
-        if (h->stream) hipStreamSynchronize(h->stream);
-        for (void* p : h->allocs) hipFree(p);
-        if (h->stream) hipStreamDestroy(h->stream);
-        h->allocs.clear(); h->stream = nullptr;
-        return s;
-    };
     if (!x || !w || !out || B < 1 || H < 1 || W < 1 || KH < 1 || KW < 1 || stride < 1 || stride > 2)
-        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: bad argument"));
-    if (precision != BOD_PRECISION_BF16 && !f32 && !x3) return done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: bad precision"));
+        return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: bad argument"));
+    if (precision != BOD_PRECISION_BF16 && !f32 && !x3) return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: bad precision"));
     if (mxp && (KH != 3 || KW != 3 || stride != 1 || !same_padding || Cin != 256 || Cout != 256 || residual || mx_mode < 0 || mx_mode > 2))
-        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: BOD_PRECISION_F16MX / F16MX4 run a head-tower layer (3x3, stride 1, SAME, 256 -> 256, no residual), round_output_bf16 in 0..2"));
-    if (f32 && round_output_bf16) return done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: round_output_bf16 is meaningless in fp32 precision"));
+        return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: BOD_PRECISION_F16MX / F16MX4 run a head-tower layer (3x3, stride 1, SAME, 256 -> 256, no residual), round_output_bf16 in 0..2"));
+    if (f32 && round_output_bf16) return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: round_output_bf16 is meaningless in fp32 precision"));
     if (Cin % 64 != 0 || ((round_output_bf16 || (dropout_rate > 0.f && !f32)) && Cout % 4 != 0))
-        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: Cin must be a multiple of 64 (and Cout of 4 for bf16 output); got %d, %d", Cin, Cout));
-    if (KH > 3 || KW > 3) return done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: kernel larger than 3x3 needs a wider zero border"));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return done(h->fail(BOD_ERR_NO_DEVICE, "no HIP device %d: libbayesod_hip has no CPU fallback", device));
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
-        return done(h->fail(BOD_ERR_HIP, "cannot set up device %d", device));
+        return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: Cin must be a multiple of 64 (and Cout of 4 for bf16 output); got %d, %d", Cin, Cout));
+    if (KH > 3 || KW > 3) return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: kernel larger than 3x3 needs a wider zero border"));
+    if (const bod_status st = sc.open(device)) return sc.done(st);
     h->cfg.batch = B;
-    int OH, OW, oy = 1, ox = 1;
-    if (same_padding) {
-        OH = (H + stride - 1) / stride; OW = (W + stride - 1) / stride;
-        oy = 1 - same_pad_before(H, KH, stride); ox = 1 - same_pad_before(W, KW, stride);
-    } else {
-        OH = (H - KH) / stride + 1; OW = (W - KW) / stride + 1;
-    }
-    if (OH < 1 || OW < 1) return done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: empty output"));
+    int OH, OW, oy, ox;
+    conv_out_geometry(H, W, KH, KW, stride, same_padding != 0, &OH, &OW, &oy, &ox);
+    if (OH < 1 || OW < 1) return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv: empty output"));
     auto run = [&]() -> bod_status {
         Plane in, res;
         BODCHK(new_plane(h, &in, B, H, W, Cin));
@@ -3011,20 +3029,14 @@ bod_status bod_stage_conv(int32_t device, const float* x, int32_t B, int32_t H, 
         float* d_out32 = nullptr; uint16_t* d_out16 = nullptr;
         const bool f32_out = f32 || (!round_output_bf16 && !drop);
         if (f32_out) BODCHK(h->dalloc(&d_out32, n_out)); else BODCHK(h->dalloc(&d_out16, n_out * (x3 ? 2 : 1)));
-        std::vector<RowEnt> rows((size_t)B * OH * OW);
-        size_t r = 0;
-        for (int b = 0; b < B; ++b)
-            for (int y = 0; y < OH; ++y)
-                for (int xx = 0; xx < OW; ++xx) {
-                    RowEnt e{};
-                    e.in_off = (int32_t)(b * in.bstride + (int64_t)(y * stride + oy) * in.pitch + (xx * stride + ox));
-                    e.in_pitch = in.pitch;
-                    e.out_off = (int32_t)(((int64_t)b * OH + y) * OW + xx);
-                    if (residual) e.res_off = (int32_t)(b * res.bstride + (int64_t)(y + 1) * res.pitch + (xx + 1));
-                    e.rng_p = y * OW + xx;
-                    e.rng_zs = b;
-                    rows[r++] = e;
-                }
+        std::vector<RowEnt> rows = forward_row_table(B, OH, OW, stride, oy, ox, in.pitch, in.bstride);
+        for (size_t r = 0; r < rows.size(); ++r) {          // dense output, the residual's plane, the dropout stream of (image, pixel)
+            const int b = (int)(r / ((size_t)OH * OW)), p = (int)(r % ((size_t)OH * OW));
+            rows[r].out_off = (int32_t)r;
+            if (residual) rows[r].res_off = (int32_t)(b * res.bstride + (int64_t)(p / OW + 1) * res.pitch + (p % OW + 1));
+            rows[r].rng_p = p;
+            rows[r].rng_zs = b;
+        }
         RowEnt* d_rows = nullptr;
         BODCHK(h->dalloc(&d_rows, rows.size(), false));
         HIPCHK(h, hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(RowEnt), hipMemcpyHostToDevice, h->stream));
@@ -3079,39 +3091,22 @@ bod_status bod_stage_conv(int32_t device, const float* x, int32_t B, int32_t H, 
         }
         return BOD_OK;
     };
-    return done(run());
+    return sc.done(run());
 }
 
 bod_status bod_stage_conv_wgrad(int32_t device, const float* x, int32_t B, int32_t H, int32_t W, int32_t Cin,
                                 const float* dy, int32_t KH, int32_t KW, int32_t Cout, int32_t stride, int32_t same_padding,
                                 int32_t ksplit, float* dw, float* db) {
-    bod_context ctx;
-    bod_context* h = &ctx;
+    StageScope sc;
+    bod_context* h = sc.h;
     h->es = 2;
-    auto done = [&](bod_status s) {
-        if (s != BOD_OK) g_create_error = h->err;
-        if (h->stream) hipStreamSynchronize(h->stream);
-        for (void* p : h->allocs) hipFree(p);
-        if (h->stream) hipStreamDestroy(h->stream);
-        h->allocs.clear(); h->stream = nullptr;
-        return s;
-    };
     if (!x || !dy || !dw || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 || KH > 3 || KW > 3 || stride < 1 || stride > 2)
-        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv_wgrad: bad argument"));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return done(h->fail(BOD_ERR_NO_DEVICE, "no HIP device %d: libbayesod_hip has no CPU fallback", device));
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
-        return done(h->fail(BOD_ERR_HIP, "cannot set up device %d", device));
+        return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv_wgrad: bad argument"));
+    if (const bod_status st = sc.open(device)) return sc.done(st);
     h->cfg.batch = B;
-    int OH, OW, oy = 1, ox = 1;
-    if (same_padding) {
-        OH = (H + stride - 1) / stride; OW = (W + stride - 1) / stride;
-        oy = 1 - same_pad_before(H, KH, stride); ox = 1 - same_pad_before(W, KW, stride);
-    } else {
-        OH = (H - KH) / stride + 1; OW = (W - KW) / stride + 1;
-    }
-    if (OH < 1 || OW < 1) return done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv_wgrad: empty output"));
+    int OH, OW, oy, ox;
+    conv_out_geometry(H, W, KH, KW, stride, same_padding != 0, &OH, &OW, &oy, &ox);
+    if (OH < 1 || OW < 1) return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_stage_conv_wgrad: empty output"));
     auto run = [&]() -> bod_status {
         const int M = B * OH * OW, taps = KH * KW;
         // ---- forward-layout inputs: padded bf16 plane of x, dense bf16 dY, the forward row table
@@ -3129,16 +3124,7 @@ bod_status bod_stage_conv_wgrad(int32_t device, const float* x, int32_t B, int32
         uint16_t* d_dy = nullptr;
         BODCHK(h->dalloc(&d_dy, hdy.size(), false));
         HIPCHK(h, hipMemcpyAsync(d_dy, hdy.data(), hdy.size() * 2, hipMemcpyHostToDevice, h->stream));
-        std::vector<RowEnt> rows((size_t)M);
-        size_t r = 0;
-        for (int b = 0; b < B; ++b)
-            for (int y = 0; y < OH; ++y)
-                for (int xx = 0; xx < OW; ++xx) {
-                    RowEnt e{};
-                    e.in_off = (int32_t)(b * in.bstride + (int64_t)(y * stride + oy) * in.pitch + (xx * stride + ox));
-                    e.in_pitch = in.pitch;
-                    rows[r++] = e;
-                }
+        const std::vector<RowEnt> rows = forward_row_table(B, OH, OW, stride, oy, ox, in.pitch, in.bstride);
         RowEnt* d_rows = nullptr;
         BODCHK(h->dalloc(&d_rows, rows.size(), false));
         HIPCHK(h, hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(RowEnt), hipMemcpyHostToDevice, h->stream));
@@ -3184,7 +3170,7 @@ bod_status bod_stage_conv_wgrad(int32_t device, const float* x, int32_t B, int32
         if (db) std::memcpy(db, ho.data() + (size_t)taps * Cin * Cout, (size_t)Cout * 4);
         return BOD_OK;
     };
-    return done(run());
+    return sc.done(run());
 }
 
 // the handle's buffers of reg_kind 5 (kernels.h: launch_loss_compact), allocated on first use -- never inside a capture: the
@@ -3206,30 +3192,18 @@ static bod_status loss_impl(int32_t device, int32_t B, int32_t A, int32_t C, con
                             const uint8_t* pos, const uint8_t* neg, int32_t do_cls, int32_t reg_kind,
                             float label_smoothing, double* out4, float w_cls, float w_reg, float* dcls, float* dbox, float* dcov,
                             const bod_loss_options* opt) {
-    bod_context ctx;
-    bod_context* h = &ctx;
-    auto done = [&](bod_status s) {
-        if (s != BOD_OK) g_create_error = h->err;
-        if (h->stream) hipStreamSynchronize(h->stream);
-        for (void* p : h->allocs) hipFree(p);
-        if (h->stream) hipStreamDestroy(h->stream);
-        h->allocs.clear(); h->stream = nullptr;
-        return s;
-    };
+    StageScope sc;
+    bod_context* h = sc.h;
     if (B < 1 || A < 1 || (C != 4 && C != 8) || !pos || !neg || !out4 || reg_kind < 0 || reg_kind > 5)
-        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_loss_forward: bad argument (C must be 4 or 8)"));
+        return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_loss_forward: bad argument (C must be 4 or 8)"));
     if (!loss_options_ok(opt))
-        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_loss_forward: energy_samples %d outside [%d, %d]", opt->energy_samples,
+        return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_loss_forward: energy_samples %d outside [%d, %d]", opt->energy_samples,
                             BOD_ENERGY_MIN_SAMPLES, BOD_ENERGY_MAX_SAMPLES));
     if (reg_kind == 5 && (long long)B * A >= 0x7fffffffLL)
-        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_loss_forward: reg_kind 5 takes fewer than 2^31 - 1 anchors in a call"));
+        return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_loss_forward: reg_kind 5 takes fewer than 2^31 - 1 anchors in a call"));
     if ((do_cls && (!cls || !cls_t)) || (reg_kind && (!box || !box_t)) || (reg_kind >= 2 && (!cov || !anchors)))
-        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_loss_forward: a tensor required by the selected losses is NULL"));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return done(h->fail(BOD_ERR_NO_DEVICE, "no HIP device %d: libbayesod_hip has no CPU fallback", device));
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
-        return done(h->fail(BOD_ERR_HIP, "cannot set up device %d", device));
+        return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_loss_forward: a tensor required by the selected losses is NULL"));
+    if (const bod_status st = sc.open(device)) return sc.done(st);
     auto run = [&]() -> bod_status {
         const size_t n = (size_t)B * A;
         LossArgs a{};
@@ -3285,7 +3259,7 @@ static bod_status loss_impl(int32_t device, int32_t B, int32_t A, int32_t C, con
         }
         return BOD_OK;
     };
-    return done(run());
+    return sc.done(run());
 }
 
 bod_status bod_loss_forward_ex(int32_t device, int32_t B, int32_t A, int32_t C, const float* cls, const float* cls_t,
@@ -3354,29 +3328,17 @@ bod_status bod_anchor_targets(int32_t device, int32_t A, const float* anchors_vu
                               const float* gt_boxes_vuvu, const float* gt_classes, int32_t C, float min_positive_iou,
                               float max_negative_iou, float* cls_targets, float* box_targets, uint8_t* positive_mask,
                               uint8_t* negative_mask, int32_t* best_gt, float* best_iou) {
-    bod_context ctx;
-    bod_context* h = &ctx;
-    auto done = [&](bod_status s) {
-        if (s != BOD_OK) g_create_error = h->err;
-        if (h->stream) hipStreamSynchronize(h->stream);
-        for (void* p : h->allocs) hipFree(p);
-        if (h->stream) hipStreamDestroy(h->stream);
-        h->allocs.clear(); h->stream = nullptr;
-        return s;
-    };
+    StageScope sc;
+    bod_context* h = sc.h;
     if (A < 1 || B < 1 || B > 65535 || C < 2)
-        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_anchor_targets: bad argument (A = %d, B = %d in 1..65535, C = %d >= 2)", A, B, C));
+        return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_anchor_targets: bad argument (A = %d, B = %d in 1..65535, C = %d >= 2)", A, B, C));
     if (!anchors_vuhw || !num_gt || !gt_boxes_vuvu || !gt_classes || !cls_targets || !box_targets || !positive_mask || !negative_mask)
-        return done(h->fail(BOD_ERR_INVALID_ARG, "bod_anchor_targets: a required array is NULL"));
+        return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_anchor_targets: a required array is NULL"));
     for (int b = 0; b < B; ++b)
         if (num_gt[b] < 1)
-            return done(h->fail(BOD_ERR_INVALID_ARG, "bod_anchor_targets: frame %d has %d ground-truth rows (at least the placeholder row is "
+            return sc.done(h->fail(BOD_ERR_INVALID_ARG, "bod_anchor_targets: frame %d has %d ground-truth rows (at least the placeholder row is "
                                 "required)", b, num_gt[b]));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return done(h->fail(BOD_ERR_NO_DEVICE, "no HIP device %d: libbayesod_hip has no CPU fallback", device));
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
-        return done(h->fail(BOD_ERR_HIP, "cannot set up device %d", device));
+    if (const bod_status st = sc.open(device)) return sc.done(st);
     auto run = [&]() -> bod_status {
         const size_t n = (size_t)B * A;
         PackedGt p;
@@ -3403,7 +3365,7 @@ bod_status bod_anchor_targets(int32_t device, int32_t A, const float* anchors_vu
         HIPCHK(h, hipStreamSynchronize(h->stream));
         return BOD_OK;
     };
-    return done(run());
+    return sc.done(run());
 }
 
 // PDQ evaluation (pdq_kernels.hip): stateless, one stream for the call
@@ -3610,7 +3572,7 @@ Rccl& rccl() { static Rccl r; return r; }
 }  // namespace
 }  // extern "C++"
 
-int32_t bod_record_width(bod_handle h) { return h ? 21 + 2 * h->cfg.num_classes + (h->parts ? 48 : 0) + (h->class_parts ? 4 : 0) : 0; }
+int32_t bod_record_width(bod_handle h) { return h ? record_layout(h).fields.width : 0; }
 
 bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, int32_t world, int32_t rank, int32_t root,
                                  float* gathered_host, float** gathered_device) {
@@ -3631,38 +3593,31 @@ bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, in
     // bod_infer_async is already enqueued they run behind its kernels -- one step of latency, nothing beside anything.
     // BOD_SIDE_STREAM=1 (the repro switch of bod_infer_async): the side stream again.
     static const bool side_on = [] { const char* e = getenv("BOD_SIDE_STREAM"); return e && atoi(e) != 0; }();
-    hipStream_t st = (slot >= 0 && slot <= 1 && !side_on && h->done_stream[slot]) ? h->done_stream[slot] : h->side;
+    hipStream_t st = (slot >= 0 && slot <= 1 && !side_on && h->rec[slot].done_stream) ? h->rec[slot].done_stream : h->side;
     if (slot < 0) {
         // synchronous bod_infer / bod_cluster_fuse: the records are the current buffers, finished on the MAIN stream -- pack and gather
         // go out on that stream too, so the next bod_infer (which rewrites nms_nsel / out_* of this slot on the main stream) and
         // bod_synchronize are ordered behind them by stream order.  (On the side stream nothing would hold the main stream back.)
-        if (!h->cluster_done) return h->fail(BOD_ERR_NOT_READY, "bod_gather_detections: bod_cluster_fuse has not run");
+        if (!h->stage.cluster) return h->fail(BOD_ERR_NOT_READY, "bod_gather_detections: bod_cluster_fuse has not run");
         BODCHK(join_overlap(h));
         sidx = h->slot;
         st = h->stream;
-    } else if (slot > 1 || !h->side_pending[slot]) {
+    } else if (slot > 1 || !h->rec[slot].pending) {
         return h->fail(BOD_ERR_NOT_READY, "bod_gather_detections: slot %d has no pending batch", slot);
     }
+    const RecordSlot& r = h->rec[sidx];
     for (int img = 0; h->parts && img < B; ++img)
-        if (!h->det_parts_ok[sidx][img]) return h->fail(BOD_ERR_NOT_READY, "bod_gather_detections: image %d was fused without its posterior's parts (bod_set_posterior_parts)", img);
+        if (!r.parts_ok[img]) return h->fail(BOD_ERR_NOT_READY, "bod_gather_detections: image %d was fused without its posterior's parts (bod_set_posterior_parts)", img);
     for (int img = 0; h->cparts && img < B; ++img)
-        if (!h->det_cparts_ok[sidx][img]) return h->fail(BOD_ERR_NOT_READY, "bod_gather_detections: image %d was fused without its posterior's class parts (bod_set_posterior_class_parts)", img);
+        if (!r.cparts_ok[img]) return h->fail(BOD_ERR_NOT_READY, "bod_gather_detections: image %d was fused without its posterior's class parts (bod_set_posterior_class_parts)", img);
     if (!h->rec_send && hipMalloc(reinterpret_cast<void**>(&h->rec_send), block * 4) != hipSuccess)
         return h->fail(BOD_ERR_OOM, "bod_gather_detections: %zu bytes", block * 4);
     // rec_send / rec_recv are shared by the ticket gathers (side stream) and the synchronous form (main stream): a gather that goes to
     // the other stream than the previous one waits for it -- nothing else orders the two streams against each other (round-4 advisor finding)
     if (h->ev_gather && h->gather_stream && h->gather_stream != st) HIPCHK(h, hipStreamWaitEvent(st, h->ev_gather, 0));
     // (on the side stream: behind the slot's event; on the records' own stream the wait is a no-op)
-    if (slot >= 0) HIPCHK(h, hipStreamWaitEvent(st, h->ev_done[slot], 0));
-    if (h->cparts)
-        HIPCHK(h, launch_pack_records_class(h->nms_nsel_s[sidx], h->out_scores_s[sidx], h->out_means_s[sidx], h->out_covs_s[sidx],
-                                            h->out_counts_s[sidx], h->out_parts_s[sidx], h->out_cparts_s[sidx], h->rec_send, B, K, C, st));
-    else if (h->parts)
-        HIPCHK(h, launch_pack_records_parts(h->nms_nsel_s[sidx], h->out_scores_s[sidx], h->out_means_s[sidx], h->out_covs_s[sidx],
-                                            h->out_counts_s[sidx], h->out_parts_s[sidx], h->rec_send, B, K, C, st));
-    else
-        HIPCHK(h, launch_pack_records(h->nms_nsel_s[sidx], h->out_scores_s[sidx], h->out_means_s[sidx], h->out_covs_s[sidx],
-                                      h->out_counts_s[sidx], h->rec_send, B, K, C, st));
+    if (slot >= 0) HIPCHK(h, hipStreamWaitEvent(st, r.done, 0));
+    HIPCHK(h, launch_pack_records(r.nms_nsel, r.scores, r.means, r.covs, r.counts, r.parts, r.cparts, h->rec_send, B, K, C, st));
     float* recv = nullptr;
     if (rank == root) {
         if (world == 1 && !nccl_comm) recv = h->rec_send;
@@ -3692,7 +3647,7 @@ bod_status bod_gather_detections(bod_handle h, int32_t slot, void* nccl_comm, in
     }
     if (!(rank == root && gathered_host) && slot >= 0) {
         // keep bod_collect / the next bod_infer_async of this slot behind the send: re-record the slot's event
-        HIPCHK(h, hipEventRecord(h->ev_done[slot], st));
+        HIPCHK(h, hipEventRecord(h->rec[slot].done, st));
     }
     if (gathered_device) *gathered_device = recv;
     return BOD_OK;
@@ -3992,8 +3947,7 @@ bod_status bod_stat_posterior(bod_handle h, uint64_t seed, uint32_t first_image_
     if (h->class_parts && h->stat_ent_k != h->stat_k)
         return h->fail(BOD_ERR_NOT_READY, "bod_stat_posterior: ent_sum holds %d of the record's %d samples (bod_stat_merge_entropy / bod_stat_set_entropy has not followed)", h->stat_ent_k, h->stat_k);
     if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called");
-    for (int sidx = 0; sidx < 2; ++sidx)
-        if (h->side_pending[sidx]) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_done[sidx], 0));
+    BODCHK(wait_pending_slots(h, h->stream));
     MarkerRange mr("bod:posterior");
     PostCfg pc = post_cfg(h, seed, first_image_id);
     pc.N = h->stat_k;                                    // the merged sample count
@@ -4007,7 +3961,7 @@ bod_status bod_stat_posterior(bod_handle h, uint64_t seed, uint32_t first_image_
     if (h->cparts) { HIPCHK(h, launch_posterior_class_parts(pc, pb, h->stat_ent, h->cparts, h->stream)); std::fill(h->cparts_ok.begin(), h->cparts_ok.end(), 1); }
     if (h->cfg.ranking_method == BOD_RANK_JOINT_ENTROPY && h->cfg.gaussian_isotropic && h->cfg.dirichlet_non_informative)
         HIPCHK(h, launch_joint_entropy_rank(pc, pb, h->stream));
-    h->posterior_done = true; h->nms_done = h->cluster_done = false; h->affinity_img = -1;
+    h->stage.posterior_ran();
     return BOD_OK;
 }
 

@@ -335,15 +335,10 @@ hipError_t launch_cluster_parts(const ClusterArgs& a, const float* parts, float*
 #define BOD_LOG_SDEN(x) (__builtin_amdgcn_logf(x) * 0.693147180559945f)
 hipError_t launch_posterior_class_parts(const PostCfg& c, const PostBuffers& b, const float* ent_sum, float* cparts, hipStream_t s);
 hipError_t launch_cluster_class_parts(const ClusterArgs& a, const float* cparts, float* out_cparts, hipStream_t s);
-// detection records [B][K][1 + 4 + 16 + 2C] of the multi-GPU gather (zero rows beyond num[b])
+// detection records [B][K][1 + 4 + 16 + 2C (+ 48 when parts != nullptr) (+ 4 when cparts != nullptr)] of the multi-GPU gather (zero rows
+// beyond num[b]); the row's field offsets: record_fields (record_state.h)
 hipError_t launch_pack_records(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
-                               float* rec, int B, int K, int C, hipStream_t s);
-// the same rows with the three covariance parts appended behind the counts: [B][K][1 + 4 + 16 + 2C + 48]
-hipError_t launch_pack_records_parts(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
-                                     const float* parts, float* rec, int B, int K, int C, hipStream_t s);
-// rows of a BOD_PARTS_CLASS handle: [B][K][1 + 4 + 16 + 2C (+ 48 when parts != nullptr) + 4], the class-entropy parts last
-hipError_t launch_pack_records_class(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
-                                     const float* parts, const float* cparts, float* rec, int B, int K, int C, hipStream_t s);
+                               const float* parts, const float* cparts, float* rec, int B, int K, int C, hipStream_t s);
 
 struct PreprocArgs {
     const uint8_t* src;        // [B, sh, sw, 3] uint8 RGB

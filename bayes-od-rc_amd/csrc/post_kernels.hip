@@ -14,6 +14,7 @@
 //   K6 iou_matrix_kernel    box_utils.bbox_iou_vuvu (only for API compatibility)     (:214-215)
 #include "kernels.h"
 #include "philox.h"
+#include "record_state.h"
 #include <algorithm>
 #include <math.h>
 
@@ -1821,12 +1822,16 @@ __global__ void iou_matrix_kernel(const float4* boxes, int M, float* out) {
 // ------------------------------------------------------------------------------------------------
 // Detection records for the path's one multi-GPU exchange: per image K padded rows of
 // W = 1 + 4 + 16 + 2C floats -- [valid, mean (v,u,h,w), covariance row-major, score[C], counts[C]] -- zero beyond the image's
-// detection count.  The layout of distributed.pack_records, written by one kernel instead of five torch ops.
+// detection count.  The layout of distributed.pack_records, written by one kernel instead of five torch ops.  A handle with
+// covariance parts appends their 48 floats behind the counts, one with class-entropy parts its four last: `parts` / `cparts`
+// are nullptr on a handle without them (record_fields, record_state.h: the row's field offsets).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pack_records_kernel(const int32_t* __restrict__ num, const float* __restrict__ scores,
                                                            const float* __restrict__ means, const float* __restrict__ covs,
-                                                           const float* __restrict__ counts, float* __restrict__ rec, int B, int K, int C) {
-    const int W = 21 + 2 * C;
+                                                           const float* __restrict__ counts, const float* __restrict__ parts,
+                                                           const float* __restrict__ cparts, float* __restrict__ rec, int B, int K, int C) {
+    const RecordFields f = record_fields(C, parts != nullptr, cparts != nullptr);
+    const int W = f.width;
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)B * K * W) return;
     const int w = (int)(i % W);
@@ -1834,88 +1839,23 @@ __global__ __launch_bounds__(256) void pack_records_kernel(const int32_t* __rest
     const int b = (int)(row / K), k = (int)(row % K);
     float v = 0.f;
     if (k < num[b]) {
-        if (w == 0) v = 1.f;
-        else if (w < 5) v = means[row * 4 + (w - 1)];
-        else if (w < 21) v = covs[row * 16 + (w - 5)];
-        else if (w < 21 + C) v = scores[row * C + (w - 21)];
-        else v = counts[row * C + (w - 21 - C)];
+        if (w < f.mean) v = 1.f;
+        else if (w < f.cov) v = means[row * REC_MEAN + (w - f.mean)];
+        else if (w < f.score) v = covs[row * REC_COV + (w - f.cov)];
+        else if (w < f.count) v = scores[row * C + (w - f.score)];
+        else if (w < f.parts) v = counts[row * C + (w - f.count)];
+        else if (w < f.cparts) v = parts[row * REC_PARTS + (w - f.parts)];
+        else v = cparts[row * REC_CPARTS + (w - f.cparts)];
     }
     rec[i] = v;
 }
 
 hipError_t launch_pack_records(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
-                               float* rec, int B, int K, int C, hipStream_t s) {
-    const long n = (long)B * K * (21 + 2 * C);
+                               const float* parts, const float* cparts, float* rec, int B, int K, int C, hipStream_t s) {
+    const long n = (long)B * K * record_fields(C, parts != nullptr, cparts != nullptr).width;
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pack_records_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, num, scores, means, covs, counts, rec, B, K, C);
-    return hipGetLastError();
-}
-
-// The record rows of a covariance_parts handle: the same row with the 48 floats of the three parts behind the counts
-__global__ __launch_bounds__(256) void pack_records_parts_kernel(const int32_t* __restrict__ num, const float* __restrict__ scores,
-                                                                 const float* __restrict__ means, const float* __restrict__ covs,
-                                                                 const float* __restrict__ counts, const float* __restrict__ parts,
-                                                                 float* __restrict__ rec, int B, int K, int C) {
-    const int W0 = 21 + 2 * C, W = W0 + 48;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)B * K * W) return;
-    const int w = (int)(i % W);
-    const long row = i / W;                      // b * K + k
-    const int b = (int)(row / K), k = (int)(row % K);
-    float v = 0.f;
-    if (k < num[b]) {
-        if (w == 0) v = 1.f;
-        else if (w < 5) v = means[row * 4 + (w - 1)];
-        else if (w < 21) v = covs[row * 16 + (w - 5)];
-        else if (w < 21 + C) v = scores[row * C + (w - 21)];
-        else if (w < W0) v = counts[row * C + (w - 21 - C)];
-        else v = parts[row * 48 + (w - W0)];
-    }
-    rec[i] = v;
-}
-
-hipError_t launch_pack_records_parts(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
-                                     const float* parts, float* rec, int B, int K, int C, hipStream_t s) {
-    const long n = (long)B * K * (21 + 2 * C + 48);
-    if (n <= 0) return hipSuccess;
-    if (!parts) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pack_records_parts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, num, scores, means, covs, counts, parts,
+    hipLaunchKernelGGL(pack_records_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, num, scores, means, covs, counts, parts, cparts,
                        rec, B, K, C);
-    return hipGetLastError();
-}
-
-// The record rows of a BOD_PARTS_CLASS handle: the row (with the 48 covariance-part floats when the handle has them) and the four
-// class-entropy parts last
-__global__ __launch_bounds__(256) void pack_records_class_kernel(const int32_t* __restrict__ num, const float* __restrict__ scores,
-                                                                 const float* __restrict__ means, const float* __restrict__ covs,
-                                                                 const float* __restrict__ counts, const float* __restrict__ parts,
-                                                                 const float* __restrict__ cparts, float* __restrict__ rec, int B, int K, int C) {
-    const int W0 = 21 + 2 * C, W1 = W0 + (parts ? 48 : 0), W = W1 + 4;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)B * K * W) return;
-    const int w = (int)(i % W);
-    const long row = i / W;                      // b * K + k
-    const int b = (int)(row / K), k = (int)(row % K);
-    float v = 0.f;
-    if (k < num[b]) {
-        if (w == 0) v = 1.f;
-        else if (w < 5) v = means[row * 4 + (w - 1)];
-        else if (w < 21) v = covs[row * 16 + (w - 5)];
-        else if (w < 21 + C) v = scores[row * C + (w - 21)];
-        else if (w < W0) v = counts[row * C + (w - 21 - C)];
-        else if (w < W1) v = parts[row * 48 + (w - W0)];
-        else v = cparts[row * 4 + (w - W1)];
-    }
-    rec[i] = v;
-}
-
-hipError_t launch_pack_records_class(const int32_t* num, const float* scores, const float* means, const float* covs, const float* counts,
-                                     const float* parts, const float* cparts, float* rec, int B, int K, int C, hipStream_t s) {
-    const long n = (long)B * K * (21 + 2 * C + (parts ? 48 : 0) + 4);
-    if (n <= 0) return hipSuccess;
-    if (!cparts) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pack_records_class_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, num, scores, means, covs, counts, parts,
-                       cparts, rec, B, K, C);
     return hipGetLastError();
 }
 

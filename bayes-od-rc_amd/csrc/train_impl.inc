@@ -921,30 +921,10 @@ bod_status bod_train_step_count(bod_handle h, int64_t* get, int64_t set) {
 
 // ------------------------------------------------------------------------------------------------
 // Stage entry points of the backward kernels that only the bf16 training handle launches (include/bayesod.h): a throw-away
-// context, host arrays in and out, the launchers called as train_backward / train_fold_all call them.  Every argument a kernel
+// context (StageScope, engine.hip), host arrays in and out, the launchers called as train_backward / train_fold_all call them.  Every argument a kernel
 // turns into an address is checked on the host first; nothing is launched on a bad one.
 // ------------------------------------------------------------------------------------------------
 namespace {
-struct StageScope {
-    bod_context ctx;
-    bod_context* h = &ctx;
-    bod_status done(bod_status s) {
-        if (s != BOD_OK) g_create_error = h->err;
-        if (h->stream) hipStreamSynchronize(h->stream);
-        for (void* p : h->allocs) hipFree(p);
-        if (h->stream) hipStreamDestroy(h->stream);
-        h->allocs.clear(); h->stream = nullptr;
-        return s;
-    }
-    bod_status open(int32_t device) {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-            return h->fail(BOD_ERR_NO_DEVICE, "no HIP device %d: libbayesod_hip has no CPU fallback", device);
-        if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
-            return h->fail(BOD_ERR_HIP, "cannot set up device %d", device);
-        return BOD_OK;
-    }
-};
 // host fp32 -> device buffer of the handle's element type (bf16: rounded like a stored activation); synchronises
 bod_status stage_upload(bod_context* h, const float* src, size_t n, bool f32, void** dst) {
     char* d = nullptr;
@@ -1045,33 +1025,20 @@ bod_status bod_stage_conv_dgrad(int32_t device, int32_t route, const float* dz, 
     if (groups < 1 || groups > 3 || (groups > 1 && route != BOD_DGRAD_FLIP)) return bad("groups: 1..3, more than one on BOD_DGRAD_FLIP only");
     const int cout_pad = (Cout + 63) / 64 * 64, taps = KH * KW;
     if (ksplit < 0 || ksplit > 64 || (ksplit > 1 && (cout_pad / 64) % ksplit != 0)) return bad("ksplit must divide the reduction's 64-channel chunks (cout_pad / 64)");
-    int OH, OW, oy = 1, ox = 1;
-    if (same_padding) {
-        OH = (H + stride - 1) / stride; OW = (W + stride - 1) / stride;
-        oy = 1 - same_pad_before(H, KH, stride); ox = 1 - same_pad_before(W, KW, stride);
-    } else {
-        OH = (H - KH) / stride + 1; OW = (W - KW) / stride + 1;
-    }
+    int OH, OW, oy, ox;
+    conv_out_geometry(H, W, KH, KW, stride, same_padding != 0, &OH, &OW, &oy, &ox);
     if (OH < 1 || OW < 1) return bad("empty output");
     // forward row table on the zero-bordered input plane (bod_stage_conv_wgrad's); BOD_DGRAD_FLIP: the output plane has the same geometry
     const int pitch = W + 2;
     const int64_t bstride = (int64_t)(H + 2) * (W + 2), npix = (int64_t)B * bstride;
     const int M = B * OH * OW;
-    std::vector<RowEnt> rows((size_t)M);
-    {
-        size_t r = 0;
-        for (int b = 0; b < B; ++b)
-            for (int y = 0; y < OH; ++y)
-                for (int xx = 0; xx < OW; ++xx) {
-                    RowEnt e{};
-                    e.in_off = (int32_t)(b * bstride + (int64_t)(y * stride + oy) * pitch + (xx * stride + ox));
-                    e.in_pitch = pitch;
-                    e.out_off = route == BOD_DGRAD_FLIP ? (int32_t)(b * bstride + (int64_t)(y + 1) * pitch + (xx + 1)) : (int32_t)r;
-                    // every pixel a window touches lies on the plane of its own image
-                    const int y0 = y * stride + oy, x0 = xx * stride + ox;
-                    if (y0 < 0 || x0 < 0 || y0 + KH - 1 > H + 1 || x0 + KW - 1 > W + 1) return bad("a window leaves the bordered plane");
-                    rows[r++] = e;
-                }
+    std::vector<RowEnt> rows = forward_row_table(B, OH, OW, stride, oy, ox, pitch, bstride);
+    for (size_t r = 0; r < rows.size(); ++r) {
+        const int b = (int)(r / ((size_t)OH * OW)), y = (int)(r % ((size_t)OH * OW)) / OW, xx = (int)(r % (size_t)OW);
+        rows[r].out_off = route == BOD_DGRAD_FLIP ? (int32_t)(b * bstride + (int64_t)(y + 1) * pitch + (xx + 1)) : (int32_t)r;
+        // every pixel a window touches lies on the plane of its own image
+        const int y0 = y * stride + oy, x0 = xx * stride + ox;
+        if (y0 < 0 || x0 < 0 || y0 + KH - 1 > H + 1 || x0 + KW - 1 > W + 1) return bad("a window leaves the bordered plane");
     }
     if (const bod_status s = sc.open(device)) return sc.done(s);
     auto run = [&]() -> bod_status {

@@ -67,7 +67,7 @@ bod_status val_check(bod_context* h, const char* who, const int32_t* num_gt, int
         if (num_gt[b] < 1)
             return h->fail(BOD_ERR_INVALID_ARG, "%s: frame %d has %d ground-truth rows (at least the placeholder row is required)", who, b, num_gt[b]);
     if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called");
-    if (need_forward && !h->forward_done) return h->fail(BOD_ERR_NOT_READY, "bod_forward / bod_set_raw has not run");
+    if (need_forward && !h->stage.forward) return h->fail(BOD_ERR_NOT_READY, "bod_forward / bod_set_raw has not run");
     return BOD_OK;
 }
 
@@ -120,7 +120,7 @@ bod_status val_gather_enqueue(bod_context* h) {
     const bod_config& c = h->cfg;
     ValGatherArgs ga{};
     ga.B = c.batch; ga.A = h->A; ga.C = c.num_classes; ga.max_out = c.nms_max_output_size;
-    ga.num_kept = h->pb.num_kept; ga.selected = h->nms_sel; ga.num_selected = h->nms_nsel; ga.score = h->pb.score; ga.corners = h->pb.corners;
+    ga.num_kept = h->pb.num_kept; ga.selected = h->cur().nms_sel; ga.num_selected = h->cur().nms_nsel; ga.score = h->pb.score; ga.corners = h->pb.corners;
     ga.out_scores = v->det_scores; ga.out_corners = v->det_corners; ga.out_num = v->det_num;
     HIPCHK(h, launch_validation_gather(ga, h->stream));
     return BOD_OK;
@@ -155,7 +155,7 @@ bod_status bod_validation_losses_boxes(bod_handle h, const int32_t* num_gt, cons
 bod_status bod_get_validation_detections_batch(bod_handle h, int32_t* num_detections, float* scores, float* corners) {
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
-    if (!h->nms_done) return h->fail(BOD_ERR_NOT_READY, "bod_nms has not run");
+    if (!h->stage.nms) return h->fail(BOD_ERR_NOT_READY, "bod_nms has not run");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     BODCHK(val_gather_enqueue(h));
     BODCHK(val_copy_detections(h, num_detections, scores, corners));
