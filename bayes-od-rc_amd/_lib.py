@@ -20,7 +20,14 @@ BOD_OK, BOD_ERR_INVALID_ARG, BOD_ERR_HIP, BOD_ERR_OOM, BOD_ERR_NOT_READY, BOD_ER
 BOD_PARTS_COVARIANCE, BOD_PARTS_CLASS = 1, 2      # bits of bod_config.covariance_parts
 BOD_MERGE_BAYES, BOD_MERGE_CENTRE, BOD_MERGE_MIXTURE = 0, 1, 2      # bod_set_merge_method
 MERGE_METHODS = {"bayes": BOD_MERGE_BAYES, "centre": BOD_MERGE_CENTRE, "mixture": BOD_MERGE_MIXTURE}
+BOD_METHOD_BAYES_OD, BOD_METHOD_BLACK_BOX = 0, 1                   # bod_set_uncertainty_method
+UNCERTAINTY_METHODS = {"bayes_od": BOD_METHOD_BAYES_OD, "black_box": BOD_METHOD_BLACK_BOX}
 BOD_VIEW_IDENTITY, BOD_VIEW_HFLIP = 0, 1         # views of a statistics handle (bod_stat_forward_view / bod_stat_merge_view)
+
+
+class BodBlackBoxOptions(C.Structure):
+    """Mirror of ``bod_blackbox_options`` (include/bayesod.h)."""
+    _fields_ = [("min_score", C.c_float), ("min_members", C.c_int32), ("affinity_threshold", C.c_float), ("reserved", C.c_int32)]
 
 
 class BodConfig(C.Structure):
@@ -268,6 +275,12 @@ SIGNATURES = {
     "bod_get_detection_merge_terms": (C.c_int, [_H, C.c_int32, _F, _F, _I]),
     "bod_get_detection_merge_terms_batch": (C.c_int, [_H, C.c_int32, _F, _F, _I]),
     "bod_device_detection_merge_terms": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
+    "bod_set_uncertainty_method": (C.c_int, [_H, C.c_int32, C.POINTER(BodBlackBoxOptions)]),
+    "bod_get_uncertainty_method": (C.c_int, [_H, _I]),
+    "bod_blackbox_samples": (C.c_int, [_H]),
+    "bod_blackbox_merge": (C.c_int, [_H]),
+    "bod_get_sample_detections": (C.c_int, [_H, C.c_int32, C.c_int32, _I, _I, _F, _F, _F]),
+    "bod_set_sample_detections": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, _I, _F, _F, _F]),
     "bod_stat_get_entropy": (C.c_int, [_H, _F]),
     "bod_stat_set_entropy": (C.c_int, [_H, _F]),
     "bod_stat_device_entropy": (C.c_int, [_H, C.POINTER(C.c_void_p)]),

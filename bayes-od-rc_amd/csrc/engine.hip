@@ -417,6 +417,13 @@ struct bod_context {
     // How run_cluster merges a cluster (bod_set_merge_method).  The slots' term buffers exist from the first
     // non-default setter call on.
     int merge_method = BOD_MERGE_BAYES;
+    // Black-box MC dropout (bod_set_uncertainty_method).  bb holds the stage's buffers from the first switch to the
+    // method on (bb.keep != nullptr); its outputs point at the record slot a call writes.  bb_samples_ok: the sample detections
+    // belong to the last forward (bod_blackbox_samples ran, or bod_set_sample_detections since).
+    int uncertainty_method = BOD_METHOD_BAYES_OD;
+    bod_blackbox_options bb_opt{0.f, 1, 0.f, 0};
+    BlackBoxArgs bb{};
+    bool bb_samples_ok = false;
     hipStream_t side = nullptr;
     // ---- CU-partitioned pipeline overlap (bod_config.pipeline_overlap; bod_infer_async only).  The memory-bound front of batch i+1
     // (stem, backbone, FPN) runs on its own stream, masked to the last `ov_front_slots` CU slots of every XCD, while the MFMA-bound
@@ -1812,7 +1819,7 @@ bod_status run_forward(bod_context* h, const float* dev_images, uint64_t seed, u
     }
     h->stage.forward_ran();
     h->last_seed = seed; h->last_first_image = first_image;
-    if (!only_flavoured) h->last_sample_base = c.mc_sample_base;
+    if (!only_flavoured) { h->last_sample_base = c.mc_sample_base; h->bb_samples_ok = false; }
     if (flavour == FLAVOUR_AGG) { h->agg_valid = true; h->raw_valid = false; h->agg_sparse = h->plan_sparse; }
     else { h->raw_valid = true; if (!only_flavoured) h->agg_valid = false; }
     return BOD_OK;
@@ -1922,6 +1929,92 @@ bod_status run_cluster(bod_context* h, hipStream_t st) {
     r.merge_terms_ok = h->merge_method != BOD_MERGE_BAYES;
     if (h->parts) { HIPCHK(h, launch_cluster_parts(a, h->parts, r.parts, st)); r.parts_ok = h->parts_ok; }
     if (h->cparts) { HIPCHK(h, launch_cluster_class_parts(a, h->cparts, r.cparts, st)); r.cparts_ok = h->cparts_ok; }
+    h->stage.cluster_ran();
+    return BOD_OK;
+}
+
+// ---- black-box MC dropout (bayesod.h) ----
+// Every buffer of the two stages, on the first switch to the method: the per-image arrays of the validation post-process and of
+// nms_kernel for batch * mc_samples virtual images, the sample detections, the pool's work arrays, and the slots' merge terms.
+bod_status alloc_blackbox(bod_context* h) {
+    if (h->bb.keep) return BOD_OK;
+    const bod_config& c = h->cfg;
+    const size_t V = (size_t)c.batch * c.mc_samples, VA = V * h->A, VK = V * c.nms_max_output_size, C = c.num_classes;
+    const size_t nblocks = (h->A + 255) / 256;
+    BlackBoxArgs& a = h->bb;
+    uint8_t* keep = nullptr;
+    BODCHK(h->dalloc(&keep, VA));
+    BODCHK(h->dalloc(&a.top, VA));
+    BODCHK(h->dalloc(&a.block_counts, V * nblocks));
+    BODCHK(h->dalloc(&a.num_kept, V));
+    BODCHK(h->dalloc(&a.ranking, VA));
+    BODCHK(h->dalloc(&a.corners, VA * 4));
+    BODCHK(h->dalloc(&a.anchor_index, VA));
+    const size_t VApad = V * ((h->A + 511) & ~(size_t)511);
+    BODCHK(h->dalloc(&a.work_scores, VApad));
+    BODCHK(h->dalloc(&a.work_begin, VApad));
+    BODCHK(h->dalloc(&a.selected, VK));
+    BODCHK(h->dalloc(&a.num_selected, V));
+    BODCHK(h->dalloc(&a.sd_score, VK * C));
+    BODCHK(h->dalloc(&a.sd_mean, VK * 4));
+    BODCHK(h->dalloc(&a.sd_cov, VK * 16));
+    BODCHK(h->dalloc(&a.sd_anchor, VK));
+    BODCHK(h->dalloc(&a.sd_count, V));
+    BODCHK(h->dalloc(&a.pool_top, VK));
+    BODCHK(h->dalloc(&a.pool_corners, VK * 4));
+    if (!h->rec[1].merge_members) {
+        const size_t BK = (size_t)c.batch * c.nms_max_output_size;
+        for (RecordSlot& r : h->rec) {
+            BODCHK(h->dalloc(&r.merge_within, BK * REC_COV));
+            BODCHK(h->dalloc(&r.merge_between, BK * REC_COV));
+            BODCHK(h->dalloc(&r.merge_members, BK));
+        }
+    }
+    a.keep = keep;                                    // last: the mark that everything above exists
+    return BOD_OK;
+}
+
+BlackBoxArgs blackbox_args(bod_context* h) {
+    const bod_config& c = h->cfg;
+    BlackBoxArgs a = h->bb;
+    a.B = c.batch; a.N = c.mc_samples; a.A = h->A; a.C = c.num_classes; a.max_out = c.nms_max_output_size;
+    a.min_score = h->bb_opt.min_score; a.min_members = h->bb_opt.min_members;
+    a.thr = h->bb_opt.affinity_threshold > 0.f ? h->bb_opt.affinity_threshold : c.nms_iou_threshold;
+    return a;
+}
+
+// stage 1: the validation post-process and the soft-NMS of every (image, sample), then the sample detections
+bod_status run_blackbox_samples(bod_context* h) {
+    if (!h->anchors_ready) return h->fail(BOD_ERR_NOT_READY, "bod_set_anchors has not been called");
+    BODCHK(materialise_raw(h));
+    BODCHK(wait_pending_slots(h, h->stream));
+    MarkerRange mr("bod:blackbox_samples");
+    const bod_config& c = h->cfg;
+    const PostCfg pc = post_cfg(h, 0, 0);
+    PostBuffers pb{};
+    pb.cls = h->raw[0]; pb.box = h->raw[1]; pb.cov = h->raw[2]; pb.anchors = h->d_anchors;
+    const BlackBoxArgs a = blackbox_args(h);
+    NmsArgs n{};
+    n.B = c.batch * c.mc_samples; n.A = h->A; n.num_kept = a.num_kept; n.corners = a.corners; n.ranking = a.ranking;
+    n.work_scores = a.work_scores; n.work_begin = a.work_begin; n.selected = a.selected; n.num_selected = a.num_selected;
+    n.max_out = c.nms_max_output_size; n.iou_thr = c.nms_iou_threshold; n.sigma = c.nms_soft_sigma; n.variant = c.nms_variant;
+    HIPCHK(h, launch_blackbox_samples(pc, pb, a, n, h->stream));
+    h->bb_samples_ok = true;
+    return BOD_OK;
+}
+
+// stage 2: the image's pool merged into the current record slot; the detection getters follow as after bod_cluster_fuse
+bod_status run_blackbox_merge(bod_context* h, hipStream_t st) {
+    MarkerRange mr("bod:blackbox_merge");
+    RecordSlot& r = h->cur();
+    BlackBoxArgs a = blackbox_args(h);
+    a.out_num = r.nms_nsel; a.out_centre = r.nms_sel;
+    a.out_scores = r.scores; a.out_means = r.means; a.out_covs = r.covs; a.out_counts = r.counts;
+    const MergeTerms terms{r.merge_within, r.merge_between, r.merge_members};
+    HIPCHK(h, launch_blackbox_merge(a, terms, st));
+    r.merge_terms_ok = true;
+    h->stage.posterior_ran();                         // the slot's centres are pooled indices now: no bod_cluster_fuse on them
+    h->stage.posterior = false;
     h->stage.cluster_ran();
     return BOD_OK;
 }
@@ -2335,7 +2428,7 @@ bod_status bod_set_raw(bod_handle h, const float* cls, const float* box, const f
     if (cov && c.has_covar_head) HIPCHK(h, hipMemcpyAsync(h->raw[2], cov, n * 40, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->stage.forward_ran();
-    h->raw_valid = true; h->agg_valid = false;
+    h->raw_valid = true; h->agg_valid = false; h->bb_samples_ok = false;
     return BOD_OK;
 }
 
@@ -2744,6 +2837,9 @@ bod_status bod_set_merge_method(bod_handle h, int32_t method) {
     if (method != BOD_MERGE_BAYES && h->cfg.covariance_parts != 0)
         return h->fail(BOD_ERR_INVALID_ARG, "bod_set_merge_method: the handle was created with bod_config.covariance_parts = %d; the covariance and "
                        "class-entropy parts are defined for the Bayesian fuse (BOD_MERGE_BAYES) only", h->cfg.covariance_parts);
+    if (method != BOD_MERGE_BAYES && h->uncertainty_method == BOD_METHOD_BLACK_BOX)
+        return h->fail(BOD_ERR_INVALID_ARG, "bod_set_merge_method: the handle's uncertainty method is BOD_METHOD_BLACK_BOX, which merges the pooled "
+                       "sample detections by its own rule; the merge methods belong to BOD_METHOD_BAYES_OD");
     if (method != BOD_MERGE_BAYES && !h->rec[1].merge_members) {
         HIPCHK(h, hipSetDevice(h->cfg.device));
         const size_t BK = (size_t)h->cfg.batch * h->cfg.nms_max_output_size;
@@ -2822,13 +2918,118 @@ bod_status bod_device_detection_merge_terms(bod_handle h, int32_t sidx, void** p
     return BOD_OK;
 }
 
+bod_status bod_set_uncertainty_method(bod_handle h, int32_t method, const bod_blackbox_options* options) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    if (method != BOD_METHOD_BAYES_OD && method != BOD_METHOD_BLACK_BOX)
+        return h->fail(BOD_ERR_INVALID_ARG, "bod_set_uncertainty_method: unknown method %d (BOD_METHOD_BAYES_OD = 0, BOD_METHOD_BLACK_BOX = 1)", method);
+    if (h->cfg.training) return h->fail(BOD_ERR_INVALID_ARG, "bod_set_uncertainty_method: a training handle has no detection stages");
+    if (method == BOD_METHOD_BLACK_BOX) {
+        if (h->cfg.mc_statistics)
+            return h->fail(BOD_ERR_INVALID_ARG, "bod_set_uncertainty_method: a statistics handle (bod_config.mc_statistics = 1) holds merged per-anchor "
+                           "statistics, not the samples' own head outputs that black-box MC dropout post-processes one by one");
+        if (h->cfg.covariance_parts != 0)
+            return h->fail(BOD_ERR_INVALID_ARG, "bod_set_uncertainty_method: the handle was created with bod_config.covariance_parts = %d; the covariance and "
+                           "class-entropy parts are defined for BOD_METHOD_BAYES_OD only", h->cfg.covariance_parts);
+        if (h->merge_method != BOD_MERGE_BAYES)
+            return h->fail(BOD_ERR_INVALID_ARG, "bod_set_uncertainty_method: the handle's merge method is %d; black-box MC dropout merges by its own rule: "
+                           "set BOD_MERGE_BAYES first", h->merge_method);
+        const bod_blackbox_options o = options ? *options : bod_blackbox_options{0.f, 1, 0.f, 0};
+        if (o.min_members < 1) return h->fail(BOD_ERR_INVALID_ARG, "bod_set_uncertainty_method: min_members %d must be >= 1", o.min_members);
+        if (!std::isfinite(o.min_score) || o.min_score < 0.f || !std::isfinite(o.affinity_threshold) || o.affinity_threshold < 0.f)
+            return h->fail(BOD_ERR_INVALID_ARG, "bod_set_uncertainty_method: min_score %g and affinity_threshold %g must be finite and >= 0",
+                           (double)o.min_score, (double)o.affinity_threshold);
+        if (o.reserved != 0) return h->fail(BOD_ERR_INVALID_ARG, "bod_set_uncertainty_method: reserved must be 0");
+        BODCHK(join_overlap(h));
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        BODCHK(alloc_blackbox(h));
+        h->bb_opt = o;
+    }
+    h->uncertainty_method = method;
+    return BOD_OK;
+}
+
+bod_status bod_get_uncertainty_method(bod_handle h, int32_t* method) {
+    if (!h || !method) return BOD_ERR_INVALID_ARG;
+    *method = h->uncertainty_method;
+    return BOD_OK;
+}
+
+bod_status bod_blackbox_samples(bod_handle h) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(join_overlap(h));
+    if (!h->bb.keep) return h->fail(BOD_ERR_NOT_READY, "bod_blackbox_samples: bod_set_uncertainty_method(BOD_METHOD_BLACK_BOX) has not been called");
+    if (!h->stage.forward) return h->fail(BOD_ERR_NOT_READY, "bod_forward / bod_set_raw has not run");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return run_blackbox_samples(h);
+}
+
+bod_status bod_blackbox_merge(bod_handle h) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(join_overlap(h));
+    if (!h->bb.keep) return h->fail(BOD_ERR_NOT_READY, "bod_blackbox_merge: bod_set_uncertainty_method(BOD_METHOD_BLACK_BOX) has not been called");
+    if (!h->bb_samples_ok) return h->fail(BOD_ERR_NOT_READY, "bod_blackbox_samples / bod_set_sample_detections has not run");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    BODCHK(wait_pending_slots(h, h->stream));
+    return run_blackbox_merge(h, h->stream);
+}
+
+static bod_status sample_index_ok(bod_handle h, const char* who, int32_t img, int32_t sample) {
+    if (!h->bb.keep) return h->fail(BOD_ERR_NOT_READY, "%s: bod_set_uncertainty_method(BOD_METHOD_BLACK_BOX) has not been called", who);
+    if (img < 0 || img >= h->cfg.batch || sample < 0 || sample >= h->cfg.mc_samples)
+        return h->fail(BOD_ERR_INVALID_ARG, "%s: image %d / sample %d out of range", who, img, sample);
+    return BOD_OK;
+}
+
+bod_status bod_get_sample_detections(bod_handle h, int32_t img, int32_t sample, int32_t* count, int32_t* anchor_index, float* scores,
+                                     float* means, float* covs) {
+    if (!h || !count) return BOD_ERR_INVALID_ARG;
+    BODCHK(join_overlap(h));
+    BODCHK(sample_index_ok(h, "bod_get_sample_detections", img, sample));
+    if (!h->bb_samples_ok) return h->fail(BOD_ERR_NOT_READY, "bod_blackbox_samples / bod_set_sample_detections has not run");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t v = (size_t)img * h->cfg.mc_samples + sample, K = (size_t)h->cfg.nms_max_output_size, C = h->cfg.num_classes;
+    HIPCHK(h, hipMemcpyAsync(count, h->bb.sd_count + v, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t k = (size_t)std::min<int64_t>(std::max<int64_t>(*count, 0), (int64_t)K);
+    BODCHK(d2h(h, anchor_index, h->bb.sd_anchor + v * K, k));
+    BODCHK(d2h(h, scores, h->bb.sd_score + v * K * C, k * C));
+    BODCHK(d2h(h, means, h->bb.sd_mean + v * K * 4, k * 4));
+    BODCHK(d2h(h, covs, h->bb.sd_cov + v * K * 16, k * 16));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BOD_OK;
+}
+
+bod_status bod_set_sample_detections(bod_handle h, int32_t img, int32_t sample, int32_t count, const int32_t* anchor_index,
+                                     const float* scores, const float* means, const float* covs) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(join_overlap(h));
+    BODCHK(sample_index_ok(h, "bod_set_sample_detections", img, sample));
+    if (count < 0 || count > h->cfg.nms_max_output_size)
+        return h->fail(BOD_ERR_INVALID_ARG, "bod_set_sample_detections: count %d outside 0..nms_max_output_size = %d", count, h->cfg.nms_max_output_size);
+    if (count > 0 && (!scores || !means || !covs)) return h->fail(BOD_ERR_INVALID_ARG, "bod_set_sample_detections: scores, means and covs are needed");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    BODCHK(wait_pending_slots(h, h->stream));
+    const size_t v = (size_t)img * h->cfg.mc_samples + sample, K = (size_t)h->cfg.nms_max_output_size, C = h->cfg.num_classes, k = (size_t)count;
+    if (k) {
+        if (anchor_index) HIPCHK(h, hipMemcpyAsync(h->bb.sd_anchor + v * K, anchor_index, k * 4, hipMemcpyHostToDevice, h->stream));
+        else HIPCHK(h, hipMemsetAsync(h->bb.sd_anchor + v * K, 0, k * 4, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->bb.sd_score + v * K * C, scores, k * C * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->bb.sd_mean + v * K * 4, means, k * 16, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->bb.sd_cov + v * K * 16, covs, k * 64, hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(h->bb.sd_count + v, &count, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->bb_samples_ok = true;
+    return BOD_OK;
+}
+
 bod_status bod_device_raw(bod_handle h, void** p, int32_t mark_ready) {
     if (!h || !p) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (mark_ready) BODCHK(ensure_raw(h)); else BODCHK(materialise_raw(h));
     p[0] = h->raw[0]; p[1] = h->raw[1]; p[2] = h->cfg.has_covar_head ? h->raw[2] : nullptr;
-    if (mark_ready) { h->kscale_now = nullptr; h->stage.forward_ran(); h->raw_valid = true; h->agg_valid = false; }
+    if (mark_ready) { h->kscale_now = nullptr; h->stage.forward_ran(); h->raw_valid = true; h->agg_valid = false; h->bb_samples_ok = false; }
     return BOD_OK;
 }
 
@@ -2844,11 +3045,17 @@ bod_status bod_infer(bod_handle h, const float* images, int32_t on_device, uint6
     if (!h) return BOD_ERR_INVALID_ARG;
     BODCHK(join_overlap(h));
     if (!h->weights_ready) return h->fail(BOD_ERR_NOT_READY, "weights not finalized");
-    if (h->cfg.mc_samples < 2) return h->fail(BOD_ERR_INVALID_ARG, "bayes_od needs mc_samples >= 2 (sample covariance divides by N-1)");
+    const bool black_box = h->uncertainty_method == BOD_METHOD_BLACK_BOX;
+    if (!black_box && h->cfg.mc_samples < 2) return h->fail(BOD_ERR_INVALID_ARG, "bayes_od needs mc_samples >= 2 (sample covariance divides by N-1)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const float* dev = nullptr;
     BODCHK(stage_images(h, images, on_device, &dev));
     h->cur_images = dev;
+    if (black_box) {                                  // per-sample head outputs, per-sample NMS, then the pooled detections merged
+        BODCHK(run_forward(h, dev, seed, first_image_id, FLAVOUR_RAW));
+        BODCHK(run_blackbox_samples(h));
+        return run_blackbox_merge(h, h->stream);
+    }
     BODCHK(run_forward(h, dev, seed, first_image_id, infer_flavour(h)));
     BODCHK(run_posterior(h, seed, first_image_id));
     BODCHK(run_nms(h, h->stream));
@@ -2859,7 +3066,8 @@ bod_status bod_infer_async(bod_handle h, const float* images, int32_t on_device,
     MarkerRange mr_api("bod:infer_async");
     if (!h || !slot_out) return BOD_ERR_INVALID_ARG;
     if (!h->weights_ready) return h->fail(BOD_ERR_NOT_READY, "weights not finalized");
-    if (h->cfg.mc_samples < 2) return h->fail(BOD_ERR_INVALID_ARG, "bayes_od needs mc_samples >= 2 (sample covariance divides by N-1)");
+    const bool black_box = h->uncertainty_method == BOD_METHOD_BLACK_BOX;
+    if (!black_box && h->cfg.mc_samples < 2) return h->fail(BOD_ERR_INVALID_ARG, "bayes_od needs mc_samples >= 2 (sample covariance divides by N-1)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int sidx = h->slot ^ 1;
     RecordSlot& r = h->rec[sidx];
@@ -2878,8 +3086,9 @@ bod_status bod_infer_async(bod_handle h, const float* images, int32_t on_device,
     const float* dev = nullptr;
     BODCHK(stage_images(h, images, on_device, &dev, ov ? h->front : h->stream));
     h->cur_images = dev;
-    BODCHK(run_forward(h, dev, seed, first_image_id, infer_flavour(h), false, ov));
-    BODCHK(run_posterior(h, seed, first_image_id));           // waits for the side stream's previous readers
+    BODCHK(run_forward(h, dev, seed, first_image_id, black_box ? FLAVOUR_RAW : infer_flavour(h), false, ov));
+    if (black_box) BODCHK(run_blackbox_samples(h));
+    else BODCHK(run_posterior(h, seed, first_image_id));      // waits for the side stream's previous readers
     HIPCHK(h, hipEventRecord(h->ev_posterior, h->stream));
     h->slot = sidx;
     // Round 5: soft-NMS + cluster-and-fuse (and the copies of the records) run on the MAIN stream, behind the posterior, not on the side
@@ -2895,8 +3104,12 @@ bod_status bod_infer_async(bod_handle h, const float* images, int32_t on_device,
     static const bool side_on = [] { const char* e = getenv("BOD_SIDE_STREAM"); return e && atoi(e) != 0; }();
     hipStream_t sd = side_on ? h->side : h->stream;
     if (side_on) HIPCHK(h, hipStreamWaitEvent(h->side, h->ev_posterior, 0));
-    BODCHK(run_nms(h, sd));
-    BODCHK(run_cluster(h, sd));
+    if (black_box) {
+        BODCHK(run_blackbox_merge(h, sd));
+    } else {
+        BODCHK(run_nms(h, sd));
+        BODCHK(run_cluster(h, sd));
+    }
     // The records follow the kernels on the side stream into pinned host memory, so bod_collect only waits for
     // this slot's event: it must never queue work behind the NEXT batch's side-stream kernels (that would
     // stall the host until the next batch has finished and drain the pipeline).

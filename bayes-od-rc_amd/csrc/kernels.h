@@ -310,6 +310,42 @@ hipError_t launch_cluster_fuse(const ClusterArgs& a, hipStream_t s);
 // and the terms: within / between [B,max_out,16], members [B,max_out].
 struct MergeTerms { float* within; float* between; int32_t* members; };
 hipError_t launch_cluster_merge(const ClusterArgs& a, int method, MergeTerms out, hipStream_t s);
+// Black-box MC dropout (bayesod.h, bod_set_uncertainty_method): every (image b, sample n) is a virtual image
+// v = b * N + n of the validation post-process and of nms_kernel, then the image's N detection sets are pooled and merged.
+//   launch_blackbox_samples  bb_flag_kernel / post_scan_kernel / bb_compact_kernel over the B*N virtual images (every scratch array
+//                            below has B*N images' worth), launch_nms on them, then bb_gather_kernel: the softmax row, the decoded
+//                            box and the sample's own aleatoric matrix of the at most max_out selected rows, KITTI-rescaled, the
+//                            rows below min_score dropped in order
+//   launch_blackbox_merge    bb_merge_kernel, one workgroup per image: greedy centre pick (block arg-max), members by iou_plus1 against
+//                            the centre, sample mean / within / between of the members; pooled index = n * max_out + rank
+struct BlackBoxArgs {
+    int32_t B, N, A, C, max_out;
+    float min_score; int32_t min_members; float thr;
+    // stage 1 scratch, per virtual image
+    uint8_t* keep;            // [B*N,A]
+    float* top;               // [B*N,A]   top softmax score per anchor (dense)
+    int32_t* block_counts;    // [B*N,nblocks]
+    int32_t* num_kept;        // [B*N]
+    float* ranking;           // [B*N,A]   compacted
+    float* corners;           // [B*N,A,4] compacted, network coordinates
+    int32_t* anchor_index;    // [B*N,A]   compacted
+    float* work_scores; int32_t* work_begin;      // nms_kernel's fallback, [B*N, A rounded up to 512]
+    int32_t* selected; int32_t* num_selected;     // [B*N,max_out], [B*N]
+    // sample detections
+    float* sd_score;          // [B*N,max_out,C]
+    float* sd_mean;           // [B*N,max_out,4]
+    float* sd_cov;            // [B*N,max_out,16]
+    int32_t* sd_anchor;       // [B*N,max_out]
+    int32_t* sd_count;        // [B*N]
+    // stage 2 work buffers for a pool beyond the LDS capacity
+    float* pool_top;          // [B,N*max_out]
+    float* pool_corners;      // [B,N*max_out,4]
+    // outputs [B,max_out,...] (a record slot and its merge terms); out_centre: pooled index of every emitted cluster's centre
+    int32_t* out_num; int32_t* out_centre;
+    float* out_scores; float* out_means; float* out_covs; float* out_counts;
+};
+hipError_t launch_blackbox_samples(const PostCfg& c, const PostBuffers& in, const BlackBoxArgs& a, const NmsArgs& nms, hipStream_t s);
+hipError_t launch_blackbox_merge(const BlackBoxArgs& a, MergeTerms terms, hipStream_t s);
 hipError_t launch_iou_matrix(const float* corners, int M, float* out, hipStream_t s);
 // Covariance parts (bod_config.covariance_parts): every covariance the two fusion steps store, split into what the fused
 // mean inherits from the epistemic noise, from the aleatoric noise and from the prior -- three symmetric 4x4 terms that sum to it.

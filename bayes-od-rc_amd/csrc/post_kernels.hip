@@ -12,6 +12,8 @@
 //   K5 cluster_fuse_kernel  bayes_od_clustering, one workgroup per (image, centre)   (:285-364)
 //      cluster_merge_kernel in its place under bod_set_merge_method: the NMS pick / the Gaussian mixture (no reference counterpart)
 //   K6 iou_matrix_kernel    box_utils.bbox_iou_vuvu (only for API compatibility)     (:214-215)
+//   black-box MC dropout (bod_set_uncertainty_method, no reference counterpart in this release): bb_flag_kernel / bb_compact_kernel /
+//      bb_gather_kernel beside the validation kernels -- K4 per (image, sample) -- and bb_merge_kernel behind cluster_merge_kernel
 #include "kernels.h"
 #include "philox.h"
 #include "record_state.h"
@@ -1076,6 +1078,168 @@ hipError_t launch_validation_gather(const ValGatherArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Black-box MC dropout, stage 1 (bayesod.h, bod_set_uncertainty_method): the validation post-process above for every
+// (image, sample) instead of sample 0.  The callers pass PostCfg with B = batch * mc_samples and N = 1, so blockIdx.y is the virtual
+// image v = b * N + n and the raw tensors [B,N,A,.] are indexed by v as they stand.  Same expressions as val_flag_kernel /
+// val_fuse_kernel (the candidates, their order, ranking and corners are theirs bit for bit), but nothing of width C or 16 is stored
+// per candidate: the dense scratch is the keep flag and the top score, the compacted rows are ranking, corners and the anchor index.
+// bb_gather_kernel recomputes the softmax row and forms the aleatoric matrix for the rows nms_kernel selected.
+// ------------------------------------------------------------------------------------------------
+template <int C>
+__global__ __launch_bounds__(POST_BLOCK) void bb_flag_kernel(PostCfg c, PostBuffers pb, BlackBoxArgs bb, int nblocks) {
+    const int a = blockIdx.x * POST_BLOCK + threadIdx.x;
+    const int v = blockIdx.y;
+    bool keep = false;
+    if (a < c.A) {
+        const float* l = pb.cls + ((size_t)v * c.A + a) * C;
+        float e[C];
+#pragma unroll
+        for (int j = 0; j < C; ++j) e[j] = l[j];
+        float mx = e[0];
+#pragma unroll
+        for (int j = 1; j < C; ++j) mx = fmaxf(mx, e[j]);
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < C; ++j) { e[j] = expf(e[j] - mx); s += e[j]; }
+        int best = 0; float bestp = e[0] / s;
+#pragma unroll
+        for (int j = 1; j < C; ++j) {
+            const float pj = e[j] / s;
+            if (pj > bestp) { bestp = pj; best = j; }                          // tf.argmax: first maximum
+        }
+        keep = best != C - 1;
+        bb.keep[(size_t)v * c.A + a] = keep ? 1 : 0;
+        bb.top[(size_t)v * c.A + a] = bestp;
+    }
+    const int n = __syncthreads_count(keep ? 1 : 0);
+    if (threadIdx.x == 0) bb.block_counts[(size_t)v * nblocks + blockIdx.x] = n;
+}
+
+__global__ __launch_bounds__(POST_BLOCK) void bb_compact_kernel(PostCfg c, PostBuffers pb, BlackBoxArgs bb, int nblocks) {
+    __shared__ int wave_off[POST_BLOCK / 64 + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int a = blockIdx.x * POST_BLOCK + tid;
+    const int v = blockIdx.y;
+    const bool keep = (a < c.A) && bb.keep[(size_t)v * c.A + a];
+    const unsigned long long bal = __ballot(keep);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_off[wave + 1] = __popcll(bal);
+    if (tid == 0) wave_off[0] = 0;
+    __syncthreads();
+    if (tid == 0)
+        for (int w = 1; w <= POST_BLOCK / 64; ++w) wave_off[w] += wave_off[w - 1];
+    __syncthreads();
+    if (!keep) return;
+    const int slot = bb.block_counts[(size_t)v * nblocks + blockIdx.x] + wave_off[wave] + before;
+    const size_t o = (size_t)v * c.A + slot;
+    const float4 anc = reinterpret_cast<const float4*>(pb.anchors)[a];
+    const float4 t = reinterpret_cast<const float4*>(pb.box)[(size_t)v * c.A + a];
+    float bx[4];
+    decode_box(anc, t, bx);
+    bb.ranking[o] = bb.top[(size_t)v * c.A + a];
+    reinterpret_cast<float4*>(bb.corners)[o] = make_float4(bx[0] - bx[2] / 2.0f, bx[1] - bx[3] / 2.0f, bx[0] + bx[2] / 2.0f, bx[1] + bx[3] / 2.0f);
+    bb.anchor_index[o] = a;
+}
+
+// One wave per virtual image walks its selected rows 64 at a time: softmax row, decoded box, the sample's own aleatoric matrix
+// (post_fuse_anchor's arithmetic on one sample's parameters), KITTI rescale, then the ordered compaction of the rows whose top score
+// is not below min_score.  c.B / c.N are the real batch and sample counts here.
+template <int C>
+__global__ __launch_bounds__(64) void bb_gather_kernel(PostCfg c, PostBuffers pb, BlackBoxArgs bb) {
+    const int v = blockIdx.x, lane = threadIdx.x;
+    const int b = v / c.N;
+    const int K = bb.max_out;
+    const int nsel = min(max(bb.num_selected[v], 0), K);
+    const int M = min(max(bb.num_kept[v], 0), c.A);
+    int nout = 0;
+    for (int k0 = 0; k0 < nsel; k0 += 64) {
+        const int k = k0 + lane;
+        const int slot = k < nsel ? bb.selected[(size_t)v * K + k] : -1;
+        const bool valid = slot >= 0 && slot < M;
+        const int a = valid ? bb.anchor_index[(size_t)v * c.A + slot] : 0;
+        float p[C];
+        const float* l = pb.cls + ((size_t)v * c.A + a) * C;
+#pragma unroll
+        for (int j = 0; j < C; ++j) p[j] = l[j];
+        float mx = p[0];
+#pragma unroll
+        for (int j = 1; j < C; ++j) mx = fmaxf(mx, p[j]);
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < C; ++j) { p[j] = expf(p[j] - mx); s += p[j]; }
+        float top = 0.f;
+#pragma unroll
+        for (int j = 0; j < C; ++j) { p[j] = p[j] / s; top = j == 0 ? p[0] : fmaxf(top, p[j]); }
+        const float4 anc = reinterpret_cast<const float4*>(pb.anchors)[a];
+        const float4 t = reinterpret_cast<const float4*>(pb.box)[(size_t)v * c.A + a];
+        float bx[4];
+        decode_box(anc, t, bx);
+        Mat4 al;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) al.m[i][j] = 0.f;
+        if (c.has_covar) {
+            float x[10];
+            const float* q = pb.cov + ((size_t)v * c.A + a) * 10;
+#pragma unroll
+            for (int i = 0; i < 10; ++i) x[i] = q[i];
+            // tfp.math.fill_triangular, as in post_fuse_anchor
+            const float d[4] = {expf(x[4]), expf(x[9]), expf(x[5]), expf(x[0])};
+            if (c.use_full_covar) {
+                const float l10 = x[8], l20 = x[7], l21 = x[6], l30 = x[3], l31 = x[2], l32 = x[1];
+                float li[4][4];
+                li[0][0] = 1.f; li[0][1] = 0.f; li[0][2] = 0.f; li[0][3] = 0.f;
+                li[1][0] = -l10; li[1][1] = 1.f; li[1][2] = 0.f; li[1][3] = 0.f;
+                li[2][0] = -(l20 * 1.f + l21 * li[1][0]); li[2][1] = -l21; li[2][2] = 1.f; li[2][3] = 0.f;
+                li[3][0] = -(l30 * 1.f + l31 * li[1][0] + l32 * li[2][0]);
+                li[3][1] = -(l31 * 1.f + l32 * li[2][1]);
+                li[3][2] = -l32; li[3][3] = 1.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j <= i; ++j) {
+                        float sm = 0.f;
+#pragma unroll
+                        for (int kk = 0; kk <= j; ++kk) sm += li[i][kk] * d[kk] * li[j][kk];
+                        al.m[i][j] = sm; al.m[j][i] = sm;
+                    }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) al.m[i][i] = d[i];
+            }
+        }
+        if (c.kitti_sh > 0.f) {                                       // S mu, S Sigma S^T, as bod_posterior does
+            float ksh = c.kitti_sh, ksw = c.kitti_sw;
+            if (c.kitti_frame) { ksh = c.kitti_frame[2 * b]; ksw = c.kitti_frame[2 * b + 1]; }
+            const float sc[4] = {ksh, ksw, ksh, ksw};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                bx[i] *= sc[i];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) al.m[i][j] = sc[i] * al.m[i][j] * sc[j];
+            }
+        }
+        const bool pass = valid && !(top < bb.min_score);
+        const unsigned long long bal = __ballot(pass);
+        if (pass) {
+            const size_t o = (size_t)v * K + nout + __popcll(bal & ((1ull << lane) - 1ull));
+#pragma unroll
+            for (int j = 0; j < C; ++j) bb.sd_score[o * C + j] = p[j];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                bb.sd_mean[o * 4 + i] = bx[i];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) bb.sd_cov[o * 16 + i * 4 + j] = al.m[i][j];
+            }
+            bb.sd_anchor[o] = a;
+        }
+        nout += __popcll(bal);
+    }
+    if (lane == 0) bb.sd_count[v] = nout;
+}
+
+// ------------------------------------------------------------------------------------------------
 // joint-entropy ranking (:169-200): min-max normalised information gains, one block per image
 // ------------------------------------------------------------------------------------------------
 // log det of an SPD 4x4 (a posterior covariance) through its Cholesky factor, in double: the cofactor expansion in fp32 loses
@@ -1810,6 +1974,185 @@ hipError_t launch_cluster_merge(const ClusterArgs& a, int method, MergeTerms out
     if (a.C == 8) hipLaunchKernelGGL(cluster_merge_kernel<8>, grid, dim3(CL_BLOCK), 0, s, a, method, out);
     else if (a.C == 4) hipLaunchKernelGGL(cluster_merge_kernel<4>, grid, dim3(CL_BLOCK), 0, s, a, method, out);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// Black-box MC dropout, stage 2 (bayesod.h): one workgroup per image merges its pool of N * max_out sample detections.
+// Pool entry i = n * max_out + rank; an entry past its sample's count, and an assigned one, has top score -inf.  Top scores and corners
+// live in LDS up to BB_POOL_LDS_CAP entries, in the global work buffers beyond.  A thread only ever touches the entries i = tid (mod
+// BB_BLOCK), in the arg-max and in the member pass alike, so the pool needs no barrier; the two LDS exchanges per centre do.
+// Centre: block arg-max of (score desc, index asc) -- the lane's strided scan, nms_kernel's wave arg-max, the four waves' results
+// compared in wave order.  Members: the centre plus every unassigned i with iou_plus1(centre, i) > thr.  Sums as cluster_merge_kernel
+// forms them (d_i = mu_i - mu_c; per-thread chain, wave butterflies, (w0 + w1) + (w2 + w3)); thread 0 writes the row.
+#define BB_BLOCK 256
+#define BB_POOL_LDS_CAP 6144
+template <int C>
+__global__ __launch_bounds__(BB_BLOCK) void bb_merge_kernel(BlackBoxArgs a, MergeTerms terms) {
+    constexpr int Q = 31 + C;                         // sum cov_i [16], sum d_i d_i^T [10], sum d_i [4], sum score_i [C], members
+    extern __shared__ __attribute__((aligned(16))) char bb_smem[];
+    __shared__ float red[4 * Q];
+    __shared__ float s_ws[4];
+    __shared__ int s_wi[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int K = a.max_out, P = a.N * K;
+    const bool lds = P <= BB_POOL_LDS_CAP;
+    float4* box = lds ? reinterpret_cast<float4*>(bb_smem) : reinterpret_cast<float4*>(a.pool_corners) + (size_t)b * P;
+    float* score = lds ? reinterpret_cast<float*>(bb_smem + (size_t)BB_POOL_LDS_CAP * 16) : a.pool_top + (size_t)b * P;
+    const size_t sd0 = (size_t)b * P;                 // the image's first sample-detection row: v * K + rank = b * P + i
+    const float NEG_INF = -INFINITY;
+    for (int i = tid; i < P; i += BB_BLOCK) {
+        const int n = i / K, rank = i - n * K;
+        const bool valid = rank < min(max(a.sd_count[b * a.N + n], 0), K);
+        float top = NEG_INF;
+        if (valid) {
+            const float* sr = a.sd_score + (sd0 + i) * C;
+            top = sr[0];
+#pragma unroll
+            for (int j = 1; j < C; ++j) top = fmaxf(top, sr[j]);
+            const float4 m = reinterpret_cast<const float4*>(a.sd_mean)[sd0 + i];
+            // box_utils.vuhw_to_vuvu
+            box[i] = make_float4(m.x - m.z / 2.0f, m.y - m.w / 2.0f, m.x + m.z / 2.0f, m.y + m.w / 2.0f);
+        }
+        score[i] = top;
+    }
+    __syncthreads();                                  // every thread reads the centre's box
+    int nout = 0;
+    while (nout < K) {
+        float bs = NEG_INF; int bi = -1;
+        for (int i = tid; i < P; i += BB_BLOCK) {
+            const float v = score[i];
+            if (v > bs) { bs = v; bi = i; }           // ascending i: the lowest index wins a tie
+        }
+        nms_wave_argmax(bs, bi);
+        if (lane == 0) { s_ws[wave] = bs; s_wi[wave] = bi; }
+        __syncthreads();
+        bs = s_ws[0]; bi = s_wi[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (nms_better(s_ws[w], s_wi[w], bs, bi)) { bs = s_ws[w]; bi = s_wi[w]; }
+        if (bi < 0) break;                            // (block-uniform) the pool is empty
+        const int centre = bi;
+        const float4 cbox = box[centre];
+        const float4 mcv = reinterpret_cast<const float4*>(a.sd_mean)[sd0 + centre];
+        const float mc[4] = {mcv.x, mcv.y, mcv.z, mcv.w};
+        float acc[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) acc[q] = 0.f;
+        for (int i = tid; i < P; i += BB_BLOCK) {
+            if (!(score[i] > NEG_INF)) continue;
+            if (i != centre && !(iou_plus1(cbox, box[i]) > a.thr)) continue;
+            score[i] = NEG_INF;
+            acc[Q - 1] += 1.f;
+            const float4 mv = reinterpret_cast<const float4*>(a.sd_mean)[sd0 + i];
+            const float d[4] = {mv.x - mc[0], mv.y - mc[1], mv.z - mc[2], mv.w - mc[3]};
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[q] += a.sd_cov[(sd0 + i) * 16 + q];
+            int t = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int q = 0; q <= r; ++q) { acc[16 + t] += d[r] * d[q]; ++t; }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[26 + r] += d[r];
+#pragma unroll
+            for (int j = 0; j < C; ++j) acc[30 + j] += a.sd_score[(sd0 + i) * C + j];
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            float v = acc[q];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (lane == 0) red[wave * Q + q] = v;
+        }
+        __syncthreads();
+        const float fn = (red[Q - 1] + red[2 * Q - 1]) + (red[3 * Q - 1] + red[4 * Q - 1]);      // (block-uniform, exact: at most 15 360)
+        if ((int)fn >= a.min_members) {
+            if (tid == 0) {
+                const size_t ob = (size_t)b * K + nout;
+#pragma unroll
+                for (int q = 0; q < Q - 1; ++q) acc[q] = (red[q] + red[Q + q]) + (red[2 * Q + q] + red[3 * Q + q]);
+                float dbar[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { dbar[r] = acc[26 + r] / fn; a.out_means[ob * 4 + r] = mc[r] + dbar[r]; }
+                const bool single = !(fn > 1.f);
+                float bt[16];
+                int t = 0;
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int q = 0; q <= r; ++q) {
+                        const float v = single ? 0.f : (acc[16 + t] - fn * (dbar[r] * dbar[q])) / (fn - 1.0f);
+                        bt[r * 4 + q] = v; bt[q * 4 + r] = v;
+                        ++t;
+                    }
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const float w = acc[q] / fn;
+                    terms.within[ob * 16 + q] = w;
+                    terms.between[ob * 16 + q] = bt[q];
+                    a.out_covs[ob * 16 + q] = w + bt[q];
+                }
+#pragma unroll
+                for (int j = 0; j < C; ++j) { a.out_counts[ob * C + j] = acc[30 + j]; a.out_scores[ob * C + j] = acc[30 + j] / fn; }
+                terms.members[ob] = (int)fn;
+                a.out_centre[ob] = centre;
+            }
+            ++nout;
+        }
+        __syncthreads();                              // red / s_ws are rewritten by the next centre
+    }
+    if (tid == 0) a.out_num[b] = nout;
+}
+
+hipError_t launch_blackbox_samples(const PostCfg& c, const PostBuffers& in, const BlackBoxArgs& a, const NmsArgs& nms, hipStream_t s) {
+    const long long V = (long long)a.B * a.N;
+    if (V < 1 || V > 65535 || a.A < 1 || a.max_out < 1 || a.max_out > NMS_MAX_OUT) return hipErrorInvalidValue;
+    PostCfg cv = c;                                   // the virtual images: B * N images of one sample each
+    cv.B = (int32_t)V; cv.N = 1;
+    PostBuffers scan{};
+    scan.block_counts = a.block_counts; scan.num_kept = a.num_kept;
+    const int nblocks = (a.A + POST_BLOCK - 1) / POST_BLOCK;
+    dim3 grid(nblocks, (unsigned)V);
+    if (a.C == 8) hipLaunchKernelGGL(bb_flag_kernel<8>, grid, dim3(POST_BLOCK), 0, s, cv, in, a, nblocks);
+    else if (a.C == 4) hipLaunchKernelGGL(bb_flag_kernel<4>, grid, dim3(POST_BLOCK), 0, s, cv, in, a, nblocks);
+    else return hipErrorInvalidValue;
+    hipLaunchKernelGGL(post_scan_kernel, dim3((unsigned)V), dim3(POST_BLOCK), 0, s, scan, nblocks);
+    hipLaunchKernelGGL(bb_compact_kernel, grid, dim3(POST_BLOCK), 0, s, cv, in, a, nblocks);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = launch_nms(nms, s);
+    if (e != hipSuccess) return e;
+    if (a.C == 8) hipLaunchKernelGGL(bb_gather_kernel<8>, dim3((unsigned)V), dim3(64), 0, s, c, in, a);
+    else hipLaunchKernelGGL(bb_gather_kernel<4>, dim3((unsigned)V), dim3(64), 0, s, c, in, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_blackbox_merge(const BlackBoxArgs& a, MergeTerms terms, hipStream_t s) {
+    if (a.B < 1 || a.N < 1 || a.max_out < 1 || a.max_out > NMS_MAX_OUT || !terms.within || !terms.between || !terms.members) return hipErrorInvalidValue;
+    const bool lds_pool = (long long)a.N * a.max_out <= BB_POOL_LDS_CAP;
+    if (!lds_pool && (!a.pool_top || !a.pool_corners)) return hipErrorInvalidValue;
+    constexpr int LDS = BB_POOL_LDS_CAP * 20;
+    const size_t dyn = lds_pool ? LDS : 0;
+    static PerDeviceOnce once8, once4;
+    if (a.C == 8) {
+        bool& attr_set = *once8.slot();
+        if (!attr_set) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bb_merge_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+            if (e != hipSuccess) return e;
+            attr_set = true;
+        }
+        hipLaunchKernelGGL(bb_merge_kernel<8>, dim3(a.B), dim3(BB_BLOCK), dyn, s, a, terms);
+    } else if (a.C == 4) {
+        bool& attr_set = *once4.slot();
+        if (!attr_set) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bb_merge_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+            if (e != hipSuccess) return e;
+            attr_set = true;
+        }
+        hipLaunchKernelGGL(bb_merge_kernel<4>, dim3(a.B), dim3(BB_BLOCK), dyn, s, a, terms);
+    } else {
+        return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

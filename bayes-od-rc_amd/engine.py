@@ -718,6 +718,59 @@ class Engine(object):
         shapes = [(self.B, self.K, 16), (self.B, self.K, 16), (self.B, self.K)]
         return {n: (int(p or 0), s) for n, p, s in zip(("within", "between", "members"), ptrs, shapes)}
 
+    # -- black-box MC dropout: per-sample NMS, then the detections merged (include/bayesod.h) ----------
+    def set_uncertainty_method(self, method, min_score=0.0, min_members=1, affinity_threshold=0.0):
+        """'bayes_od' (the default) or 'black_box': every MC sample through the validation post-process and the soft-NMS on its own,
+        the image's detection sets pooled, grouped by overlap and merged to their sample mean and covariance, for the next
+        infer / infer_async (``bod_set_uncertainty_method``).  The three options belong to 'black_box'."""
+        if method not in _lib.UNCERTAINTY_METHODS:
+            raise ValueError("uncertainty_method must be one of %s, got %r" % (sorted(_lib.UNCERTAINTY_METHODS), method))
+        opt = _lib.BodBlackBoxOptions(float(min_score), int(min_members), float(affinity_threshold), 0)
+        self._chk(self.lib.bod_set_uncertainty_method(self.h, _lib.UNCERTAINTY_METHODS[method], C.byref(opt)))
+
+    @property
+    def uncertainty_method(self):
+        m = C.c_int32(0)
+        self._chk(self.lib.bod_get_uncertainty_method(self.h, C.byref(m)))
+        return {v: k for k, v in _lib.UNCERTAINTY_METHODS.items()}[int(m.value)]
+
+    def blackbox_samples(self):
+        """Stage 1 on the last forward's (or ``set_raw``'s) head outputs (``bod_blackbox_samples``)."""
+        self._chk(self.lib.bod_blackbox_samples(self.h))
+
+    def blackbox_merge(self):
+        """Stage 2: the pooled sample detections merged into detections; ``get_detections`` / ``get_detection_merge_terms`` follow
+        (``bod_blackbox_merge``)."""
+        self._chk(self.lib.bod_blackbox_merge(self.h))
+
+    def get_sample_detections(self, image_index=0, sample_index=0):
+        """{'anchor_index' [k], 'scores' [k,C], 'means' [k,4], 'covs' [k,4,4]} of one (image, MC sample)
+        (``bod_get_sample_detections``)."""
+        k = self.K
+        idx = np.empty(k, np.int32)
+        scores = np.empty((k, self.Ccls), np.float32)
+        means = np.empty((k, 4), np.float32)
+        covs = np.empty((k, 4, 4), np.float32)
+        n = C.c_int32(0)
+        self._chk(self.lib.bod_get_sample_detections(self.h, image_index, sample_index, C.byref(n), iptr(idx), fptr(scores),
+                                                     fptr(means), fptr(covs)))
+        n = n.value
+        return {"anchor_index": idx[:n].copy(), "scores": scores[:n].copy(), "means": means[:n].copy(), "covs": covs[:n].copy()}
+
+    def set_sample_detections(self, image_index, sample_index, scores, means, covs, anchor_index=None):
+        """Replace the sample detections of one (image, MC sample); the others stay (``bod_set_sample_detections``)."""
+        scores = as_f32(scores).reshape(-1, self.Ccls)
+        means = as_f32(means).reshape(-1, 4)
+        covs = as_f32(covs).reshape(-1, 16)
+        k = scores.shape[0]
+        if means.shape[0] != k or covs.shape[0] != k:
+            raise ValueError("scores, means and covs must have the same number of rows")
+        idx = None if anchor_index is None else np.ascontiguousarray(anchor_index, dtype=np.int32)
+        if idx is not None and idx.shape != (k,):
+            raise ValueError("anchor_index must have one entry per row")
+        self._chk(self.lib.bod_set_sample_detections(self.h, image_index, sample_index, k, iptr(idx), fptr(scores), fptr(means),
+                                                     fptr(covs)))
+
     def get_detections(self, image_index=0):
         k = self.K
         scores = np.empty((k, self.Ccls), np.float32)

@@ -204,15 +204,43 @@ def _checked_merge_method(merge_method, covariance_parts=False, class_parts=Fals
     return merge_method
 
 
+BLACKBOX_OPTIONS = ('min_score', 'min_members', 'affinity_threshold')
+
+
+def _checked_uncertainty_method(uncertainty_method, blackbox_options, merge_method='bayes', covariance_parts=False, class_parts=False):
+    """('bayes_od' | 'black_box', options dict); ValueError for what the library refuses (``bod_set_uncertainty_method``)."""
+    from . import _lib
+    if uncertainty_method not in _lib.UNCERTAINTY_METHODS:
+        raise ValueError("uncertainty_method must be one of %s, got %r" % (sorted(_lib.UNCERTAINTY_METHODS), uncertainty_method))
+    opts = dict(blackbox_options or {})
+    unknown = sorted(set(opts) - set(BLACKBOX_OPTIONS))
+    if unknown:
+        raise ValueError("blackbox_options: unknown key(s) %s (known: %s)" % (unknown, list(BLACKBOX_OPTIONS)))
+    if uncertainty_method == 'black_box':
+        if covariance_parts or class_parts:
+            raise ValueError("uncertainty_method='black_box' does not go with covariance_parts / class_parts: the parts are defined "
+                             "for 'bayes_od' only")
+        if merge_method != 'bayes':
+            raise ValueError("uncertainty_method='black_box' does not go with merge_method=%r: black-box MC dropout merges the pooled "
+                             "sample detections by its own rule" % merge_method)
+    elif opts:
+        raise ValueError("blackbox_options belong to uncertainty_method='black_box'")
+    return uncertainty_method, opts
+
+
 class BayesOdPipeline(object):
     """Batched, fully device-resident form of the reference's per-image loop body
     (src/retina_net/experiments/run_inference.py:137-161): forward -> posterior -> soft-NMS ->
-    cluster-and-fuse for ``batch`` images per call, no host round trip in between."""
+    cluster-and-fuse for ``batch`` images per call, no host round trip in between.  ``uncertainty_method='black_box'`` (with
+    ``blackbox_options``: min_score, min_members, affinity_threshold) runs the baseline in its place: every MC sample through the
+    validation post-process and the soft-NMS on its own, then the pooled detections merged."""
 
     def __init__(self, model, image_hw, batch, bayes_od_config, nms_config, use_full_covar=True,
                  dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, covariance_parts=False, class_parts=False,
-                 merge_method='bayes'):
+                 merge_method='bayes', uncertainty_method='bayes_od', blackbox_options=None):
         self._merge = _checked_merge_method(merge_method, covariance_parts, class_parts)
+        self._method, self._bb = _checked_uncertainty_method(uncertainty_method, blackbox_options, merge_method, covariance_parts,
+                                                             class_parts)
         self._kw = dict(bayes_od_config=bayes_od_config, nms_config=nms_config, use_full_covar=use_full_covar,
                         dataset_name=dataset_name, nms_variant=nms_variant, orig_size=orig_size)
         if covariance_parts:
@@ -232,11 +260,16 @@ class BayesOdPipeline(object):
         if orig_size is not None:
             self._kw['orig_size'] = tuple(orig_size)
         self.engine = self.model.engine_for(self._hw, batch=self._batch, mc_samples=self.model.mc_dropout_samples, **self._kw)
-        self.engine.set_merge_method(self._merge)          # (the handle is shared: set on every bind, the default included)
+        if self._method == 'bayes_od':                     # (the handle is shared: both set on every bind, the defaults included)
+            self.engine.set_uncertainty_method('bayes_od')
+        self.engine.set_merge_method(self._merge)
+        if self._method != 'bayes_od':
+            self.engine.set_uncertainty_method(self._method, **self._bb)
         return self.engine
 
     def merge_terms(self):
-        """Per image (within [K,4,4], between [K,4,4], members [K]) of the last call's detections ('centre' / 'mixture' only)."""
+        """Per image (within [K,4,4], between [K,4,4], members [K]) of the last call's detections ('centre' / 'mixture' merges and
+        uncertainty_method 'black_box')."""
         return [self.engine.get_detection_merge_terms(b) for b in range(self.engine.B)]
 
     def upload_mixed(self, frames, means, aspect_resize=True, corruption=None):

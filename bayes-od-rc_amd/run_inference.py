@@ -26,9 +26,8 @@ from .model import RetinaNetModel
 def test_model(config, args):
     test_config = config['testing_config']
     want_class = _want_class_parts(config, args)          # decided once: the writer and every pipeline get the same answer
-    if test_config['uncertainty_method'] != 'bayes_od':
-        raise ValueError("only uncertainty_method 'bayes_od' is supported (as in the reference release)")
     merge = check_merge_options(config, args)             # likewise; refuses what does not go together before anything is built
+    method, bb_options = check_uncertainty_options(config, args)
     dataset_config = config['dataset_config']
     training_dataset = dataset_config['dataset']
     test_dataset = test_config['test_dataset']
@@ -61,11 +60,11 @@ def test_model(config, args):
             pipes[b] = _make_pipeline(model, args, hw, b, test_config['bayes_od_config'], nms_config,
                                       use_full_covar=test_config['use_full_covar'],
                                       dataset_name=test_dataset, orig_size=orig, anchors=anchors, class_parts=want_class,
-                                      merge_method=merge)
+                                      merge_method=merge, uncertainty_method=method, blackbox_options=bb_options)
         return pipes[b]
     predictions_dir = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'], 'predictions')
     writer = writers.PredictionWriter(predictions_dir, test_dataset, test_config['ckpt_idx'],
-                                      test_config['uncertainty_method'],
+                                      method,
                                       writer_fusion_name(test_config['bayes_od_config']['fusion_method'], merge),
                                       cov_parts=_want_parts(args), class_parts=want_class)
     categories = dataset_config[training_dataset]['training_data_config']['categories']
@@ -140,9 +139,56 @@ def check_merge_options(config, args):
     if merge != 'bayes' and _want_class_parts(config, args):
         raise ValueError("--merge_method %s does not go with --class_uncertainty: the class-entropy parts are defined for the "
                          "Bayesian fuse only" % merge)
-    if merge == 'bayes' and _want_merge_terms(args):
+    if merge == 'bayes' and _want_merge_terms(args) and resolve_uncertainty_method(config, getattr(args, 'uncertainty_method', None)) != 'black_box':
         raise ValueError("--merge_terms needs --merge_method centre or mixture: the Bayesian fuse has no merge terms")
     return merge
+
+
+UNCERTAINTY_METHODS = ('bayes_od', 'black_box')
+
+
+def resolve_uncertainty_method(config, flag=None):
+    """--uncertainty_method if given, else the yaml's testing_config.uncertainty_method, else 'bayes_od'.  ValueError for any other
+    name (the reference's other methods are not implemented)."""
+    name = flag
+    if name is None:
+        name = (config.get('testing_config') or {}).get('uncertainty_method')
+    if name is None:
+        name = 'bayes_od'
+    if name not in UNCERTAINTY_METHODS:
+        raise ValueError("uncertainty_method must be one of %s, got %r" % (list(UNCERTAINTY_METHODS), name))
+    return name
+
+
+def check_uncertainty_options(config, args):
+    """(method, black-box options); ValueError, with the reason, for what black-box MC dropout does not go with: the covariance and
+    class-entropy parts and a non-default merge method (defined for 'bayes_od' only), --ensemble and --tta_flip (they merge
+    per-anchor statistics, and the method needs every sample's own head outputs), and its options without it."""
+    method = resolve_uncertainty_method(config, getattr(args, 'uncertainty_method', None))
+    opts = {}
+    if getattr(args, 'bb_min_score', None) is not None:
+        opts['min_score'] = float(args.bb_min_score)
+    if getattr(args, 'bb_min_members', None) is not None:
+        opts['min_members'] = int(args.bb_min_members)
+    if method != 'black_box':
+        if opts:
+            raise ValueError("--bb_min_score / --bb_min_members belong to --uncertainty_method black_box")
+        return method, None
+    if _want_parts(args):
+        raise ValueError("--uncertainty_method black_box does not go with --covariance_parts: the covariance parts are defined for "
+                         "bayes_od only")
+    if _want_class_parts(config, args):
+        raise ValueError("--uncertainty_method black_box does not go with --class_uncertainty: the class-entropy parts are defined "
+                         "for bayes_od only")
+    if getattr(args, 'ensemble', None) or getattr(args, 'tta_flip', False):
+        raise ValueError("--uncertainty_method black_box does not go with --ensemble / --tta_flip: they merge per-anchor statistics, "
+                         "and black-box MC dropout post-processes every sample's own head outputs")
+    if resolve_merge_method(config, getattr(args, 'merge_method', None)) != 'bayes':
+        raise ValueError("--uncertainty_method black_box does not go with --merge_method %s: it merges the pooled sample detections "
+                         "by its own rule" % resolve_merge_method(config, getattr(args, 'merge_method', None)))
+    if opts.get('min_members', 1) < 1 or not (0.0 <= opts.get('min_score', 0.0) < float('inf')):
+        raise ValueError("--bb_min_members must be >= 1 and --bb_min_score finite and >= 0")
+    return method, opts
 
 
 def _want_merge_terms(args):
@@ -185,6 +231,11 @@ def _make_pipeline(model, args, hw, batch, bayes_od_config, nms_config, **kw):
         kw = dict(kw, class_parts=True)
     if isinstance(model, list) or tta:
         members = model if isinstance(model, list) else [model]
+        # statistics handles: bayes_od only (check_uncertainty_options has refused black_box with --ensemble / --tta_flip)
+        kw = dict(kw)
+        if kw.pop('uncertainty_method', 'bayes_od') != 'bayes_od':
+            raise ValueError("uncertainty_method 'black_box' does not go with --ensemble / --tta_flip")
+        kw.pop('blackbox_options', None)
         return inference_utils.EnsemblePipeline(members, hw, batch, bayes_od_config, nms_config, members[0].mc_dropout_samples,
                                                 passes=int(getattr(args, 'mc_passes', 1) or 1),
                                                 views=('identity', 'hflip') if tta else ('identity',), **kw)
@@ -198,13 +249,14 @@ def _test_model_on_dataset(config, args, model):
     test_config = config['testing_config']
     want_class = _want_class_parts(config, args)
     merge = check_merge_options(config, args)
+    method, bb_options = check_uncertainty_options(config, args)
     dataset_config = config['dataset_config']
     training_dataset, test_dataset = dataset_config['dataset'], test_config['test_dataset']
     handler = datasets.build_dataset(dict(dataset_config, dataset=test_dataset), 'test')
     kitti = test_dataset == 'kitti'
     predictions_dir = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'], 'predictions')
     writer = writers.PredictionWriter(predictions_dir, test_dataset, test_config['ckpt_idx'],
-                                      test_config['uncertainty_method'],
+                                      method,
                                       writer_fusion_name(test_config['bayes_od_config']['fusion_method'], merge),
                                       cov_parts=_want_parts(args), class_parts=want_class)
     categories = dataset_config[training_dataset]['training_data_config']['categories']
@@ -243,7 +295,8 @@ def _test_model_on_dataset(config, args, model):
             pipes[key] = _make_pipeline(
                 model, args, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
                 use_full_covar=test_config['use_full_covar'], dataset_name=test_dataset, orig_size=hw,
-                anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class, merge_method=merge)
+                anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class, merge_method=merge,
+                uncertainty_method=method, blackbox_options=bb_options)
         pipe = pipes[key]
         # (a frame's corruption is keyed on its dataset index: the same whatever batch or run it falls into)
         corruption = None if corrupt is None else (corrupt[0], [p[2] for p in pending], corrupt[1])
@@ -264,7 +317,8 @@ def _test_model_on_dataset(config, args, model):
             pipes[key] = _make_pipeline(
                 model, args, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
                 use_full_covar=test_config['use_full_covar'], dataset_name=test_dataset, orig_size=src_hw,
-                anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class, merge_method=merge)
+                anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class, merge_method=merge,
+                uncertainty_method=method, blackbox_options=bb_options)
         pipe = pipes[key]
         pipe.bind(orig_size=src_hw)      # the handle may be shared with a pipe of another source size: re-apply the KITTI scale
         pipe.engine.upload_frames_u8(frames, constants.MEANS_DICT[handler.im_normalization], aspect_resize=kitti)
@@ -349,8 +403,17 @@ def main(argv=None):
                     'NMS would; mixture is the equal-weight Gaussian mixture of the members.  The tree of a non-default method is '
                     'bayes_od_<fusion_method>-<merge_method>; yaml key: testing_config.bayes_od_config.merge_method (the flag wins); not '
                     'with --covariance_parts / --class_uncertainty')
-    ap.add_argument('--merge_terms', action='store_true', help='with --merge_method centre / mixture: also write merge_within/, '
-                    'merge_between/ ([K,4,4] each; cov = within + between) and merge_members/ ([K]) beside cov/')
+    ap.add_argument('--merge_terms', action='store_true', help='with --merge_method centre / mixture or --uncertainty_method black_box: '
+                    'also write merge_within/, merge_between/ ([K,4,4] each; cov = within + between) and merge_members/ ([K]) beside cov/')
+    ap.add_argument('--uncertainty_method', choices=UNCERTAINTY_METHODS, default=None, help='bayes_od (default), or black_box: every '
+                    'MC sample goes through the ordinary post-processing and NMS on its own, the detection sets are grouped by overlap and '
+                    'each group becomes one detection with the sample mean and covariance of its members.  The tree is '
+                    'black_box_<fusion_method>, beside the default one; yaml key: testing_config.uncertainty_method (the flag wins); not '
+                    'with --covariance_parts, --class_uncertainty, --ensemble, --tta_flip or a non-default --merge_method')
+    ap.add_argument('--bb_min_score', type=float, default=None, help='with black_box: sample detections whose top score is below this '
+                    'are discarded before pooling (default 0)')
+    ap.add_argument('--bb_min_members', type=int, default=None, help='with black_box: a group with fewer members is not reported '
+                    '(default 1)')
     ap.add_argument('--corrupt', type=str, default=None, metavar='NAME:SEVERITY', help='with --dataset: corrupt every frame on the '
                     'GPU before preprocessing, to score uncertainty under dataset shift (gaussian_noise, impulse_noise, defocus_blur, '
                     'motion_blur, gaussian_blur, pixelate, jpeg_compression, contrast, brightness, low_light, fog; severity 1..5); '
@@ -378,6 +441,7 @@ def main(argv=None):
         ap.error('--device_jpeg requires --dataset')
     try:
         check_merge_options(config, args)
+        check_uncertainty_options(config, args)
     except ValueError as e:
         ap.error(str(e))
     if args.device_png and not args.dataset:

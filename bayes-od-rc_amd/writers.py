@@ -52,7 +52,7 @@ class PredictionWriter(object):
                  class_parts=False):
         self.dataset = dataset
         root = os.path.join(predictions_dir, 'testing', dataset, str(ckpt_id), uncertainty_method)
-        if uncertainty_method == 'bayes_od':
+        if uncertainty_method in ('bayes_od', 'black_box'):      # the reference's <uncertainty_method>_<fusion> layout
             root += '_' + fusion_method
         self.root = root
         self.dirs = {k: os.path.join(root, k) for k in ('data', 'mean', 'cov', 'cat_param', 'cat_count')}

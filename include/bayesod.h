@@ -993,6 +993,63 @@ bod_status bod_get_detection_merge_terms(bod_handle h, int32_t image_index, floa
 bod_status bod_get_detection_merge_terms_batch(bod_handle h, int32_t slot, float* within, float* between, int32_t* members);
 bod_status bod_device_detection_merge_terms(bod_handle h, int32_t slot, void** ptrs3);
 
+/* ---- black-box MC dropout: per-sample NMS, then the detections merged ----
+ * The baseline BayesOD is compared against: every stochastic pass goes through the detector's ordinary post-processing on its own,
+ * the N detection sets of an image are grouped by overlap, and each group becomes one detection with the sample mean and the sample
+ * covariance of its members.  Kmax = nms_max_output_size, theta = affinity_threshold (0: nms_iou_threshold).
+ * Stage 1 (bod_blackbox_samples), for every image b and sample n -- bod_validation_post + bod_nms applied to sample n:
+ *   1. softmax of the sample's class row; anchors whose arg-max is background (first maximum wins) are dropped; the rest are ranked
+ *      by their top softmax score, their boxes decoded from the sample's own deltas;
+ *   2. nms_kernel with the handle's nms_* settings, in network coordinates: up to Kmax indices;
+ *   3. every selected candidate becomes a sample detection: score[C] = the softmax row (not the decayed NMS score), mean[4] (v,u,h,w),
+ *      anchor_index, cov[16] = the sample's own aleatoric matrix -- L D L^T with L = inv(unit_lower(params)), D = exp(diag) when
+ *      use_full_covar, else D; zeros when has_covar_head == 0 (bod_posterior's arithmetic on ONE sample's parameters);
+ *   4. the KITTI rescale of bod_posterior (S mu, S Sigma S^T; a ragged upload's per-frame factors included) here, after the NMS;
+ *   5. detections whose top score is below min_score are discarded; the others keep their order.
+ * Stage 2 (bod_blackbox_merge), per image.  The pool holds the image's sample detections at pooled index n * Kmax + rank; the corners
+ * of a detection are vuhw_to_vuvu of its (rescaled) mean.  Greedy:
+ *   1. the unassigned detection with the highest top score becomes a centre c; ties go to the lower pooled index;
+ *   2. its members are c itself (whatever its self-IoU under the reference's +1 formula) and every unassigned i with
+ *      bbox_iou_vuvu(corners_c, corners_i) > theta (bod_cluster_fuse's affinity); all of them become assigned;
+ *   3. with n members and d_i = mu_i - mu_c:  dbar = (1/n) sum d_i,  mean = mu_c + dbar,  within = (1/n) sum cov_i,
+ *      between = (sum d_i d_i^T - n dbar dbar^T) / (n - 1) for n >= 2 -- the unbiased sample covariance, centred as in
+ *      BOD_MERGE_MIXTURE -- and exactly 0 for n = 1,  cov = within + between (no factor 70, no 10:1 mix),
+ *      counts = sum score_i,  scores = counts / n,  members = n;
+ *   4. a cluster with n < min_members emits nothing; its members stay consumed;
+ *   5. stop after Kmax emitted clusters or when the pool is empty; detections appear in emission order.
+ * Clustering is class-agnostic.  fp32, no fused multiply-add; the sums over the members are re-associated (256 threads, wave
+ * butterflies), deterministically.
+ * bod_set_uncertainty_method(h, BOD_METHOD_BLACK_BOX, opt): opt == NULL means {0, 1, 0}.  The first switch allocates the stage's
+ * buffers (B * N virtual images' worth of keep flags, top scores, block counts, ranking, corners, anchor indices and nms_kernel's
+ * work arrays; the sample detections; the pool's work arrays; the merge-term buffers).  BOD_ERR_INVALID_ARG, with the reason, for
+ * an unknown method, a training handle, a statistics handle, covariance_parts != 0, a merge method other than BOD_MERGE_BAYES,
+ * min_members < 1, a min_score or affinity_threshold that is not finite or is negative, reserved != 0; the handle's method is
+ * unchanged then.  While black box is on, bod_set_merge_method refuses a non-default method.  BOD_METHOD_BAYES_OD brings back the
+ * default path: plans, buffers written and result bytes as on a handle that was never switched.
+ * In black-box mode bod_infer / bod_infer_async run the forward with the per-sample head outputs, then the two stages into the
+ * ticket's record slot, and mc_samples = 1 is allowed (the sampling-free baseline: members = 1, between = 0).  bod_collect,
+ * bod_get_detections[_batch], bod_gather_detections and bod_get_detection_merge_terms[_batch] serve the result as they stand.
+ * The stage entries work in either mode: bod_blackbox_samples needs the anchors and a forward / bod_set_raw
+ * (BOD_ERR_NOT_READY), bod_blackbox_merge needs sample detections newer than the last forward / bod_set_raw: bod_blackbox_samples, or
+ * bod_set_sample_detections (stage-level tests), which replaces ONE (image, sample) and leaves the others as they are -- empty on a
+ * handle whose stage 1 never ran.  The stage entries need the buffers: BOD_ERR_NOT_READY before the first switch to black box.
+ * bod_get_sample_detections: count, then anchor_index [count], scores [count][C], means [count][4], covs [count][16]; NULLs skipped. */
+enum { BOD_METHOD_BAYES_OD = 0, BOD_METHOD_BLACK_BOX = 1 };
+typedef struct bod_blackbox_options {   /* 16 bytes */
+    float   min_score;           /* stage 1, rule 5; default 0 */
+    int32_t min_members;         /* stage 2, rule 4; >= 1, default 1 */
+    float   affinity_threshold;  /* theta; 0 = nms_iou_threshold */
+    int32_t reserved;            /* 0 */
+} bod_blackbox_options;
+bod_status bod_set_uncertainty_method(bod_handle h, int32_t method, const bod_blackbox_options* options);
+bod_status bod_get_uncertainty_method(bod_handle h, int32_t* method);
+bod_status bod_blackbox_samples(bod_handle h);
+bod_status bod_blackbox_merge(bod_handle h);
+bod_status bod_get_sample_detections(bod_handle h, int32_t image_index, int32_t sample_index, int32_t* count, int32_t* anchor_index,
+                                     float* scores, float* means, float* covs);
+bod_status bod_set_sample_detections(bod_handle h, int32_t image_index, int32_t sample_index, int32_t count,
+                                     const int32_t* anchor_index, const float* scores, const float* means, const float* covs);
+
 /* What the handle's plan looks like (tests / bench report it; nothing on the hot path reads it).  info8[0] = 1 when the MC
  * statistics are reduced inside the last tower layers' tiles (no [B,N,A,.] tensors on the bod_infer path), [1] = 1 when the 1x1
  * head output convs are fused into the last tower layers' epilogues, [2] = 1 when the per-sample tower layers run on the

@@ -315,6 +315,21 @@ bod_status bod_get_merge_method(bod_handle h, int32_t* method);
 bod_status bod_get_detection_merge_terms(bod_handle h, int32_t image_index, float* within, float* between, int32_t* members);
 bod_status bod_get_detection_merge_terms_batch(bod_handle h, int32_t slot, float* within, float* between, int32_t* members);
 bod_status bod_device_detection_merge_terms(bod_handle h, int32_t slot, void** ptrs3);
+enum { BOD_METHOD_BAYES_OD = 0, BOD_METHOD_BLACK_BOX = 1 };
+typedef struct bod_blackbox_options {
+    float   min_score;
+    int32_t min_members;
+    float   affinity_threshold;
+    int32_t reserved;
+} bod_blackbox_options;
+bod_status bod_set_uncertainty_method(bod_handle h, int32_t method, const bod_blackbox_options* options);
+bod_status bod_get_uncertainty_method(bod_handle h, int32_t* method);
+bod_status bod_blackbox_samples(bod_handle h);
+bod_status bod_blackbox_merge(bod_handle h);
+bod_status bod_get_sample_detections(bod_handle h, int32_t image_index, int32_t sample_index, int32_t* count, int32_t* anchor_index,
+                                     float* scores, float* means, float* covs);
+bod_status bod_set_sample_detections(bod_handle h, int32_t image_index, int32_t sample_index, int32_t count,
+                                     const int32_t* anchor_index, const float* scores, const float* means, const float* covs);
 bod_status bod_plan_info(bod_handle h, int32_t* info8);
 bod_status bod_plan_info_n(bod_handle h, int32_t* info, int32_t n);
 bod_status bod_stat_reset(bod_handle h);
