@@ -30,6 +30,11 @@ class BodBlackBoxOptions(C.Structure):
     _fields_ = [("min_score", C.c_float), ("min_members", C.c_int32), ("affinity_threshold", C.c_float), ("reserved", C.c_int32)]
 
 
+class BodAcquisitionOptions(C.Structure):
+    """Mirror of ``bod_acquisition_options`` (include/bayesod.h)."""
+    _fields_ = [("min_foreground", C.c_float), ("top_k", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class BodConfig(C.Structure):
     _fields_ = [
         ("device", C.c_int32), ("image_h", C.c_int32), ("image_w", C.c_int32), ("batch", C.c_int32),
@@ -285,6 +290,8 @@ SIGNATURES = {
     "bod_stat_set_entropy": (C.c_int, [_H, _F]),
     "bod_stat_device_entropy": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
     "bod_stat_merge_entropy": (C.c_int, [_H, C.c_void_p, C.c_int32]),
+    "bod_stat_acquisition": (C.c_int, [_H, C.POINTER(BodAcquisitionOptions), _D, _D]),
+    "bod_stat_acquisition_map": (C.c_int, [_H, _F]),
     "bod_gather_detections": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
     "bod_profile_end": (C.c_int, [_H, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -23,6 +23,8 @@ SOURCES = [
     # the merge of MC statistics is compared with a float64 statement of its formula, the reduction from raw outputs with the
     # fused epilogues' (which are bracketed by `#pragma clang fp contract(off)`) for equality
     ("stat_kernels.hip", ["-ffp-contract=off"]),
+    # the acquisition scores of a statistics record are compared with a float64 statement of their formulas
+    ("acq_kernels.hip", ["-ffp-contract=off"]),
     ("train_kernels.hip", []),
     # integer code only (the JPEG inverse DCT, upsampling and colour conversion: DESIGN.md 9.11)
     ("jpeg_kernels.hip", []),

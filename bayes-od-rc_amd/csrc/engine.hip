@@ -412,6 +412,10 @@ struct bod_context {
     // [B,K,4] double-buffered with the records; the *_ok flags as for the covariance parts.
     bool class_parts = false;
     float* ent = nullptr; float* stat_ent = nullptr; int stat_ent_k = 0;
+    // bod_stat_acquisition, allocated by its first call: the [B,A] MI scratch, the workgroups' partial rows, the
+    // outputs ([B,12] then [B,C-1,3] doubles)
+    float* acq_mi = nullptr; double* acq_partials = nullptr; double* acq_out = nullptr;
+    bool acq_ran = false;
     float* cparts = nullptr;
     std::vector<char> cparts_ok;
     // How run_cluster merges a cluster (bod_set_merge_method).  The slots' term buffers exist from the first
@@ -4175,6 +4179,51 @@ bod_status bod_stat_posterior(bod_handle h, uint64_t seed, uint32_t first_image_
     if (h->cfg.ranking_method == BOD_RANK_JOINT_ENTROPY && h->cfg.gaussian_isotropic && h->cfg.dirichlet_non_informative)
         HIPCHK(h, launch_joint_entropy_rank(pc, pb, h->stream));
     h->stage.posterior_ran();
+    return BOD_OK;
+}
+
+// Acquisition scores of the accumulator (include/bayesod.h; acq_kernels.hip): reads the record, writes buffers of its own
+bod_status bod_stat_acquisition(bod_handle h, const bod_acquisition_options* opt, double* frame_scores, double* per_class) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(stat_handle(h, "bod_stat_acquisition"));
+    const bod_acquisition_options o = opt ? *opt : bod_acquisition_options{0.05f, 16, {0, 0}};
+    if (!(o.min_foreground >= 0.f && o.min_foreground <= 1.f))
+        return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_acquisition: min_foreground must lie in [0, 1], got %g", (double)o.min_foreground);
+    if (o.top_k < 1 || o.top_k > 1024) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_acquisition: top_k must lie in 1..1024, got %d", o.top_k);
+    if (o.reserved[0] != 0 || o.reserved[1] != 0) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_acquisition: reserved fields must be 0");
+    if (!frame_scores) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_acquisition: frame_scores is NULL");
+    const bod_config& c = h->cfg;
+    if (c.num_classes != 4 && c.num_classes != 8) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_acquisition: num_classes must be 4 or 8, got %d", c.num_classes);
+    if (h->stat_k < 2) return h->fail(BOD_ERR_NOT_READY, "bod_stat_acquisition: the accumulator holds %d samples; the box spread divides by K-1", h->stat_k);
+    if (h->class_parts && h->stat_ent_k != h->stat_k)
+        return h->fail(BOD_ERR_NOT_READY, "bod_stat_acquisition: ent_sum holds %d of the record's %d samples (bod_stat_merge_entropy / bod_stat_set_entropy has not followed)", h->stat_ent_k, h->stat_k);
+    const size_t B = (size_t)c.batch, npc = (size_t)(c.num_classes - 1) * 3;
+    const int G = acq_groups(h->A);
+    if (!h->acq_partials) BODCHK(h->dalloc(&h->acq_partials, B * G * ACQ_ROW_MAX));      // (each on its own: a failed call allocates nothing twice)
+    if (!h->acq_out) BODCHK(h->dalloc(&h->acq_out, B * (12 + npc)));
+    if (!h->acq_mi) BODCHK(h->dalloc(&h->acq_mi, B * h->A));
+    MarkerRange mr("bod:acquisition");
+    AcqArgs a{};
+    a.B = c.batch; a.A = h->A; a.C = c.num_classes; a.K = h->stat_k; a.G = G; a.top_k = o.top_k;
+    a.thr = (float)((1.0 - (double)o.min_foreground) * (double)h->stat_k);
+    a.cls_sum = h->stat_acc[0]; a.box_moments = h->stat_acc[1]; a.cov_sum = c.has_covar_head ? h->stat_acc[2] : nullptr;
+    a.ent_sum = h->class_parts ? h->stat_ent : nullptr;
+    a.mi = h->acq_mi; a.partials = h->acq_partials; a.scores = h->acq_out; a.per_class = h->acq_out + B * 12;
+    HIPCHK(h, launch_acquisition(a, h->stream));
+    h->acq_ran = true;
+    BODCHK(d2h(h, frame_scores, h->acq_out, B * 12));
+    BODCHK(d2h(h, per_class, h->acq_out + B * 12, B * npc));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BOD_OK;
+}
+
+bod_status bod_stat_acquisition_map(bod_handle h, float* mi) {
+    if (!h) return BOD_ERR_INVALID_ARG;
+    BODCHK(stat_handle(h, "bod_stat_acquisition_map"));
+    if (!mi) return h->fail(BOD_ERR_INVALID_ARG, "bod_stat_acquisition_map: mi is NULL");
+    if (!h->acq_ran) return h->fail(BOD_ERR_NOT_READY, "bod_stat_acquisition_map: bod_stat_acquisition has not been called");
+    BODCHK(d2h(h, mi, h->acq_mi, (size_t)h->cfg.batch * h->A));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return BOD_OK;
 }
 

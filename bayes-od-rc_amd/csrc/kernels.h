@@ -575,6 +575,28 @@ hipError_t launch_stat_merge_entropy(float* acc, const float* src, int64_t BA, i
 hipError_t launch_mirror_images(const float* in, float* out, int B, int H, int W, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
+// Acquisition scores of a statistics record (acq_kernels.hip; include/bayesod.h bod_stat_acquisition): one streaming
+// pass over the accumulator, G = acq_groups(A) workgroups per frame, then one workgroup per frame that folds their partial rows and
+// finds the top-k mean of the MI scratch by bisection.  Reads the record only; no atomics.
+#define ACQ_MAX_GROUPS 64                                       // workgroups per frame at most
+#define ACQ_ROW_MAX 33                                          // doubles per partial row (C = 8: 16 sums, 17 maxima)
+struct AcqArgs {
+    int32_t B, A, C, K;                                         // frames, anchors per frame, classes (4 or 8), samples in the record (>= 2)
+    int32_t G;                                                  // acq_groups(A)
+    int32_t top_k;
+    float thr;                                                  // foreground gate: cls_sum[C-1] <= thr
+    const float* cls_sum; const float* box_moments;             // [B,A,C], [B,A,16], 16-byte aligned
+    const float* cov_sum;                                       // [B,A,10] or nullptr (no covariance head)
+    const float* ent_sum;                                       // [B,A] or nullptr (no BOD_PARTS_CLASS)
+    float* mi;                                                  // [B,A] scratch: every anchor's MI, NaN outside the foreground set
+    double* partials;                                           // [B,G,ACQ_ROW_MAX] at most
+    double* scores;                                             // [B,12]
+    double* per_class;                                          // [B,C-1,3] or nullptr
+};
+int acq_groups(int A);
+hipError_t launch_acquisition(const AcqArgs& a, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // Streaming pointwise (1x1) convolution for reductions of <= 256 channels (conv_pointwise.hip); launch_conv_igemm routes eligible
 // launches there (BOD_POINTWISE=0: off)
 bool conv_pointwise_eligible(const ConvArgs& a);

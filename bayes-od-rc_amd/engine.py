@@ -921,6 +921,22 @@ class Engine(object):
         """posterior() on the accumulator with N = stat_samples (``bod_stat_posterior``); nms() / cluster_fuse() follow."""
         self._chk(self.lib.bod_stat_posterior(self.h, seed, first_image_id))
 
+    def stat_acquisition(self, min_foreground=0.05, top_k=16):
+        """Acquisition scores of the accumulator (``bod_stat_acquisition``): ``(scores [B,12], per_class [B,C-1,3])``
+        float64; the columns are ``acquisition.COLUMNS`` / ``acquisition.PER_CLASS_COLUMNS``.  Reads the record only."""
+        opt = _lib.BodAcquisitionOptions(float(min_foreground), int(top_k), (C.c_int32 * 2)(0, 0))
+        scores = np.empty((self.B, 12), np.float64)
+        per_class = np.empty((self.B, self.Ccls - 1, 3), np.float64)
+        self._chk(self.lib.bod_stat_acquisition(self.h, C.byref(opt), _lib.dptr(scores), _lib.dptr(per_class)))
+        return scores, per_class
+
+    def stat_acquisition_map(self):
+        """[B,A] float32: every anchor's mutual information of the last ``stat_acquisition``, NaN outside the foreground set
+        (``bod_stat_acquisition_map``, a test hook)."""
+        mi = np.empty((self.B, self.A), np.float32)
+        self._chk(self.lib.bod_stat_acquisition_map(self.h, fptr(mi)))
+        return mi
+
     def bench_head_conv(self, layer=1, variant=0, iters=10):
         ms, fl = C.c_double(0), C.c_double(0)
         self._chk(self.lib.bod_bench_head_conv(self.h, layer, variant, iters, C.byref(ms), C.byref(fl)))

@@ -302,13 +302,24 @@ class EnsemblePipeline(object):
     of one model with ``passes = k`` is "N = k * n on one handle".  Same call and return shape as ``BayesOdPipeline``.
     ``views``: the test-time views every pass runs, ``'identity'`` and / or ``'hflip'`` (the frames mirrored left-right on the
     device, the record mapped back to the anchors of the frames as given while it is folded: ``Engine.stat_forward(view=)``);
-    with V views member m, pass p, view index v draws the samples ``((m * passes + p) * V + v) * n ..``."""
+    with V views member m, pass p, view index v draws the samples ``((m * passes + p) * V + v) * n ..``.
+    ``acquisition``: ``dict(min_foreground=, top_k=)`` (either may be left out) -- after the folds into member 0 and before its
+    posterior, the merged record is reduced to acquisition scores (``Engine.stat_acquisition``), kept as
+    ``.acquisition`` = (scores [B,12], per_class [B,C-1,3]); ``acquisition_only=True`` stops there: no posterior, NMS, clustering
+    or records, and ``__call__`` returns the acquisition alone."""
 
     def __init__(self, models, image_hw, batch, bayes_od_config, nms_config, samples_per_member, passes=1, use_full_covar=True,
                  dataset_name='bdd', orig_size=None, nms_variant='A', anchors=None, views=('identity',), covariance_parts=False,
-                 class_parts=False, merge_method='bayes'):
+                 class_parts=False, merge_method='bayes', acquisition=None, acquisition_only=False):
         from .engine import Engine, make_config
         self._merge = _checked_merge_method(merge_method, covariance_parts, class_parts)
+        if acquisition is not None and set(acquisition) - {'min_foreground', 'top_k'}:
+            raise ValueError("acquisition takes min_foreground and top_k, got %s" % sorted(acquisition))
+        if acquisition_only and acquisition is None:
+            raise ValueError("acquisition_only needs acquisition=dict(...)")
+        self._acq = None if acquisition is None else dict(acquisition)
+        self._acq_only = bool(acquisition_only)
+        self.acquisition = None
         models = list(models)
         if not models:
             raise ValueError("EnsemblePipeline needs at least one model")
@@ -388,6 +399,10 @@ class EnsemblePipeline(object):
                         eng.stat_forward(images, seed=seed, first_image_id=first_image_id, sample_base=base, view=view)
         for eng in self.engines[1:]:
             self.engine.stat_merge_from(eng)
+        if self._acq is not None:
+            self.acquisition = self.engine.stat_acquisition(**self._acq)
+            if self._acq_only:
+                return self.acquisition
         self.engine.stat_posterior(seed=seed, first_image_id=first_image_id)
         self.engine.nms()
         self.engine.cluster_fuse()

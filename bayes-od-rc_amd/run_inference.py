@@ -28,6 +28,7 @@ def test_model(config, args):
     want_class = _want_class_parts(config, args)          # decided once: the writer and every pipeline get the same answer
     merge = check_merge_options(config, args)             # likewise; refuses what does not go together before anything is built
     method, bb_options = check_uncertainty_options(config, args)
+    acq = check_acquisition_options(config, args)         # None, or the options of --acquisition
     dataset_config = config['dataset_config']
     training_dataset = dataset_config['dataset']
     test_dataset = test_config['test_dataset']
@@ -60,12 +61,22 @@ def test_model(config, args):
             pipes[b] = _make_pipeline(model, args, hw, b, test_config['bayes_od_config'], nms_config,
                                       use_full_covar=test_config['use_full_covar'],
                                       dataset_name=test_dataset, orig_size=orig, anchors=anchors, class_parts=want_class,
-                                      merge_method=merge, uncertainty_method=method, blackbox_options=bb_options)
+                                      merge_method=merge, uncertainty_method=method, blackbox_options=bb_options,
+                                      acquisition=acq)
         return pipes[b]
     predictions_dir = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'], 'predictions')
+    fusion = writer_fusion_name(test_config['bayes_od_config']['fusion_method'], merge)
+    log = _AcquisitionLog(acq, writers.tree_root(predictions_dir, test_dataset, test_config['ckpt_idx'], method, fusion),
+                          only=getattr(args, 'acq_only', False))
+    if log.only:                                         # --acq_only: the scores alone, no prediction tree
+        for lo in range(0, len(frames), batch):
+            chunk = frames[lo:lo + batch]
+            pipe = pipe_for(len(chunk))
+            pipe(chunk, seed=args.seed, first_image_id=lo)
+            log.add(['%06d' % (lo + b) for b in range(len(chunk))], pipe)
+        return log.write()
     writer = writers.PredictionWriter(predictions_dir, test_dataset, test_config['ckpt_idx'],
-                                      method,
-                                      writer_fusion_name(test_config['bayes_od_config']['fusion_method'], merge),
+                                      method, fusion,
                                       cov_parts=_want_parts(args), class_parts=want_class)
     categories = dataset_config[training_dataset]['training_data_config']['categories']
     start = time.time()
@@ -73,6 +84,7 @@ def test_model(config, args):
     for lo in range(0, len(frames), batch):              # every frame, like the reference's loop (run_inference.py:137)
         chunk = frames[lo:lo + batch]
         dets = pipe_for(len(chunk))(chunk, seed=args.seed, first_image_id=lo)
+        log.add(['%06d' % (lo + b) for b in range(len(chunk))], pipe_for(len(chunk)))
         if _want_merge_terms(args):
             _write_merge_terms(writer.root, ['%06d' % (lo + b) for b in range(len(chunk))], pipe_for(len(chunk)).merge_terms())
         for b, (classes, boxes_vuhw, covs, counts, *parts) in enumerate(dets):
@@ -89,6 +101,7 @@ def test_model(config, args):
             _render_batch(args, writer.root, ['%06d' % (lo + b) for b in range(len(chunk))], list(rgb), categories)
         sys.stdout.write('\r{}'.format(n_done) + ' /' + str(len(frames)))
     writer.close()
+    log.write()
     elapsed = time.time() - start
     print("\nMean frame rate: " + str(n_done / max(elapsed, 1e-9)))
     return writer.root
@@ -191,6 +204,69 @@ def check_uncertainty_options(config, args):
     return method, opts
 
 
+def _want_acquisition(args):
+    return bool(getattr(args, 'acquisition', False) or getattr(args, 'acq_only', False))
+
+
+def check_acquisition_options(config, args):
+    """None, or ``dict(min_foreground=, top_k=)`` for --acquisition / --acq_only; ValueError, with the reason, for what does not go
+    with them: black-box MC dropout (it has no statistics handle to score), a non-default merge method (the handles carry the
+    class-entropy parts, defined for the Bayesian fuse only), the options without the flag, and with --acq_only everything that
+    needs the detections it skips."""
+    from . import acquisition
+    opts = {}
+    if getattr(args, 'acq_min_foreground', None) is not None:
+        opts['min_foreground'] = float(args.acq_min_foreground)
+    if getattr(args, 'acq_top_k', None) is not None:
+        opts['top_k'] = int(args.acq_top_k)
+    if not _want_acquisition(args):
+        if opts:
+            raise ValueError("--acq_min_foreground / --acq_top_k belong to --acquisition")
+        return None
+    if resolve_uncertainty_method(config, getattr(args, 'uncertainty_method', None)) == 'black_box':
+        raise ValueError("--acquisition does not go with --uncertainty_method black_box: the scores are read from a statistics handle, "
+                         "and black-box MC dropout has none")
+    if getattr(args, 'acq_only', False):
+        for flag, on in (('--render', getattr(args, 'render', None)), ('--covariance_parts', _want_parts(args)),
+                         ('--class_uncertainty', _want_class_parts(config, args)),
+                         ('--merge_method', getattr(args, 'merge_method', None) is not None), ('--merge_terms', _want_merge_terms(args))):
+            if on:
+                raise ValueError("--acq_only does not go with %s: it skips the posterior, NMS and clustering, so there are no "
+                                 "detections" % flag)
+    elif resolve_merge_method(config, getattr(args, 'merge_method', None)) != 'bayes':
+        raise ValueError("--acquisition does not go with a non-default merge method: its handles carry the class-entropy parts, which "
+                         "are defined for the Bayesian fuse only")
+    opts = dict(acquisition.DEFAULTS, **opts)
+    if not 0.0 <= opts['min_foreground'] <= 1.0 or not 1 <= opts['top_k'] <= 1024:
+        raise ValueError("--acq_min_foreground must lie in [0, 1] and --acq_top_k in 1..1024")
+    return opts
+
+
+class _AcquisitionLog(object):
+    """--acquisition: every batch's scores (``EnsemblePipeline.acquisition``) under its frames' names, written as
+    <tree>/acquisition.npz (``frames``, ``columns``, ``scores``, ``per_class``) at the end.  Inert without the flag."""
+
+    def __init__(self, options, root, only=False):
+        self.on, self.root = options is not None, root
+        self.only = self.on and bool(only)            # --acq_only: the pipelines return no detections and no tree is written
+        self.names, self.scores, self.per_class = [], [], []
+
+    def add(self, names, pipe):
+        if self.on:
+            scores, per_class = pipe.acquisition
+            self.names.extend(names)
+            self.scores.append(np.array(scores[:len(names)]))
+            self.per_class.append(np.array(per_class[:len(names)]))
+
+    def write(self):
+        if self.on and self.names:
+            from . import acquisition
+            os.makedirs(self.root, exist_ok=True)
+            acquisition.save(os.path.join(self.root, 'acquisition.npz'), self.names, np.concatenate(self.scores),
+                             np.concatenate(self.per_class))
+        return self.root
+
+
 def _want_merge_terms(args):
     return bool(getattr(args, 'merge_terms', False))
 
@@ -223,13 +299,18 @@ def _make_pipeline(model, args, hw, batch, bayes_od_config, nms_config, **kw):
     """``class_parts=``: the caller's ``_want_class_parts(config, args)`` -- the same value its writer was made with.
     BayesOdPipeline of the one model, or -- ``model`` a list (--ensemble) -- EnsemblePipeline with the yaml's
     mc_dropout_samples per member and --mc_passes passes each.  --tta_flip: every pass runs the frames as given and mirrored
-    left-right; without --ensemble that is a one-member EnsemblePipeline of the one model."""
+    left-right; without --ensemble that is a one-member EnsemblePipeline of the one model, and so is --acquisition."""
     tta = bool(getattr(args, 'tta_flip', False))
+    acq = kw.pop('acquisition', None)     # --acquisition: check_acquisition_options' answer, decided once by the caller
     if _want_parts(args):                 # --covariance_parts: every detection's epistemic / aleatoric / prior covariance
         kw = dict(kw, covariance_parts=True)
     if kw.pop('class_parts', False):      # --class_uncertainty / testing_config.class_uncertainty, decided once by the caller
         kw = dict(kw, class_parts=True)
-    if isinstance(model, list) or tta:
+    if acq is not None:                   # statistics handles that carry ent_sum, so that the mutual information exists
+        kw = dict(kw, class_parts=True, acquisition=dict(acq), acquisition_only=bool(getattr(args, 'acq_only', False)))
+        if kw['acquisition_only']:        # (no cluster is merged: a yaml's merge method has nothing to act on)
+            kw['merge_method'] = 'bayes'
+    if isinstance(model, list) or tta or acq is not None:
         members = model if isinstance(model, list) else [model]
         # statistics handles: bayes_od only (check_uncertainty_options has refused black_box with --ensemble / --tta_flip)
         kw = dict(kw)
@@ -250,15 +331,17 @@ def _test_model_on_dataset(config, args, model):
     want_class = _want_class_parts(config, args)
     merge = check_merge_options(config, args)
     method, bb_options = check_uncertainty_options(config, args)
+    acq = check_acquisition_options(config, args)
     dataset_config = config['dataset_config']
     training_dataset, test_dataset = dataset_config['dataset'], test_config['test_dataset']
     handler = datasets.build_dataset(dict(dataset_config, dataset=test_dataset), 'test')
     kitti = test_dataset == 'kitti'
     predictions_dir = os.path.join(config_utils.data_dir(), 'outputs', config['checkpoint_name'], 'predictions')
-    writer = writers.PredictionWriter(predictions_dir, test_dataset, test_config['ckpt_idx'],
-                                      method,
-                                      writer_fusion_name(test_config['bayes_od_config']['fusion_method'], merge),
-                                      cov_parts=_want_parts(args), class_parts=want_class)
+    fusion = writer_fusion_name(test_config['bayes_od_config']['fusion_method'], merge)
+    log = _AcquisitionLog(acq, writers.tree_root(predictions_dir, test_dataset, test_config['ckpt_idx'], method, fusion),
+                          only=getattr(args, 'acq_only', False))
+    writer = None if log.only else writers.PredictionWriter(predictions_dir, test_dataset, test_config['ckpt_idx'], method, fusion,
+                                                            cov_parts=_want_parts(args), class_parts=want_class)
     categories = dataset_config[training_dataset]['training_data_config']['categories']
     gen = FpnAnchorGenerator(dataset_config['anchor_generator'])
     pipes = {}
@@ -272,6 +355,10 @@ def _test_model_on_dataset(config, args, model):
     handler.defer_png = device_png           # PNG files likewise
 
     def emit(dets, pipe):
+        log.add([p[0] for p in pending], pipe)
+        if log.only:                         # (dets is the acquisition itself)
+            del pending[:]
+            return
         if _want_merge_terms(args):
             _write_merge_terms(writer.root, [p[0] for p in pending], pipe.merge_terms())
         for (name, _, _), (classes, boxes_vuhw, covs, counts, *parts) in zip(pending, dets):
@@ -296,7 +383,7 @@ def _test_model_on_dataset(config, args, model):
                 model, args, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
                 use_full_covar=test_config['use_full_covar'], dataset_name=test_dataset, orig_size=hw,
                 anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class, merge_method=merge,
-                uncertainty_method=method, blackbox_options=bb_options)
+                uncertainty_method=method, blackbox_options=bb_options, acquisition=acq)
         pipe = pipes[key]
         # (a frame's corruption is keyed on its dataset index: the same whatever batch or run it falls into)
         corruption = None if corrupt is None else (corrupt[0], [p[2] for p in pending], corrupt[1])
@@ -318,7 +405,7 @@ def _test_model_on_dataset(config, args, model):
                 model, args, hw, len(pending), test_config['bayes_od_config'], test_config['nms_config'],
                 use_full_covar=test_config['use_full_covar'], dataset_name=test_dataset, orig_size=src_hw,
                 anchors=gen.generate_all((hw[0], hw[1], 3)), class_parts=want_class, merge_method=merge,
-                uncertainty_method=method, blackbox_options=bb_options)
+                uncertainty_method=method, blackbox_options=bb_options, acquisition=acq)
         pipe = pipes[key]
         pipe.bind(orig_size=src_hw)      # the handle may be shared with a pipe of another source size: re-apply the KITTI scale
         pipe.engine.upload_frames_u8(frames, constants.MEANS_DICT[handler.im_normalization], aspect_resize=kitti)
@@ -333,9 +420,11 @@ def _test_model_on_dataset(config, args, model):
         pending.append((name, rgb, idx))
         n_done += 1
     flush()
-    writer.close()
+    if writer is not None:
+        writer.close()
+    log.write()
     print("\nMean frame rate: " + str(n_done / max(time.time() - start, 1e-9)))
-    return writer.root
+    return log.root
 
 
 def _render_batch(args, tree, names, frames, categories):
@@ -426,6 +515,17 @@ def main(argv=None):
     ap.add_argument('--render_view', choices=('overlay', 'heat', 'both'), default='overlay', help='with --render: the overlay, the '
                     'jet-coloured spatial-probability map, or both')
     ap.add_argument('--render_min_score', type=float, default=0.5, help='with --render: detections below this score are not drawn')
+    ap.add_argument('--acquisition', action='store_true', help='active learning: also score every frame by the model\'s uncertainty '
+                    'about it, from the per-anchor MC statistics on the GPU, and write acquisition.npz (frames, columns, scores [F,12], '
+                    'per_class [F,C-1,3]) into the prediction tree; choose frames from it with python -m bayes_od_rc_amd.select_frames.  '
+                    'Runs on statistics handles like --tta_flip; works with --ensemble, --mc_passes, --tta_flip, --corrupt, '
+                    '--mixed_sizes, --device_jpeg and --device_png; not with --uncertainty_method black_box or a non-default --merge_method')
+    ap.add_argument('--acq_only', action='store_true', help='--acquisition without the posterior, NMS and clustering: acquisition.npz '
+                    'is the only output; not with --render, --covariance_parts, --class_uncertainty, --merge_method or --merge_terms')
+    ap.add_argument('--acq_min_foreground', type=float, default=None, help='with --acquisition: an anchor counts as foreground when '
+                    'its mean background probability is at most 1 - this (default 0.05)')
+    ap.add_argument('--acq_top_k', type=int, default=None, help='with --acquisition: mi_topk is the mean of this many largest '
+                    'per-anchor mutual informations of a frame (default 16, at most 1024)')
     args = ap.parse_args(argv)
     if args.corrupt:
         if not args.dataset:
@@ -442,6 +542,7 @@ def main(argv=None):
     try:
         check_merge_options(config, args)
         check_uncertainty_options(config, args)
+        check_acquisition_options(config, args)
     except ValueError as e:
         ap.error(str(e))
     if args.device_png and not args.dataset:

@@ -40,6 +40,14 @@ def predictions_to_kitti_format(output_boxes, output_classes):
     return np.asarray(rows)
 
 
+def tree_root(predictions_dir, dataset, ckpt_id, uncertainty_method='bayes_od', fusion_method='none'):
+    """The directory a PredictionWriter of these arguments writes its tree into (nothing is created)."""
+    root = os.path.join(predictions_dir, 'testing', dataset, str(ckpt_id), uncertainty_method)
+    if uncertainty_method in ('bayes_od', 'black_box'):      # the reference's <uncertainty_method>_<fusion> layout
+        root += '_' + fusion_method
+    return root
+
+
 class PredictionWriter(object):
     """Directory layout predictions/testing/<dataset>/<ckpt_id>/<method>_<fusion>/{data,mean,cov,
     cat_param,cat_count} and per-frame files (run_inference.py:90-115,174-236).  ``cov_parts=True`` adds three directories beside
@@ -51,9 +59,7 @@ class PredictionWriter(object):
     def __init__(self, predictions_dir, dataset, ckpt_id, uncertainty_method='bayes_od', fusion_method='none', cov_parts=False,
                  class_parts=False):
         self.dataset = dataset
-        root = os.path.join(predictions_dir, 'testing', dataset, str(ckpt_id), uncertainty_method)
-        if uncertainty_method in ('bayes_od', 'black_box'):      # the reference's <uncertainty_method>_<fusion> layout
-            root += '_' + fusion_method
+        root = tree_root(predictions_dir, dataset, ckpt_id, uncertainty_method, fusion_method)
         self.root = root
         self.dirs = {k: os.path.join(root, k) for k in ('data', 'mean', 'cov', 'cat_param', 'cat_count')}
         if cov_parts:

@@ -1147,6 +1147,36 @@ bod_status bod_stat_set_entropy(bod_handle h, const float* ent_sum);
 bod_status bod_stat_device_entropy(bod_handle h, void** ptr);
 bod_status bod_stat_merge_entropy(bod_handle h, const void* ent_sum, int32_t view);
 
+/* ---- acquisition scores of a statistics handle: the accumulator of K >= 2 samples reduced, in one streaming pass
+ * on the handle's stream, to a few numbers per frame for ranking unlabeled frames by the model's uncertainty (active learning).
+ * Per anchor, fp32, with C classes of which the last is the background:
+ *   bad     any non-finite float in the anchor's record; a bad anchor is counted in n_bad and enters nothing else
+ *   W       the frame's foreground set: cls_sum[C-1] <= (float)((1.0 - (double)min_foreground) * K)
+ *   H       -sum_j p_j ln p_j with p_j = cls_sum[j] / K (p_j <= 0 contributes 0);  Ha = ent_sum / K;  MI = max(H - Ha, 0)
+ *   fg      1 - cls_sum[C-1] / K
+ *   e_box   (M2_00 + M2_11 + M2_22 + M2_33) / (K - 1) / (h^2 + w^2) with h, w = box_moments[2], [3]: the box's epistemic spread
+ *   lda     (x[0] + x[4] + x[5] + x[9]) / K, x the cov_sum row: the log-determinant of the aleatoric covariance
+ *   cls     arg max_{j < C-1} cls_sum[j], the first maximum
+ * frame_scores [B,12], fp64: n_fg = |W|, n_bad, entropy_mean (H over W), aleatoric_entropy_mean (Ha over W), mi_mean, mi_max (MI over
+ * W), mi_soft (sum fg MI / sum fg over every good anchor), mi_topk (mean of the min(top_k, n_fg) largest MI of W), box_epistemic_mean,
+ * box_epistemic_max (e_box over W), box_aleatoric_mean, box_aleatoric_max (lda over W).  per_class [B,C-1,3], fp64 (NULL: skipped):
+ * for class j the number of W anchors with cls = j, their largest MI and their largest e_box.  A mean or maximum over an empty set
+ * is NaN; columns 3-7 and per_class' MI are NaN without BOD_PARTS_CLASS (no ent_sum), columns 10-11 without the covariance head.
+ * No atomics: the same record gives the same bits, and a frame's row depends on that frame's record alone.
+ * The call is ordered behind whatever wrote the accumulator, copies the outputs to the host and returns when they are complete.
+ * The accumulator, K and every posterior / record buffer are left as they are: bod_stat_posterior may follow, precede or not happen.
+ * BOD_ERR_INVALID_ARG: no mc_statistics, min_foreground outside [0, 1], top_k outside 1..1024, non-zero reserved.
+ * BOD_ERR_NOT_READY: K < 2, ent_sum behind the record.  options = NULL: min_foreground 0.05, top_k 16. */
+typedef struct bod_acquisition_options {   /* 16 bytes */
+    float min_foreground;
+    int32_t top_k;
+    int32_t reserved[2];
+} bod_acquisition_options;
+bod_status bod_stat_acquisition(bod_handle h, const bod_acquisition_options* options, double* frame_scores, double* per_class);
+/* Test hook: the [B,A] scratch of the last bod_stat_acquisition -- every anchor's MI, NaN outside W, for bad anchors and without
+ * ent_sum.  BOD_ERR_NOT_READY before any bod_stat_acquisition (the scratch is allocated by the first one). */
+bod_status bod_stat_acquisition_map(bod_handle h, float* mi);
+
 #ifdef __cplusplus
 }
 #endif

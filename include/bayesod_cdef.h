@@ -349,3 +349,10 @@ bod_status bod_stat_get_entropy(bod_handle h, float* ent_sum);
 bod_status bod_stat_set_entropy(bod_handle h, const float* ent_sum);
 bod_status bod_stat_device_entropy(bod_handle h, void** ptr);
 bod_status bod_stat_merge_entropy(bod_handle h, const void* ent_sum, int32_t view);
+typedef struct bod_acquisition_options {
+    float min_foreground;
+    int32_t top_k;
+    int32_t reserved[2];
+} bod_acquisition_options;
+bod_status bod_stat_acquisition(bod_handle h, const bod_acquisition_options* options, double* frame_scores, double* per_class);
+bod_status bod_stat_acquisition_map(bod_handle h, float* mi);
